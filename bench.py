@@ -8,7 +8,20 @@ the environment) and N > 1 it starts the N ranks itself as a child process (self
 OUTPUT: the LAST stdout line is one short (<= 4 KB) strict-JSON record -- the reference harness prints one short statistics
 line per run too (tests/common/aoclsparse_stats.cpp:266-340) -- carrying the headline, `roofline`, `cpu_baseline`, `parity`
 and ONE number per leg (`legs`).  The full report (every leg with its quartiles, per-case rooflines and parity verdicts) goes
-to the file named by --record (default bench_legs.json next to this file), not to stdout.
+to the file named by --record (default with --full: bench_legs.json next to this file), not to stdout.
+
+PLAIN RUN vs --full: a plain run does what the headline needs and nothing else -- set up, W warm-up steps, the K timed steps
+(timed region 1 below), the outputs of --dump-outputs, the record (`cpu_baseline` and `parity` null, `legs` empty).  --full adds
+timed region 2 (back to back), the parity check of the timed product against the CPU oracle, the CPU baseline and the legs
+(--legs selects among them), and writes the full report.
+Time outside the steps: a step is the product's device time, so the 1 GiB flush before each product, the two events around it
+and the Python loop fall outside every step: about 0.28 ms per step (warm-up steps included) next to ~0.174 ms per step on the
+4096 grid, plus about 3.5 s of set-up (imports, matrix, optimize).  Measured: --steps 40000 --warmup 10 ran 21.7 s, 14.7 s of it
+outside the steps; so 30 s outside the steps is reached near K + W = 95,000.  Any K works (the event ring is drained every
+LAP_CHUNK steps).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller: DIR/y.npy (float64),
+the whole y when it has <= DUMP_SAMPLE rows, else those rows of a fixed seeded sample, in ascending row order.  The inputs
+depend on --grid only, so two builds run with the same arguments can be compared output for output.
 
   step      = one aoclsparse_dmv (alpha=1, beta=0) over the whole matrix, x and y resident in HBM.
   workload  = 5-point Laplacian, BASELINE.json configs[1] scaled from its 100x100 grid (795 KB,
@@ -248,6 +261,38 @@ def bound_of(working_set_bytes):
 
 
 COMPACT_LIMIT = 4096  # bytes: the driver keeps a bounded tail of stdout, the record must fit it with room to spare
+# steps between two drains of the library's per-step event ring (aoclsparse_mi355_timer_mark holds 65,536 marks; a cold step
+# records two): any --steps works, the drain (one host wait) falls between a product and the next flush
+LAP_CHUNK = 16384
+DUMP_SAMPLE = 1 << 22  # rows of y that --dump-outputs writes at most (32 MiB of float64)
+DUMP_SEED = 20261016
+
+
+def dump_rows(m):
+    """the rows of y that --dump-outputs writes: all of them, or a fixed seeded sample of DUMP_SAMPLE rows in ascending order
+    (the same rows for the same m, whatever the build)"""
+    import numpy as np
+
+    if m <= DUMP_SAMPLE:
+        return np.arange(m, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def sample_y(torch, y):
+    """the rows dump_rows() names of the device vector y, on the host"""
+    rows = dump_rows(y.numel())
+    return y.cpu().numpy() if len(rows) == y.numel() else y[torch.from_numpy(rows).to(y.device)].cpu().numpy()
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every (name, float32 / float64 array) of `arrays`"""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _short(text, n):
@@ -497,8 +542,14 @@ def main():
     ap.add_argument("--grid", type=int, default=4096, help="Laplacian grid edge of the headline workload")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: CPU tensors on the wire, ranks may share one GPU (control-flow tests on a 1-GPU box)")
-    ap.add_argument("--legs", default="all",
-                    help="comma list of l100,dcsrmv_csr_adaptive,headline_twins,mix,csrmm,csrmm_sharded,spmv_row_sharded,sp2m_row_sharded,trsv,sp2m,cpu,inlib_multi (or all / none)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: timed region 2 (back to back), parity against the CPU oracle, the CPU "
+                         "baseline, the legs and the full report (--record)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (y, or a fixed seeded sample of its rows) "
+                         "as DIR/y.npy")
+    ap.add_argument("--legs", default=None,
+                    help="with --full: comma list of l100,dcsrmv_csr_adaptive,headline_twins,mix,csrmm,csrmm_sharded,spmv_row_sharded,sp2m_row_sharded,trsv,sp2m,cpu,inlib_multi (or all / none; default all)")
     ap.add_argument("--mm-grid", type=int, default=1000, help="csrmm: A = Laplacian on grid^2")
     ap.add_argument("--mm-cols", type=int, default=256)
     ap.add_argument("--shard-grid", type=int, default=0,
@@ -516,17 +567,27 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch check only: the ranks rendezvous (gloo), sum their ranks and rank 0 prints a record with "
                          "metric 'launch-check'; no GPU is touched and nothing is measured (CPU-tier test of the launch convention)")
-    ap.add_argument("--record", default=os.path.join(ROOT, "bench_legs.json"),
-                    help="file that receives the FULL report (stdout only gets the short record); '' = do not write it")
+    ap.add_argument("--record", default=None,
+                    help="file that receives the FULL report (stdout only gets the short record); '' = do not write it; default: "
+                         "bench_legs.json next to this file with --full, none without")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU-baseline budget per thread count")
     ap.add_argument("--small", action="store_true", help="mix / trsv legs on the two small matrices only")
     ap.add_argument("--cold-only", action="store_true",
-                    help="skip timed region 2 (the back-to-back products): every launch of the headline kernel in the run is then a "
-                         "cold one, so a rocprofv3 --kernel-trace --stats average of that kernel is the cold average")
+                    help="with --full: skip timed region 2 (the back-to-back products; a plain run has none): every launch of the "
+                         "headline kernel in the run is then a cold one, so a rocprofv3 --kernel-trace --stats average of that "
+                         "kernel is the cold average")
     args = ap.parse_args()
+    if args.legs is None:
+        args.legs = "all" if args.full else "none"
+    elif not args.full and args.legs != "none":
+        ap.error("--legs %s needs --full (a plain run measures the headline only)" % args.legs)
+    if args.record is None:
+        args.record = os.path.join(ROOT, "bench_legs.json") if args.full else ""
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # not under torch.distributed.run: start the ranks ourselves (as a child; nothing here has touched the GPU)
-        sys.exit(self_launch(sys.argv[1:], args.gpus))
+        # not under torch.distributed.run: start the ranks ourselves (as a child; nothing here has touched the GPU).  The child runs
+        # in this file's directory: the dump directory goes to it as an absolute path (the last occurrence of an option wins)
+        argv = sys.argv[1:] + (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
+        sys.exit(self_launch(argv, args.gpus))
     all_legs = ["l100", "dcsrmv_csr_adaptive", "headline_twins", "mix", "csrmm", "csrmm_sharded", "spmv_row_sharded", "sp2m_row_sharded", "trsv", "sp2m", "cpu",
                 "inlib_multi"]
     legs = set(all_legs) if args.legs == "all" else set(x for x in args.legs.split(",") if x and x != "none")
@@ -648,30 +709,41 @@ def main():
     pkg.timer_laps()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    laps = []
+    for i in range(args.steps):
         flush.sum()
         pkg.timer_mark()
         step()
         pkg.timer_mark()
-    all_laps = pkg.timer_laps()  # drains the stream
+        if (i + 1) % LAP_CHUNK == 0 or i + 1 == args.steps:
+            # drains the stream; between a product and the next flush, so outside every step
+            laps += pkg.timer_laps()[0::2]  # per-product device ms (the odd laps are the flushes)
     barrier()
     wall_cold = time.perf_counter() - t0
-    laps = all_laps[0::2]  # per-product device ms (the odd laps are the flushes)
     assert len(laps) == args.steps
     elapsed = float(sum(laps)) * 1e-3  # seconds of the K cold products on this rank
+    if args.dump_outputs and rank == 0:
+        # y of the last timed step, as its caller receives it (before anything else writes y)
+        dump_outputs(args.dump_outputs, {"y": sample_y(torch, y)})
 
-    # Timed region 2: the same K products back to back (what an iterative solver that does nothing else between products sees)
+    # Timed region 2 (--full): the same K products back to back (what an iterative solver that does nothing else between products
+    # sees)
     b2b = None
-    if not args.cold_only:
+    if args.full and not args.cold_only:
         for _ in range(args.warmup):
             step()
         barrier()
         t1 = time.perf_counter()
         pkg.timer_mark()
-        for _ in range(args.steps):
+        laps_b2b = []
+        for i in range(args.steps):
             step()
             pkg.timer_mark()
-        laps_b2b = pkg.timer_laps()
+            if (i + 1) % LAP_CHUNK == 0 and i + 1 < args.steps:
+                laps_b2b += pkg.timer_laps()  # (drains the stream once per chunk; the next chunk starts at a fresh mark)
+                pkg.timer_mark()
+        laps_b2b += pkg.timer_laps()
+        assert len(laps_b2b) == args.steps
         barrier()
         elapsed_b2b = time.perf_counter() - t1
         b2b = (elapsed_b2b, laps_b2b)
@@ -864,7 +936,7 @@ def main():
 
     run_leg("sp2m_row_sharded", leg_sp2m_row_sharded, collective=True)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         import oracle
 
         # ---- parity of the timed configuration against the oracle (checker, not timed) ----

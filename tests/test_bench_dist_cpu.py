@@ -288,6 +288,32 @@ def test_bench_gpus_n_starts_its_own_ranks_dry():
         assert "needs a GPU" in r.stderr
 
 
+def test_bench_legs_need_full():
+    """A plain run measures the headline only: asking it for a leg is an error before anything starts, not a silent no-op."""
+    import subprocess
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--legs", "mix"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_rows_and_files(tmp_path):
+    """--dump-outputs: the whole y when it is small, else a fixed seeded sample of DUMP_SAMPLE distinct rows in ascending order
+    (the same rows on every call); the files are DIR/<name>.npy in the array's own float type."""
+    assert np.array_equal(bench.dump_rows(1000), np.arange(1000))
+    m = bench.DUMP_SAMPLE + 12345
+    a, b = bench.dump_rows(m), bench.dump_rows(m)
+    assert len(a) == bench.DUMP_SAMPLE and np.array_equal(a, b)
+    assert a[0] >= 0 and a[-1] < m and np.all(np.diff(a) > 0)
+    y = np.sin(np.arange(10.0))
+    bench.dump_outputs(str(tmp_path / "out"), {"y": y, "yf": y.astype(np.float32)})
+    assert np.array_equal(np.load(tmp_path / "out" / "y.npy"), y) and np.load(tmp_path / "out" / "y.npy").dtype == np.float64
+    assert np.load(tmp_path / "out" / "yf.npy").dtype == np.float32
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "out"), {"i": np.arange(3)})
+
+
 def test_laplace5_rows_are_the_rows_of_laplace5():
     g = 7
     m, rp, ci, v = entry.laplace5(g)

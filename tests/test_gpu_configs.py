@@ -202,7 +202,7 @@ def test_bench_two_ranks_gloo_one_gpu(tmp_path):
     with their efficiency T1 / (N TN), the A broadcast, the C all-gather and the parity verdicts."""
     rec = str(tmp_path / "legs.json")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "5",
            "--warmup", "2", "--grid", "512", "--mm-grid", "200", "--mm-cols", "64", "--shard-grid", "301", "--bell-nodes", "6", "--legs",
            "csrmm_sharded,spmv_row_sharded,sp2m_row_sharded", "--sp2m-grid", "150", "--record", rec]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4"), capture_output=True,
@@ -230,7 +230,7 @@ def test_bench_one_rank_under_the_launcher_with_the_nccl_backend(tmp_path):
     RCCL version), the collective legs run (their exchanges are identities at world 1) and return the reference's bits."""
     rec = str(tmp_path / "legs.json")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2",
            "--grid", "512", "--mm-grid", "200", "--mm-cols", "64", "--shard-grid", "301", "--bell-nodes", "6", "--legs",
            "csrmm_sharded,spmv_row_sharded,sp2m_row_sharded", "--sp2m-grid", "150", "--record", rec]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4"), capture_output=True,
@@ -286,7 +286,7 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
     as a child process, relays rank 0's record as its own last line and exits with the child's code."""
     rec = str(tmp_path / "legs.json")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2",
                         "--grid", "512", "--mm-grid", "200", "--mm-cols", "64", "--shard-grid", "301", "--bell-nodes", "6", "--legs",
                         "csrmm_sharded,spmv_row_sharded", "--record", rec], cwd=ROOT, env=dict(env, OMP_NUM_THREADS="4"),
                        capture_output=True, text=True, timeout=900)
@@ -294,7 +294,7 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
     short, res = _bench_record(r.stdout, rec)
     _check_two_rank_record(short, res, own_rows=False)
     # the row-sharded SpMV leg as the multi-GPU run takes it: every rank builds ITS rows, no rank holds the whole matrix
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2",
                         "--grid", "512", "--shard-grid", "301", "--shard-own-rows", "--legs", "spmv_row_sharded", "--record", rec],
                        cwd=ROOT, env=dict(env, OMP_NUM_THREADS="4"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, "rc=%d\nstdout:\n%s\nstderr:\n%s" % (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
@@ -315,7 +315,7 @@ def test_bench_single_process_small_legs(tmp_path):
     """`python bench.py` with every leg on small inputs: the short record as the last line, and a full report whose legs all
     carry a roofline object and a bit-exact verdict (the driver-timed run uses the full sizes)."""
     rec = str(tmp_path / "legs.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--grid", "512",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--grid", "512",
                         "--mm-grid", "200", "--mm-cols", "64", "--shard-grid", "300", "--bell-nodes", "6", "--small", "--cpu-seconds", "0.5",
                         "--record", rec], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -992,3 +992,50 @@ def _super_group_checks(which, m, rp, ci, v, rng):
     torch.cuda.synchronize()
     ref = _col_reference(1.0, 0, v2, ci, rp, m, m, Br, n, n, 0.0, np.zeros(m * n), n)
     assert np.array_equal(Cd.cpu().numpy().reshape(m, n), ref)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline alone (K timed steps, no back-to-back
+    region, no legs, no CPU baseline, no parity run, no report file), and DIR/y.npy is what the last timed step returned --
+    the oracle's product of the same inputs, bit for bit."""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--grid", "512",
+                        "--dump-outputs", str(out)], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    short = json.loads(r.stdout.splitlines()[-1])
+    assert len(r.stdout.splitlines()[-1]) <= bench.COMPACT_LIMIT
+    assert short["steps"] == 7 and short["warmup"] == 2 and short["unit"] == "GFLOP/s" and short["dtype"] == "f64"
+    assert short["higher_is_better"] is True and short["value"] > 0 and short["ms_per_step"] > 0
+    assert abs(short["roofline"]["kernel_ms"] - short["ms_per_step"]) < 2e-6
+    assert short["cpu_baseline"] is None and short["parity"] is None and short["legs"] == {}
+    assert "value_back_to_back" not in short and "full_report" not in short
+    assert sorted(os.listdir(out)) == ["y.npy"]
+    y = np.load(out / "y.npy")
+    m, rp, ci, v = laplace5(512)
+    assert y.dtype == np.float64 and y.shape == (m,)
+    so, yref = oracle.dcsrmv(-1, 0, 1.0, m, len(v), v, ci, rp, np.sin(0.01 * np.arange(m)), 0.0, np.zeros(m))
+    assert so == 0 and np.array_equal(y, yref)
+
+
+def test_bench_steps_beyond_the_event_ring(tmp_path):
+    """--steps sets the number of timed steps whatever it is: 32,773 cold steps need 65,546 events, more than the library's ring of
+    65,536 holds, so bench.py drains it every LAP_CHUNK steps.  Both timed regions (cold and back to back) keep one lap per step."""
+    steps = 2 * bench.LAP_CHUNK + 5
+    rec = str(tmp_path / "legs.json")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--legs", "none", "--steps", str(steps), "--warmup", "2",
+                        "--grid", "256", "--record", rec], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    short, res = _bench_record(r.stdout, rec)
+    assert short["steps"] == steps and short["ms_per_step"] > 0
+    assert res["stats"]["n"] == steps and res["stats_back_to_back"]["n"] == steps and res["parity"]["bit_exact"] is True
+
+
+def test_bench_dump_sample_gathers_the_named_rows(monkeypatch):
+    """The sampled branch of --dump-outputs (taken by the default 4096 grid): the device gather returns y at dump_rows(m)."""
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    m = 5003
+    yh = np.random.default_rng(5).uniform(-1, 1, m)
+    rows = bench.dump_rows(m)
+    got = bench.sample_y(torch, dev(yh))
+    assert len(rows) == 1000 and got.dtype == np.float64 and np.array_equal(got, yh[rows])
+    assert np.array_equal(bench.sample_y(torch, dev(yh[:999])), yh[:999])

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-csrmv_xcd}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 PY=/usr/bin/python3
-ARGS="--steps 20 --warmup 3 --cold-only --legs dcsrmv_csr_adaptive --record ''"
+ARGS="--full --steps 20 --warmup 3 --cold-only --legs dcsrmv_csr_adaptive --record ''"
 for ord in 0 1; do
   export AOCLSPARSE_MI355_SPMV_XCD_ORDER=$ord
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t$ord -o x -- $PY $R/bench.py $ARGS > /dev/null 2> $OUT/t$ord.err
