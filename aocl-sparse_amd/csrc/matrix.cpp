@@ -1196,29 +1196,24 @@ aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A)
     if(!A)
         return aoclsparse_status_invalid_pointer;
     std::unique_lock<std::shared_mutex> w(A->guard);
-    for(auto &r : A->replicas) // the replicas on other devices mirror the same arrays: rebuilt on the next multi-device call
-        if(r)
-            aoclsparse_destroy(&r);
-    A->replicas_cloned = 0;
-    A->dev_user.valid = A->dev_trans.valid = false;
-    A->plan_user.valid = A->plan_trans.valid = false;
-    A->plan_user.sell.valid = A->plan_user.sell.tried = false;
-    A->plan_trans.sell.valid = A->plan_trans.sell.tried = false;
-    A->plan_user.merge.valid = A->plan_user.merge.tried = false;
-    A->plan_trans.merge.valid = A->plan_trans.merge.tried = false;
-    A->plan_user.mm.valid = A->plan_user.mm.tried = false;
-    A->plan_trans.mm.valid = A->plan_trans.mm.tried = false;
-    A->plan_user.mm.pairs = A->plan_user.mm.pairs_tried = false;
-    A->plan_trans.mm.pairs = A->plan_trans.mm.pairs_tried = false;
-    A->plan_user.bell.valid = A->plan_user.bell.tried = false;
-    A->plan_trans.bell.valid = A->plan_trans.bell.tried = false;
-    A->plan_user.mm.win = A->plan_user.mm.win_tried = false;
-    A->plan_trans.mm.win = A->plan_trans.mm.win_tried = false;
-    A->plan_user.mm.row_runs = A->plan_user.mm.runs_tried = false;
-    A->plan_trans.mm.row_runs = A->plan_trans.mm.runs_tried = false;
-    for(auto &p : A->trsv_plan)
-        p.valid = p.rows_valid = false, p.nlevels = -1, p.blk.valid = p.blk.tried = false, p.blk.chunk.valid = p.blk.chunk.tried = false;
-    A->trans.reset();
+    if(A->csc_ptr) // a handle created from CSC aliases the caller's CSC arrays: its own CSR is a copy of them, refreshed first
+    {
+        aoclsparse_status st = csc_refresh_csr(A);
+        if(st != aoclsparse_status_success)
+            return st;
+    }
+    // every copy of the values (the one list: drop_derived_state) ...
+    drop_derived_state(A);
+    // ... and the structural plans of the device CSR, which a value change alone leaves valid
+    for(SpmvPlan *p : {&A->plan_user, &A->plan_trans})
+    {
+        p->valid       = false; // row blocks
+        p->merge.valid = p->merge.tried = false;
+        p->mm.valid = p->mm.tried = false; // row groups
+        p->mm.pairs = p->mm.pairs_tried = false;
+        p->mm.win = p->mm.win_tried = false;
+        p->mm.row_runs = p->mm.runs_tried = false;
+    }
     return aoclsparse_status_success;
 }
 
@@ -1229,29 +1224,31 @@ aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A)
 // deletes every derived copy.  Same here, device mirrors included: they are rebuilt lazily.
 namespace mi355
 {
+// THE list of what holds A's values besides the caller's arrays (?set_value, ?update_values, aoclsparse_order_mat, the CSC refresh
+// and aoclsparse_mi355_invalidate all come here).  A copy added to the handle that holds values is dropped here, nowhere else.
 void drop_derived_state(aoclsparse_matrix A)
 {
-    if(A->opt != &A->user)
+    if(A->opt != &A->user) // the clean copy of unsorted arrays / arrays that miss a diagonal entry
     {
         A->opt_copy.reset();
         A->opt       = nullptr;
         A->optimized = false;
     }
-    A->trans.reset();
-    A->derived.clear();
+    A->trans.reset(); // host transpose
+    A->derived.clear(); // symmetric / triangular expansions (host + device + their plans)
     for(auto &r : A->replicas) // multi-device replicas hold device copies of the old values
         if(r)
             aoclsparse_destroy(&r);
     A->replicas_cloned = 0;
-    A->dev_user.valid = A->dev_trans.valid = false; // row-block plans stay valid: structure is unchanged
+    A->dev_user.valid = A->dev_trans.valid = false; // device CSRs; row-block plans stay valid: structure is unchanged
     A->plan_user.sell.valid = A->plan_user.sell.tried = false; // the SELL copies hold values: rebuilt on optimize
     A->plan_trans.sell.valid = A->plan_trans.sell.tried = false;
     // ... and so does the blocked-ELL copy of csrmm (round 6: it was left standing, and a product after aoclsparse_?set_value /
     // ?update_values on a block-dense handle used the OLD values -- found by tests/test_gpu_r6.py)
     A->plan_user.bell.valid = A->plan_user.bell.tried = false;
     A->plan_trans.bell.valid = A->plan_trans.bell.tried = false;
-    A->dev_diag.release();
-    for(auto &p : A->trsv_plan)
+    A->dev_diag.release(); // diagonal of the clean CSR (non-unit solves, SymGS scaling)
+    for(auto &p : A->trsv_plan) // level-ordered triangles: row, block and chunk plans
         p.valid = p.rows_valid = false, p.nlevels = -1, p.blk.valid = p.blk.tried = false, p.blk.chunk.valid = p.blk.chunk.tried = false;
 }
 } // namespace mi355

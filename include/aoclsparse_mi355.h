@@ -274,7 +274,14 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_trsv_status(aoclsparse_matrix A);
  * the `kid` of aoclsparse_?trsv_kid selects the arithmetic (0: ref_trsv_*; 1/2: 256-bit KT kernels; 3: 512-bit KT kernels), as
  * in the reference (library/src/level2/aoclsparse_trsv.cpp:321-353).  Process-wide; for tests and measurements. */
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_set_trsv_schedule(aoclsparse_int schedule);
-/* drop every device-side copy/plan of the handle (call after mutating the aliased arrays) */
+/* Call after writing into the VALUES of the arrays the handle aliases (on a handle created with aoclsparse_create_?csc: the
+ * caller's CSC arrays, from which the handle's own CSR is refreshed first).  Drops every copy the handle holds of them -- the clean
+ * copy of unsorted / diagonal-less arrays, the host transpose, the derived symmetric / triangular matrices, the device CSRs,
+ * the SELL-64 and blocked-ELL copies, the TRSV plans (row, block and chunk), the device diagonal and the multi-device replicas:
+ * the list ?set_value / ?update_values drop -- and the structural plans of the device CSR (row blocks, merge-path tiles, csrmm
+ * row groups, row runs, row pairs and windows).  Each is rebuilt from the arrays on first use.  The ILU(0) factor is kept, as
+ * after ?update_values (it is computed once, from the values seen at the first factorisation).  The caller's ptr / ind arrays
+ * must be unchanged. */
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A);
 /* free the library's staging buffers in HBM (process-wide: the primary device's and those of every device a multi-device call has
  * used; each device's stream is synchronised first): the grow-only scratch that host-pointer calls (?csrmv, ?mv, ?trsv, the ELL
