@@ -27,6 +27,7 @@ STAGE_NNZ_COUNT, STAGE_FINALIZE, STAGE_FULL = 0, 1, 2
 MEM_MINIMAL, MEM_UNRESTRICTED = 0, 1
 PTR_AUTO, PTR_HOST, PTR_DEVICE = 0, 1, 2
 OPTION_SPMV_KERNEL, OPTION_SELL, OPTION_SPMV_STRICT, OPTION_ALTERNATE_SWEEPS, OPTION_TRSV_CHUNKS = 0, 1, 2, 3, 4  # aoclsparse_mi355_set_option
+OPTION_SELL_VALUES = 5
 
 STATUS = {
     0: "success", 1: "not_implemented", 2: "invalid_pointer", 3: "invalid_size", 4: "internal_error",
@@ -384,6 +385,7 @@ SIGNATURES = {
     "aoclsparse_mi355_scsrmm_shard": (c_int, [c_int, c_float, _P, _P, c_int, _P, _I, _I, c_float, _P, _I, _I, _I]),
     "aoclsparse_mi355_export_diag": (c_int, [_P, POINTER(_P), POINTER(_P), POINTER(_I)]),
     "aoclsparse_mi355_get_spmv_info": (c_int, [_P, c_int, POINTER(SpmvInfo)]),
+    "aoclsparse_mi355_get_sell_values": (c_int, [_P, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_levels": (c_int, [_P, c_int, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_info": (c_int, [_P, c_int, c_int, POINTER(TrsvInfo)]),
     "aoclsparse_mi355_trsv_status": (c_int, [_P]),
@@ -539,6 +541,12 @@ class Matrix:
         st = lib().aoclsparse_mi355_get_spmv_info(self.h, op, byref(info))
         assert st == 0
         return info
+
+    def sell_values(self, op=OP_NONE):
+        """entries of the value table of the SELL-64 copy of op(A) (0: the cells hold the values, or no copy)"""
+        n = _I(-1)
+        assert lib().aoclsparse_mi355_get_sell_values(self.h, op, byref(n)) == 0
+        return n.value
 
     def trsv_info(self, fill, op=OP_NONE):
         info = TrsvInfo()

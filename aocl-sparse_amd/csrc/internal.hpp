@@ -274,6 +274,10 @@ struct SellPlan
     bool           shared = false;
     long long      ccells = 0;
     DeviceBuffer   cptr, lead;
+    // value table (sell_kernels.hip): ntab > 0 -> vidx holds one byte per cell (same cell order and offsets as val would) indexing
+    // vtab, ntab values sorted by bit pattern, and val is not allocated; ntab = 0 -> the values are in val
+    int            ntab = 0;
+    DeviceBuffer   vtab, vidx;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
@@ -807,7 +811,13 @@ template <typename T>
 aoclsparse_status launch_sell_fill(hipStream_t s, int pack, aoclsparse_int m, int base, const aoclsparse_int *row_ptr,
                                    const aoclsparse_int *col, const T *val, aoclsparse_int nslices,
                                    const long long *slice_ptr, T *sval, aoclsparse_int *scol, aoclsparse_int *rowlen,
-                                   const long long *cptr = nullptr, const unsigned short *lead = nullptr);
+                                   const long long *cptr = nullptr, const unsigned short *lead = nullptr,
+                                   unsigned char *sidx = nullptr, const T *vtab = nullptr, int ntab = 0);
+// (sidx != nullptr: the cells get one-byte indices into vtab, ntab entries sorted by bit pattern, instead of the values; sval unused)
+// distinct bit patterns of n values of vsize (4 / 8) bytes on the device: *ntab of them, ascending, in table (room for
+// SELL_VTAB_MAX words); *ntab = 0 when there are more than SELL_VTAB_MAX
+constexpr int     SELL_VTAB_MAX = 256;
+aoclsparse_status sell_value_table(hipStream_t s, size_t vsize, long long n, const void *val, unsigned long long *table, int *ntab);
 template <typename R>
 aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha, aoclsparse_int m, aoclsparse_int nslices,
                                         const long long *slice_ptr, const cplx<R> *sval, const aoclsparse_int *scol,
@@ -820,7 +830,9 @@ aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoc
                                 const long long *slice_ptr, const T *sval, const aoclsparse_int *scol,
                                 const aoclsparse_int *rowlen, const T *x, T beta, T *y, const long long *cptr = nullptr,
                                 const unsigned short *lead = nullptr,
-                                aoclsparse_int max_width = 0, int rev = 0);
+                                aoclsparse_int max_width = 0, int rev = 0, const unsigned char *sidx = nullptr,
+                                const T *vtab = nullptr);
+// (vtab != nullptr: the cells are sidx, one-byte indices into vtab; sval is not read)
 // BLKCSR (blk_kernels.hip): value offset of every block (three small launches: per-chunk popcount scan, scan of
 // the chunk totals in part[], add), then the product
 constexpr int     BLK_PART_SHIFT = 10;

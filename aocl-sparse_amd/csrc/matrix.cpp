@@ -672,6 +672,8 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     if(sp.valid || sp.tried)
         return aoclsparse_status_success;
     sp.tried = true;
+    sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
+    sp.vtab.release(), sp.vidx.release();
     const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
         return aoclsparse_status_success;
@@ -745,7 +747,42 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         else
             sp.lead.release();
     }
-    if(st == aoclsparse_status_success)
+    // Value table: at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil holds two) -> one byte per cell instead
+    // of 4 / 8 (sell_kernels.hip).  Real types only; the same size gate as the shared lists (a matrix that lives in the caches gains
+    // nothing); aoclsparse_mi355_set_option(sell_values, 0 / 1): never / whatever the size.  One pass over the device values.
+    const int vmode = plan_option(aoclsparse_mi355_option_sell_values); // -1 automatic (default), 0 never, 1 whatever the size
+    if(st == aoclsparse_status_success && !complex_values && (vsize == sizeof(double) || vsize == sizeof(float)) && vmode != 0
+       && (vmode == 1 || d.nnz >= (1 << 17)))
+    {
+        unsigned long long bits[SELL_VTAB_MAX];
+        int                ntab = 0;
+        st = sell_value_table(rt.stream(), vsize, d.nnz, d.val.ptr, bits, &ntab);
+        if(st == aoclsparse_status_success && ntab > 0)
+        {
+            unsigned char tab[sizeof(double) * SELL_VTAB_MAX];
+            for(int k = 0; k < ntab; k++) // (the low vsize bytes of each word: the pattern of a float or a double)
+            {
+                if(vsize == sizeof(float))
+                {
+                    const unsigned u = (unsigned)bits[k];
+                    std::memcpy(tab + sizeof(float) * k, &u, sizeof(float));
+                }
+                else
+                    std::memcpy(tab + sizeof(double) * k, &bits[k], sizeof(double));
+            }
+            st = sp.vtab.upload(tab, vsize * (size_t)ntab, rt.stream());
+            if(st == aoclsparse_status_success)
+                st = sp.vidx.alloc((size_t)std::max<long long>(cells, 4));
+            if(st == aoclsparse_status_success)
+            {
+                sp.ntab = ntab;
+                sp.val.release();
+            }
+        }
+        if(PhaseTimer::on())
+            std::fprintf(stderr, "[mi355 timing] sell: %d distinct value patterns%s\n", ntab, ntab ? "" : " (more than 256, or none)");
+    }
+    if(st == aoclsparse_status_success && sp.ntab == 0)
         st = sp.val.alloc(vsize * (size_t)std::max<long long>(cells, 1));
     if(st == aoclsparse_status_success)
         st = sp.col.alloc(sizeof(aoclsparse_int) * (size_t)std::max<long long>(sp.ccells, 1));
@@ -762,11 +799,13 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     else if(vsize == sizeof(float))
         st = launch_sell_fill<float>(rt.stream(), pack, m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(),
                                      d.val.as<float>(), nslices, sp.slice_ptr.as<long long>(), sp.val.as<float>(),
-                                     sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld);
+                                     sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld,
+                                     sp.ntab ? sp.vidx.as<unsigned char>() : nullptr, sp.vtab.as<float>(), sp.ntab);
     else
         st = launch_sell_fill<double>(rt.stream(), pack, m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(),
                                       d.val.as<double>(), nslices, sp.slice_ptr.as<long long>(), sp.val.as<double>(),
-                                      sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld);
+                                      sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld,
+                                      sp.ntab ? sp.vidx.as<unsigned char>() : nullptr, sp.vtab.as<double>(), sp.ntab);
     if(st != aoclsparse_status_success)
         return st;
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr (host) are read by the uploads until here

@@ -17,7 +17,9 @@
 // gathers; cells <= 1.15 nnz or the handle stays on the CSR-Adaptive kernel (matrix.cpp: build_sell).
 #include "internal.hpp"
 
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -120,6 +122,165 @@ __device__ __forceinline__ long long cell_of(int p, int lane)
     return PACK == 1 ? (long long)p * 64 + lane : (long long)(p >> 2) * 256 + lane * 4 + (p & 3);
 }
 
+// ---- value tables (SELL-64 with one byte per cell: an index into <= 256 distinct value bit patterns) ---------------------
+// A matrix whose values take at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil: two) stores one byte
+// per cell and a table sorted by ascending bit pattern; the kernels read table[index], i.e. the very bits of the value, so every
+// summation order gives the same results as with the values stored in the cells (CSR-VI, Kourtis, Goumas and Koziris, CF 2008).
+// Bit patterns, not values: -0.0 and +0.0 are two entries, NaN payloads are kept.
+template <typename T>
+using vbits_t = std::conditional_t<sizeof(T) == 8, unsigned long long, unsigned>;
+
+// the value cells as the kernels read them: values, or (IDX) table indices
+template <typename T, bool IDX>
+struct SellCell
+{
+    using src = T; // stored
+    using raw = T; // loaded
+};
+template <typename T>
+struct SellCell<T, true>
+{
+    using src = unsigned char;
+    using raw = int;
+};
+template <bool IDX, typename T, typename R>
+__device__ __forceinline__ T cell_value(R raw, const T *__restrict__ vtab)
+{
+    if constexpr(IDX)
+        return vtab[raw];
+    else
+        return raw;
+}
+
+// index of v in the sorted table (v is in it: the table holds every pattern of the matrix)
+template <typename T>
+__device__ __forceinline__ unsigned char vtab_index(T v, const T *__restrict__ vtab, int ntab)
+{
+    using U     = vbits_t<T>;
+    const U key = __builtin_bit_cast(U, v);
+    int     lo = 0, hi = ntab - 1;
+    while(lo < hi)
+    {
+        const int mid = (lo + hi) >> 1;
+        if(__builtin_bit_cast(U, vtab[mid]) < key)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return (unsigned char)lo;
+}
+
+// writes cell o: the value, or (sidx) its table index; padding cells hold 0 / index 0 (their column is -1: never used)
+template <typename T>
+__device__ __forceinline__ void fill_cell(long long o, bool in, const T *__restrict__ vp, T *__restrict__ sval,
+                                          unsigned char *__restrict__ sidx, const T *__restrict__ vtab, int ntab)
+{
+    if constexpr(std::is_floating_point_v<T>)
+    {
+        if(sidx)
+        {
+            sidx[o] = in ? vtab_index(*vp, vtab, ntab) : (unsigned char)0;
+            return;
+        }
+    }
+    sval[o] = in ? *vp : T(0);
+}
+
+// Distinct bit patterns of n values, on the device: every workgroup collects what it sees in an LDS hash set, then merges it
+// into the global set (VT_SLOTS entries, VT_EMPTY = free).  state[0] = patterns in the global set, state[1] = 1 once more than
+// SELL_VTAB_MAX patterns were seen (everyone stops early), state[2] = 1 if the pattern VT_EMPTY itself (a double NaN) occurs.
+// A set that fills up also means "more than SELL_VTAB_MAX": a set has 4 x the slots that can be taken before a stop is seen.
+constexpr int                VT_LDS_SLOTS  = 1024;
+constexpr int                VT_SLOTS      = 4096;
+constexpr unsigned long long VT_EMPTY      = ~0ull;
+
+__device__ __forceinline__ unsigned vt_hash(unsigned long long k)
+{
+    k ^= k >> 33; // (murmur3's finaliser: the patterns of simple doubles differ in their top bits only)
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return (unsigned)k;
+}
+
+// 1: k was inserted, 0: it was there already, -1: the set is full
+__device__ __forceinline__ int vt_insert(unsigned long long *set, int slots, unsigned long long k)
+{
+    unsigned h = vt_hash(k) & (unsigned)(slots - 1);
+    for(int probe = 0; probe < slots; probe++)
+    {
+        unsigned long long cur = __hip_atomic_load(set + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if(cur == k)
+            return 0;
+        if(cur == VT_EMPTY)
+        {
+            cur = atomicCAS(set + h, VT_EMPTY, k);
+            if(cur == VT_EMPTY)
+                return 1;
+            if(cur == k)
+                return 0;
+        }
+        h = (h + 1) & (unsigned)(slots - 1);
+    }
+    return -1;
+}
+
+template <typename U>
+__global__ __launch_bounds__(256) void sell_vtab_count_kernel(long long n, const U *__restrict__ val, unsigned long long *__restrict__ set,
+                                                              unsigned *__restrict__ state)
+{
+    constexpr int                 UNR = 4;
+    __shared__ unsigned long long lset[VT_LDS_SLOTS];
+    __shared__ int                lcount, lstop, lempty;
+    for(int k = threadIdx.x; k < VT_LDS_SLOTS; k += blockDim.x)
+        lset[k] = VT_EMPTY;
+    if(threadIdx.x == 0)
+        lcount = 0, lstop = 0, lempty = 0;
+    __syncthreads();
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for(long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += UNR * stride)
+    {
+        if(__hip_atomic_load(&lstop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+           || __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            break;
+        unsigned long long k[UNR];
+#pragma unroll
+        for(int u = 0; u < UNR; u++)
+            k[u] = (unsigned long long)val[i0 + u * stride < n ? i0 + u * stride : i0];
+#pragma unroll
+        for(int u = 0; u < UNR; u++)
+        {
+            if(k[u] == VT_EMPTY)
+            {
+                lempty = 1;
+                continue;
+            }
+            const int r = vt_insert(lset, VT_LDS_SLOTS, k[u]);
+            if(r < 0 || (r > 0 && atomicAdd(&lcount, 1) + 1 > SELL_VTAB_MAX))
+                lstop = 1;
+        }
+    }
+    __syncthreads();
+    if(lstop)
+    {
+        if(threadIdx.x == 0)
+            atomicOr(state + 1, 1u);
+        return;
+    }
+    if(threadIdx.x == 0 && lempty)
+        atomicOr(state + 2, 1u);
+    for(int k = threadIdx.x; k < VT_LDS_SLOTS; k += blockDim.x)
+    {
+        const unsigned long long key = lset[k];
+        if(key == VT_EMPTY || __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            continue;
+        const int r = vt_insert(set, VT_SLOTS, key);
+        if(r < 0 || (r > 0 && atomicAdd(state, 1u) + 1u > (unsigned)SELL_VTAB_MAX))
+            atomicOr(state + 1, 1u);
+    }
+}
+
 template <typename T, int PACK>
 __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int base,
                                                         const aoclsparse_int *__restrict__ row_ptr,
@@ -127,7 +288,8 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
                                                         const T *__restrict__ val, aoclsparse_int nslices,
                                                         const long long *__restrict__ slice_ptr,
                                                         T *__restrict__ sval, aoclsparse_int *__restrict__ scol,
-                                                        aoclsparse_int *__restrict__ rowlen)
+                                                        aoclsparse_int *__restrict__ rowlen, unsigned char *__restrict__ sidx,
+                                                        const T *__restrict__ vtab, int ntab)
 {
     const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -147,7 +309,7 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
     {
         const long long o  = o0 + cell_of<PACK>(p, lane);
         const bool      in = p < len;
-        sval[o]            = in ? val[b + p] : T(0);
+        fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
         scol[o]            = in ? col[b + p] - base : -1;
     }
 }
@@ -221,7 +383,8 @@ __global__ __launch_bounds__(256) void sell_fill_shared_kernel(aoclsparse_int m,
                                                                const long long *__restrict__ cptr,
                                                                const unsigned short *__restrict__ follow, T *__restrict__ sval,
                                                                aoclsparse_int *__restrict__ scol,
-                                                               aoclsparse_int *__restrict__ rowlen)
+                                                               aoclsparse_int *__restrict__ rowlen, unsigned char *__restrict__ sidx,
+                                                               const T *__restrict__ vtab, int ntab)
 {
     const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -244,7 +407,7 @@ __global__ __launch_bounds__(256) void sell_fill_shared_kernel(aoclsparse_int m,
     for(int p = 0; p < w; p++)
     {
         const bool in = p < len;
-        sval[o0 + cell_of<PACK>(p, lane)] = in ? val[b + p] : T(0);
+        fill_cell(o0 + cell_of<PACK>(p, lane), in, val + b + p, sval, sidx, vtab, ntab);
         if(leader)
             scol[c0 + (PACK == 1 ? (long long)p * nl + k : (long long)(p >> 2) * 4 * nl + 4 * k + (p & 3))] = in ? col[b + p] - base : -1;
     }
@@ -266,11 +429,18 @@ __device__ __forceinline__ void load4(const aoclsparse_int *p, int (&o)[4])
     const int4 a = *reinterpret_cast<const int4 *>(p);
     o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w;
 }
+// (table indices: four bytes of one lane = one dword, 256 B per wavefront)
+__device__ __forceinline__ void load4(const unsigned char *p, int (&o)[4])
+{
+    const unsigned a = *reinterpret_cast<const unsigned *>(p);
+    o[0] = (int)(a & 0xffu), o[1] = (int)((a >> 8) & 0xffu), o[2] = (int)((a >> 16) & 0xffu), o[3] = (int)(a >> 24);
+}
 
-// loads the G cells p0 .. p0+G-1 of this lane (wave-uniform guards against the slice width w)
+// loads the G cells p0 .. p0+G-1 of this lane (wave-uniform guards against the slice width w): stored S, loaded as R
+// (values, or table indices)
 // cs = lanes per column row: 64, or the slice's number of leaders when the column lists are shared
-template <typename T, int PACK, int G>
-__device__ __forceinline__ void load_step(const T *v, const aoclsparse_int *c, int p0, int w, T (&vv)[G], int (&cc)[G],
+template <typename S, typename R, int PACK, int G>
+__device__ __forceinline__ void load_step(const S *v, const aoclsparse_int *c, int p0, int w, R (&vv)[G], int (&cc)[G],
                                           int cs = 64)
 {
     if constexpr(PACK == 1)
@@ -279,7 +449,7 @@ __device__ __forceinline__ void load_step(const T *v, const aoclsparse_int *c, i
         for(int q = 0; q < G; q++)
         {
             const bool ok = p0 + q < w;
-            vv[q]         = ok ? v[(p0 + q) * 64] : T(0);
+            vv[q]         = ok ? (R)v[(p0 + q) * 64] : R(0);
             cc[q]         = ok ? c[(p0 + q) * cs] : -1;
         }
     }
@@ -288,7 +458,7 @@ __device__ __forceinline__ void load_step(const T *v, const aoclsparse_int *c, i
 #pragma unroll
         for(int k = 0; k < G / 4; k++)
         {
-            T   tv[4] = {T(0), T(0), T(0), T(0)};
+            R   tv[4] = {R(0), R(0), R(0), R(0)};
             int tc[4] = {-1, -1, -1, -1};
             if(p0 + 4 * k < w) // w is a multiple of 4: the pack is whole or absent
             {
@@ -304,16 +474,20 @@ __device__ __forceinline__ void load_step(const T *v, const aoclsparse_int *c, i
 }
 
 // WAVES slices per workgroup (1 for small matrices so that every slice gets its own CU)
-template <typename T, int ORDER, int WAVES, int PACK, bool SHARED = false, bool CONJ = false>
+// IDX: sval holds one byte per cell, an index into vtab (the value table); otherwise the values and vtab is unused
+template <typename T, int ORDER, int WAVES, int PACK, bool SHARED = false, bool CONJ = false, bool IDX = false>
 __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, aoclsparse_int nslices,
                                                              const long long *__restrict__ slice_ptr,
-                                                             const T *__restrict__ sval,
+                                                             const typename SellCell<T, IDX>::src *__restrict__ sval,
                                                              const aoclsparse_int *__restrict__ scol,
                                                              const aoclsparse_int *__restrict__ rowlen, T alpha,
                                                              const T *__restrict__ x, T beta, T *__restrict__ y,
                                                              bool nt, const long long *__restrict__ cptr = nullptr,
-                                                             const unsigned short *__restrict__ follow = nullptr, int rev = 0)
+                                                             const unsigned short *__restrict__ follow = nullptr, int rev = 0,
+                                                             const T *__restrict__ vtab = nullptr)
 {
+    using S = typename SellCell<T, IDX>::src;
+    using R = typename SellCell<T, IDX>::raw;
     // rev: the slices in descending order.  Consecutive products of a handle ALTERNATE the direction (SellPlan::products): the
     // end of the matrix, which the previous product left in the 256 MB Infinity Cache, is where this one starts -- round 5,
     // profiles/r5/sell_placement.txt: shell-like 90-101 -> 81-87 us, the headline 0.178 -> 0.165 ms.  Same slices, same bits.
@@ -324,7 +498,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         return;
     const long long       o0 = slice_ptr[s];
     const int             w  = (int)((slice_ptr[s + 1] - o0) >> 6);
-    const T              *v  = sval + o0 + lane * PACK;
+    const S              *v  = sval + o0 + lane * PACK;
     const int             i  = s * 64 + lane;
     const aoclsparse_int *c  = scol + o0 + lane * PACK;
     int                   cs = 64, dl = 0;
@@ -358,13 +532,14 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         auto batch = [&](auto wtag) {
             constexpr int W = decltype(wtag)::value;
             T             vv[W], xx[W];
+            R             rr[W];
             int           cc[W];
 #pragma unroll
             for(int q = 0; q < W; q++)
-                vv[q] = s_cj<CONJ>(v[q * 64]), cc[q] = c[q * cs];
+                rr[q] = v[q * 64], cc[q] = c[q * cs];
 #pragma unroll
             for(int q = 0; q < W; q++)
-                xx[q] = x[cc[q] >= 0 ? cc[q] + dl : 0];
+                xx[q] = x[cc[q] >= 0 ? cc[q] + dl : 0], vv[q] = s_cj<CONJ>(cell_value<IDX>(rr[q], vtab));
 #pragma unroll
             for(int q = 0; q < W; q++)
                 r = cc[q] >= 0 ? s_fma(vv[q], xx[q], r) : r;
@@ -380,12 +555,13 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         }
         for(; p + 4 <= w; p += 4)
         {
-            const T   v0 = s_cj<CONJ>(v[(p + 0) * 64]), v1 = s_cj<CONJ>(v[(p + 1) * 64]), v2 = s_cj<CONJ>(v[(p + 2) * 64]),
-                      v3 = s_cj<CONJ>(v[(p + 3) * 64]);
+            const R   r0 = v[(p + 0) * 64], r1 = v[(p + 1) * 64], r2 = v[(p + 2) * 64], r3 = v[(p + 3) * 64];
             const int c0 = c[(p + 0) * cs], c1 = c[(p + 1) * cs], c2 = c[(p + 2) * cs], c3 = c[(p + 3) * cs];
             // (a padding cell, -1, is never used, but its gather must stay inside x: index 0)
             const T   x0 = x[c0 >= 0 ? c0 + dl : 0], x1 = x[c1 >= 0 ? c1 + dl : 0], x2 = x[c2 >= 0 ? c2 + dl : 0],
                       x3 = x[c3 >= 0 ? c3 + dl : 0];
+            const T   v0 = s_cj<CONJ>(cell_value<IDX>(r0, vtab)), v1 = s_cj<CONJ>(cell_value<IDX>(r1, vtab)),
+                      v2 = s_cj<CONJ>(cell_value<IDX>(r2, vtab)), v3 = s_cj<CONJ>(cell_value<IDX>(r3, vtab));
             r = c0 >= 0 ? s_fma(v0, x0, r) : r;
             r = c1 >= 0 ? s_fma(v1, x1, r) : r;
             r = c2 >= 0 ? s_fma(v2, x2, r) : r;
@@ -393,9 +569,9 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         }
         for(; p < w; p++)
         {
-            const T   v0 = s_cj<CONJ>(v[p * 64]);
+            const R   r0 = v[p * 64];
             const int c0 = c[p * cs];
-            const T   x0 = x[c0 >= 0 ? c0 + dl : 0];
+            const T   x0 = x[c0 >= 0 ? c0 + dl : 0], v0 = s_cj<CONJ>(cell_value<IDX>(r0, vtab));
             r = c0 >= 0 ? s_fma(v0, x0, r) : r;
         }
     }
@@ -412,21 +588,23 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         for(int q = 0; q < G; q++)
             l[q] = T(0);
         bool reduced = false;
-        T    vn[G];
+        R    vn[G];
         int  cn[G];
-        load_step<T, PACK, G>(v, c, 0, w, vn, cn, cs);
+        load_step<S, R, PACK, G>(v, c, 0, w, vn, cn, cs);
         for(int p0 = 0; p0 < w; p0 += G)
         {
             T   vv[G], xx[G];
+            R   vr[G];
             int cc[G];
 #pragma unroll
             for(int q = 0; q < G; q++)
-                vv[q] = vn[q], cc[q] = cn[q];
+                vr[q] = vn[q], cc[q] = cn[q];
             if(p0 + G < w)
-                load_step<T, PACK, G>(v, c, p0 + G, w, vn, cn, cs);
+                load_step<S, R, PACK, G>(v, c, p0 + G, w, vn, cn, cs);
+            // (IDX: the table reads go out with the x gathers, after the next step's lines)
 #pragma unroll
             for(int q = 0; q < G; q++)
-                xx[q] = x[cc[q] >= 0 ? cc[q] + dl : 0]; // (a padding cell, -1, is never used; its gather stays inside x)
+                xx[q] = x[cc[q] >= 0 ? cc[q] + dl : 0], vv[q] = cell_value<IDX>(vr[q], vtab); // (a padding cell, -1, is never used; its gather stays inside x)
             if constexpr(ORDER == 0)
             {
 #pragma unroll
@@ -463,15 +641,18 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
 // profiles/r3/sell_width_switch.txt): general kernel before the width switch 0.1845-0.186 ms, with it 0.1786-0.1793, this
 // kernel with 1 / 2 / 4 slices per workgroup 0.180-0.181 / 0.180-0.181 / 0.1773-0.1779; TWO or more slices per WAVEFRONT
 // (walked together, twice the bytes in flight per wave) 0.183-0.236 ms -- more registers, fewer waves, no gain.
-template <typename T, int WMAX, int WAVES, bool SHARED, int SPW = 1, bool CONJ = false>
+template <typename T, int WMAX, int WAVES, bool SHARED, int SPW = 1, bool CONJ = false, bool IDX = false>
 __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_int m, aoclsparse_int nslices,
                                                                    const long long *__restrict__ slice_ptr,
-                                                                   const T *__restrict__ sval,
+                                                                   const typename SellCell<T, IDX>::src *__restrict__ sval,
                                                                    const aoclsparse_int *__restrict__ scol, T alpha,
                                                                    const T *__restrict__ x, T beta, T *__restrict__ y, bool nt,
                                                                    const long long *__restrict__ cptr,
-                                                                   const unsigned short *__restrict__ follow, int rev = 0)
+                                                                   const unsigned short *__restrict__ follow, int rev = 0,
+                                                                   const T *__restrict__ vtab = nullptr)
 {
+    using S = typename SellCell<T, IDX>::src;
+    using R = typename SellCell<T, IDX>::raw;
     // SPW slices per wavefront, walked TOGETHER (all value / column loads of the SPW slices, then all gathers, then the chains):
     // SPW times the bytes in flight per wavefront.  Lost for double (two: 0.183-0.236 vs 0.177 ms, round 3); float moves half the
     // bytes per load instruction, and large float launches run four (round 4: sell_launch_short).
@@ -481,6 +662,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
     if(sb >= nslices)
         return;
     T   vv[SPW][WMAX], xx[SPW][WMAX];
+    R   rr[SPW][WMAX];
     int cc[SPW][WMAX], w[SPW], dl[SPW];
 #pragma unroll
     for(int u = 0; u < SPW; u++)
@@ -488,7 +670,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
         const int             s  = min(sb + u, (int)nslices - 1); // (beyond the last slice: it is walked again, nothing is stored)
         const long long       o0 = slice_ptr[s];
         const int             i  = s * 64 + lane;
-        const T              *v  = sval + o0 + lane;
+        const S              *v  = sval + o0 + lane;
         const aoclsparse_int *c  = scol + o0 + lane;
         int                   cs = 64;
         w[u]                     = (int)((slice_ptr[s + 1] - o0) >> 6);
@@ -513,7 +695,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
             for(int q = 0; q < WMAX; q++)
             {
                 const int qq = min(q, w[u] - 1); // wave-uniform
-                vv[u][q]     = s_cj<CONJ>(v[qq * 64]);
+                rr[u][q]     = v[qq * 64];
                 cc[u][q]     = c[qq * cs];
             }
         }
@@ -521,14 +703,15 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
         {
 #pragma unroll
             for(int q = 0; q < WMAX; q++)
-                vv[u][q] = T(0), cc[u][q] = -1;
+                rr[u][q] = R(0), cc[u][q] = -1;
         }
     }
+    // (IDX: the table reads, 2 KB at most and cache-resident, go out in the same batch as the x gathers)
 #pragma unroll
     for(int u = 0; u < SPW; u++)
 #pragma unroll
         for(int q = 0; q < WMAX; q++)
-            xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + dl[u] : 0];
+            xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + dl[u] : 0], vv[u][q] = s_cj<CONJ>(cell_value<IDX>(rr[u][q], vtab));
 #pragma unroll
     for(int u = 0; u < SPW; u++)
     {
@@ -544,26 +727,29 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
 
 constexpr aoclsparse_int SELL_SHORT_SPW4_SLICES = 100000;
 
-template <typename T, bool SHARED>
-bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int nslices, const long long *slice_ptr, const T *sval,
-                       const aoclsparse_int *scol, T alpha, const T *x, T beta, T *y, bool nt, const long long *cptr,
-                       const unsigned short *lead, int rev = 0)
+template <typename T, bool SHARED, bool IDX>
+bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int nslices, const long long *slice_ptr,
+                       const typename SellCell<T, IDX>::src *sval, const aoclsparse_int *scol, T alpha, const T *x, T beta, T *y,
+                       bool nt, const long long *cptr, const unsigned short *lead, int rev, const T *vtab)
 {
     constexpr int WAVES = 4;
     // float, >= 100,000 slices: four slices per wavefront (a float load instruction moves half the bytes of a double one; same box,
     // tools/history/exp_float_headline.py, 1 / 4 / 8 slices per wavefront: 4096^2 0.1013 / 0.0949 / 0.1218 ms, 3000^2 0.0512 / 0.0479 /
-    // 0.0543, 2000^2 0.0229 / 0.0235 / 0.0267 -- and no change for double, which stays at one: profiles/r4/float_headline.txt)
-    const bool      four   = sizeof(T) == 4 && nslices >= SELL_SHORT_SPW4_SLICES;
-    const long long per_wg = (long long)WAVES * (four ? 4 : 1);
+    // 0.0543, 2000^2 0.0229 / 0.0235 / 0.0267 -- and no change for double, which stays at one: profiles/r4/float_headline.txt).
+    // The same with a value table (1-byte cells; 4096^2, cold products, profiles/r7/ab_sweep.txt): double 1 / 2 / 4 slices per
+    // wavefront 0.145 / 0.144 / 0.164 ms, float 0.093 / 0.086 / 0.075 ms.
+    constexpr int   SPW_BIG = sizeof(T) == 4 ? 4 : 1;
+    const bool      big     = SPW_BIG > 1 && nslices >= SELL_SHORT_SPW4_SLICES;
+    const long long per_wg  = (long long)WAVES * (big ? SPW_BIG : 1);
     const dim3      grid((unsigned)((nslices + per_wg - 1) / per_wg)), block(64 * WAVES);
-#define MI355_SHORT(W)                                                                                                    \
-    case W:                                                                                                               \
-        if(four)                                                                                                          \
-            hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SHARED, 4>), grid, block, 0, s, m, nslices, slice_ptr, sval, \
-                               scol, alpha, x, beta, y, nt, cptr, lead, rev);                                             \
-        else                                                                                                              \
-            hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SHARED>), grid, block, 0, s, m, nslices, slice_ptr, sval, \
-                               scol, alpha, x, beta, y, nt, cptr, lead, rev);                                             \
+#define MI355_SHORT(W)                                                                                                          \
+    case W:                                                                                                                     \
+        if(big)                                                                                                                 \
+            hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SHARED, SPW_BIG, false, IDX>), grid, block, 0, s, m, nslices, \
+                               slice_ptr, sval, scol, alpha, x, beta, y, nt, cptr, lead, rev, vtab);                            \
+        else                                                                                                                    \
+            hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SHARED, 1, false, IDX>), grid, block, 0, s, m, nslices,       \
+                               slice_ptr, sval, scol, alpha, x, beta, y, nt, cptr, lead, rev, vtab);                            \
         return true
     switch(wmax)
     {
@@ -580,10 +766,10 @@ bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int
 #undef MI355_SHORT
 }
 
-template <typename T, int ORDER, int PACK>
-void sell_launch(hipStream_t s, aoclsparse_int m, aoclsparse_int nslices, const long long *slice_ptr, const T *sval,
-                 const aoclsparse_int *scol, const aoclsparse_int *rowlen, T alpha, const T *x, T beta, T *y,
-                 const long long *cptr, const unsigned short *lead, int rev = 0)
+template <typename T, int ORDER, int PACK, bool IDX>
+void sell_launch(hipStream_t s, aoclsparse_int m, aoclsparse_int nslices, const long long *slice_ptr,
+                 const typename SellCell<T, IDX>::src *sval, const aoclsparse_int *scol, const aoclsparse_int *rowlen, T alpha,
+                 const T *x, T beta, T *y, const long long *cptr, const unsigned short *lead, int rev, const T *vtab)
 {
     // one slice per workgroup while the launch is small (every slice its own CU), two otherwise
     // (swept on the headline workload: 1 / 2 / 4 / 8 slices per workgroup = 0.221 / 0.218 / 0.221 / 0.222 ms)
@@ -591,19 +777,20 @@ void sell_launch(hipStream_t s, aoclsparse_int m, aoclsparse_int nslices, const 
     if(cptr)
     {
         if(nslices < 2048)
-            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, true>), dim3(nslices), dim3(64), 0, s, m, nslices, slice_ptr,
-                               sval, scol, rowlen, alpha, x, beta, y, nt, cptr, lead, rev);
+            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, true, false, IDX>), dim3(nslices), dim3(64), 0, s, m, nslices,
+                               slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, cptr, lead, rev, vtab);
         else
-            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, true>), dim3((nslices + 1) / 2), dim3(128), 0, s, m, nslices,
-                               slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, cptr, lead, rev);
+            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, true, false, IDX>), dim3((nslices + 1) / 2), dim3(128), 0, s, m,
+                               nslices, slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, cptr, lead, rev, vtab);
     }
     else if(nslices < 2048)
-        hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK>), dim3(nslices), dim3(64), 0, s, m, nslices, slice_ptr,
-                           sval, scol, rowlen, alpha, x, beta, y, nt, (const long long *)nullptr, (const unsigned short *)nullptr, rev);
+        hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, false, false, IDX>), dim3(nslices), dim3(64), 0, s, m, nslices, slice_ptr,
+                           sval, scol, rowlen, alpha, x, beta, y, nt, (const long long *)nullptr, (const unsigned short *)nullptr, rev,
+                           vtab);
     else
-        hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK>), dim3((nslices + 1) / 2), dim3(128), 0, s, m, nslices,
-                           slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, (const long long *)nullptr,
-                           (const unsigned short *)nullptr, rev);
+        hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, false, false, IDX>), dim3((nslices + 1) / 2), dim3(128), 0, s, m,
+                           nslices, slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, (const long long *)nullptr,
+                           (const unsigned short *)nullptr, rev, vtab);
 }
 
 } // namespace
@@ -612,7 +799,8 @@ template <typename T>
 aoclsparse_status launch_sell_fill(hipStream_t s, int pack, aoclsparse_int m, int base, const aoclsparse_int *row_ptr,
                                    const aoclsparse_int *col, const T *val, aoclsparse_int nslices,
                                    const long long *slice_ptr, T *sval, aoclsparse_int *scol, aoclsparse_int *rowlen,
-                                   const long long *cptr, const unsigned short *lead)
+                                   const long long *cptr, const unsigned short *lead, unsigned char *sidx, const T *vtab,
+                                   int ntab)
 {
     if(nslices <= 0)
         return aoclsparse_status_success;
@@ -620,18 +808,61 @@ aoclsparse_status launch_sell_fill(hipStream_t s, int pack, aoclsparse_int m, in
     {
         if(pack == 4)
             hipLaunchKernelGGL((sell_fill_shared_kernel<T, 4>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr,
-                               col, val, nslices, slice_ptr, cptr, lead, sval, scol, rowlen);
+                               col, val, nslices, slice_ptr, cptr, lead, sval, scol, rowlen, sidx, vtab, ntab);
         else
             hipLaunchKernelGGL((sell_fill_shared_kernel<T, 1>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr,
-                               col, val, nslices, slice_ptr, cptr, lead, sval, scol, rowlen);
+                               col, val, nslices, slice_ptr, cptr, lead, sval, scol, rowlen, sidx, vtab, ntab);
     }
     else if(pack == 4)
         hipLaunchKernelGGL((sell_fill_kernel<T, 4>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr, col,
-                           val, nslices, slice_ptr, sval, scol, rowlen);
+                           val, nslices, slice_ptr, sval, scol, rowlen, sidx, vtab, ntab);
     else
         hipLaunchKernelGGL((sell_fill_kernel<T, 1>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr, col,
-                           val, nslices, slice_ptr, sval, scol, rowlen);
+                           val, nslices, slice_ptr, sval, scol, rowlen, sidx, vtab, ntab);
     MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
+// distinct bit patterns of the n values of `val` (vsize 4 or 8 bytes each): on return *ntab = their number and table[0 .. *ntab)
+// = the patterns in ascending order (as 8-byte words), or *ntab = 0 if there are more than SELL_VTAB_MAX of them
+aoclsparse_status sell_value_table(hipStream_t s, size_t vsize, long long n, const void *val, unsigned long long *table, int *ntab)
+{
+    *ntab = 0;
+    if(n <= 0 || (vsize != 4 && vsize != 8))
+        return aoclsparse_status_success;
+    DeviceBuffer      set;
+    aoclsparse_status st = set.alloc(sizeof(unsigned long long) * VT_SLOTS + 4 * sizeof(unsigned));
+    if(st != aoclsparse_status_success)
+        return st;
+    unsigned long long *d_set   = set.as<unsigned long long>();
+    unsigned           *d_state = reinterpret_cast<unsigned *>(d_set + VT_SLOTS);
+    MI355_HIP_TRY(hipMemsetAsync(d_set, 0xff, sizeof(unsigned long long) * VT_SLOTS, s)); // VT_EMPTY everywhere
+    MI355_HIP_TRY(hipMemsetAsync(d_state, 0, 4 * sizeof(unsigned), s));
+    // a few workgroups per CU, each walking the values with a grid stride (a workgroup that has seen > 256 patterns stops all)
+    const long long blocks = std::min<long long>(2048, std::max<long long>(1, (n + 1023) / 1024));
+    if(vsize == 8)
+        hipLaunchKernelGGL(sell_vtab_count_kernel<unsigned long long>, dim3((unsigned)blocks), dim3(256), 0, s, n,
+                           static_cast<const unsigned long long *>(val), d_set, d_state);
+    else
+        hipLaunchKernelGGL(sell_vtab_count_kernel<unsigned>, dim3((unsigned)blocks), dim3(256), 0, s, n,
+                           static_cast<const unsigned *>(val), d_set, d_state);
+    MI355_HIP_TRY(hipGetLastError());
+    unsigned state[4];
+    MI355_HIP_TRY(hipMemcpyAsync(state, d_state, sizeof(state), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if(state[1] || state[0] + state[2] > (unsigned)SELL_VTAB_MAX)
+        return aoclsparse_status_success;
+    std::vector<unsigned long long> h((size_t)VT_SLOTS);
+    MI355_HIP_TRY(hipMemcpyAsync(h.data(), d_set, sizeof(unsigned long long) * VT_SLOTS, hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    int k = 0;
+    for(unsigned long long v : h)
+        if(v != VT_EMPTY && k < SELL_VTAB_MAX)
+            table[k++] = v;
+    if(state[2] && k < SELL_VTAB_MAX)
+        table[k++] = VT_EMPTY;
+    std::sort(table, table + k); // (ascending bit pattern: the plan does not depend on the order the device found them in)
+    *ntab = k;
     return aoclsparse_status_success;
 }
 
@@ -639,44 +870,57 @@ template <typename T>
 aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoclsparse_int m, aoclsparse_int nslices,
                                 const long long *slice_ptr, const T *sval, const aoclsparse_int *scol,
                                 const aoclsparse_int *rowlen, const T *x, T beta, T *y, const long long *cptr,
-                                const unsigned short *lead, aoclsparse_int max_width, int rev)
+                                const unsigned short *lead, aoclsparse_int max_width, int rev, const unsigned char *sidx,
+                                const T *vtab)
 {
     if(m <= 0 || nslices <= 0)
         return aoclsparse_status_success;
     if(order < 0 || order > 2 || (pack != 1 && pack != 4))
         return aoclsparse_status_invalid_kid;
-    // widest slice <= 8 cells, scalar order, a launch large enough that four slices per workgroup still spread over every CU
-    if(order == 0 && pack == 1 && max_width >= 1 && max_width <= 8 && nslices >= 4096)
-    {
-        const bool nt   = (size_t)m * sizeof(T) > ((size_t)32 << 20);
-        const bool done = cptr ? sell_launch_short<T, true>(s, (int)max_width, m, nslices, slice_ptr, sval, scol, alpha, x, beta, y, nt, cptr, lead, rev)
-                               : sell_launch_short<T, false>(s, (int)max_width, m, nslices, slice_ptr, sval, scol, alpha, x, beta, y, nt,
-                                                             nullptr, nullptr, rev);
-        if(done)
+    // vtab: the cells are one-byte indices into it (sidx); else the values themselves (sval)
+    auto go = [&](auto idx_tag) {
+        constexpr bool IDX = decltype(idx_tag)::value;
+        const typename SellCell<T, IDX>::src *cells;
+        if constexpr(IDX)
+            cells = sidx;
+        else
+            cells = sval;
+        // widest slice <= 8 cells, scalar order, a launch large enough that four slices per workgroup still spread over every CU
+        if(order == 0 && pack == 1 && max_width >= 1 && max_width <= 8 && nslices >= 4096)
         {
-            MI355_HIP_TRY(hipGetLastError());
-            return aoclsparse_status_success;
+            const bool nt = (size_t)m * sizeof(T) > ((size_t)32 << 20);
+            const bool done
+                = cptr ? sell_launch_short<T, true, IDX>(s, (int)max_width, m, nslices, slice_ptr, cells, scol, alpha, x, beta, y, nt,
+                                                         cptr, lead, rev, vtab)
+                       : sell_launch_short<T, false, IDX>(s, (int)max_width, m, nslices, slice_ptr, cells, scol, alpha, x, beta, y, nt,
+                                                          nullptr, nullptr, rev, vtab);
+            if(done)
+                return;
         }
-    }
-#define SELL_CASE(O, P)                                                                        \
-    sell_launch<T, O, P>(s, m, nslices, slice_ptr, sval, scol, rowlen, alpha, x, beta, y, cptr, lead, rev); \
+#define SELL_CASE(O, P)                                                                                            \
+    sell_launch<T, O, P, IDX>(s, m, nslices, slice_ptr, cells, scol, rowlen, alpha, x, beta, y, cptr, lead, rev, vtab); \
     break
-    switch(order * 2 + (pack == 4 ? 1 : 0))
-    {
-    case 0:
-        SELL_CASE(0, 1);
-    case 1:
-        SELL_CASE(0, 4);
-    case 2:
-        SELL_CASE(1, 1);
-    case 3:
-        SELL_CASE(1, 4);
-    case 4:
-        SELL_CASE(2, 1);
-    case 5:
-        SELL_CASE(2, 4);
-    }
+        switch(order * 2 + (pack == 4 ? 1 : 0))
+        {
+        case 0:
+            SELL_CASE(0, 1);
+        case 1:
+            SELL_CASE(0, 4);
+        case 2:
+            SELL_CASE(1, 1);
+        case 3:
+            SELL_CASE(1, 4);
+        case 4:
+            SELL_CASE(2, 1);
+        case 5:
+            SELL_CASE(2, 4);
+        }
 #undef SELL_CASE
+    };
+    if(vtab)
+        go(std::true_type{});
+    else
+        go(std::false_type{});
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }
@@ -750,7 +994,8 @@ template aoclsparse_status launch_sellmv_complex<float>(hipStream_t, bool, cfloa
 // (the fill kernels only move values: cfloat cells are filled as 8-byte doubles, cdouble cells need their own instantiation)
 template aoclsparse_status launch_sell_fill<cdouble>(hipStream_t, int, aoclsparse_int, int, const aoclsparse_int *, const aoclsparse_int *,
                                                      const cdouble *, aoclsparse_int, const long long *, cdouble *, aoclsparse_int *,
-                                                     aoclsparse_int *, const long long *, const unsigned short *);
+                                                     aoclsparse_int *, const long long *, const unsigned short *, unsigned char *,
+                                                     const cdouble *, int);
 
 aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base, const aoclsparse_int *row_ptr, const aoclsparse_int *col,
                                       aoclsparse_int nslices, unsigned short *lead, aoclsparse_int *nl)
@@ -766,11 +1011,13 @@ aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base,
     template aoclsparse_status launch_sell_fill<T>(hipStream_t, int, aoclsparse_int, int, const aoclsparse_int *,     \
                                                    const aoclsparse_int *, const T *, aoclsparse_int,                 \
                                                    const long long *, T *, aoclsparse_int *, aoclsparse_int *,        \
-                                                   const long long *, const unsigned short *);                         \
+                                                   const long long *, const unsigned short *, unsigned char *, const T *, \
+                                                   int);                                                              \
     template aoclsparse_status launch_sellmv<T>(hipStream_t, int, int, T, aoclsparse_int, aoclsparse_int,             \
                                                 const long long *, const T *, const aoclsparse_int *,                 \
                                                 const aoclsparse_int *, const T *, T, T *, const long long *,          \
-                                                const unsigned short *, aoclsparse_int, int);
+                                                const unsigned short *, aoclsparse_int, int, const unsigned char *,    \
+                                                const T *);
 MI355_SELL_INSTANTIATE(double)
 MI355_SELL_INSTANTIATE(float)
 

@@ -120,7 +120,8 @@ aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const Devic
                               plan.sell.rowlen.as<aoclsparse_int>(), static_cast<const T *>(ax.dev), beta,
                               static_cast<T *>(ay.dev), plan.sell.shared ? plan.sell.cptr.as<long long>() : nullptr,
                               plan.sell.shared ? plan.sell.lead.as<unsigned short>() : nullptr, plan.max_row_nnz,
-                              plan.sell.next_direction());
+                              plan.sell.next_direction(), plan.sell.ntab ? plan.sell.vidx.as<unsigned char>() : nullptr,
+                              plan.sell.ntab ? plan.sell.vtab.as<T>() : nullptr);
     else if(plan.merge.valid && order == 0 && !strict) // balanced tiles for irregular rows (scalar order, no pinned kid)
     {
         // one launch; the pieces of cut rows meet in the piece set of this stream (internal.hpp, MergePlan).  Finding the set
@@ -696,6 +697,16 @@ aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_matrix A, aocl
     if(plan_option(aoclsparse_mi355_option_spmv_strict) == 1)
         strict = true;
     info->tree_min = ((info->kernel == 1 || info->kernel == 2) && order == 0 && !strict) ? SPMV_TREE_MIN : 0;
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_get_sell_values(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *table_entries)
+{
+    if(!A || !table_entries)
+        return aoclsparse_status_invalid_pointer;
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
+    *table_entries                        = p.sell.valid ? p.sell.ntab : 0;
     return aoclsparse_status_success;
 }
 

@@ -48,7 +48,11 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_set_pointer_mode(aoclsparse_mi355_
  *   trsv_chunks  -1 (default): the two-level TRSV schedule (chunks of consecutive blocks, hand-offs inside a chunk through LDS;
  *                schedule 5) is built when the plan-time model of the triangle's DAG predicts a gain over the lane-per-block
  *                schedule (deep, narrow DAGs: a mesh numbered line by line); 0 never; 1 whenever the triangle has the shape the
- *                kernel serves.  Read when a TRSV plan is built.  Same bits on every schedule. */
+ *                kernel serves.  Read when a TRSV plan is built.  Same bits on every schedule.
+ *   sell_values  -1 (default): a SELL-64 copy of a real matrix with >= 2^17 non-zeros whose values take at most 256 distinct bit
+ *                patterns stores one byte per cell, an index into a table of those patterns (aoclsparse_mi355_get_sell_values);
+ *                0 never (the values in the cells); 1 whenever there are at most 256 patterns, whatever the size.  Read when the
+ *                SELL-64 copy is built.  Same bits either way: the table holds the values' exact bit patterns. */
 typedef enum aoclsparse_mi355_option_
 {
     aoclsparse_mi355_option_spmv_kernel = 0,
@@ -56,7 +60,8 @@ typedef enum aoclsparse_mi355_option_
     aoclsparse_mi355_option_spmv_strict = 2,
     aoclsparse_mi355_option_alternate_sweeps = 3,
     aoclsparse_mi355_option_trsv_chunks = 4,
-    aoclsparse_mi355_option_count       = 5
+    aoclsparse_mi355_option_sell_values = 5,
+    aoclsparse_mi355_option_count       = 6
 } aoclsparse_mi355_option;
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_set_option(aoclsparse_mi355_option option, aoclsparse_int value);
 /* aoclsparse_?csrmm with beta == 0.  Default (0): C is read and multiplied by zero, exactly as every kernel of the reference
@@ -232,6 +237,11 @@ typedef struct aoclsparse_mi355_spmv_info_
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_matrix     A,
                                                             aoclsparse_operation        op,
                                                             aoclsparse_mi355_spmv_info *info);
+/* entries of the value table of op(A)'s SELL-64 copy (aoclsparse_mi355_option_sell_values): 1..256 when the cells hold one-byte
+ * indices into it, 0 when they hold the values (or there is no SELL-64 copy).  Derived (symmetric / triangular) operators are not
+ * reported. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_values(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                              aoclsparse_int *table_entries);
 /* The plan behind mm_bell_xcd_chunk / the lattice sweep, computed from host arrays (no device involved; what aoclsparse_optimize runs on the
  * blocked-ELL copy's block columns): bcol = nbr x width block columns, ascending per block row, empty slots (-1) last; nbc = block columns of
  * the matrix.  forced: -2 automatic, -1 the lattice sweep whenever a lattice is found, 0 launch order, c >= 1 chunks of c block rows.
