@@ -395,6 +395,7 @@ SIGNATURES = {
     "aoclsparse_mi355_release_staging": (c_int, [POINTER(ctypes.c_size_t)]),
     "mi355_csrmv_plan_bound": (_I, [_I, _I]),
     "mi355_csrmv_plan_host": (_I, [_I, _I, _I, _P, _P]),
+    "mi355_sell_slice_records": (_I, [_I, _P, _P, ctypes.c_longlong, _P]),
     "mi355_dcsrmv": (c_int, [_P, _I, _I, _I, _I, c_double, _I, _P, _P, _P, _P, _I, _P, c_double, _P]),
     "mi355_scsrmv": (c_int, [_P, _I, _I, _I, _I, c_float, _I, _P, _P, _P, _P, _I, _P, c_float, _P]),
     "mi355_dcsrmm": (c_int, [_P, _I, _I, c_double, _I, _I, _P, _P, _P, _P, _I, _I, c_double, _P, _I]),

@@ -18,6 +18,7 @@
 #include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <cstdint>
 #include <exception>
 #include <memory>
 #include <mutex>
@@ -259,6 +260,29 @@ struct DeviceCsr
     bool           valid = false;
 };
 
+// What the short-row SELL-64 kernel (sell_kernels.hip: sell_mv_short_kernel) reads about a slice, in ONE scalar load: where its
+// value cells and its column lists start (48-bit offsets), its width, the stride between the column rows of a lane (the number
+// of leaders with shared column lists, 64 without) and how a lane finds its list (mode).
+struct SellSliceDesc
+{
+    uint32_t cell_lo, col_lo; // low words of the first value cell (slice_ptr[s]) and of the first column entry
+    uint32_t hi; // bits 0-15: bits 32-47 of the value-cell offset; bits 16-31: those of the column offset
+    uint32_t wsm; // bits 0-7 width (cells per row), 8-15 column stride, 16-23 mode
+};
+// modes: 0 lead[row] = list | shift << 8; 1 one list, shift = lane; 2 one list, no shift; 3 list = lane, no shift (lists not shared)
+constexpr int            SELL_DESC_MODE_FOLLOW = 0, SELL_DESC_MODE_LANE_SHIFT = 1, SELL_DESC_MODE_ONE = 2, SELL_DESC_MODE_OWN = 3;
+constexpr int            SELL_SHORT_WMAX       = 8;
+constexpr aoclsparse_int SELL_SHORT_MIN_SLICES = 4096;
+// records after the last slice (width 0, pointing at the padding cells): the last workgroup's 4 waves x 4 slices read them
+constexpr int            SELL_DESC_PAD = 16;
+// cells after the last one in val / vidx, entries after the last one in col (value 0 / index 0, column -1): what a slice of
+// width 0 reads instead of nothing, so that the kernel has no branch around its loads
+constexpr int            SELL_CELL_PAD = 64;
+// nslices + SELL_DESC_PAD records from the host arrays: slice_ptr (nslices + 1), leaders[s] = leaders | mode << 8 as
+// sell_leaders_kernel writes them (nullptr: column lists not shared, entry of a cell = its cell offset), ccells = column entries in all
+void sell_pack_descriptors(aoclsparse_int nslices, const long long *slice_ptr, const aoclsparse_int *leaders, long long ccells,
+                           SellSliceDesc *out);
+
 // SELL-64 twin of a device CSR (sell_kernels.hip): built by aoclsparse_optimize for an mv hint when the
 // padding stays small; the handle's ?mv then runs on it instead of the CSR-Adaptive kernel.
 struct SellPlan
@@ -278,6 +302,9 @@ struct SellPlan
     // vtab, ntab values sorted by bit pattern, and val is not allocated; ntab = 0 -> the values are in val
     int            ntab = 0;
     DeviceBuffer   vtab, vidx;
+    // one 16-byte record per slice for the short-row kernel (SellSliceDesc; nslices + SELL_DESC_PAD of them), allocated only
+    // when that kernel can serve the copy (pack 1, widest slice <= SELL_SHORT_WMAX, >= SELL_SHORT_MIN_SLICES slices)
+    DeviceBuffer   desc;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
@@ -822,7 +849,8 @@ template <typename R>
 aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha, aoclsparse_int m, aoclsparse_int nslices,
                                         const long long *slice_ptr, const cplx<R> *sval, const aoclsparse_int *scol,
                                         const aoclsparse_int *rowlen, const cplx<R> *x, cplx<R> beta, cplx<R> *y,
-                                        const long long *cptr, const unsigned short *lead, aoclsparse_int max_width, int rev = 0);
+                                        const long long *cptr, const unsigned short *lead, aoclsparse_int max_width, int rev = 0,
+                                        const SellSliceDesc *desc = nullptr);
 aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base, const aoclsparse_int *row_ptr, const aoclsparse_int *col,
                                       aoclsparse_int nslices, unsigned short *lead, aoclsparse_int *nl);
 template <typename T>
@@ -831,8 +859,9 @@ aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoc
                                 const aoclsparse_int *rowlen, const T *x, T beta, T *y, const long long *cptr = nullptr,
                                 const unsigned short *lead = nullptr,
                                 aoclsparse_int max_width = 0, int rev = 0, const unsigned char *sidx = nullptr,
-                                const T *vtab = nullptr);
-// (vtab != nullptr: the cells are sidx, one-byte indices into vtab; sval is not read)
+                                const T *vtab = nullptr, const SellSliceDesc *desc = nullptr, int ntab = 0);
+// (vtab != nullptr: the cells are sidx, one-byte indices into vtab (ntab entries, SELL_VTAB_MAX allocated); sval is not read)
+// (desc != nullptr: the plan's slice records -- order 0 then runs the short-row kernel)
 // BLKCSR (blk_kernels.hip): value offset of every block (three small launches: per-chunk popcount scan, scan of
 // the chunk totals in part[], add), then the product
 constexpr int     BLK_PART_SHIFT = 10;

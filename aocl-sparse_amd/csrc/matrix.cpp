@@ -666,6 +666,34 @@ aoclsparse_status build_spmv_plan(aoclsparse_int m, aoclsparse_int nnz, aoclspar
     return aoclsparse_status_success;
 }
 
+void sell_pack_descriptors(aoclsparse_int nslices, const long long *slice_ptr, const aoclsparse_int *leaders, long long ccells,
+                           SellSliceDesc *out)
+{
+    auto pack = [](long long cell, long long col, int w, int stride, int mode) {
+        SellSliceDesc d;
+        d.cell_lo = (uint32_t)cell, d.col_lo = (uint32_t)col;
+        d.hi      = (uint32_t)((cell >> 32) & 0xffff) | (uint32_t)((col >> 32) & 0xffff) << 16;
+        d.wsm     = (uint32_t)w | (uint32_t)stride << 8 | (uint32_t)mode << 16;
+        return d;
+    };
+    long long c0 = 0;
+    for(aoclsparse_int s = 0; s < nslices; s++)
+    {
+        const int w = (int)((slice_ptr[s + 1] - slice_ptr[s]) >> 6);
+        if(leaders)
+        {
+            const int nl = leaders[s] & 0xff;
+            out[s]       = pack(slice_ptr[s], c0, w, nl, leaders[s] >> 8);
+            c0 += (long long)nl * w;
+        }
+        else
+            out[s] = pack(slice_ptr[s], slice_ptr[s], w, 64, SELL_DESC_MODE_OWN);
+    }
+    // past the end: empty slices on the padding cells (one list, no shift: nothing but the padding is read)
+    for(int k = 0; k < SELL_DESC_PAD; k++)
+        out[nslices + k] = pack(slice_ptr[nslices], ccells, 0, 1, SELL_DESC_MODE_ONE);
+}
+
 aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr &d, size_t vsize, SpmvPlan &plan, bool complex_values)
 {
     SellPlan &sp = plan.sell;
@@ -673,7 +701,7 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         return aoclsparse_status_success;
     sp.tried = true;
     sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
-    sp.vtab.release(), sp.vidx.release();
+    sp.vtab.release(), sp.vidx.release(), sp.desc.release();
     const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
         return aoclsparse_status_success;
@@ -692,12 +720,14 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     // (complex values: PACK 1 only -- their kernels are the scalar-chain ones)
     const int pack = (!complex_values && (long long)d.nnz >= 16LL * m) ? 4 : 1;
     sptr[0] = 0;
+    aoclsparse_int wmax = 0; // widest slice
     for(aoclsparse_int s = 0; s < nslices; s++)
     {
         aoclsparse_int w = 0;
         for(aoclsparse_int i = s * 64; i < std::min<aoclsparse_int>(m, s * 64 + 64); i++)
             w = std::max(w, row_ptr_host[i + 1] - row_ptr_host[i]);
         w           = (w + pack - 1) / pack * pack;
+        wmax        = std::max(wmax, w);
         sptr[s + 1] = sptr[s] + 64LL * w;
     }
     const long long cells = sptr[nslices];
@@ -713,7 +743,8 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     // shifted by one (the rows of a stencil) -- keep ONE copy per slice.  Leaders are found on the device (one compare
     // pass over the CSR arrays); used when the column stream shrinks to <= 70 %.
     sp.shared = false, sp.ccells = cells;
-    std::vector<long long> cptr;
+    std::vector<long long>      cptr;
+    std::vector<aoclsparse_int> nlh; // leaders | mode << 8 of every slice
     // (not for matrices that live in the caches anyway: the leader / shift words are one more dependent load, and the 10k x 10k
     // Laplacian of BASELINE configs[0] -- 50 k non-zeros, launch-bound -- ran at 5.4 instead of 4.6 us per call with them)
     if(st == aoclsparse_status_success && d.nnz >= (1 << 17))
@@ -727,7 +758,7 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
                                      sp.lead.as<unsigned short>(), nl.as<aoclsparse_int>());
         if(st != aoclsparse_status_success)
             return st;
-        std::vector<aoclsparse_int> nlh((size_t)nslices);
+        nlh.resize((size_t)nslices);
         MI355_HIP_TRY(hipMemcpyAsync(nlh.data(), nl.ptr, sizeof(aoclsparse_int) * (size_t)nslices, hipMemcpyDeviceToHost, rt.stream()));
         MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
         cptr.resize((size_t)nslices + 1);
@@ -770,9 +801,11 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
                 else
                     std::memcpy(tab + sizeof(double) * k, &bits[k], sizeof(double));
             }
-            st = sp.vtab.upload(tab, vsize * (size_t)ntab, rt.stream());
+            // (SELL_VTAB_MAX entries whatever ntab is, the unused ones 0: the short-row kernel copies the whole table to LDS)
+            std::memset(tab + vsize * (size_t)ntab, 0, vsize * (size_t)(SELL_VTAB_MAX - ntab));
+            st = sp.vtab.upload(tab, vsize * (size_t)SELL_VTAB_MAX, rt.stream());
             if(st == aoclsparse_status_success)
-                st = sp.vidx.alloc((size_t)std::max<long long>(cells, 4));
+                st = sp.vidx.alloc((size_t)cells + SELL_CELL_PAD);
             if(st == aoclsparse_status_success)
             {
                 sp.ntab = ntab;
@@ -782,14 +815,38 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         if(PhaseTimer::on())
             std::fprintf(stderr, "[mi355 timing] sell: %d distinct value patterns%s\n", ntab, ntab ? "" : " (more than 256, or none)");
     }
+    // (SELL_CELL_PAD cells / column entries after the last: value 0, index 0, column -1 -- what the short-row kernel reads for a
+    // slice of width 0)
     if(st == aoclsparse_status_success && sp.ntab == 0)
-        st = sp.val.alloc(vsize * (size_t)std::max<long long>(cells, 1));
+        st = sp.val.alloc(vsize * ((size_t)cells + SELL_CELL_PAD));
     if(st == aoclsparse_status_success)
-        st = sp.col.alloc(sizeof(aoclsparse_int) * (size_t)std::max<long long>(sp.ccells, 1));
+        st = sp.col.alloc(sizeof(aoclsparse_int) * ((size_t)sp.ccells + SELL_CELL_PAD));
     if(st == aoclsparse_status_success)
         st = sp.rowlen.alloc(sizeof(aoclsparse_int) * (size_t)m);
     if(st != aoclsparse_status_success)
         return st;
+    if(sp.ntab)
+        MI355_HIP_TRY(hipMemsetAsync(sp.vidx.as<unsigned char>() + cells, 0, SELL_CELL_PAD, rt.stream()));
+    else
+        MI355_HIP_TRY(hipMemsetAsync(sp.val.as<unsigned char>() + vsize * (size_t)cells, 0, vsize * SELL_CELL_PAD, rt.stream()));
+    MI355_HIP_TRY(hipMemsetAsync(sp.col.as<aoclsparse_int>() + sp.ccells, 0xff, sizeof(aoclsparse_int) * SELL_CELL_PAD, rt.stream()));
+    // slice records for the short-row kernel (sell_kernels.hip), where it can serve this copy
+    std::vector<SellSliceDesc> desc;
+    if(pack == 1 && wmax >= 1 && wmax <= SELL_SHORT_WMAX && nslices >= SELL_SHORT_MIN_SLICES)
+    {
+        try
+        {
+            desc.resize((size_t)nslices + SELL_DESC_PAD);
+        }
+        catch(const std::bad_alloc &)
+        {
+            return aoclsparse_status_memory_error;
+        }
+        sell_pack_descriptors(nslices, sptr.data(), sp.shared ? nlh.data() : nullptr, sp.ccells, desc.data());
+        st = sp.desc.upload(desc.data(), sizeof(SellSliceDesc) * desc.size(), rt.stream());
+        if(st != aoclsparse_status_success)
+            return st;
+    }
     const long long     *cp = sp.shared ? sp.cptr.as<long long>() : nullptr;
     const unsigned short *ld = sp.shared ? sp.lead.as<unsigned short>() : nullptr;
     if(vsize == sizeof(cdouble))
@@ -808,7 +865,7 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
                                       sp.ntab ? sp.vidx.as<unsigned char>() : nullptr, sp.vtab.as<double>(), sp.ntab);
     if(st != aoclsparse_status_success)
         return st;
-    MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr (host) are read by the uploads until here
+    MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr / desc (host) are read by the uploads until here
     sp.nslices = nslices, sp.cells = cells, sp.pack = pack, sp.valid = sp.wanted = true;
     return aoclsparse_status_success;
 }
@@ -980,6 +1037,18 @@ aoclsparse_status ensure_spmv(aoclsparse_matrix A, bool transposed, DeviceCsr *&
 
 // =====================================================================================================
 extern "C" {
+
+aoclsparse_int mi355_sell_slice_records(aoclsparse_int nslices, const long long *slice_ptr, const aoclsparse_int *leaders,
+                                                   long long column_entries, unsigned int *records)
+{
+    static_assert(sizeof(mi355::SellSliceDesc) == 4 * sizeof(unsigned int), "a slice record is four words");
+    if(!records)
+        return nslices < 0 ? -1 : nslices + mi355::SELL_DESC_PAD;
+    if(nslices < 0 || !slice_ptr)
+        return -1;
+    mi355::sell_pack_descriptors(nslices, slice_ptr, leaders, column_entries, reinterpret_cast<mi355::SellSliceDesc *>(records));
+    return nslices + mi355::SELL_DESC_PAD;
+}
 
 aoclsparse_int mi355_csrmv_plan_bound(aoclsparse_int m, aoclsparse_int /*nnz*/)
 {

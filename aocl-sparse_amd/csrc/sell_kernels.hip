@@ -18,6 +18,7 @@
 #include "internal.hpp"
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -80,6 +81,35 @@ __device__ __forceinline__ cplx<R> s_cj(cplx<R> v)
     if constexpr(CONJ)
         v.im = -v.im;
     return v;
+}
+
+// pins v to a register HERE: the loads and the chain behind it are not moved into a branch that follows (the compiler sinks
+// what only a guarded store uses into the guard, and then the loads of one slice wait for the store of the slice before)
+__device__ __forceinline__ void s_pin(double &v)
+{
+    asm volatile("" : "+v"(v));
+}
+__device__ __forceinline__ void s_pin(float &v)
+{
+    asm volatile("" : "+v"(v));
+}
+template <typename R>
+__device__ __forceinline__ void s_pin(cplx<R> &v)
+{
+    s_pin(v.re), s_pin(v.im);
+}
+
+// the same for a kernel argument: it is read with the first batch of scalar loads, not in front of its first use (one more
+// scalar-cache round trip at the tail of a wave's life otherwise)
+template <typename A>
+__device__ __forceinline__ void s_pin_arg(A a)
+{
+    asm volatile("" : : "s"(a));
+}
+template <typename R>
+__device__ __forceinline__ void s_pin_arg(cplx<R> a)
+{
+    s_pin_arg(a.re), s_pin_arg(a.im);
 }
 
 template <typename T>
@@ -634,122 +664,194 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         s_store(y + i, s_finish(r, alpha, beta, y + i), nt);
 }
 
-// Short rows (round 3): matrices whose widest slice has WMAX <= 8 cells, scalar summation order, PACK 1, large launches.  ONE
-// batch of WMAX value / column line loads (index clamped to the slice's own width: no guard inside the batch; a narrower
-// boundary slice re-reads its last line and skips the FMA), then the WMAX gathers, then the chain: three dependent round trips
-// per slice, four slices per workgroup.  Same-box sweep on the headline workload (tools/history/exp_r3_short.sh,
-// profiles/r3/sell_width_switch.txt): general kernel before the width switch 0.1845-0.186 ms, with it 0.1786-0.1793, this
-// kernel with 1 / 2 / 4 slices per workgroup 0.180-0.181 / 0.180-0.181 / 0.1773-0.1779; TWO or more slices per WAVEFRONT
-// (walked together, twice the bytes in flight per wave) 0.183-0.236 ms -- more registers, fewer waves, no gain.
-template <typename T, int WMAX, int WAVES, bool SHARED, int SPW = 1, bool CONJ = false, bool IDX = false>
-__global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_int m, aoclsparse_int nslices,
-                                                                   const long long *__restrict__ slice_ptr,
-                                                                   const typename SellCell<T, IDX>::src *__restrict__ sval,
-                                                                   const aoclsparse_int *__restrict__ scol, T alpha,
+// Short rows: matrices whose widest slice has WMAX <= 8 cells, scalar summation order, PACK 1, large launches.  A wavefront
+// takes SPW consecutive slices and walks them TOGETHER, with no branch and no loop on the common path, so that its life is four
+// dependent round trips whatever SPW is:
+//   1. the kernel arguments (one scalar batch: the sweep direction is the pair g0 / gstep, not a branch);
+//   2. the SPW slice records (SellSliceDesc, one wide scalar load: offsets, width, column stride, mode -- no slice_ptr / cptr
+//      pairs, no division);
+//   3. all SPW x WMAX value / column line loads (index clamped to the slice's own width, and to 0 for an EMPTY slice, which
+//      reads the padding cells behind the arrays: a narrower slice re-reads its last line and skips the FMA);
+//   4. all SPW x WMAX x gathers; then the chains and the stores.
+// Only a group with a mode-0 slice (lead[] says which list a lane follows: 2 slices in 64 on a stencil) takes a fifth, the lead[]
+// loads of the whole group, issued together in front of the line loads.
+// TAB: 0 = the cells hold values; 2 = one-byte indices into a table of <= 2 values, held in scalar registers and selected;
+// 256 = indices into a table of <= SELL_VTAB_MAX values, copied to LDS once per workgroup (its load goes out with the records,
+// the barrier sits behind the line loads) -- no table read goes through the vector memory path.
+// The records, the padding cells and the table are padded at plan time (build_sell) so that nothing here needs a bound check:
+// SELL_DESC_PAD empty records behind the last slice, SELL_CELL_PAD cells, SELL_VTAB_MAX table entries.
+template <typename T, int WMAX, int WAVES, int SPW, bool CONJ, int TAB>
+__global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_int m, aoclsparse_int nslices, int g0, int gstep,
+                                                                   const uint4 *__restrict__ desc,
+                                                                   const typename SellCell<T, TAB != 0>::src *__restrict__ sval,
+                                                                   const aoclsparse_int *__restrict__ scol,
+                                                                   const unsigned short *__restrict__ follow, T alpha,
                                                                    const T *__restrict__ x, T beta, T *__restrict__ y, bool nt,
-                                                                   const long long *__restrict__ cptr,
-                                                                   const unsigned short *__restrict__ follow, int rev = 0,
-                                                                   const T *__restrict__ vtab = nullptr)
+                                                                   const T *__restrict__ vtab)
 {
-    using S = typename SellCell<T, IDX>::src;
-    using R = typename SellCell<T, IDX>::raw;
-    // SPW slices per wavefront, walked TOGETHER (all value / column loads of the SPW slices, then all gathers, then the chains):
-    // SPW times the bytes in flight per wavefront.  Lost for double (two: 0.183-0.236 vs 0.177 ms, round 3); float moves half the
-    // bytes per load instruction, and large float launches run four (round 4: sell_launch_short).
-    const unsigned bx = rev ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
-    const int sb   = __builtin_amdgcn_readfirstlane((int)(bx * WAVES + (threadIdx.x >> 6)) * SPW);
+    using R = typename SellCell<T, TAB != 0>::raw;
+    static_assert(WAVES * SPW <= SELL_DESC_PAD && 64 * WAVES == SELL_VTAB_MAX, "padding of the slice records / one table entry per lane");
+    // group g of WAVES x SPW slices; consecutive products of a handle ALTERNATE the direction (SellPlan::products): g0 = last
+    // group, gstep = -1 on odd ones
+    const int sb   = __builtin_amdgcn_readfirstlane(((g0 + gstep * (int)blockIdx.x) * WAVES + (int)(threadIdx.x >> 6)) * SPW);
     const int lane = threadIdx.x & 63;
-    if(sb >= nslices)
-        return;
-    T   vv[SPW][WMAX], xx[SPW][WMAX];
-    R   rr[SPW][WMAX];
-    int cc[SPW][WMAX], w[SPW], dl[SPW];
+    s_pin_arg(alpha), s_pin_arg(beta), s_pin_arg(y), s_pin_arg((int)nt), s_pin_arg(x), s_pin_arg(sval), s_pin_arg(scol), s_pin_arg(follow);
+    [[maybe_unused]] T t0, t1;
+    if constexpr(TAB == 2)
+        t0 = vtab[0], t1 = vtab[1];
+    else if constexpr(TAB != 0)
+        t0 = vtab[threadIdx.x];
+    uint4 d[SPW];
+#pragma unroll
+    for(int u = 0; u < SPW; u++)
+        d[u] = desc[sb + u];
+    int  f[SPW]; // list of this lane | column shift << 8
+    bool follows = false;
 #pragma unroll
     for(int u = 0; u < SPW; u++)
     {
-        const int             s  = min(sb + u, (int)nslices - 1); // (beyond the last slice: it is walked again, nothing is stored)
-        const long long       o0 = slice_ptr[s];
-        const int             i  = s * 64 + lane;
-        const S              *v  = sval + o0 + lane;
-        const aoclsparse_int *c  = scol + o0 + lane;
-        int                   cs = 64;
-        w[u]                     = (int)((slice_ptr[s + 1] - o0) >> 6);
-        dl[u]                    = 0;
-        if constexpr(SHARED)
-        {
-            const long long cw   = cptr[s];
-            const long long c0   = cw & SELL_CPTR_MASK;
-            const int       mode = (int)(cw >> SELL_CPTR_MODE_SHIFT);
-            int             f    = 0;
-            if(mode == 0)
-                f = i < m ? follow[i] : 0;
-            else if(mode == 1)
-                f = lane << 8;
-            cs    = w[u] > 0 ? (int)(((cptr[s + 1] & SELL_CPTR_MASK) - c0) / w[u]) : 1;
-            c     = scol + c0 + (f & 0xff);
-            dl[u] = f >> 8;
-        }
-        if(w[u] > 0) // (an empty slice has no cell to read)
-        {
+        const int mode = (int)(d[u].w >> 16) & 0xff;
+        follows        = follows || mode == SELL_DESC_MODE_FOLLOW;
+        f[u]           = mode == SELL_DESC_MODE_LANE_SHIFT ? lane << 8 : (mode == SELL_DESC_MODE_OWN ? lane : 0);
+    }
+    if(follows) // wave-uniform
+    {
+        int ff[SPW];
 #pragma unroll
-            for(int q = 0; q < WMAX; q++)
-            {
-                const int qq = min(q, w[u] - 1); // wave-uniform
-                rr[u][q]     = v[qq * 64];
-                cc[u][q]     = c[qq * cs];
-            }
-        }
-        else
-        {
+        for(int u = 0; u < SPW; u++)
+            ff[u] = follow[min((sb + u) * 64 + lane, (int)m - 1)];
 #pragma unroll
-            for(int q = 0; q < WMAX; q++)
-                rr[u][q] = R(0), cc[u][q] = -1;
+        for(int u = 0; u < SPW; u++)
+            f[u] = ((int)(d[u].w >> 16) & 0xff) == SELL_DESC_MODE_FOLLOW ? ff[u] : f[u];
+    }
+    R   rr[SPW][WMAX];
+    int cc[SPW][WMAX];
+#pragma unroll
+    for(int u = 0; u < SPW; u++)
+    {
+        const long long o0 = (long long)d[u].x | (long long)(d[u].z & 0xffffu) << 32;
+        const long long c0 = (long long)d[u].y | (long long)(d[u].z >> 16) << 32;
+        const int       w = (int)(d[u].w & 0xffu), cs = (int)(d[u].w >> 8) & 0xff;
+        const auto     *v = sval + o0 + lane;
+        const aoclsparse_int *c = scol + c0 + (f[u] & 0xff);
+#pragma unroll
+        for(int q = 0; q < WMAX; q++)
+        {
+            const int qq = max(min(q, w - 1), 0); // wave-uniform
+            rr[u][q]     = v[qq * 64];
+            cc[u][q]     = c[qq * cs];
         }
     }
-    // (IDX: the table reads, 2 KB at most and cache-resident, go out in the same batch as the x gathers)
+    __builtin_amdgcn_sched_barrier(0); // (every line load is issued before the first wait for one)
+    T vv[SPW][WMAX], xx[SPW][WMAX];
+#pragma unroll
+    for(int u = 0; u < SPW; u++)
+#pragma unroll
+        for(int q = 0; q < WMAX; q++) // (a padding cell, -1, is never used, but its gather must stay inside x: index 0)
+            xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + (f[u] >> 8) : 0];
+    [[maybe_unused]] __shared__ T ltab[TAB > 2 ? SELL_VTAB_MAX : 1];
+    if constexpr(TAB > 2) // (behind the gathers: the barrier is waited for while they are in flight)
+    {
+        ltab[threadIdx.x] = t0;
+        __syncthreads();
+    }
 #pragma unroll
     for(int u = 0; u < SPW; u++)
 #pragma unroll
         for(int q = 0; q < WMAX; q++)
-            xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + dl[u] : 0], vv[u][q] = s_cj<CONJ>(cell_value<IDX>(rr[u][q], vtab));
+        {
+            if constexpr(TAB == 0)
+                vv[u][q] = s_cj<CONJ>(rr[u][q]);
+            else if constexpr(TAB == 2)
+                vv[u][q] = rr[u][q] ? t1 : t0;
+            else
+                vv[u][q] = ltab[rr[u][q]];
+        }
+    T r[SPW];
 #pragma unroll
     for(int u = 0; u < SPW; u++)
     {
-        T r = T(0);
+        const int w = (int)(d[u].w & 0xffu);
+        r[u]        = T(0);
 #pragma unroll
         for(int q = 0; q < WMAX; q++)
-            r = (q < w[u] && cc[u][q] >= 0) ? s_fma(vv[u][q], xx[u][q], r) : r;
+            r[u] = (q < w && cc[u][q] >= 0) ? s_fma(vv[u][q], xx[u][q], r[u]) : r[u];
+    }
+#pragma unroll
+    for(int u = 0; u < SPW; u++)
+        s_pin(r[u]); // (every load above is issued before the first guarded store)
+#pragma unroll
+    for(int u = 0; u < SPW; u++)
+    {
         const int i = (sb + u) * 64 + lane;
         if(sb + u < nslices && i < m)
-            s_store(y + i, s_finish(r, alpha, beta, y + i), nt);
+            s_store(y + i, s_finish(r[u], alpha, beta, y + i), nt);
     }
 }
 
-constexpr aoclsparse_int SELL_SHORT_SPW4_SLICES = 100000;
-
-template <typename T, bool SHARED, bool IDX>
-bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int nslices, const long long *slice_ptr,
-                       const typename SellCell<T, IDX>::src *sval, const aoclsparse_int *scol, T alpha, const T *x, T beta, T *y,
-                       bool nt, const long long *cptr, const unsigned short *lead, int rev, const T *vtab)
+// slices per wavefront of the short-row kernel: AOCLSPARSE_MI355_SELL_SPW = 1 / 2 / 4 overrides the rule (measurements only;
+// read once per process)
+inline int sell_short_spw_override()
 {
-    constexpr int WAVES = 4;
-    // float, >= 100,000 slices: four slices per wavefront (a float load instruction moves half the bytes of a double one; same box,
-    // tools/history/exp_float_headline.py, 1 / 4 / 8 slices per wavefront: 4096^2 0.1013 / 0.0949 / 0.1218 ms, 3000^2 0.0512 / 0.0479 /
-    // 0.0543, 2000^2 0.0229 / 0.0235 / 0.0267 -- and no change for double, which stays at one: profiles/r4/float_headline.txt).
-    // The same with a value table (1-byte cells; 4096^2, cold products, profiles/r7/ab_sweep.txt): double 1 / 2 / 4 slices per
-    // wavefront 0.145 / 0.144 / 0.164 ms, float 0.093 / 0.086 / 0.075 ms.
-    constexpr int   SPW_BIG = sizeof(T) == 4 ? 4 : 1;
-    const bool      big     = SPW_BIG > 1 && nslices >= SELL_SHORT_SPW4_SLICES;
-    const long long per_wg  = (long long)WAVES * (big ? SPW_BIG : 1);
-    const dim3      grid((unsigned)((nslices + per_wg - 1) / per_wg)), block(64 * WAVES);
-#define MI355_SHORT(W)                                                                                                          \
-    case W:                                                                                                                     \
-        if(big)                                                                                                                 \
-            hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SHARED, SPW_BIG, false, IDX>), grid, block, 0, s, m, nslices, \
-                               slice_ptr, sval, scol, alpha, x, beta, y, nt, cptr, lead, rev, vtab);                            \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SHARED, 1, false, IDX>), grid, block, 0, s, m, nslices,       \
-                               slice_ptr, sval, scol, alpha, x, beta, y, nt, cptr, lead, rev, vtab);                            \
+    static const int v = [] {
+        const char *e = std::getenv("AOCLSPARSE_MI355_SELL_SPW");
+        const int   k = e ? std::atoi(e) : 0;
+        return (k == 1 || k == 2 || k == 4) ? k : 0;
+    }();
+    return v;
+}
+
+constexpr aoclsparse_int SELL_SHORT_SPW_SLICES = 60000;
+
+// TAB as the kernel's; CONJ for complex T only
+template <typename T, int TAB, bool CONJ = false>
+bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int nslices, const SellSliceDesc *desc,
+                       const typename SellCell<T, TAB != 0>::src *sval, const aoclsparse_int *scol, T alpha, const T *x, T beta, T *y,
+                       bool nt, const unsigned short *lead, int rev, const T *vtab)
+{
+    constexpr int  WAVES   = 4;
+    constexpr bool COMPLEX = !std::is_floating_point_v<T>;
+    // Slices per wavefront, by measurement (5-point Laplacians, cold products, one box, median of 20, ms; 1 / 2 / 4 slices per
+    // wavefront; profiles/r8/spw_sweep.txt, which also has the VGPRs and the occupancy of each variant):
+    //                       4096^2 (262,144 slices)    3000^2 (140,625)          2000^2 (62,500)
+    //   double, table       0.1264 / 0.1204 / 0.1276   0.0729 / 0.0683 / 0.0722  0.0354 / 0.0333 / 0.0350
+    //   double, values      0.2025 / 0.2032 / 0.2073   0.1250 / 0.1252 / 0.1294  0.0686 / 0.0712 / 0.0739
+    //   float, table        0.1086 / 0.0747 / 0.0706   0.0590 / 0.0413 / 0.0415  0.0282 / 0.0218 / 0.0221
+    //   float, values       0.1289 / 0.1193 / 0.1234   0.0780 / 0.0803 / 0.0820  0.0418 / 0.0409 / 0.0422
+    // -> from 60,000 slices on: double with a table 2, float with a table 4, float values 2; double values stay at 1 (8-byte
+    // cells: the bytes in flight of ONE slice already fill the wave's share).  Not measured below 60,000 slices: 1.  Complex: 1.
+    int spw = 1;
+    if constexpr(!COMPLEX)
+    {
+        if(nslices >= SELL_SHORT_SPW_SLICES)
+            spw = sizeof(T) == 4 ? (TAB != 0 ? 4 : 2) : (TAB != 0 ? 2 : 1);
+        if(sell_short_spw_override())
+            spw = sell_short_spw_override();
+    }
+    const long long per_wg = (long long)WAVES * spw;
+    const int       groups = (int)((nslices + per_wg - 1) / per_wg);
+    const dim3      grid((unsigned)groups), block(64 * WAVES);
+    const int       g0 = rev ? groups - 1 : 0, gstep = rev ? -1 : 1;
+    const uint4    *dp = reinterpret_cast<const uint4 *>(desc);
+#define MI355_SHORT_SPW(W, SPW)                                                                                                 \
+    hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SPW, CONJ, TAB>), grid, block, 0, s, m, nslices, g0, gstep, dp, sval, \
+                       scol, lead, alpha, x, beta, y, nt, vtab)
+#define MI355_SHORT(W)                      \
+    case W:                                 \
+        if constexpr(!COMPLEX)              \
+        {                                   \
+            if(spw == 4)                    \
+            {                               \
+                MI355_SHORT_SPW(W, 4);      \
+                return true;                \
+            }                               \
+            if(spw == 2)                    \
+            {                               \
+                MI355_SHORT_SPW(W, 2);      \
+                return true;                \
+            }                               \
+        }                                   \
+        MI355_SHORT_SPW(W, 1);              \
         return true
     switch(wmax)
     {
@@ -764,6 +866,7 @@ bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int
     default: return false;
     }
 #undef MI355_SHORT
+#undef MI355_SHORT_SPW
 }
 
 template <typename T, int ORDER, int PACK, bool IDX>
@@ -871,7 +974,7 @@ aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoc
                                 const long long *slice_ptr, const T *sval, const aoclsparse_int *scol,
                                 const aoclsparse_int *rowlen, const T *x, T beta, T *y, const long long *cptr,
                                 const unsigned short *lead, aoclsparse_int max_width, int rev, const unsigned char *sidx,
-                                const T *vtab)
+                                const T *vtab, const SellSliceDesc *desc, int ntab)
 {
     if(m <= 0 || nslices <= 0)
         return aoclsparse_status_success;
@@ -885,15 +988,19 @@ aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoc
             cells = sidx;
         else
             cells = sval;
-        // widest slice <= 8 cells, scalar order, a launch large enough that four slices per workgroup still spread over every CU
-        if(order == 0 && pack == 1 && max_width >= 1 && max_width <= 8 && nslices >= 4096)
+        // the plan has slice records (build_sell: widest slice <= 8 cells, pack 1, a launch large enough that four slices per
+        // workgroup still spread over every CU) and the order is the scalar one: the short-row kernel
+        if(order == 0 && pack == 1 && desc)
         {
             const bool nt = (size_t)m * sizeof(T) > ((size_t)32 << 20);
-            const bool done
-                = cptr ? sell_launch_short<T, true, IDX>(s, (int)max_width, m, nslices, slice_ptr, cells, scol, alpha, x, beta, y, nt,
-                                                         cptr, lead, rev, vtab)
-                       : sell_launch_short<T, false, IDX>(s, (int)max_width, m, nslices, slice_ptr, cells, scol, alpha, x, beta, y, nt,
-                                                          nullptr, nullptr, rev, vtab);
+            bool       done;
+            if constexpr(!IDX)
+                done = sell_launch_short<T, 0>(s, (int)max_width, m, nslices, desc, cells, scol, alpha, x, beta, y, nt, lead, rev, vtab);
+            else if(ntab <= 2)
+                done = sell_launch_short<T, 2>(s, (int)max_width, m, nslices, desc, cells, scol, alpha, x, beta, y, nt, lead, rev, vtab);
+            else
+                done = sell_launch_short<T, SELL_VTAB_MAX>(s, (int)max_width, m, nslices, desc, cells, scol, alpha, x, beta, y, nt, lead,
+                                                           rev, vtab);
             if(done)
                 return;
         }
@@ -925,13 +1032,14 @@ aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoc
     return aoclsparse_status_success;
 }
 
-// aoclsparse_{c,z}mv on the SELL-64 copy (PACK 1, the scalar chain per row): the short-row kernel for large launches whose
-// widest slice has <= 8 cells, the general kernel otherwise
+// aoclsparse_{c,z}mv on the SELL-64 copy (PACK 1, the scalar chain per row): the short-row kernel where the plan has slice
+// records (large launches whose widest slice has <= 8 cells), the general kernel otherwise
 template <typename R>
 aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha, aoclsparse_int m, aoclsparse_int nslices,
                                         const long long *slice_ptr, const cplx<R> *sval, const aoclsparse_int *scol,
                                         const aoclsparse_int *rowlen, const cplx<R> *x, cplx<R> beta, cplx<R> *y,
-                                        const long long *cptr, const unsigned short *lead, aoclsparse_int max_width, int rev)
+                                        const long long *cptr, const unsigned short *lead, aoclsparse_int max_width, int rev,
+                                        const SellSliceDesc *desc)
 {
     using C = cplx<R>;
     if(m <= 0 || nslices <= 0)
@@ -941,28 +1049,8 @@ aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha,
         constexpr bool SH = decltype(shared_tag)::value, CJ = decltype(conj_tag)::value;
         const long long      *cp = SH ? cptr : nullptr;
         const unsigned short *ld = SH ? lead : nullptr;
-        if(max_width >= 1 && max_width <= 8 && nslices >= 4096)
-        {
-            constexpr int WAVES = 4;
-            const dim3    grid((unsigned)((nslices + WAVES - 1) / WAVES)), block(64 * WAVES);
-#define MI355_CSHORT(W)                                                                                                          \
-    case W:                                                                                                                      \
-        hipLaunchKernelGGL((sell_mv_short_kernel<C, W, WAVES, SH, 1, CJ>), grid, block, 0, s, m, nslices, slice_ptr, sval, scol, \
-                           alpha, x, beta, y, nt, cp, ld, rev);                                                                  \
-        return
-            switch((int)max_width)
-            {
-                MI355_CSHORT(1);
-                MI355_CSHORT(2);
-                MI355_CSHORT(3);
-                MI355_CSHORT(4);
-                MI355_CSHORT(5);
-                MI355_CSHORT(6);
-                MI355_CSHORT(7);
-                MI355_CSHORT(8);
-            }
-#undef MI355_CSHORT
-        }
+        if(desc && sell_launch_short<C, 0, CJ>(s, (int)max_width, m, nslices, desc, sval, scol, alpha, x, beta, y, nt, ld, rev, nullptr))
+            return;
         if(nslices < 2048)
             hipLaunchKernelGGL((sell_mv_kernel<C, 0, 1, 1, SH, CJ>), dim3(nslices), dim3(64), 0, s, m, nslices, slice_ptr, sval, scol,
                                rowlen, alpha, x, beta, y, nt, cp, ld, rev);
@@ -987,10 +1075,11 @@ aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha,
 template aoclsparse_status launch_sellmv_complex<double>(hipStream_t, bool, cdouble, aoclsparse_int, aoclsparse_int, const long long *,
                                                          const cdouble *, const aoclsparse_int *, const aoclsparse_int *,
                                                          const cdouble *, cdouble, cdouble *, const long long *,
-                                                         const unsigned short *, aoclsparse_int, int);
+                                                         const unsigned short *, aoclsparse_int, int, const SellSliceDesc *);
 template aoclsparse_status launch_sellmv_complex<float>(hipStream_t, bool, cfloat, aoclsparse_int, aoclsparse_int, const long long *,
                                                         const cfloat *, const aoclsparse_int *, const aoclsparse_int *, const cfloat *,
-                                                        cfloat, cfloat *, const long long *, const unsigned short *, aoclsparse_int, int);
+                                                        cfloat, cfloat *, const long long *, const unsigned short *, aoclsparse_int, int,
+                                                        const SellSliceDesc *);
 // (the fill kernels only move values: cfloat cells are filled as 8-byte doubles, cdouble cells need their own instantiation)
 template aoclsparse_status launch_sell_fill<cdouble>(hipStream_t, int, aoclsparse_int, int, const aoclsparse_int *, const aoclsparse_int *,
                                                      const cdouble *, aoclsparse_int, const long long *, cdouble *, aoclsparse_int *,
@@ -1017,7 +1106,7 @@ aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base,
                                                 const long long *, const T *, const aoclsparse_int *,                 \
                                                 const aoclsparse_int *, const T *, T, T *, const long long *,          \
                                                 const unsigned short *, aoclsparse_int, int, const unsigned char *,    \
-                                                const T *);
+                                                const T *, const SellSliceDesc *, int);
 MI355_SELL_INSTANTIATE(double)
 MI355_SELL_INSTANTIATE(float)
 

@@ -121,7 +121,7 @@ aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const Devic
                               static_cast<T *>(ay.dev), plan.sell.shared ? plan.sell.cptr.as<long long>() : nullptr,
                               plan.sell.shared ? plan.sell.lead.as<unsigned short>() : nullptr, plan.max_row_nnz,
                               plan.sell.next_direction(), plan.sell.ntab ? plan.sell.vidx.as<unsigned char>() : nullptr,
-                              plan.sell.ntab ? plan.sell.vtab.as<T>() : nullptr);
+                              plan.sell.ntab ? plan.sell.vtab.as<T>() : nullptr, plan.sell.desc.as<SellSliceDesc>(), plan.sell.ntab);
     else if(plan.merge.valid && order == 0 && !strict) // balanced tiles for irregular rows (scalar order, no pinned kid)
     {
         // one launch; the pieces of cut rows meet in the piece set of this stream (internal.hpp, MergePlan).  Finding the set

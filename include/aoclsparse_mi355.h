@@ -332,6 +332,15 @@ DLL_PUBLIC aoclsparse_int mi355_csrmv_plan_host(aoclsparse_int        m,
                                                 aoclsparse_int        tile,
                                                 const aoclsparse_int *row_ptr_host,
                                                 aoclsparse_int       *blocks_host);
+/* The slice records of a SELL-64 copy as aoclsparse_optimize packs them for the short-row SpMV kernel, from host arrays (no device
+ * involved): slice_ptr = nslices + 1 cell offsets (64 x width each); leaders[s] = column lists of slice s | mode << 8 (mode 0: a table
+ * says which list a row follows and with which column shift, 1: one list, shift = row within the slice, 2: one list, no shift), or NULL
+ * when every row keeps its own list (mode 3: a cell's column entry sits at the cell's offset); column_entries = column entries in all.
+ * A record is four 32-bit words {cell offset bits 0-31, column offset bits 0-31, cell offset bits 32-47 | column offset bits 32-47 << 16,
+ * width | column stride << 8 | mode << 16}.  Returns the number of records written, nslices + the padding (empty slices that start
+ * at the end of both arrays); records == NULL only returns that number; < 0 on error. */
+DLL_PUBLIC aoclsparse_int mi355_sell_slice_records(aoclsparse_int nslices, const long long *slice_ptr, const aoclsparse_int *leaders,
+                                                   long long column_entries, unsigned int *records);
 /* y = alpha*A*x + beta*y; order: 0 scalar chain, 1 4-lane, 2 8-lane (reference kid 0 / 1,2 / 3);
  * strict != 0 keeps the reference order for rows longer than one LDS tile too; tile must be the
  * value the plan was built with; blocks is the DEVICE copy of the plan. */
