@@ -118,12 +118,8 @@ aoclsparse_status cmv_t(aoclsparse_operation op, const cplx<R> *alpha, aoclspars
     MI355_TRY(ax.in(rt, 3, x, sizeof(C) * (size_t)dcsr->n, true));
     MI355_TRY(ay.in(rt, 4, y, sizeof(C) * (size_t)dcsr->m, !b0));
     if(plan && plan->sell.valid)
-        MI355_TRY(launch_sellmv_complex<R>(rt.stream(), conj, *alpha, dcsr->m, plan->sell.nslices, plan->sell.slice_ptr.as<long long>(),
-                                           plan->sell.val.as<C>(), plan->sell.col.as<aoclsparse_int>(),
-                                           plan->sell.rowlen.as<aoclsparse_int>(), static_cast<const C *>(ax.dev), *beta,
-                                           static_cast<C *>(ay.dev), plan->sell.shared ? plan->sell.cptr.as<long long>() : nullptr,
-                                           plan->sell.shared ? plan->sell.lead.as<unsigned short>() : nullptr, plan->max_row_nnz,
-                                           plan->sell.next_direction(), plan->sell.desc.as<SellSliceDesc>()));
+        MI355_TRY(launch_sellmv<C>(rt.stream(), plan->sell.view(dcsr->m, plan->max_row_nnz), 0, conj, *alpha, static_cast<const C *>(ax.dev),
+                                   *beta, static_cast<C *>(ay.dev), plan->sell.next_direction()));
     else
         MI355_TRY(launch_cspmv<R>(rt.stream(), dcsr->base, conj, *alpha, dcsr->m, dcsr->nnz, dcsr->val.as<C>(),
                                   dcsr->ind.as<aoclsparse_int>(), dcsr->ptr.as<aoclsparse_int>(),

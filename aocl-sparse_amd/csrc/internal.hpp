@@ -271,6 +271,9 @@ struct SellSliceDesc
 };
 // modes: 0 lead[row] = list | shift << 8; 1 one list, shift = lane; 2 one list, no shift; 3 list = lane, no shift (lists not shared)
 constexpr int            SELL_DESC_MODE_FOLLOW = 0, SELL_DESC_MODE_LANE_SHIFT = 1, SELL_DESC_MODE_ONE = 2, SELL_DESC_MODE_OWN = 3;
+// the general kernel reads the same mode (0 / 1 / 2) from the top byte of a slice's cptr word, the offset from the bits below
+constexpr int            SELL_CPTR_MODE_SHIFT = 56;
+constexpr long long      SELL_CPTR_MASK       = (1LL << SELL_CPTR_MODE_SHIFT) - 1;
 constexpr int            SELL_SHORT_WMAX       = 8;
 constexpr aoclsparse_int SELL_SHORT_MIN_SLICES = 4096;
 // records after the last slice (width 0, pointing at the padding cells): the last workgroup's 4 waves x 4 slices read them
@@ -283,8 +286,25 @@ constexpr int            SELL_CELL_PAD = 64;
 void sell_pack_descriptors(aoclsparse_int nslices, const long long *slice_ptr, const aoclsparse_int *leaders, long long ccells,
                            SellSliceDesc *out);
 
-// SELL-64 twin of a device CSR (sell_kernels.hip): built by aoclsparse_optimize for an mv hint when the
-// padding stays small; the handle's ?mv then runs on it instead of the CSR-Adaptive kernel.
+// What a SELL-64 launcher reads of a plan (SellPlan::view): sizes and device pointers, nothing owned.
+struct SellView
+{
+    aoclsparse_int        m = 0, nslices = 0;
+    int                   pack = 1;
+    aoclsparse_int        max_width = 0; // widest slice, in cells per row
+    int                   ntab = 0;
+    const long long      *slice_ptr = nullptr;
+    const void           *cells = nullptr; // the values, or (ntab > 0) the one-byte indices into vtab
+    const aoclsparse_int *col = nullptr, *rowlen = nullptr;
+    const long long      *cptr = nullptr; // cptr, lead: nullptr when the column lists are not shared
+    const unsigned short *lead = nullptr;
+    const void           *vtab = nullptr; // nullptr without a table
+    const SellSliceDesc  *desc = nullptr; // nullptr when the plan has no slice records
+};
+
+// SELL-64 twin of a device CSR (matrix.cpp: build_sell; layout in sell_build_kernels.hip, products in sell_kernels.hip): built by
+// aoclsparse_optimize for an mv hint when the padding stays small; the handle's ?mv then runs on it instead of the CSR-Adaptive
+// kernel.
 struct SellPlan
 {
     aoclsparse_int nslices = 0;
@@ -293,12 +313,12 @@ struct SellPlan
     DeviceBuffer   slice_ptr; // nslices+1 cell offsets (long long)
     DeviceBuffer   val, col; // cells values / 0-based columns (-1 = padding)
     DeviceBuffer   rowlen; // m row lengths (read by the 4- and 8-lane orders only)
-    // shared column lists (sell_kernels.hip): col holds one list per leader lane of a slice, ccells entries in all;
+    // shared column lists (sell_build_kernels.hip): col holds one list per leader lane of a slice, ccells entries in all;
     // cptr = nslices+1 offsets into it, lead = m x 16 bits (leader index of a row inside its slice | column shift << 8)
     bool           shared = false;
     long long      ccells = 0;
     DeviceBuffer   cptr, lead;
-    // value table (sell_kernels.hip): ntab > 0 -> vidx holds one byte per cell (same cell order and offsets as val would) indexing
+    // value table (sell_build_kernels.hip): ntab > 0 -> vidx holds one byte per cell (same cell order and offsets as val would) indexing
     // vtab, ntab values sorted by bit pattern, and val is not allocated; ntab = 0 -> the values are in val
     int            ntab = 0;
     DeviceBuffer   vtab, vidx;
@@ -311,6 +331,20 @@ struct SellPlan
     // Infinity Cache (the END of its sweep) is where the next one starts (sell_kernels.hip); the bits do not depend on it
     mutable std::atomic<unsigned> products{0};
     int next_direction() const;
+    // m = rows of the CSR this copy mirrors, max_width = its longest row
+    SellView view(aoclsparse_int m, aoclsparse_int max_width) const
+    {
+        SellView v;
+        v.m = m, v.nslices = nslices, v.pack = pack, v.max_width = max_width, v.ntab = ntab;
+        v.slice_ptr = slice_ptr.as<long long>();
+        v.cells     = ntab ? vidx.ptr : val.ptr;
+        v.col = col.as<aoclsparse_int>(), v.rowlen = rowlen.as<aoclsparse_int>();
+        v.cptr = shared ? cptr.as<long long>() : nullptr;
+        v.lead = shared ? lead.as<unsigned short>() : nullptr;
+        v.vtab = ntab ? vtab.ptr : nullptr;
+        v.desc = desc.as<SellSliceDesc>();
+        return v;
+    }
 };
 
 // csrmm row groups (csrmm_kernels.hip: csrmm_rowgroup_kernel): runs of consecutive rows with one column pattern
@@ -834,34 +868,21 @@ aoclsparse_status launch_csrmv(hipStream_t s, int order, bool strict, int tile, 
                                aoclsparse_int max_row_nnz = 1 << 30, unsigned int *stale = nullptr);
 // (stale != nullptr: the block table is a cached plan of a raw-array call -- every workgroup validates its own entry against
 // the live row_ptr, computes its rows from the live arrays on a mismatch and sets *stale, a pinned host word)
-template <typename T>
-aoclsparse_status launch_sell_fill(hipStream_t s, int pack, aoclsparse_int m, int base, const aoclsparse_int *row_ptr,
-                                   const aoclsparse_int *col, const T *val, aoclsparse_int nslices,
-                                   const long long *slice_ptr, T *sval, aoclsparse_int *scol, aoclsparse_int *rowlen,
-                                   const long long *cptr = nullptr, const unsigned short *lead = nullptr,
-                                   unsigned char *sidx = nullptr, const T *vtab = nullptr, int ntab = 0);
-// (sidx != nullptr: the cells get one-byte indices into vtab, ntab entries sorted by bit pattern, instead of the values; sval unused)
-// distinct bit patterns of n values of vsize (4 / 8) bytes on the device: *ntab of them, ascending, in table (room for
-// SELL_VTAB_MAX words); *ntab = 0 when there are more than SELL_VTAB_MAX
+// SELL-64 plan kernels (sell_build_kernels.hip)
+// fills the cells, columns and row lengths of the copy v describes from d (values of vsize bytes; cells / col / rowlen are v's
+// arrays, writable); with a table (v.ntab > 0) the cells get one-byte indices into it instead of the values
+aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
+                                   aoclsparse_int *rowlen);
+// distinct bit patterns of n values of vsize (4 / 8) bytes on the device: *ntab of them; table = SELL_VTAB_MAX entries of vsize
+// bytes ready to upload, ascending by bit pattern, the unused ones 0; *ntab = 0 when there are more than SELL_VTAB_MAX
 constexpr int     SELL_VTAB_MAX = 256;
-aoclsparse_status sell_value_table(hipStream_t s, size_t vsize, long long n, const void *val, unsigned long long *table, int *ntab);
-template <typename R>
-aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha, aoclsparse_int m, aoclsparse_int nslices,
-                                        const long long *slice_ptr, const cplx<R> *sval, const aoclsparse_int *scol,
-                                        const aoclsparse_int *rowlen, const cplx<R> *x, cplx<R> beta, cplx<R> *y,
-                                        const long long *cptr, const unsigned short *lead, aoclsparse_int max_width, int rev = 0,
-                                        const SellSliceDesc *desc = nullptr);
+aoclsparse_status sell_value_table(hipStream_t s, size_t vsize, long long n, const void *val, void *table, int *ntab);
 aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base, const aoclsparse_int *row_ptr, const aoclsparse_int *col,
                                       aoclsparse_int nslices, unsigned short *lead, aoclsparse_int *nl);
+// y = alpha op(A) x + beta y on the SELL-64 copy (sell_kernels.hip): double, float, cdouble, cfloat.  conj: complex T only;
+// complex copies are pack 1 without a table and run order 0.  Order 0 on a plan with slice records runs the short-row kernel.
 template <typename T>
-aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoclsparse_int m, aoclsparse_int nslices,
-                                const long long *slice_ptr, const T *sval, const aoclsparse_int *scol,
-                                const aoclsparse_int *rowlen, const T *x, T beta, T *y, const long long *cptr = nullptr,
-                                const unsigned short *lead = nullptr,
-                                aoclsparse_int max_width = 0, int rev = 0, const unsigned char *sidx = nullptr,
-                                const T *vtab = nullptr, const SellSliceDesc *desc = nullptr, int ntab = 0);
-// (vtab != nullptr: the cells are sidx, one-byte indices into vtab (ntab entries, SELL_VTAB_MAX allocated); sval is not read)
-// (desc != nullptr: the plan's slice records -- order 0 then runs the short-row kernel)
+aoclsparse_status launch_sellmv(hipStream_t s, const SellView &v, int order, bool conj, T alpha, const T *x, T beta, T *y, int rev);
 // BLKCSR (blk_kernels.hip): value offset of every block (three small launches: per-chunk popcount scan, scan of
 // the chunk totals in part[], add), then the product
 constexpr int     BLK_PART_SHIFT = 10;

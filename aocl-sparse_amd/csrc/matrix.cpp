@@ -770,8 +770,8 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
             std::fprintf(stderr, "[mi355 timing] sell: %lld cells, %lld column cells with shared lists (%d slices)\n", cells, ctotal, (int)nslices);
         if((double)ctotal <= 0.7 * (double)cells)
         {
-            for(aoclsparse_int s = 0; s < nslices; s++) // the slice's mode (sell_kernels.hip) rides in the top byte
-                cptr[s] |= (long long)(nlh[s] >> 8) << 56;
+            for(aoclsparse_int s = 0; s < nslices; s++) // the slice's mode rides in the top byte
+                cptr[s] |= (long long)(nlh[s] >> 8) << SELL_CPTR_MODE_SHIFT;
             sp.shared = true, sp.ccells = ctotal;
             st        = sp.cptr.upload(cptr.data(), sizeof(long long) * cptr.size(), rt.stream());
         }
@@ -779,30 +779,17 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
             sp.lead.release();
     }
     // Value table: at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil holds two) -> one byte per cell instead
-    // of 4 / 8 (sell_kernels.hip).  Real types only; the same size gate as the shared lists (a matrix that lives in the caches gains
+    // of 4 / 8 (sell_build_kernels.hip).  Real types only; the same size gate as the shared lists (a matrix that lives in the caches gains
     // nothing); aoclsparse_mi355_set_option(sell_values, 0 / 1): never / whatever the size.  One pass over the device values.
     const int vmode = plan_option(aoclsparse_mi355_option_sell_values); // -1 automatic (default), 0 never, 1 whatever the size
     if(st == aoclsparse_status_success && !complex_values && (vsize == sizeof(double) || vsize == sizeof(float)) && vmode != 0
        && (vmode == 1 || d.nnz >= (1 << 17)))
     {
-        unsigned long long bits[SELL_VTAB_MAX];
-        int                ntab = 0;
-        st = sell_value_table(rt.stream(), vsize, d.nnz, d.val.ptr, bits, &ntab);
+        unsigned char tab[sizeof(double) * SELL_VTAB_MAX];
+        int           ntab = 0;
+        st = sell_value_table(rt.stream(), vsize, d.nnz, d.val.ptr, tab, &ntab);
         if(st == aoclsparse_status_success && ntab > 0)
         {
-            unsigned char tab[sizeof(double) * SELL_VTAB_MAX];
-            for(int k = 0; k < ntab; k++) // (the low vsize bytes of each word: the pattern of a float or a double)
-            {
-                if(vsize == sizeof(float))
-                {
-                    const unsigned u = (unsigned)bits[k];
-                    std::memcpy(tab + sizeof(float) * k, &u, sizeof(float));
-                }
-                else
-                    std::memcpy(tab + sizeof(double) * k, &bits[k], sizeof(double));
-            }
-            // (SELL_VTAB_MAX entries whatever ntab is, the unused ones 0: the short-row kernel copies the whole table to LDS)
-            std::memset(tab + vsize * (size_t)ntab, 0, vsize * (size_t)(SELL_VTAB_MAX - ntab));
             st = sp.vtab.upload(tab, vsize * (size_t)SELL_VTAB_MAX, rt.stream());
             if(st == aoclsparse_status_success)
                 st = sp.vidx.alloc((size_t)cells + SELL_CELL_PAD);
@@ -847,26 +834,13 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         if(st != aoclsparse_status_success)
             return st;
     }
-    const long long     *cp = sp.shared ? sp.cptr.as<long long>() : nullptr;
-    const unsigned short *ld = sp.shared ? sp.lead.as<unsigned short>() : nullptr;
-    if(vsize == sizeof(cdouble))
-        st = launch_sell_fill<cdouble>(rt.stream(), pack, m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(),
-                                       d.val.as<cdouble>(), nslices, sp.slice_ptr.as<long long>(), sp.val.as<cdouble>(),
-                                       sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld);
-    else if(vsize == sizeof(float))
-        st = launch_sell_fill<float>(rt.stream(), pack, m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(),
-                                     d.val.as<float>(), nslices, sp.slice_ptr.as<long long>(), sp.val.as<float>(),
-                                     sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld,
-                                     sp.ntab ? sp.vidx.as<unsigned char>() : nullptr, sp.vtab.as<float>(), sp.ntab);
-    else
-        st = launch_sell_fill<double>(rt.stream(), pack, m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(),
-                                      d.val.as<double>(), nslices, sp.slice_ptr.as<long long>(), sp.val.as<double>(),
-                                      sp.col.as<aoclsparse_int>(), sp.rowlen.as<aoclsparse_int>(), cp, ld,
-                                      sp.ntab ? sp.vidx.as<unsigned char>() : nullptr, sp.vtab.as<double>(), sp.ntab);
+    sp.nslices = nslices, sp.cells = cells, sp.pack = pack;
+    st = launch_sell_fill(rt.stream(), d, vsize, sp.view(m, plan.max_row_nnz), sp.ntab ? sp.vidx.ptr : sp.val.ptr, sp.col.as<aoclsparse_int>(),
+                          sp.rowlen.as<aoclsparse_int>());
     if(st != aoclsparse_status_success)
         return st;
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr / desc (host) are read by the uploads until here
-    sp.nslices = nslices, sp.cells = cells, sp.pack = pack, sp.valid = sp.wanted = true;
+    sp.valid = sp.wanted = true;
     return aoclsparse_status_success;
 }
 

@@ -1,0 +1,386 @@
+// sell_build_kernels.hip -- plan-time kernels of the SELL-64 copy (matrix.cpp: build_sell); the products are in sell_kernels.hip.
+//
+// The layout: sliced ELL with one slice per 64-wide wavefront.  Slice s holds rows [64 s, 64 s + 64) column-major, cell (p, lane) at
+// slice_ptr[s] + 64 p + lane, padded to the slice's longest row (column -1, value 0); matrices with >= 16 non-zeros per row keep
+// four consecutive cells of a row adjacent instead (PACK 4: cell at slice_ptr[s] + 256 (p/4) + 4 lane + p%4, width rounded up to a
+// multiple of 4), so that a wavefront's load is one contiguous 2 KB piece -- the in-flight slices of a long-row matrix are otherwise
+// 512-byte accesses strided by the slice size, which costs HBM page locality.  Lane i of a wave owns row i.
+#include "internal.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+namespace mi355
+{
+
+namespace
+{
+
+// ---- value tables (SELL-64 with one byte per cell: an index into <= 256 distinct value bit patterns) ---------------------
+// A matrix whose values take at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil: two) stores one byte
+// per cell and a table sorted by ascending bit pattern; the kernels read table[index], i.e. the very bits of the value, so every
+// summation order gives the same results as with the values stored in the cells (CSR-VI, Kourtis, Goumas and Koziris, CF 2008).
+// Bit patterns, not values: -0.0 and +0.0 are two entries, NaN payloads are kept.
+template <typename T>
+using vbits_t = std::conditional_t<sizeof(T) == 8, unsigned long long, unsigned>;
+
+// index of v in the sorted table (v is in it: the table holds every pattern of the matrix)
+template <typename T>
+__device__ __forceinline__ unsigned char vtab_index(T v, const T *__restrict__ vtab, int ntab)
+{
+    using U     = vbits_t<T>;
+    const U key = __builtin_bit_cast(U, v);
+    int     lo = 0, hi = ntab - 1;
+    while(lo < hi)
+    {
+        const int mid = (lo + hi) >> 1;
+        if(__builtin_bit_cast(U, vtab[mid]) < key)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return (unsigned char)lo;
+}
+
+// writes cell o: the value, or (sidx) its table index; padding cells hold 0 / index 0 (their column is -1: never used)
+template <typename T>
+__device__ __forceinline__ void fill_cell(long long o, bool in, const T *__restrict__ vp, T *__restrict__ sval,
+                                          unsigned char *__restrict__ sidx, const T *__restrict__ vtab, int ntab)
+{
+    if constexpr(std::is_floating_point_v<T>)
+    {
+        if(sidx)
+        {
+            sidx[o] = in ? vtab_index(*vp, vtab, ntab) : (unsigned char)0;
+            return;
+        }
+    }
+    sval[o] = in ? *vp : T(0);
+}
+
+// Distinct bit patterns of n values, on the device: every workgroup collects what it sees in an LDS hash set, then merges it
+// into the global set (VT_SLOTS entries, VT_EMPTY = free).  state[0] = patterns in the global set, state[1] = 1 once more than
+// SELL_VTAB_MAX patterns were seen (everyone stops early), state[2] = 1 if the pattern VT_EMPTY itself (a double NaN) occurs.
+// A set that fills up also means "more than SELL_VTAB_MAX": a set has 4 x the slots that can be taken before a stop is seen.
+constexpr int                VT_LDS_SLOTS  = 1024;
+constexpr int                VT_SLOTS      = 4096;
+constexpr unsigned long long VT_EMPTY      = ~0ull;
+
+__device__ __forceinline__ unsigned vt_hash(unsigned long long k)
+{
+    k ^= k >> 33; // (murmur3's finaliser: the patterns of simple doubles differ in their top bits only)
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return (unsigned)k;
+}
+
+// 1: k was inserted, 0: it was there already, -1: the set is full
+__device__ __forceinline__ int vt_insert(unsigned long long *set, int slots, unsigned long long k)
+{
+    unsigned h = vt_hash(k) & (unsigned)(slots - 1);
+    for(int probe = 0; probe < slots; probe++)
+    {
+        unsigned long long cur = __hip_atomic_load(set + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if(cur == k)
+            return 0;
+        if(cur == VT_EMPTY)
+        {
+            cur = atomicCAS(set + h, VT_EMPTY, k);
+            if(cur == VT_EMPTY)
+                return 1;
+            if(cur == k)
+                return 0;
+        }
+        h = (h + 1) & (unsigned)(slots - 1);
+    }
+    return -1;
+}
+
+template <typename U>
+__global__ __launch_bounds__(256) void sell_vtab_count_kernel(long long n, const U *__restrict__ val, unsigned long long *__restrict__ set,
+                                                              unsigned *__restrict__ state)
+{
+    constexpr int                 UNR = 4;
+    __shared__ unsigned long long lset[VT_LDS_SLOTS];
+    __shared__ int                lcount, lstop, lempty;
+    for(int k = threadIdx.x; k < VT_LDS_SLOTS; k += blockDim.x)
+        lset[k] = VT_EMPTY;
+    if(threadIdx.x == 0)
+        lcount = 0, lstop = 0, lempty = 0;
+    __syncthreads();
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for(long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += UNR * stride)
+    {
+        if(__hip_atomic_load(&lstop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+           || __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            break;
+        unsigned long long k[UNR];
+#pragma unroll
+        for(int u = 0; u < UNR; u++)
+            k[u] = (unsigned long long)val[i0 + u * stride < n ? i0 + u * stride : i0];
+#pragma unroll
+        for(int u = 0; u < UNR; u++)
+        {
+            if(k[u] == VT_EMPTY)
+            {
+                lempty = 1;
+                continue;
+            }
+            const int r = vt_insert(lset, VT_LDS_SLOTS, k[u]);
+            if(r < 0 || (r > 0 && atomicAdd(&lcount, 1) + 1 > SELL_VTAB_MAX))
+                lstop = 1;
+        }
+    }
+    __syncthreads();
+    if(lstop)
+    {
+        if(threadIdx.x == 0)
+            atomicOr(state + 1, 1u);
+        return;
+    }
+    if(threadIdx.x == 0 && lempty)
+        atomicOr(state + 2, 1u);
+    for(int k = threadIdx.x; k < VT_LDS_SLOTS; k += blockDim.x)
+    {
+        const unsigned long long key = lset[k];
+        if(key == VT_EMPTY || __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            continue;
+        const int r = vt_insert(set, VT_SLOTS, key);
+        if(r < 0 || (r > 0 && atomicAdd(state, 1u) + 1u > (unsigned)SELL_VTAB_MAX))
+            atomicOr(state + 1, 1u);
+    }
+}
+
+} // namespace
+
+aoclsparse_status sell_value_table(hipStream_t s, size_t vsize, long long n, const void *val, void *table, int *ntab)
+{
+    *ntab = 0;
+    if(vsize != 4 && vsize != 8)
+        return aoclsparse_status_success;
+    // (SELL_VTAB_MAX entries whatever *ntab is, the unused ones 0: the short-row kernel copies the whole table to LDS)
+    std::memset(table, 0, vsize * (size_t)SELL_VTAB_MAX);
+    if(n <= 0)
+        return aoclsparse_status_success;
+    DeviceBuffer      set;
+    aoclsparse_status st = set.alloc(sizeof(unsigned long long) * VT_SLOTS + 4 * sizeof(unsigned));
+    if(st != aoclsparse_status_success)
+        return st;
+    unsigned long long *d_set   = set.as<unsigned long long>();
+    unsigned           *d_state = reinterpret_cast<unsigned *>(d_set + VT_SLOTS);
+    MI355_HIP_TRY(hipMemsetAsync(d_set, 0xff, sizeof(unsigned long long) * VT_SLOTS, s)); // VT_EMPTY everywhere
+    MI355_HIP_TRY(hipMemsetAsync(d_state, 0, 4 * sizeof(unsigned), s));
+    // a few workgroups per CU, each walking the values with a grid stride (a workgroup that has seen > 256 patterns stops all)
+    const long long blocks = std::min<long long>(2048, std::max<long long>(1, (n + 1023) / 1024));
+    if(vsize == 8)
+        hipLaunchKernelGGL(sell_vtab_count_kernel<unsigned long long>, dim3((unsigned)blocks), dim3(256), 0, s, n,
+                           static_cast<const unsigned long long *>(val), d_set, d_state);
+    else
+        hipLaunchKernelGGL(sell_vtab_count_kernel<unsigned>, dim3((unsigned)blocks), dim3(256), 0, s, n,
+                           static_cast<const unsigned *>(val), d_set, d_state);
+    MI355_HIP_TRY(hipGetLastError());
+    unsigned state[4];
+    MI355_HIP_TRY(hipMemcpyAsync(state, d_state, sizeof(state), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if(state[1] || state[0] + state[2] > (unsigned)SELL_VTAB_MAX)
+        return aoclsparse_status_success;
+    std::vector<unsigned long long> h((size_t)VT_SLOTS);
+    MI355_HIP_TRY(hipMemcpyAsync(h.data(), d_set, sizeof(unsigned long long) * VT_SLOTS, hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    int k = 0;
+    unsigned long long bits[SELL_VTAB_MAX];
+    for(unsigned long long v : h)
+        if(v != VT_EMPTY && k < SELL_VTAB_MAX)
+            bits[k++] = v;
+    if(state[2] && k < SELL_VTAB_MAX)
+        bits[k++] = VT_EMPTY;
+    std::sort(bits, bits + k); // (ascending bit pattern: the plan does not depend on the order the device found them in)
+    for(int e = 0; e < k; e++) // (the low vsize bytes of each word: the pattern of a float or a double)
+    {
+        const unsigned lo = (unsigned)bits[e];
+        if(vsize == 4)
+            std::memcpy(static_cast<unsigned char *>(table) + 4 * e, &lo, 4);
+        else
+            std::memcpy(static_cast<unsigned char *>(table) + 8 * e, &bits[e], 8);
+    }
+    *ntab = k;
+    return aoclsparse_status_success;
+}
+
+namespace
+{
+
+// ---- shared column lists (SELL-64 with one column list per run of rows that repeat it) --------------------------------
+// Two kinds of repetition, found the same way: the rows of a mesh node (several dofs) carry the SAME column list, and the
+// rows of a stencil carry the list of the row before SHIFTED BY ONE (row i of a 5-point Laplacian: i-g, i-1, i, i+1, i+g).
+// A slice stores its columns once per "leader" (lane 0, and every lane whose list is neither the previous lane's nor the
+// previous lane's plus one): cell (p, leader k) of slice s at cptr[s] + nl_s p + k (PACK 4: cptr[s] + 4 nl_s (p / 4) + 4 k
+// + p % 4).  follow[i] (16 bits per row) = leader index inside the slice | shift << 8, where shift = how many of the rows
+// between the leader and row i were "plus one" steps: a lane's column is its leader's + shift.  Values stay where they are.
+// The column stream shrinks from 4 B per cell to 4 B / (rows per list): 12 -> 8.8 B per cell for 5-dof nodes, 12 -> ~8.1 B for
+// the Laplacian (one list per 64 rows, broken at the grid edges).
+// One wavefront per slice: each lane compares its row with its predecessor, indices and shifts by ballot + popcount.
+__global__ __launch_bounds__(256) void sell_leaders_kernel(aoclsparse_int m, int base, const aoclsparse_int *__restrict__ row_ptr,
+                                                           const aoclsparse_int *__restrict__ col, aoclsparse_int nslices,
+                                                           unsigned short *__restrict__ follow, aoclsparse_int *__restrict__ nl)
+{
+    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if(s >= nslices)
+        return;
+    const int i      = s * 64 + lane;
+    bool      leader = false, plus1 = false;
+    if(i < m)
+    {
+        leader = lane == 0;
+        if(!leader)
+        {
+            const int b = row_ptr[i] - base, len = row_ptr[i + 1] - base - b, bp = row_ptr[i - 1] - base;
+            bool      same = len == b - bp, shifted = same && len > 0; // (column VALUES: only differences are used)
+            for(int k = 0; k < len && (same || shifted); k++)
+            {
+                const int dcol = col[b + k] - col[bp + k];
+                same           = same && dcol == 0;
+                shifted        = shifted && dcol == 1;
+            }
+            leader = !same && !shifted;
+            plus1  = shifted;
+        }
+    }
+    const unsigned long long upto = (2ull << lane) - 1ull; // lanes 0 .. lane
+    const unsigned long long bal  = __builtin_amdgcn_ballot_w64(leader);
+    const unsigned long long p1   = __builtin_amdgcn_ballot_w64(plus1);
+    if(i < m)
+    {
+        const unsigned long long mine = bal & upto; // never 0: lane 0 is a leader
+        const int                ll   = 63 - __builtin_clzll(mine); // my leader's lane
+        const unsigned long long span = upto & ~((2ull << ll) - 1ull); // lanes ll + 1 .. lane
+        follow[i] = (unsigned short)((__builtin_popcountll(mine) - 1) | (__builtin_popcountll(p1 & span) << 8));
+    }
+    // a FULL slice with one leader whose followers are all "plus one" (the interior of a stencil) or all "same" needs no
+    // follow[] at run time: mode 1 -> shift = lane, mode 2 -> shift = 0 (bits 8.. of nl[s]; the host moves them into cptr)
+    if(lane == 0)
+    {
+        const bool full = s * 64 + 63 < m;
+        const int  mode = (full && bal == 1ull) ? (p1 == ~1ull ? 1 : (p1 == 0ull ? 2 : 0)) : 0;
+        nl[s]           = (aoclsparse_int)__builtin_popcountll(bal) | (mode << 8);
+    }
+}
+
+} // namespace
+
+aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base, const aoclsparse_int *row_ptr, const aoclsparse_int *col,
+                                      aoclsparse_int nslices, unsigned short *lead, aoclsparse_int *nl)
+{
+    if(nslices <= 0)
+        return aoclsparse_status_success;
+    hipLaunchKernelGGL(sell_leaders_kernel, dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr, col, nslices, lead, nl);
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
+namespace
+{
+
+// cell (p, k) of a slice whose rows of cells are n wide (64 value cells; the column lists of a slice with shared lists: its n
+// leaders): PACK 1 -> n p + k; PACK 4 -> four consecutive cells of a row are adjacent: 4 n (p / 4) + 4 k + p % 4 (slice width is a
+// multiple of 4 there)
+template <int PACK>
+__device__ __forceinline__ long long cell_of(int p, int k, int n = 64)
+{
+    return PACK == 1 ? (long long)p * n + k : (long long)(p >> 2) * 4 * n + k * 4 + (p & 3);
+}
+
+// SHARED: the columns go to the slice's lists (cptr, follow: see above), written by the first row of every list
+template <typename T, int PACK, bool SHARED>
+__global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int base,
+                                                        const aoclsparse_int *__restrict__ row_ptr,
+                                                        const aoclsparse_int *__restrict__ col,
+                                                        const T *__restrict__ val, aoclsparse_int nslices,
+                                                        const long long *__restrict__ slice_ptr,
+                                                        const long long *__restrict__ cptr,
+                                                        const unsigned short *__restrict__ follow, T *__restrict__ sval,
+                                                        aoclsparse_int *__restrict__ scol,
+                                                        aoclsparse_int *__restrict__ rowlen, unsigned char *__restrict__ sidx,
+                                                        const T *__restrict__ vtab, int ntab)
+{
+    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if(s >= nslices)
+        return;
+    const int       i  = s * 64 + lane;
+    const long long o0 = slice_ptr[s];
+    const int       w  = (int)((slice_ptr[s + 1] - o0) >> 6);
+    long long       c0 = 0;
+    int             nl = 0;
+    if constexpr(SHARED)
+    {
+        c0 = cptr[s] & SELL_CPTR_MASK;
+        nl = w > 0 ? (int)(((cptr[s + 1] & SELL_CPTR_MASK) - c0) / w) : 0;
+    }
+    int  b = 0, len = 0, k = 0;
+    bool leader = !SHARED; // (own lists: every lane writes its columns, the padding rows behind m too)
+    if(i < m)
+    {
+        b   = row_ptr[i] - base;
+        len = row_ptr[i + 1] - base - b;
+        rowlen[i] = len;
+        if constexpr(SHARED)
+        {
+            k      = follow[i] & 0xff;
+            leader = lane == 0 || (follow[i - 1] & 0xff) != k;
+        }
+    }
+    for(int p = 0; p < w; p++)
+    {
+        const long long o  = o0 + cell_of<PACK>(p, lane);
+        const bool      in = p < len;
+        fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
+        if(leader)
+            scol[SHARED ? c0 + cell_of<PACK>(p, k, nl) : o] = in ? col[b + p] - base : -1;
+    }
+}
+
+template <typename T>
+void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *cells, aoclsparse_int *scol, aoclsparse_int *rowlen)
+{
+    T             *sval = v.ntab ? nullptr : static_cast<T *>(cells);
+    unsigned char *sidx = v.ntab ? static_cast<unsigned char *>(cells) : nullptr;
+    auto           go   = [&](auto pack, auto shared) {
+        hipLaunchKernelGGL((sell_fill_kernel<T, decltype(pack)::value, decltype(shared)::value>), dim3((v.nslices + 3) / 4), dim3(256),
+                           0, s, v.m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.as<T>(), v.nslices,
+                           v.slice_ptr, v.cptr, v.lead, sval, scol, rowlen, sidx, static_cast<const T *>(v.vtab), v.ntab);
+    };
+    using P1 = std::integral_constant<int, 1>;
+    using P4 = std::integral_constant<int, 4>;
+    if(v.cptr)
+        v.pack == 4 ? go(P4{}, std::true_type{}) : go(P1{}, std::true_type{});
+    else
+        v.pack == 4 ? go(P4{}, std::false_type{}) : go(P1{}, std::false_type{});
+}
+
+} // namespace
+
+aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
+                                   aoclsparse_int *rowlen)
+{
+    if(v.nslices <= 0)
+        return aoclsparse_status_success;
+    // (the kernel only moves values: cfloat cells are filled as 8-byte doubles, cdouble cells need their own instantiation)
+    if(vsize == sizeof(cdouble))
+        sell_fill_as<cdouble>(s, d, v, cells, col, rowlen);
+    else if(vsize == sizeof(float))
+        sell_fill_as<float>(s, d, v, cells, col, rowlen);
+    else
+        sell_fill_as<double>(s, d, v, cells, col, rowlen);
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
+} // namespace mi355

@@ -2,12 +2,7 @@
 //
 // The reference's optimize step re-stores a hinted matrix in the format its CPU kernels like best
 // (br4 / ELLT-HYB / blocked CSR, analysis.cpp:146-382).  The GPU analogue is sliced ELL with one slice
-// per 64-wide wavefront: slice s holds rows [64 s, 64 s + 64) column-major, cell (p, lane) at
-// slice_ptr[s] + 64 p + lane, padded to the slice's longest row (column -1, value 0); matrices with >= 16
-// non-zeros per row keep four consecutive cells of a row adjacent instead (PACK 4: cell at
-// slice_ptr[s] + 256 (p/4) + 4 lane + p%4, width rounded up to a multiple of 4), so that a wavefront's load is
-// one contiguous 2 KB piece -- the in-flight slices of a long-row matrix are otherwise 512-byte accesses
-// strided by the slice size, which costs HBM page locality.  Lane i of a wave owns row i:
+// per 64-wide wavefront (the layout, and the kernels that build it: sell_build_kernels.hip).  Lane i of a wave owns row i:
 //   * every val / col access is one coalesced line per wavefront instruction, no row_ptr, no LDS;
 //   * a lane walks its row front to back, so the reference's summation orders are reproduced exactly:
 //     order 0 is the scalar FMA chain (csrmv_kr.hpp:448-513); orders 1 / 2 keep 4 / 8 partial sums per
@@ -17,10 +12,8 @@
 // gathers; cells <= 1.15 nnz or the handle stays on the CSR-Adaptive kernel (matrix.cpp: build_sell).
 #include "internal.hpp"
 
-#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -144,23 +137,7 @@ __device__ __forceinline__ T lanes_sum(const T (&l)[G])
         return ((l[0] + l[4]) + (l[2] + l[6])) + ((l[1] + l[5]) + (l[3] + l[7])); // csrmv_kr.hpp:788-806
 }
 
-// cell (p, lane) of a slice that starts at o0: PACK 1 -> o0 + 64 p + lane; PACK 4 -> four consecutive cells of a
-// row are adjacent: o0 + 256 (p / 4) + 4 lane + p % 4 (slice width is a multiple of 4 there)
-template <int PACK>
-__device__ __forceinline__ long long cell_of(int p, int lane)
-{
-    return PACK == 1 ? (long long)p * 64 + lane : (long long)(p >> 2) * 256 + lane * 4 + (p & 3);
-}
-
-// ---- value tables (SELL-64 with one byte per cell: an index into <= 256 distinct value bit patterns) ---------------------
-// A matrix whose values take at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil: two) stores one byte
-// per cell and a table sorted by ascending bit pattern; the kernels read table[index], i.e. the very bits of the value, so every
-// summation order gives the same results as with the values stored in the cells (CSR-VI, Kourtis, Goumas and Koziris, CF 2008).
-// Bit patterns, not values: -0.0 and +0.0 are two entries, NaN payloads are kept.
-template <typename T>
-using vbits_t = std::conditional_t<sizeof(T) == 8, unsigned long long, unsigned>;
-
-// the value cells as the kernels read them: values, or (IDX) table indices
+// the value cells as the kernels read them: values, or (IDX) indices into the plan's value table (sell_build_kernels.hip)
 template <typename T, bool IDX>
 struct SellCell
 {
@@ -181,268 +158,7 @@ __device__ __forceinline__ T cell_value(R raw, const T *__restrict__ vtab)
     else
         return raw;
 }
-
-// index of v in the sorted table (v is in it: the table holds every pattern of the matrix)
-template <typename T>
-__device__ __forceinline__ unsigned char vtab_index(T v, const T *__restrict__ vtab, int ntab)
-{
-    using U     = vbits_t<T>;
-    const U key = __builtin_bit_cast(U, v);
-    int     lo = 0, hi = ntab - 1;
-    while(lo < hi)
-    {
-        const int mid = (lo + hi) >> 1;
-        if(__builtin_bit_cast(U, vtab[mid]) < key)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return (unsigned char)lo;
-}
-
-// writes cell o: the value, or (sidx) its table index; padding cells hold 0 / index 0 (their column is -1: never used)
-template <typename T>
-__device__ __forceinline__ void fill_cell(long long o, bool in, const T *__restrict__ vp, T *__restrict__ sval,
-                                          unsigned char *__restrict__ sidx, const T *__restrict__ vtab, int ntab)
-{
-    if constexpr(std::is_floating_point_v<T>)
-    {
-        if(sidx)
-        {
-            sidx[o] = in ? vtab_index(*vp, vtab, ntab) : (unsigned char)0;
-            return;
-        }
-    }
-    sval[o] = in ? *vp : T(0);
-}
-
-// Distinct bit patterns of n values, on the device: every workgroup collects what it sees in an LDS hash set, then merges it
-// into the global set (VT_SLOTS entries, VT_EMPTY = free).  state[0] = patterns in the global set, state[1] = 1 once more than
-// SELL_VTAB_MAX patterns were seen (everyone stops early), state[2] = 1 if the pattern VT_EMPTY itself (a double NaN) occurs.
-// A set that fills up also means "more than SELL_VTAB_MAX": a set has 4 x the slots that can be taken before a stop is seen.
-constexpr int                VT_LDS_SLOTS  = 1024;
-constexpr int                VT_SLOTS      = 4096;
-constexpr unsigned long long VT_EMPTY      = ~0ull;
-
-__device__ __forceinline__ unsigned vt_hash(unsigned long long k)
-{
-    k ^= k >> 33; // (murmur3's finaliser: the patterns of simple doubles differ in their top bits only)
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (unsigned)k;
-}
-
-// 1: k was inserted, 0: it was there already, -1: the set is full
-__device__ __forceinline__ int vt_insert(unsigned long long *set, int slots, unsigned long long k)
-{
-    unsigned h = vt_hash(k) & (unsigned)(slots - 1);
-    for(int probe = 0; probe < slots; probe++)
-    {
-        unsigned long long cur = __hip_atomic_load(set + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if(cur == k)
-            return 0;
-        if(cur == VT_EMPTY)
-        {
-            cur = atomicCAS(set + h, VT_EMPTY, k);
-            if(cur == VT_EMPTY)
-                return 1;
-            if(cur == k)
-                return 0;
-        }
-        h = (h + 1) & (unsigned)(slots - 1);
-    }
-    return -1;
-}
-
-template <typename U>
-__global__ __launch_bounds__(256) void sell_vtab_count_kernel(long long n, const U *__restrict__ val, unsigned long long *__restrict__ set,
-                                                              unsigned *__restrict__ state)
-{
-    constexpr int                 UNR = 4;
-    __shared__ unsigned long long lset[VT_LDS_SLOTS];
-    __shared__ int                lcount, lstop, lempty;
-    for(int k = threadIdx.x; k < VT_LDS_SLOTS; k += blockDim.x)
-        lset[k] = VT_EMPTY;
-    if(threadIdx.x == 0)
-        lcount = 0, lstop = 0, lempty = 0;
-    __syncthreads();
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for(long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += UNR * stride)
-    {
-        if(__hip_atomic_load(&lstop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-           || __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            break;
-        unsigned long long k[UNR];
-#pragma unroll
-        for(int u = 0; u < UNR; u++)
-            k[u] = (unsigned long long)val[i0 + u * stride < n ? i0 + u * stride : i0];
-#pragma unroll
-        for(int u = 0; u < UNR; u++)
-        {
-            if(k[u] == VT_EMPTY)
-            {
-                lempty = 1;
-                continue;
-            }
-            const int r = vt_insert(lset, VT_LDS_SLOTS, k[u]);
-            if(r < 0 || (r > 0 && atomicAdd(&lcount, 1) + 1 > SELL_VTAB_MAX))
-                lstop = 1;
-        }
-    }
-    __syncthreads();
-    if(lstop)
-    {
-        if(threadIdx.x == 0)
-            atomicOr(state + 1, 1u);
-        return;
-    }
-    if(threadIdx.x == 0 && lempty)
-        atomicOr(state + 2, 1u);
-    for(int k = threadIdx.x; k < VT_LDS_SLOTS; k += blockDim.x)
-    {
-        const unsigned long long key = lset[k];
-        if(key == VT_EMPTY || __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            continue;
-        const int r = vt_insert(set, VT_SLOTS, key);
-        if(r < 0 || (r > 0 && atomicAdd(state, 1u) + 1u > (unsigned)SELL_VTAB_MAX))
-            atomicOr(state + 1, 1u);
-    }
-}
-
-template <typename T, int PACK>
-__global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int base,
-                                                        const aoclsparse_int *__restrict__ row_ptr,
-                                                        const aoclsparse_int *__restrict__ col,
-                                                        const T *__restrict__ val, aoclsparse_int nslices,
-                                                        const long long *__restrict__ slice_ptr,
-                                                        T *__restrict__ sval, aoclsparse_int *__restrict__ scol,
-                                                        aoclsparse_int *__restrict__ rowlen, unsigned char *__restrict__ sidx,
-                                                        const T *__restrict__ vtab, int ntab)
-{
-    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if(s >= nslices)
-        return;
-    const int       i  = s * 64 + lane;
-    const long long o0 = slice_ptr[s];
-    const int       w  = (int)((slice_ptr[s + 1] - o0) >> 6);
-    int             b = 0, len = 0;
-    if(i < m)
-    {
-        b   = row_ptr[i] - base;
-        len = row_ptr[i + 1] - base - b;
-        rowlen[i] = len;
-    }
-    for(int p = 0; p < w; p++)
-    {
-        const long long o  = o0 + cell_of<PACK>(p, lane);
-        const bool      in = p < len;
-        fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
-        scol[o]            = in ? col[b + p] - base : -1;
-    }
-}
-
-// ---- shared column lists (SELL-64 with one column list per run of rows that repeat it) --------------------------------
-// Two kinds of repetition, found the same way: the rows of a mesh node (several dofs) carry the SAME column list, and the
-// rows of a stencil carry the list of the row before SHIFTED BY ONE (row i of a 5-point Laplacian: i-g, i-1, i, i+1, i+g).
-// A slice stores its columns once per "leader" (lane 0, and every lane whose list is neither the previous lane's nor the
-// previous lane's plus one): cell (p, leader k) of slice s at cptr[s] + nl_s p + k (PACK 4: cptr[s] + 4 nl_s (p / 4) + 4 k
-// + p % 4).  follow[i] (16 bits per row) = leader index inside the slice | shift << 8, where shift = how many of the rows
-// between the leader and row i were "plus one" steps: a lane's column is its leader's + shift.  Values stay where they are.
-// The column stream shrinks from 4 B per cell to 4 B / (rows per list): 12 -> 8.8 B per cell for 5-dof nodes, 12 -> ~8.1 B for
-// the Laplacian (one list per 64 rows, broken at the grid edges).
-// One wavefront per slice: each lane compares its row with its predecessor, indices and shifts by ballot + popcount.
-constexpr int       SELL_CPTR_MODE_SHIFT = 56;
-constexpr long long SELL_CPTR_MASK       = (1LL << SELL_CPTR_MODE_SHIFT) - 1;
-
-__global__ __launch_bounds__(256) void sell_leaders_kernel(aoclsparse_int m, int base, const aoclsparse_int *__restrict__ row_ptr,
-                                                           const aoclsparse_int *__restrict__ col, aoclsparse_int nslices,
-                                                           unsigned short *__restrict__ follow, aoclsparse_int *__restrict__ nl)
-{
-    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if(s >= nslices)
-        return;
-    const int i      = s * 64 + lane;
-    bool      leader = false, plus1 = false;
-    if(i < m)
-    {
-        leader = lane == 0;
-        if(!leader)
-        {
-            const int b = row_ptr[i] - base, len = row_ptr[i + 1] - base - b, bp = row_ptr[i - 1] - base;
-            bool      same = len == b - bp, shifted = same && len > 0; // (column VALUES: only differences are used)
-            for(int k = 0; k < len && (same || shifted); k++)
-            {
-                const int dcol = col[b + k] - col[bp + k];
-                same           = same && dcol == 0;
-                shifted        = shifted && dcol == 1;
-            }
-            leader = !same && !shifted;
-            plus1  = shifted;
-        }
-    }
-    const unsigned long long upto = (2ull << lane) - 1ull; // lanes 0 .. lane
-    const unsigned long long bal  = __builtin_amdgcn_ballot_w64(leader);
-    const unsigned long long p1   = __builtin_amdgcn_ballot_w64(plus1);
-    if(i < m)
-    {
-        const unsigned long long mine = bal & upto; // never 0: lane 0 is a leader
-        const int                ll   = 63 - __builtin_clzll(mine); // my leader's lane
-        const unsigned long long span = upto & ~((2ull << ll) - 1ull); // lanes ll + 1 .. lane
-        follow[i] = (unsigned short)((__builtin_popcountll(mine) - 1) | (__builtin_popcountll(p1 & span) << 8));
-    }
-    // a FULL slice with one leader whose followers are all "plus one" (the interior of a stencil) or all "same" needs no
-    // follow[] at run time: mode 1 -> shift = lane, mode 2 -> shift = 0 (bits 8.. of nl[s]; the host moves them into cptr)
-    if(lane == 0)
-    {
-        const bool full = s * 64 + 63 < m;
-        const int  mode = (full && bal == 1ull) ? (p1 == ~1ull ? 1 : (p1 == 0ull ? 2 : 0)) : 0;
-        nl[s]           = (aoclsparse_int)__builtin_popcountll(bal) | (mode << 8);
-    }
-}
-
-template <typename T, int PACK>
-__global__ __launch_bounds__(256) void sell_fill_shared_kernel(aoclsparse_int m, int base,
-                                                               const aoclsparse_int *__restrict__ row_ptr,
-                                                               const aoclsparse_int *__restrict__ col,
-                                                               const T *__restrict__ val, aoclsparse_int nslices,
-                                                               const long long *__restrict__ slice_ptr,
-                                                               const long long *__restrict__ cptr,
-                                                               const unsigned short *__restrict__ follow, T *__restrict__ sval,
-                                                               aoclsparse_int *__restrict__ scol,
-                                                               aoclsparse_int *__restrict__ rowlen, unsigned char *__restrict__ sidx,
-                                                               const T *__restrict__ vtab, int ntab)
-{
-    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if(s >= nslices)
-        return;
-    const int       i  = s * 64 + lane;
-    const long long o0 = slice_ptr[s], c0 = cptr[s] & SELL_CPTR_MASK;
-    const int       w  = (int)((slice_ptr[s + 1] - o0) >> 6);
-    const int       nl = w > 0 ? (int)(((cptr[s + 1] & SELL_CPTR_MASK) - c0) / w) : 0;
-    int             b = 0, len = 0, k = 0;
-    bool            leader = false;
-    if(i < m)
-    {
-        b   = row_ptr[i] - base;
-        len = row_ptr[i + 1] - base - b;
-        rowlen[i] = len;
-        k         = follow[i] & 0xff;
-        leader    = lane == 0 || (follow[i - 1] & 0xff) != k;
-    }
-    for(int p = 0; p < w; p++)
-    {
-        const bool in = p < len;
-        fill_cell(o0 + cell_of<PACK>(p, lane), in, val + b + p, sval, sidx, vtab, ntab);
-        if(leader)
-            scol[c0 + (PACK == 1 ? (long long)p * nl + k : (long long)(p >> 2) * 4 * nl + 4 * k + (p & 3))] = in ? col[b + p] - base : -1;
-    }
-}
-
+// (shared column lists -- cptr, follow -- and the slice modes in cptr's top byte: sell_build_kernels.hip)
 // four adjacent cells of one lane as vector loads (PACK 4): 32 B of values (16 B for float), 16 B of columns
 __device__ __forceinline__ void load4(const double *p, double (&o)[4])
 {
@@ -803,14 +519,13 @@ inline int sell_short_spw_override()
 
 constexpr aoclsparse_int SELL_SHORT_SPW_SLICES = 60000;
 
-// TAB as the kernel's; CONJ for complex T only
-template <typename T, int TAB, bool CONJ = false>
-bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int nslices, const SellSliceDesc *desc,
-                       const typename SellCell<T, TAB != 0>::src *sval, const aoclsparse_int *scol, T alpha, const T *x, T beta, T *y,
-                       bool nt, const unsigned short *lead, int rev, const T *vtab)
+// TAB as the kernel's; CONJ for complex T only.  false: no kernel for this width (v.max_width > SELL_SHORT_WMAX)
+template <typename T, int TAB, bool CONJ>
+bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T beta, T *y, bool nt, int rev)
 {
-    constexpr int  WAVES   = 4;
-    constexpr bool COMPLEX = !std::is_floating_point_v<T>;
+    constexpr int        WAVES   = 4;
+    constexpr bool       COMPLEX = !std::is_floating_point_v<T>;
+    const aoclsparse_int m = v.m, nslices = v.nslices;
     // Slices per wavefront, by measurement (5-point Laplacians, cold products, one box, median of 20, ms; 1 / 2 / 4 slices per
     // wavefront; profiles/r8/spw_sweep.txt, which also has the VGPRs and the occupancy of each variant):
     //                       4096^2 (262,144 slices)    3000^2 (140,625)          2000^2 (62,500)
@@ -832,10 +547,12 @@ bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int
     const int       groups = (int)((nslices + per_wg - 1) / per_wg);
     const dim3      grid((unsigned)groups), block(64 * WAVES);
     const int       g0 = rev ? groups - 1 : 0, gstep = rev ? -1 : 1;
-    const uint4    *dp = reinterpret_cast<const uint4 *>(desc);
+    const uint4    *dp = reinterpret_cast<const uint4 *>(v.desc);
+    const auto     *sval = static_cast<const typename SellCell<T, TAB != 0>::src *>(v.cells);
+    const T        *vtab = static_cast<const T *>(v.vtab);
 #define MI355_SHORT_SPW(W, SPW)                                                                                                 \
     hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SPW, CONJ, TAB>), grid, block, 0, s, m, nslices, g0, gstep, dp, sval, \
-                       scol, lead, alpha, x, beta, y, nt, vtab)
+                       v.col, v.lead, alpha, x, beta, y, nt, vtab)
 #define MI355_SHORT(W)                      \
     case W:                                 \
         if constexpr(!COMPLEX)              \
@@ -853,7 +570,7 @@ bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int
         }                                   \
         MI355_SHORT_SPW(W, 1);              \
         return true
-    switch(wmax)
+    switch((int)v.max_width)
     {
         MI355_SHORT(1);
         MI355_SHORT(2);
@@ -869,245 +586,79 @@ bool sell_launch_short(hipStream_t s, int wmax, aoclsparse_int m, aoclsparse_int
 #undef MI355_SHORT_SPW
 }
 
-template <typename T, int ORDER, int PACK, bool IDX>
-void sell_launch(hipStream_t s, aoclsparse_int m, aoclsparse_int nslices, const long long *slice_ptr,
-                 const typename SellCell<T, IDX>::src *sval, const aoclsparse_int *scol, const aoclsparse_int *rowlen, T alpha,
-                 const T *x, T beta, T *y, const long long *cptr, const unsigned short *lead, int rev, const T *vtab)
-{
-    // one slice per workgroup while the launch is small (every slice its own CU), two otherwise
-    // (swept on the headline workload: 1 / 2 / 4 / 8 slices per workgroup = 0.221 / 0.218 / 0.221 / 0.222 ms)
-    const bool nt = (size_t)m * sizeof(T) > ((size_t)32 << 20);
-    if(cptr)
-    {
-        if(nslices < 2048)
-            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, true, false, IDX>), dim3(nslices), dim3(64), 0, s, m, nslices,
-                               slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, cptr, lead, rev, vtab);
-        else
-            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, true, false, IDX>), dim3((nslices + 1) / 2), dim3(128), 0, s, m,
-                               nslices, slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, cptr, lead, rev, vtab);
-    }
-    else if(nslices < 2048)
-        hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, false, false, IDX>), dim3(nslices), dim3(64), 0, s, m, nslices, slice_ptr,
-                           sval, scol, rowlen, alpha, x, beta, y, nt, (const long long *)nullptr, (const unsigned short *)nullptr, rev,
-                           vtab);
-    else
-        hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, false, false, IDX>), dim3((nslices + 1) / 2), dim3(128), 0, s, m,
-                           nslices, slice_ptr, sval, scol, rowlen, alpha, x, beta, y, nt, (const long long *)nullptr,
-                           (const unsigned short *)nullptr, rev, vtab);
-}
-
 } // namespace
 
 template <typename T>
-aoclsparse_status launch_sell_fill(hipStream_t s, int pack, aoclsparse_int m, int base, const aoclsparse_int *row_ptr,
-                                   const aoclsparse_int *col, const T *val, aoclsparse_int nslices,
-                                   const long long *slice_ptr, T *sval, aoclsparse_int *scol, aoclsparse_int *rowlen,
-                                   const long long *cptr, const unsigned short *lead, unsigned char *sidx, const T *vtab,
-                                   int ntab)
+aoclsparse_status launch_sellmv(hipStream_t s, const SellView &v, int order, bool conj, T alpha, const T *x, T beta, T *y, int rev)
 {
-    if(nslices <= 0)
+    constexpr bool COMPLEX = !std::is_floating_point_v<T>;
+    if(v.m <= 0 || v.nslices <= 0)
         return aoclsparse_status_success;
-    if(cptr)
-    {
-        if(pack == 4)
-            hipLaunchKernelGGL((sell_fill_shared_kernel<T, 4>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr,
-                               col, val, nslices, slice_ptr, cptr, lead, sval, scol, rowlen, sidx, vtab, ntab);
-        else
-            hipLaunchKernelGGL((sell_fill_shared_kernel<T, 1>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr,
-                               col, val, nslices, slice_ptr, cptr, lead, sval, scol, rowlen, sidx, vtab, ntab);
-    }
-    else if(pack == 4)
-        hipLaunchKernelGGL((sell_fill_kernel<T, 4>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr, col,
-                           val, nslices, slice_ptr, sval, scol, rowlen, sidx, vtab, ntab);
-    else
-        hipLaunchKernelGGL((sell_fill_kernel<T, 1>), dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr, col,
-                           val, nslices, slice_ptr, sval, scol, rowlen, sidx, vtab, ntab);
-    MI355_HIP_TRY(hipGetLastError());
-    return aoclsparse_status_success;
-}
-
-// distinct bit patterns of the n values of `val` (vsize 4 or 8 bytes each): on return *ntab = their number and table[0 .. *ntab)
-// = the patterns in ascending order (as 8-byte words), or *ntab = 0 if there are more than SELL_VTAB_MAX of them
-aoclsparse_status sell_value_table(hipStream_t s, size_t vsize, long long n, const void *val, unsigned long long *table, int *ntab)
-{
-    *ntab = 0;
-    if(n <= 0 || (vsize != 4 && vsize != 8))
-        return aoclsparse_status_success;
-    DeviceBuffer      set;
-    aoclsparse_status st = set.alloc(sizeof(unsigned long long) * VT_SLOTS + 4 * sizeof(unsigned));
-    if(st != aoclsparse_status_success)
-        return st;
-    unsigned long long *d_set   = set.as<unsigned long long>();
-    unsigned           *d_state = reinterpret_cast<unsigned *>(d_set + VT_SLOTS);
-    MI355_HIP_TRY(hipMemsetAsync(d_set, 0xff, sizeof(unsigned long long) * VT_SLOTS, s)); // VT_EMPTY everywhere
-    MI355_HIP_TRY(hipMemsetAsync(d_state, 0, 4 * sizeof(unsigned), s));
-    // a few workgroups per CU, each walking the values with a grid stride (a workgroup that has seen > 256 patterns stops all)
-    const long long blocks = std::min<long long>(2048, std::max<long long>(1, (n + 1023) / 1024));
-    if(vsize == 8)
-        hipLaunchKernelGGL(sell_vtab_count_kernel<unsigned long long>, dim3((unsigned)blocks), dim3(256), 0, s, n,
-                           static_cast<const unsigned long long *>(val), d_set, d_state);
-    else
-        hipLaunchKernelGGL(sell_vtab_count_kernel<unsigned>, dim3((unsigned)blocks), dim3(256), 0, s, n,
-                           static_cast<const unsigned *>(val), d_set, d_state);
-    MI355_HIP_TRY(hipGetLastError());
-    unsigned state[4];
-    MI355_HIP_TRY(hipMemcpyAsync(state, d_state, sizeof(state), hipMemcpyDeviceToHost, s));
-    MI355_HIP_TRY(hipStreamSynchronize(s));
-    if(state[1] || state[0] + state[2] > (unsigned)SELL_VTAB_MAX)
-        return aoclsparse_status_success;
-    std::vector<unsigned long long> h((size_t)VT_SLOTS);
-    MI355_HIP_TRY(hipMemcpyAsync(h.data(), d_set, sizeof(unsigned long long) * VT_SLOTS, hipMemcpyDeviceToHost, s));
-    MI355_HIP_TRY(hipStreamSynchronize(s));
-    int k = 0;
-    for(unsigned long long v : h)
-        if(v != VT_EMPTY && k < SELL_VTAB_MAX)
-            table[k++] = v;
-    if(state[2] && k < SELL_VTAB_MAX)
-        table[k++] = VT_EMPTY;
-    std::sort(table, table + k); // (ascending bit pattern: the plan does not depend on the order the device found them in)
-    *ntab = k;
-    return aoclsparse_status_success;
-}
-
-template <typename T>
-aoclsparse_status launch_sellmv(hipStream_t s, int order, int pack, T alpha, aoclsparse_int m, aoclsparse_int nslices,
-                                const long long *slice_ptr, const T *sval, const aoclsparse_int *scol,
-                                const aoclsparse_int *rowlen, const T *x, T beta, T *y, const long long *cptr,
-                                const unsigned short *lead, aoclsparse_int max_width, int rev, const unsigned char *sidx,
-                                const T *vtab, const SellSliceDesc *desc, int ntab)
-{
-    if(m <= 0 || nslices <= 0)
-        return aoclsparse_status_success;
-    if(order < 0 || order > 2 || (pack != 1 && pack != 4))
+    if(order < 0 || order > 2 || (v.pack != 1 && v.pack != 4))
         return aoclsparse_status_invalid_kid;
-    // vtab: the cells are one-byte indices into it (sidx); else the values themselves (sval)
-    auto go = [&](auto idx_tag) {
-        constexpr bool IDX = decltype(idx_tag)::value;
-        const typename SellCell<T, IDX>::src *cells;
-        if constexpr(IDX)
-            cells = sidx;
-        else
-            cells = sval;
+    if(COMPLEX ? (order != 0 || v.pack != 1 || v.ntab != 0) : conj)
+        return aoclsparse_status_invalid_kid;
+    const bool nt = (size_t)v.m * sizeof(T) > ((size_t)32 << 20);
+    // one combination of the kernels' template arguments, each a std::integral_constant
+    auto run = [&](auto o, auto p, auto sh, auto cj, auto ix) {
+        constexpr int  ORDER = decltype(o)::value, PACK = decltype(p)::value;
+        constexpr bool SHARED = decltype(sh)::value, CONJ = decltype(cj)::value, IDX = decltype(ix)::value;
         // the plan has slice records (build_sell: widest slice <= 8 cells, pack 1, a launch large enough that four slices per
         // workgroup still spread over every CU) and the order is the scalar one: the short-row kernel
-        if(order == 0 && pack == 1 && desc)
+        if constexpr(ORDER == 0 && PACK == 1)
         {
-            const bool nt = (size_t)m * sizeof(T) > ((size_t)32 << 20);
-            bool       done;
-            if constexpr(!IDX)
-                done = sell_launch_short<T, 0>(s, (int)max_width, m, nslices, desc, cells, scol, alpha, x, beta, y, nt, lead, rev, vtab);
-            else if(ntab <= 2)
-                done = sell_launch_short<T, 2>(s, (int)max_width, m, nslices, desc, cells, scol, alpha, x, beta, y, nt, lead, rev, vtab);
-            else
-                done = sell_launch_short<T, SELL_VTAB_MAX>(s, (int)max_width, m, nslices, desc, cells, scol, alpha, x, beta, y, nt, lead,
-                                                           rev, vtab);
-            if(done)
-                return;
+            if(v.desc)
+            {
+                bool done;
+                if constexpr(!IDX)
+                    done = sell_launch_short<T, 0, CONJ>(s, v, alpha, x, beta, y, nt, rev);
+                else if(v.ntab <= 2)
+                    done = sell_launch_short<T, 2, CONJ>(s, v, alpha, x, beta, y, nt, rev);
+                else
+                    done = sell_launch_short<T, SELL_VTAB_MAX, CONJ>(s, v, alpha, x, beta, y, nt, rev);
+                if(done)
+                    return;
+            }
         }
-#define SELL_CASE(O, P)                                                                                            \
-    sell_launch<T, O, P, IDX>(s, m, nslices, slice_ptr, cells, scol, rowlen, alpha, x, beta, y, cptr, lead, rev, vtab); \
-    break
-        switch(order * 2 + (pack == 4 ? 1 : 0))
-        {
-        case 0:
-            SELL_CASE(0, 1);
-        case 1:
-            SELL_CASE(0, 4);
-        case 2:
-            SELL_CASE(1, 1);
-        case 3:
-            SELL_CASE(1, 4);
-        case 4:
-            SELL_CASE(2, 1);
-        case 5:
-            SELL_CASE(2, 4);
-        }
-#undef SELL_CASE
-    };
-    if(vtab)
-        go(std::true_type{});
-    else
-        go(std::false_type{});
-    MI355_HIP_TRY(hipGetLastError());
-    return aoclsparse_status_success;
-}
-
-// aoclsparse_{c,z}mv on the SELL-64 copy (PACK 1, the scalar chain per row): the short-row kernel where the plan has slice
-// records (large launches whose widest slice has <= 8 cells), the general kernel otherwise
-template <typename R>
-aoclsparse_status launch_sellmv_complex(hipStream_t s, bool conj, cplx<R> alpha, aoclsparse_int m, aoclsparse_int nslices,
-                                        const long long *slice_ptr, const cplx<R> *sval, const aoclsparse_int *scol,
-                                        const aoclsparse_int *rowlen, const cplx<R> *x, cplx<R> beta, cplx<R> *y,
-                                        const long long *cptr, const unsigned short *lead, aoclsparse_int max_width, int rev,
-                                        const SellSliceDesc *desc)
-{
-    using C = cplx<R>;
-    if(m <= 0 || nslices <= 0)
-        return aoclsparse_status_success;
-    const bool nt = (size_t)m * sizeof(C) > ((size_t)32 << 20);
-    auto       go = [&](auto shared_tag, auto conj_tag) {
-        constexpr bool SH = decltype(shared_tag)::value, CJ = decltype(conj_tag)::value;
-        const long long      *cp = SH ? cptr : nullptr;
-        const unsigned short *ld = SH ? lead : nullptr;
-        if(desc && sell_launch_short<C, 0, CJ>(s, (int)max_width, m, nslices, desc, sval, scol, alpha, x, beta, y, nt, ld, rev, nullptr))
-            return;
-        if(nslices < 2048)
-            hipLaunchKernelGGL((sell_mv_kernel<C, 0, 1, 1, SH, CJ>), dim3(nslices), dim3(64), 0, s, m, nslices, slice_ptr, sval, scol,
-                               rowlen, alpha, x, beta, y, nt, cp, ld, rev);
+        // one slice per workgroup while the launch is small (every slice its own CU), two otherwise
+        // (swept on the headline workload: 1 / 2 / 4 / 8 slices per workgroup = 0.221 / 0.218 / 0.221 / 0.222 ms)
+        const auto *cells = static_cast<const typename SellCell<T, IDX>::src *>(v.cells);
+        const T    *vtab  = static_cast<const T *>(v.vtab);
+        if(v.nslices < 2048)
+            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, SHARED, CONJ, IDX>), dim3(v.nslices), dim3(64), 0, s, v.m, v.nslices,
+                               v.slice_ptr, cells, v.col, v.rowlen, alpha, x, beta, y, nt, v.cptr, v.lead, rev, vtab);
         else
-            hipLaunchKernelGGL((sell_mv_kernel<C, 0, 2, 1, SH, CJ>), dim3((nslices + 1) / 2), dim3(128), 0, s, m, nslices, slice_ptr,
-                               sval, scol, rowlen, alpha, x, beta, y, nt, cp, ld, rev);
+            hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, SHARED, CONJ, IDX>), dim3((v.nslices + 1) / 2), dim3(128), 0, s, v.m,
+                               v.nslices, v.slice_ptr, cells, v.col, v.rowlen, alpha, x, beta, y, nt, v.cptr, v.lead, rev, vtab);
     };
-    if(cptr)
-    {
-        if(conj)
-            go(std::true_type{}, std::true_type{});
+    auto pick = [](bool b, auto f) { b ? f(std::true_type{}) : f(std::false_type{}); };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using I4 = std::integral_constant<int, 4>;
+    pick(v.cptr != nullptr, [&](auto sh) {
+        if constexpr(COMPLEX)
+            pick(conj, [&](auto cj) { run(I0{}, I1{}, sh, cj, std::false_type{}); });
         else
-            go(std::true_type{}, std::false_type{});
-    }
-    else if(conj)
-        go(std::false_type{}, std::true_type{});
-    else
-        go(std::false_type{}, std::false_type{});
+            pick(v.ntab != 0, [&](auto ix) {
+                constexpr std::false_type cj{};
+                switch(order * 2 + (v.pack == 4 ? 1 : 0))
+                {
+                case 0: run(I0{}, I1{}, sh, cj, ix); break;
+                case 1: run(I0{}, I4{}, sh, cj, ix); break;
+                case 2: run(I1{}, I1{}, sh, cj, ix); break;
+                case 3: run(I1{}, I4{}, sh, cj, ix); break;
+                case 4: run(I2{}, I1{}, sh, cj, ix); break;
+                case 5: run(I2{}, I4{}, sh, cj, ix); break;
+                }
+            });
+    });
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }
-template aoclsparse_status launch_sellmv_complex<double>(hipStream_t, bool, cdouble, aoclsparse_int, aoclsparse_int, const long long *,
-                                                         const cdouble *, const aoclsparse_int *, const aoclsparse_int *,
-                                                         const cdouble *, cdouble, cdouble *, const long long *,
-                                                         const unsigned short *, aoclsparse_int, int, const SellSliceDesc *);
-template aoclsparse_status launch_sellmv_complex<float>(hipStream_t, bool, cfloat, aoclsparse_int, aoclsparse_int, const long long *,
-                                                        const cfloat *, const aoclsparse_int *, const aoclsparse_int *, const cfloat *,
-                                                        cfloat, cfloat *, const long long *, const unsigned short *, aoclsparse_int, int,
-                                                        const SellSliceDesc *);
-// (the fill kernels only move values: cfloat cells are filled as 8-byte doubles, cdouble cells need their own instantiation)
-template aoclsparse_status launch_sell_fill<cdouble>(hipStream_t, int, aoclsparse_int, int, const aoclsparse_int *, const aoclsparse_int *,
-                                                     const cdouble *, aoclsparse_int, const long long *, cdouble *, aoclsparse_int *,
-                                                     aoclsparse_int *, const long long *, const unsigned short *, unsigned char *,
-                                                     const cdouble *, int);
-
-aoclsparse_status launch_sell_leaders(hipStream_t s, aoclsparse_int m, int base, const aoclsparse_int *row_ptr, const aoclsparse_int *col,
-                                      aoclsparse_int nslices, unsigned short *lead, aoclsparse_int *nl)
-{
-    if(nslices <= 0)
-        return aoclsparse_status_success;
-    hipLaunchKernelGGL(sell_leaders_kernel, dim3((nslices + 3) / 4), dim3(256), 0, s, m, base, row_ptr, col, nslices, lead, nl);
-    MI355_HIP_TRY(hipGetLastError());
-    return aoclsparse_status_success;
-}
-
-#define MI355_SELL_INSTANTIATE(T)                                                                                     \
-    template aoclsparse_status launch_sell_fill<T>(hipStream_t, int, aoclsparse_int, int, const aoclsparse_int *,     \
-                                                   const aoclsparse_int *, const T *, aoclsparse_int,                 \
-                                                   const long long *, T *, aoclsparse_int *, aoclsparse_int *,        \
-                                                   const long long *, const unsigned short *, unsigned char *, const T *, \
-                                                   int);                                                              \
-    template aoclsparse_status launch_sellmv<T>(hipStream_t, int, int, T, aoclsparse_int, aoclsparse_int,             \
-                                                const long long *, const T *, const aoclsparse_int *,                 \
-                                                const aoclsparse_int *, const T *, T, T *, const long long *,          \
-                                                const unsigned short *, aoclsparse_int, int, const unsigned char *,    \
-                                                const T *, const SellSliceDesc *, int);
-MI355_SELL_INSTANTIATE(double)
-MI355_SELL_INSTANTIATE(float)
+template aoclsparse_status launch_sellmv<double>(hipStream_t, const SellView &, int, bool, double, const double *, double, double *, int);
+template aoclsparse_status launch_sellmv<float>(hipStream_t, const SellView &, int, bool, float, const float *, float, float *, int);
+template aoclsparse_status launch_sellmv<cdouble>(hipStream_t, const SellView &, int, bool, cdouble, const cdouble *, cdouble, cdouble *, int);
+template aoclsparse_status launch_sellmv<cfloat>(hipStream_t, const SellView &, int, bool, cfloat, const cfloat *, cfloat, cfloat *, int);
 
 } // namespace mi355

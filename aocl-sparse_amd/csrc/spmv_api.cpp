@@ -115,13 +115,8 @@ aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const Devic
     if(st != aoclsparse_status_success)
         return st;
     if(plan.sell.valid) // format chosen by optimize for an mv hint: every order is exact there
-        st = launch_sellmv<T>(rt.stream(), order, plan.sell.pack, alpha, d.m, plan.sell.nslices, plan.sell.slice_ptr.as<long long>(),
-                              plan.sell.val.as<T>(), plan.sell.col.as<aoclsparse_int>(),
-                              plan.sell.rowlen.as<aoclsparse_int>(), static_cast<const T *>(ax.dev), beta,
-                              static_cast<T *>(ay.dev), plan.sell.shared ? plan.sell.cptr.as<long long>() : nullptr,
-                              plan.sell.shared ? plan.sell.lead.as<unsigned short>() : nullptr, plan.max_row_nnz,
-                              plan.sell.next_direction(), plan.sell.ntab ? plan.sell.vidx.as<unsigned char>() : nullptr,
-                              plan.sell.ntab ? plan.sell.vtab.as<T>() : nullptr, plan.sell.desc.as<SellSliceDesc>(), plan.sell.ntab);
+        st = launch_sellmv<T>(rt.stream(), plan.sell.view(d.m, plan.max_row_nnz), order, false, alpha, static_cast<const T *>(ax.dev), beta,
+                              static_cast<T *>(ay.dev), plan.sell.next_direction());
     else if(plan.merge.valid && order == 0 && !strict) // balanced tiles for irregular rows (scalar order, no pinned kid)
     {
         // one launch; the pieces of cut rows meet in the piece set of this stream (internal.hpp, MergePlan).  Finding the set
