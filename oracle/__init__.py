@@ -21,9 +21,8 @@ P = ctypes.c_void_p
 
 def build(force=False):
     """Compile oracle.c with the committed Makefile (gcc only)."""
-    src = os.path.join(_HERE, "oracle.c")
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(
-        os.path.getmtime(src), os.path.getmtime(os.path.join(_HERE, "oracle.h"))
+        os.path.getmtime(os.path.join(_HERE, f)) for f in ("oracle.c", "oracle.h", "oracle_tmpl.h")
     ):
         subprocess.check_call(["make", "-C", _HERE, "-s", "clean", "all"])
     return _LIB_PATH
@@ -151,6 +150,16 @@ def dtrsv(kind, alpha, m, base, a, icol, ilrow, ilend, b, unit, incb=1, incx=1, 
     x = np.zeros(max(1, (m - 1) * incx + 1), dtype=np.float64) if x0 is None else _f64(x0).copy()
     fn = getattr(lib(), "orc_dtrsv_" + kind)
     st = fn(c_dbl(alpha), c_i32(m), c_int(base), _p(a), _p(icol), _p(ilrow), _p(ilend), _p(b),
+            c_i32(incb), _p(x), c_i32(incx), c_int(1 if unit else 0))
+    return st, x
+
+
+def strsv(kind, alpha, m, base, a, icol, ilrow, ilend, b, unit, incb=1, incx=1, x0=None):
+    """float twin of dtrsv: kind in {'l','lt','u','ut'}; ilend = idiag (l, lt) or iurow (u, ut)."""
+    a, icol, ilrow, ilend, b = _f32(a), _i32(icol), _i32(ilrow), _i32(ilend), _f32(b)
+    x = np.zeros(max(1, (m - 1) * incx + 1), dtype=np.float32) if x0 is None else _f32(x0).copy()
+    fn = getattr(lib(), "orc_strsv_" + kind)
+    st = fn(c_flt(alpha), c_i32(m), c_int(base), _p(a), _p(icol), _p(ilrow), _p(ilend), _p(b),
             c_i32(incb), _p(x), c_i32(incx), c_int(1 if unit else 0))
     return st, x
 
@@ -335,8 +344,21 @@ def dsymgs(mtype, fill, trans, base, alpha, m, val, col, ptr, idiag, iurow, b, x
     return st, x
 
 
+def ssymgs(mtype, fill, trans, base, alpha, m, val, col, ptr, idiag, iurow, b, x0, reversed=False):
+    """float twin of dsymgs; reversed: every row of the two triangular products summed in the opposite order."""
+    val, col, ptr, idiag, iurow, b = _f32(val), _i32(col), _i32(ptr), _i32(idiag), _i32(iurow), _f32(b)
+    x = _f32(x0).copy()
+    st = lib().orc_ssymgs(c_int(mtype), c_int(fill), c_int(trans), c_int(base), c_flt(alpha), c_i32(m), _p(val),
+                          _p(col), _p(ptr), _p(idiag), _p(iurow), _p(b), _p(x), c_int(1 if reversed else 0))
+    return st, x
+
+
 def csr2ell(layout, m, base, row_ptr, col_ind, val):
-    """layout 'ell' | 'ellt' -> (width, ell_col, ell_val); 'hyb' -> (width, ell_m, map, ell_col, ell_val)."""
+    """layout 'ell' | 'ellt' -> (width, ell_col, ell_val); 'hyb' -> (width, ell_m, map, ell_col, ell_val).
+    float32 values come back as float32 (the conversion copies values: exact through the double kernels)."""
+    if np.asarray(val).dtype == np.float32:
+        out = csr2ell(layout, m, base, row_ptr, col_ind, np.asarray(val, dtype=np.float64))
+        return out[:-1] + (out[-1].astype(np.float32),)
     row_ptr, col_ind, val = _i32(row_ptr), _i32(col_ind), _f64(val)
     L = lib()
     w, em = c_i32(0), c_i32(0)
@@ -371,6 +393,13 @@ def sellmv(base, alpha, m, val, col, width, x, beta, y):
     y = _f32(y).copy()
     st = lib().orc_sellmv(c_int(base), ctypes.c_float(alpha), c_i32(m), _p(val), _p(col), c_i32(width), _p(x),
                           ctypes.c_float(beta), _p(y))
+    return st, y
+
+
+def selltmv(base, alpha, m, val, col, width, x, beta, y):
+    val, col, x = _f32(val), _i32(col), _f32(x)
+    y = _f32(y).copy()
+    st = lib().orc_selltmv(c_int(base), c_flt(alpha), c_i32(m), _p(val), _p(col), c_i32(width), _p(x), c_flt(beta), _p(y))
     return st, y
 
 
@@ -439,6 +468,25 @@ def dgmres(n, base, ptr, col, val, b, x0, restart, rtol, atol, maxit, precond):
     x, rinfo = _f64(x0).copy(), np.zeros(100)
     st = lib().orc_dgmres(c_i32(n), c_int(base), _p(ptr), _p(col), _p(val), _p(b), _p(x), c_i32(restart), c_dbl(rtol),
                           c_dbl(atol), c_i32(maxit), c_int(precond), _p(rinfo))
+    return st, x, rinfo
+
+
+def scg(n, base, ptr, col, val, idiag, iurow, b, x0, rtol, atol, maxit, precond, dots="forward"):
+    """float twin of dcg (float arithmetic throughout); dots 'forward' | 'pairwise': how every dot product and norm is summed."""
+    ptr, col, val, idiag, iurow, b = _i32(ptr), _i32(col), _f32(val), _i32(idiag), _i32(iurow), _f32(b)
+    x, rinfo = _f32(x0).copy(), np.zeros(100, np.float32)
+    st = lib().orc_scg(c_i32(n), c_int(base), _p(ptr), _p(col), _p(val), _p(idiag), _p(iurow), _p(b), _p(x),
+                       c_flt(rtol), c_flt(atol), c_i32(maxit), c_int(precond), _p(rinfo),
+                       c_int({"forward": 0, "pairwise": 1}[dots]))
+    return st, x, rinfo
+
+
+def sgmres(n, base, ptr, col, val, b, x0, restart, rtol, atol, maxit, precond, dots="forward"):
+    """float twin of dgmres (float arithmetic throughout); dots as in scg."""
+    ptr, col, val, b = _i32(ptr), _i32(col), _f32(val), _f32(b)
+    x, rinfo = _f32(x0).copy(), np.zeros(100, np.float32)
+    st = lib().orc_sgmres(c_i32(n), c_int(base), _p(ptr), _p(col), _p(val), _p(b), _p(x), c_i32(restart), c_flt(rtol),
+                          c_flt(atol), c_i32(maxit), c_int(precond), _p(rinfo), c_int({"forward": 0, "pairwise": 1}[dots]))
     return st, x, rinfo
 
 
@@ -621,6 +669,13 @@ def dsorv(n, base, ptr, ind, val, omega, alpha, x, b):
     """One forward SOR sweep (solvers/aoclsparse_sorv.hpp:78-113); returns (status, x)."""
     ptr, ind, val, x, b = _i32(ptr), _i32(ind), _f64(val), _f64(x).copy(), _f64(b)
     st = lib().orc_dsorv(c_i32(n), c_int(base), _p(ptr), _p(ind), _p(val), c_dbl(omega), c_dbl(alpha), _p(x), _p(b))
+    return st, x
+
+
+def ssorv(n, base, ptr, ind, val, omega, alpha, x, b):
+    """float twin of dsorv; returns (status, x)."""
+    ptr, ind, val, x, b = _i32(ptr), _i32(ind), _f32(val), _f32(x).copy(), _f32(b)
+    st = lib().orc_ssorv(c_i32(n), c_int(base), _p(ptr), _p(ind), _p(val), c_flt(omega), c_flt(alpha), _p(x), _p(b))
     return st, x
 
 

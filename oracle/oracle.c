@@ -9,6 +9,7 @@
  */
 #include "oracle.h"
 
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -404,69 +405,6 @@ int orc_dcsrmv_symm(int base, double alpha, oint m, int diag, int fill, const do
     return ORC_SUCCESS;
 }
 
-/* csrmv_kr.hpp:658-728 (ref_csrmv_tri): rows [rs[i], re[i]) of the clean CSR, i.e. strict triangle
- * plus the stored diagonal; unit/zero diag drop the stored diagonal, unit adds x[i]. */
-int orc_dcsrmv_tri(int base, double alpha, oint m, int diag, int fill, const double *val,
-                   const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
-                   const double *x, double beta, double *y)
-{
-    (void)iurow;
-    scale_y_d(y, m, beta);
-    for(oint i = 0; i < m; i++)
-    {
-        /* lower: [ptr[i], iurow[i]) ; upper: [idiag[i], ptr[i+1]) (csrmv.hpp:110-123) */
-        oint rs = fill == 0 ? ptr[i] : idiag[i], re = fill == 0 ? iurow[i] : ptr[i + 1];
-        int  so = 0, eo = 0;
-        if(diag != 0)
-        {
-            if(fill == 0)
-                eo = -1;
-            else
-                so = 1;
-        }
-        double r = 0.0;
-        if(so && diag == 1)
-            r += x[i];
-        for(oint j = rs + so; j < re + eo; j++)
-            r = CH_D(val[j - base], x[col[j - base] - base], r);
-        if(eo && diag == 1)
-            r += x[i];
-        y[i] = fma(alpha, r, y[i]);
-    }
-    return ORC_SUCCESS;
-}
-
-/* csrmv_kr.hpp:577-649 (ref_csrmv_tri_th): transposed triangular SpMV, column sweep. */
-int orc_dcsrmv_tri_t(int base, double alpha, oint m, oint n, int diag, int fill, const double *val,
-                     const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
-                     const double *x, double beta, double *y)
-{
-    scale_y_d(y, n, beta);
-    for(oint i = 0; i < m; i++)
-    {
-        oint rs = fill == 0 ? ptr[i] : idiag[i], re = fill == 0 ? iurow[i] : ptr[i + 1];
-        int  so = 0, eo = 0;
-        if(diag != 0)
-        {
-            if(fill == 0)
-                eo = -1;
-            else
-                so = 1;
-        }
-        double axi = alpha * x[i];
-        if(so && diag == 1)
-            y[i] += axi;
-        for(oint j = rs + so; j < re + eo; j++)
-        {
-            oint c = col[j - base] - base;
-            y[c]   = fma(val[j - base], axi, y[c]);
-        }
-        if(eo && diag == 1)
-            y[i] += axi;
-    }
-    return ORC_SUCCESS;
-}
-
 /* ------------------------------------------------------------------------------------ */
 /* TRSV reference kernels, trsv_kr.hpp:38-222.  "xi -= a*x" contracts to fma(-a, x, xi). */
 /* ------------------------------------------------------------------------------------ */
@@ -504,48 +442,6 @@ int orc_dcsrmv_tri_t(int base, double alpha, oint m, oint n, int diag, int fill,
 
 DEF_TRSV(double, d, fma, CH_D)
 DEF_TRSV(float, s, fmaf, CH_S)
-
-/* trsv_kr.hpp:101-120: x = alpha*b; for i = m-1..0: x[i] /= d; x[col] -= a*x[i]. */
-int orc_dtrsv_lt(double alpha, oint m, int base, const double *a, const oint *icol,
-                 const oint *ilrow, const oint *idiag, const double *b, oint incb, double *x,
-                 oint incx, int unit)
-{
-    for(oint i = 0; i < m; i++)
-        x[(size_t)i * incx] = alpha * b[(size_t)i * incb];
-    for(oint i = m - 1; i >= 0; i--)
-    {
-        if(!unit)
-            x[(size_t)i * incx] /= a[idiag[i] - base];
-        double xi = x[(size_t)i * incx];
-        for(oint idx = ilrow[i]; idx < idiag[i]; idx++)
-        {
-            size_t c = (size_t)(icol[idx - base] - base) * incx;
-            x[c]     = fma(-a[idx - base], xi, x[c]);
-        }
-    }
-    return ORC_SUCCESS;
-}
-
-/* trsv_kr.hpp:196-221: x = alpha*b; for i = 0..m-1: x[i] /= d; x[col] -= a*x[i]. */
-int orc_dtrsv_ut(double alpha, oint m, int base, const double *a, const oint *icol,
-                 const oint *ilrow, const oint *iurow, const double *b, oint incb, double *x,
-                 oint incx, int unit)
-{
-    for(oint i = 0; i < m; i++)
-        x[(size_t)i * incx] = alpha * b[(size_t)i * incb];
-    for(oint i = 0; i < m; i++)
-    {
-        if(!unit)
-            x[(size_t)i * incx] /= a[iurow[i] - 1 - base];
-        double xi = x[(size_t)i * incx];
-        for(oint idx = iurow[i]; idx <= ilrow[i + 1] - 1; idx++)
-        {
-            size_t c = (size_t)(icol[idx - base] - base) * incx;
-            x[c]     = fma(-a[idx - base], xi, x[c]);
-        }
-    }
-    return ORC_SUCCESS;
-}
 
 /* ------------------------------------------------------------------------------------ */
 /* KT ("kernel template") TRSV kernels, level2/aoclsparse_trsv_kt.cpp:64-531 -- what the  */
@@ -1169,131 +1065,6 @@ int orc_dcsr2csc(oint m, oint n, oint nnz, int base_csr, int base_csc, const oin
     return ORC_SUCCESS;
 }
 
-/* ilu0.hpp:35-107: IKJ ILU(0) in place; lu_diag_ptr[i] = 0-based position of the diagonal.
- * Restated with the reference's mapper convention (a stored position of 0 means "absent",
- * :83-86), so the entry at array position 0 is never updated -- kept for fidelity. */
-int orc_dilu0(oint n, int base, oint *lu_diag_ptr, double *val, const oint *row_ptr,
-              const oint *col_ind)
-{
-    oint *mapper = (oint *)calloc((size_t)(n > 0 ? n : 1), sizeof(oint));
-    if(!mapper)
-        return ORC_MEMORY_ERROR;
-    for(oint i = 0; i < n; i++)
-    {
-        oint j1 = row_ptr[i] - base, j2 = row_ptr[i + 1] - base, j, k = -1;
-        for(j = j1; j < j2; j++)
-            mapper[col_ind[j] - base] = j;
-        for(j = j1; j < j2; j++)
-        {
-            k = col_ind[j] - base;
-            if(k >= i)
-                break;
-            double d = val[lu_diag_ptr[k]];
-            if(fabs(d) <= 1e-2 * 2.0 * 2.220446049250313e-16) /* aoclsparse_is_nearzero, extra/aoclsparse_utils.hpp:598-613 */
-            {
-                free(mapper);
-                return ORC_NUMERICAL_ERROR;
-            }
-            val[j] = val[j] / d;
-            for(oint jj = lu_diag_ptr[k] + 1; jj < row_ptr[k + 1] - base; jj++)
-            {
-                oint jw = mapper[col_ind[jj] - base];
-                if(jw != 0)
-                    val[jw] = fma(-val[j], val[jj], val[jw]);
-            }
-        }
-        lu_diag_ptr[i] = j;
-        if(j >= j2 || k != i || fabs(val[j]) <= 1e-2 * 2.0 * 2.220446049250313e-16)
-        {
-            free(mapper);
-            return ORC_NUMERICAL_ERROR;
-        }
-        for(oint mn = j1; mn < j2; mn++)
-            mapper[col_ind[mn] - base] = 0;
-    }
-    free(mapper);
-    return ORC_SUCCESS;
-}
-
-/* ------------------------------------------------------------------------------------ */
-/* Symmetric Gauss-Seidel sweep, solvers/aoclsparse_symgs.hpp:62-258 (symgs_ref), built   */
-/* from the triangular SpMV and TRSV restatements above exactly as the reference chains   */
-/* aoclsparse::mv / aoclsparse::trsv on the clean CSR.  type: 0 general, 1 symmetric,     */
-/* 3 triangular; fill 0 lower / 1 upper; trans 0 none / 1 transpose.                      */
-/* ------------------------------------------------------------------------------------ */
-static int symgs_mv(int tr, int base, double alpha, oint m, int diag, int fill, const double *val,
-                    const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
-                    const double *x, double *y)
-{
-    /* beta = 0: the triangular kernels zero y first (csrmv_kr.hpp:535-542) */
-    return tr ? orc_dcsrmv_tri_t(base, alpha, m, m, diag, fill, val, col, ptr, idiag, iurow, x, 0.0, y)
-              : orc_dcsrmv_tri(base, alpha, m, diag, fill, val, col, ptr, idiag, iurow, x, 0.0, y);
-}
-static int symgs_sv(int tr, int fill, int base, oint m, const double *val, const oint *col,
-                    const oint *ptr, const oint *idiag, const oint *iurow, const double *b, double *x)
-{
-    if(fill == 0)
-        return tr ? orc_dtrsv_lt(1.0, m, base, val, col, ptr, idiag, b, 1, x, 1, 0)
-                  : orc_dtrsv_l(1.0, m, base, val, col, ptr, idiag, b, 1, x, 1, 0);
-    return tr ? orc_dtrsv_ut(1.0, m, base, val, col, ptr, iurow, b, 1, x, 1, 0)
-              : orc_dtrsv_u(1.0, m, base, val, col, ptr, iurow, b, 1, x, 1, 0);
-}
-int orc_dsymgs(int type, int fill, int trans, int base, double alpha, oint m, const double *val,
-               const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
-               const double *b, double *x, double *y, int fuse_mv)
-{
-    if(type == 3) /* :128-149 */
-        return symgs_sv(trans, fill, base, m, val, col, ptr, idiag, iurow, b, x);
-    int u_tr = 1, l_tr = 0, u_fill = 0, l_fill = 0; /* symmetric, lower stored (:151-163) */
-    if(type == 1 && fill == 1)
-        u_fill = l_fill = 1, u_tr = 0, l_tr = 1;
-    else if(type == 0 && trans == 0)
-        u_tr = l_tr = 0, u_fill = 1;
-    else if(type == 0 && trans == 1)
-        u_tr = l_tr = 1, l_fill = 1, u_fill = 0;
-    double *r = (double *)malloc(sizeof(double) * (size_t)(m > 0 ? m : 1));
-    double *q = (double *)malloc(sizeof(double) * (size_t)(m > 0 ? m : 1));
-    if(!r || !q)
-    {
-        free(r), free(q);
-        return ORC_MEMORY_ERROR;
-    }
-    symgs_mv(u_tr, base, alpha, m, 2, u_fill, val, col, ptr, idiag, iurow, x, q); /* q = alpha U x0 */
-    for(oint i = 0; i < m; i++)
-        r[i] = b[i] - q[i];
-    symgs_sv(l_tr, l_fill, base, m, val, col, ptr, idiag, iurow, r, q); /* (L+D) x1 = r */
-    symgs_mv(l_tr, base, 1.0, m, 2, l_fill, val, col, ptr, idiag, iurow, q, r); /* r = L x1 */
-    for(oint i = 0; i < m; i++)
-        q[i] = b[i] - r[i];
-    symgs_sv(u_tr, u_fill, base, m, val, col, ptr, idiag, iurow, q, x); /* (U+D) x = q */
-    free(r), free(q);
-    (void)y, (void)fuse_mv; /* the closing product is checked by the callers with orc_dcsrmv* */
-    return ORC_SUCCESS;
-}
-
-/* ILU(0) solve, solvers/aoclsparse_ilu0.hpp:113-156: L y = b (unit lower), U x = y; "sum - val*x"  */
-/* contracts to an FMA under the reference's -ffp-contract=fast.                                    */
-int orc_dilu_solve(oint n, int base, const oint *lu_diag_ptr, const double *val, const oint *row_ptr,
-                   const oint *col_ind, double *x, const double *b)
-{
-    for(oint i = 0; i < n; i++)
-    {
-        double sum = b[i];
-        for(oint k = row_ptr[i] - base; k < lu_diag_ptr[i]; k++)
-            sum = fma(-val[k], x[col_ind[k] - base], sum);
-        x[i] = sum;
-    }
-    for(oint i = n - 1; i >= 0; i--)
-    {
-        for(oint k = lu_diag_ptr[i] + 1; k < row_ptr[i + 1] - base; k++)
-            x[i] = fma(-val[k], x[col_ind[k] - base], x[i]);
-        double d = val[lu_diag_ptr[i]];
-        if(!(fabs(d) <= 1e-2 * 2.0 * 2.220446049250313e-16))
-            x[i] = x[i] / d;
-    }
-    return ORC_SUCCESS;
-}
-
 /* ------------------------------------------------------------------------------------ */
 /* ELL family, level2/aoclsparse_ellmv.hpp.  Padding of row-major ELL = column -1.        */
 /* ------------------------------------------------------------------------------------ */
@@ -1359,19 +1130,6 @@ int orc_sellmv(int base, float alpha, oint m, const float *val, const oint *col,
         if(beta != 0.0f)
             r = fmaf(beta, y[i], r);
         y[i] = r;
-    }
-    return ORC_SUCCESS;
-}
-/* aoclsparse_elltmv_avx2 / _ref, ellmv.hpp:316-444: one FMA chain per row over the column-major cells */
-int orc_delltmv(int base, double alpha, oint m, const double *val, const oint *col, oint width,
-                const double *x, double beta, double *y)
-{
-    for(oint j = 0; j < m; j++)
-    {
-        double r = 0.0;
-        for(oint i = 0; i < width; i++)
-            r = fma(val[(size_t)i * m + j], x[col[(size_t)i * m + j] - base], r);
-        y[j] = ell_finish_d(r, alpha, beta, y[j]);
     }
     return ORC_SUCCESS;
 }
@@ -1677,245 +1435,6 @@ int orc_dcsr2ellthyb(oint m, int base, oint *ell_m, const oint *row_ptr, const o
             ell_col[(size_t)k * m + i] = pad, ell_val[(size_t)k * m + i] = 0.0;
     }
     return ORC_SUCCESS;
-}
-
-/* ------------------------------------------------------------------------------------ */
-/* Iterative solvers, solvers/aoclsparse_itsol_functions.hpp: CG :632-875 (+ the built-in */
-/* SymGS preconditioner :390-479), restarted GMRES :910-1367 (+ ILU(0) preconditioner).   */
-/* The reference's level-1 steps are AOCL-BLAS calls (not vendored): plain loops here.    */
-/* A is a general clean CSR holding the whole (for CG: symmetric) matrix.                 */
-/* precond: CG 0 none / 3 SymGS; GMRES 0 none / 2 ILU0.  Returns the reference's status;   */
-/* rinfo[0] residual norm, rinfo[1] ||b|| (GMRES: rtol*||b||), rinfo[30] iterations.       */
-/* ------------------------------------------------------------------------------------ */
-static double orc_nrm2(oint n, const double *v)
-{
-    double s = 0.0;
-    for(oint i = 0; i < n; i++)
-        s += v[i] * v[i];
-    return sqrt(s);
-}
-static void orc_mv(oint n, int base, const oint *ptr, const oint *col, const double *val,
-                   const double *x, double *y)
-{
-    orc_dcsrmv_ref(base, 1.0, n, val, col, ptr, x, 0.0, y);
-}
-int orc_dcg(oint n, int base, const oint *ptr, const oint *col, const double *val,
-            const oint *idiag, const oint *iurow, const double *b, double *x, double rtol,
-            double atol, oint maxit, int precond, double *rinfo)
-{
-    const double tiny = 1e-2 * 2.0 * 2.220446049250313e-16;
-    double      *w    = (double *)calloc(5 * (size_t)(n > 0 ? n : 1), sizeof(double));
-    if(!w)
-        return ORC_MEMORY_ERROR;
-    double *r = w, *z = w + n, *p = w + 2 * (size_t)n, *q = w + 3 * (size_t)n, *y = w + 4 * (size_t)n;
-    int     status = ORC_SUCCESS;
-    for(int i = 0; i < 100; i++)
-        rinfo[i] = 0.0;
-    for(oint i = 0; i < n; i++)
-        r[i] = -b[i], p[i] = x[i];
-    double bnorm = orc_nrm2(n, b), brtol = rtol * bnorm;
-    rinfo[1]     = bnorm;
-    orc_mv(n, base, ptr, col, val, p, q);
-    for(oint i = 0; i < n; i++)
-        r[i] += q[i], p[i] = 0.0;
-    double rnorm = orc_nrm2(n, r), rz = 1.0;
-    rinfo[0]     = rnorm;
-    oint niter   = 0;
-    for(;;)
-    {
-        if((0.0 < atol && rnorm <= atol) || (0.0 < rtol && rnorm <= brtol))
-            break;
-        if(maxit > 0 && niter > maxit)
-        {
-            status = 7; /* aoclsparse_status_maxit */
-            break;
-        }
-        niter++;
-        rinfo[30] = (double)niter;
-        if(precond == 3)
-        {
-            /* (L+D) y = r ; y = D y ; (U+D) z = y */
-            orc_dtrsv_l(1.0, n, base, val, col, ptr, idiag, r, 1, y, 1, 0);
-            for(oint i = 0; i < n; i++)
-                y[i] *= val[idiag[i] - base];
-            orc_dtrsv_u(1.0, n, base, val, col, ptr, iurow, y, 1, z, 1, 0);
-        }
-        else
-            for(oint i = 0; i < n; i++)
-                z[i] = r[i];
-        double rz_new = 0.0;
-        for(oint i = 0; i < n; i++)
-            rz_new += r[i] * z[i];
-        if(rz <= tiny)
-        {
-            status = ORC_NUMERICAL_ERROR;
-            break;
-        }
-        double beta = rz_new / rz;
-        rz          = rz_new;
-        for(oint i = 0; i < n; i++)
-            p[i] = beta * p[i] - z[i];
-        orc_mv(n, base, ptr, col, val, p, q);
-        double pq = 0.0;
-        for(oint i = 0; i < n; i++)
-            pq += p[i] * q[i];
-        if(pq <= tiny)
-        {
-            status = ORC_NUMERICAL_ERROR;
-            break;
-        }
-        double alpha = rz / pq;
-        for(oint i = 0; i < n; i++)
-            x[i] += alpha * p[i], r[i] += alpha * q[i];
-        rnorm    = orc_nrm2(n, r);
-        rinfo[0] = rnorm;
-    }
-    free(w);
-    return status;
-}
-
-/* LAPACK 3.10 dlartg, unscaled branch (the values met here are far from the over/underflow limits) */
-static void orc_lartg(double f, double g, double *c, double *s, double *r)
-{
-    if(g == 0.0)
-        *c = 1.0, *s = 0.0, *r = f;
-    else if(f == 0.0)
-        *c = 0.0, *s = copysign(1.0, g), *r = fabs(g);
-    else
-    {
-        double d = sqrt(f * f + g * g);
-        *c = fabs(f) / d, *r = copysign(d, f), *s = g / *r;
-    }
-}
-int orc_dgmres(oint n, int base, const oint *ptr, const oint *col, const double *val,
-               const double *b, double *x, oint m, double rtol, double atol, oint maxit,
-               int precond, double *rinfo)
-{
-    const double tiny = 1e-2 * 2.0 * 2.220446049250313e-16;
-    size_t       nn = (size_t)(n > 0 ? n : 1), mm = (size_t)m;
-    double      *V = (double *)calloc((mm + 1) * nn, sizeof(double)), *Z = (double *)calloc((mm + 1) * nn, sizeof(double));
-    double      *h = (double *)calloc(mm * mm, sizeof(double)), *g = (double *)calloc(mm + 1, sizeof(double));
-    double      *c = (double *)calloc(mm, sizeof(double)), *s = (double *)calloc(mm, sizeof(double));
-    double      *lu = NULL;
-    oint        *ludiag = NULL;
-    int          status = ORC_SUCCESS;
-    if(!V || !Z || !h || !g || !c || !s)
-    {
-        status = ORC_MEMORY_ERROR;
-        goto done;
-    }
-    if(precond == 2)
-    {
-        oint nnz = ptr[n] - base;
-        lu       = (double *)malloc(sizeof(double) * (size_t)(nnz > 0 ? nnz : 1));
-        ludiag   = (oint *)malloc(sizeof(oint) * nn);
-        if(!lu || !ludiag)
-        {
-            status = ORC_MEMORY_ERROR;
-            goto done;
-        }
-        memcpy(lu, val, sizeof(double) * (size_t)nnz);
-        status = orc_dilu0(n, base, ludiag, lu, ptr, col);
-        if(status != ORC_SUCCESS)
-            goto done;
-    }
-    oint niter = 0;
-    for(;;) /* one restart cycle per pass */
-    {
-        orc_mv(n, base, ptr, col, val, x, V);
-        double bnorm = orc_nrm2(n, b), brtol = rtol * bnorm;
-        rinfo[1]     = brtol;
-        if(fabs(atol) <= tiny && fabs(brtol) <= tiny)
-        {
-            status = 5; /* invalid_value */
-            goto done;
-        }
-        for(oint i = 0; i < n; i++)
-            V[i] = b[i] - V[i];
-        double rnorm = orc_nrm2(n, V);
-        g[0] = rnorm, rinfo[0] = rnorm;
-        if((0.0 < rnorm && (rnorm <= atol || rnorm <= brtol)) || rnorm == 0.0)
-        {
-            rinfo[30] = (double)niter;
-            goto done;
-        }
-        for(oint i = 0; i < n; i++)
-            V[i] *= 1.0 / rnorm;
-        oint j = 0;
-        for(; j < m; j++)
-        {
-            double *vj = V + (size_t)j * nn, *w = V + (size_t)(j + 1) * nn, *zj = Z + (size_t)j * nn;
-            if(precond == 2)
-                orc_dilu_solve(n, base, ludiag, lu, ptr, col, zj, vj);
-            orc_mv(n, base, ptr, col, val, precond ? zj : vj, w);
-            for(oint i = 0; i <= j; i++)
-            {
-                double d = 0.0;
-                for(oint k = 0; k < n; k++)
-                    d += w[k] * V[(size_t)i * nn + k];
-                h[(size_t)i * mm + j] = d;
-            }
-            for(oint k = 0; k < n; k++)
-            {
-                double hv = 0.0;
-                for(oint i = 0; i <= j; i++)
-                    hv += h[(size_t)i * mm + j] * V[(size_t)i * nn + k];
-                w[k] -= hv;
-            }
-            double hh = orc_nrm2(n, w);
-            if(hh < atol || hh < brtol)
-            {
-                niter += j + 1;
-                rinfo[30] = (double)niter, rinfo[0] = hh;
-                goto done;
-            }
-            for(oint k = 0; k < n; k++)
-                w[k] *= 1.0 / hh;
-            for(oint i = 0; i < j; i++)
-            {
-                double r1 = h[(size_t)i * mm + j], r2 = h[(size_t)(i + 1) * mm + j];
-                h[(size_t)i * mm + j]       = c[i] * r1 - s[i] * r2;
-                h[(size_t)(i + 1) * mm + j] = s[i] * r1 + c[i] * r2;
-            }
-            double rr = h[(size_t)j * mm + j];
-            orc_lartg(rr, -hh, &c[j], &s[j], &h[(size_t)j * mm + j]);
-            double g0 = g[j];
-            g[j] = c[j] * g0, g[j + 1] = s[j] * g0;
-            rinfo[0] = fabs(g[j]);
-        }
-        for(oint jj = m - 1; jj >= 0; jj--)
-        {
-            double yj = g[jj];
-            for(oint i = jj + 1; i < m; i++)
-                yj -= h[(size_t)jj * mm + i] * s[i];
-            if(fabs(h[(size_t)jj * mm + jj]) <= tiny)
-            {
-                status = ORC_NUMERICAL_ERROR;
-                goto done;
-            }
-            s[jj] = yj / h[(size_t)jj * mm + jj];
-        }
-        for(oint k = 0; k < n; k++)
-        {
-            double acc = 0.0;
-            for(oint t = 0; t < m; t++)
-                acc += (precond ? Z : V)[(size_t)t * nn + k] * s[t];
-            x[k] += acc;
-        }
-        rnorm = fabs(g[m]);
-        niter += m;
-        rinfo[30] = (double)niter, rinfo[0] = rnorm;
-        if((0.0 < atol && rnorm <= atol) || (0.0 < rnorm && rnorm <= brtol))
-            goto done;
-        if(maxit > 0 && niter >= maxit)
-        {
-            status = 7;
-            goto done;
-        }
-    }
-done:
-    free(V), free(Z), free(h), free(g), free(c), free(s), free(lu), free(ludiag);
-    return status;
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -2343,39 +1862,74 @@ void orc_dbsrmv(double alpha, oint mb, oint dim, int base, const double *val, co
         }
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* The restatements that exist in both precisions (oracle_tmpl.h): triangular SpMV,       */
+/* transposed TRSV, ILU(0), SymGS, ELL-T, SOR, CG and GMRES.                              */
+/* ------------------------------------------------------------------------------------ */
+#define ORC_T double
+#define ORC_S d
+#define ORC_FMA fma
+#define ORC_CH CH_D
+#define ORC_SQRT sqrt
+#define ORC_FABS fabs
+#define ORC_COPYSIGN copysign
+#define ORC_EPS DBL_EPSILON
+#include "oracle_tmpl.h"
+#undef ORC_T
+#undef ORC_S
+#undef ORC_FMA
+#undef ORC_CH
+#undef ORC_SQRT
+#undef ORC_FABS
+#undef ORC_COPYSIGN
+#undef ORC_EPS
 
-/* ---- forward SOR sweep: solvers/aoclsparse_sorv.hpp:78-113 and :212-226 (x = alpha*x first; exact zeros for
- * alpha == 0).  Returns 5 (invalid_value) when a row lacks a single non-zero diagonal entry (:32-75). */
-int orc_dsorv(oint n, int base, const oint *ptr, const oint *ind, const double *val, double omega, double alpha,
-              double *x, const double *b)
+#define ORC_T float
+#define ORC_S s
+#define ORC_FMA fmaf
+#define ORC_CH CH_S
+#define ORC_SQRT sqrtf
+#define ORC_FABS fabsf
+#define ORC_COPYSIGN copysignf
+#define ORC_EPS FLT_EPSILON
+#include "oracle_tmpl.h"
+#undef ORC_T
+#undef ORC_S
+#undef ORC_FMA
+#undef ORC_CH
+#undef ORC_SQRT
+#undef ORC_FABS
+#undef ORC_COPYSIGN
+#undef ORC_EPS
+
+int orc_dsymgs(int type, int fill, int trans, int base, double alpha, oint m, const double *val, const oint *col,
+               const oint *ptr, const oint *idiag, const oint *iurow, const double *b, double *x, double *y, int fuse_mv)
 {
-    for(oint i = 0; i < n; i++)
-    {
-        int found = 0;
-        for(oint j = ptr[i] - base; j < ptr[i + 1] - base; j++)
-            if(ind[j] - base == i)
-            {
-                if(found || val[j] == 0.0)
-                    return ORC_INVALID_VALUE;
-                found = 1;
-            }
-        if(!found)
-            return ORC_INVALID_VALUE;
-    }
-    for(oint i = 0; i < n; i++)
-        x[i] = alpha != 0.0 ? alpha * x[i] : 0.0;
-    for(oint i = 0; i < n; i++)
-    {
-        double axi = 0.0, d = 1.0;
-        for(oint j = ptr[i] - base; j < ptr[i + 1] - base; j++)
-        {
-            const oint c = ind[j] - base;
-            if(c != i)
-                axi = fma(val[j], x[c], axi);
-            else
-                d = val[j];
-        }
-        x[i] = fma(omega, (b[i] - axi) / d - x[i], x[i]);
-    }
-    return ORC_SUCCESS;
+    (void)y, (void)fuse_mv; /* the closing product is checked by the callers with orc_dcsrmv* */
+    return tmpl_dsymgs(type, fill, trans, base, alpha, m, val, col, ptr, idiag, iurow, b, x, 0);
+}
+int orc_ssymgs(int type, int fill, int trans, int base, float alpha, oint m, const float *val, const oint *col,
+               const oint *ptr, const oint *idiag, const oint *iurow, const float *b, float *x, int reversed)
+{
+    return tmpl_ssymgs(type, fill, trans, base, alpha, m, val, col, ptr, idiag, iurow, b, x, reversed);
+}
+int orc_dcg(oint n, int base, const oint *ptr, const oint *col, const double *val, const oint *idiag, const oint *iurow,
+            const double *b, double *x, double rtol, double atol, oint maxit, int precond, double *rinfo)
+{
+    return tmpl_dcg(n, base, ptr, col, val, idiag, iurow, b, x, rtol, atol, maxit, precond, rinfo, 0);
+}
+int orc_scg(oint n, int base, const oint *ptr, const oint *col, const float *val, const oint *idiag, const oint *iurow,
+            const float *b, float *x, float rtol, float atol, oint maxit, int precond, float *rinfo, int pairwise)
+{
+    return tmpl_scg(n, base, ptr, col, val, idiag, iurow, b, x, rtol, atol, maxit, precond, rinfo, pairwise);
+}
+int orc_dgmres(oint n, int base, const oint *ptr, const oint *col, const double *val, const double *b, double *x, oint m,
+               double rtol, double atol, oint maxit, int precond, double *rinfo)
+{
+    return tmpl_dgmres(n, base, ptr, col, val, b, x, m, rtol, atol, maxit, precond, rinfo, 0);
+}
+int orc_sgmres(oint n, int base, const oint *ptr, const oint *col, const float *val, const float *b, float *x, oint m,
+               float rtol, float atol, oint maxit, int precond, float *rinfo, int pairwise)
+{
+    return tmpl_sgmres(n, base, ptr, col, val, b, x, m, rtol, atol, maxit, precond, rinfo, pairwise);
 }

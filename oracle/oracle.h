@@ -89,6 +89,13 @@ int orc_dcsrmv_tri(int base, double alpha, oint m, int diag, int fill, const dou
 int orc_dcsrmv_tri_t(int base, double alpha, oint m, oint n, int diag, int fill, const double *val,
                      const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
                      const double *x, double beta, double *y);
+/* float twins of the two triangular kernels (the same template: oracle_tmpl.h) */
+int orc_scsrmv_tri(int base, float alpha, oint m, int diag, int fill, const float *val,
+                   const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
+                   const float *x, float beta, float *y);
+int orc_scsrmv_tri_t(int base, float alpha, oint m, oint n, int diag, int fill, const float *val,
+                     const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
+                     const float *x, float beta, float *y);
 /* OpenMP static-row version of orc_dcsrmv (same per-row arithmetic); CPU baseline leg. */
 int orc_dcsrmv_omp(int kid, int base, double alpha, oint m, oint nnz, const double *val,
                    const oint *col, const oint *row, const double *x, double beta, double *y,
@@ -117,6 +124,12 @@ int orc_strsv_l(float alpha, oint m, int base, const float *a, const oint *icol,
 int orc_strsv_u(float alpha, oint m, int base, const float *a, const oint *icol,
                 const oint *ilrow, const oint *iurow, const float *b, oint incb, float *x,
                 oint incx, int unit);
+int orc_strsv_lt(float alpha, oint m, int base, const float *a, const oint *icol,
+                 const oint *ilrow, const oint *idiag, const float *b, oint incb, float *x,
+                 oint incx, int unit);
+int orc_strsv_ut(float alpha, oint m, int base, const float *a, const oint *icol,
+                 const oint *ilrow, const oint *iurow, const float *b, oint incb, float *x,
+                 oint incx, int unit);
 
 /* 1 (default): every "acc += a*b" of the reference is one fma (clang / AOCC build, or GCC without znver tuning);
  * 0: loop-carried scalar accumulations are a multiplication and an addition (GCC build with the reference's -march=znver2). */
@@ -188,16 +201,25 @@ int orc_dcsr2csc(oint m, oint n, oint nnz, int base_csr, int base_csc, const oin
 /* ---- ILU(0), solvers/aoclsparse_ilu0.hpp:35-107 (test-input generator for TRSV) ------ */
 int orc_dilu0(oint n, int base, oint *lu_diag_ptr, double *val, const oint *row_ptr,
               const oint *col_ind);
+int orc_silu0(oint n, int base, oint *lu_diag_ptr, float *val, const oint *row_ptr,
+              const oint *col_ind);
 
 /* solvers/aoclsparse_ilu0.hpp:113-156: x = U^-1 L^-1 b on the factors orc_dilu0 produced */
 int orc_dilu_solve(oint n, int base, const oint *lu_diag_ptr, const double *val, const oint *row_ptr,
                    const oint *col_ind, double *x, const double *b);
+int orc_silu_solve(oint n, int base, const oint *lu_diag_ptr, const float *val, const oint *row_ptr,
+                   const oint *col_ind, float *x, const float *b);
 
 /* ---- symmetric Gauss-Seidel, solvers/aoclsparse_symgs.hpp:62-258 --------------------- */
 /* clean CSR + idiag/iurow; type 0 general / 1 symmetric / 3 triangular; x in: guess, out: sweep */
 int orc_dsymgs(int type, int fill, int trans, int base, double alpha, oint m, const double *val,
                const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
                const double *b, double *x, double *y, int fuse_mv);
+/* the same composition over the float solves and float triangular products; reversed = 1 walks every row of the two
+ * triangular products in the opposite order (no reference kernel does: the spread between two orders of one row) */
+int orc_ssymgs(int type, int fill, int trans, int base, float alpha, oint m, const float *val,
+               const oint *col, const oint *ptr, const oint *idiag, const oint *iurow,
+               const float *b, float *x, int reversed);
 
 /* ---- ELL family, level2/aoclsparse_ellmv.hpp + conversion/aoclsparse_convert.{hpp,cpp} ----- */
 int orc_dellmv(int base, double alpha, oint m, const double *val, const oint *col, oint width,
@@ -206,6 +228,8 @@ int orc_sellmv(int base, float alpha, oint m, const float *val, const oint *col,
                const float *x, float beta, float *y);
 int orc_delltmv(int base, double alpha, oint m, const double *val, const oint *col, oint width,
                 const double *x, double beta, double *y);
+int orc_selltmv(int base, float alpha, oint m, const float *val, const oint *col, oint width,
+                const float *x, float beta, float *y);
 int orc_dellthybmv(int base, double alpha, oint m, const double *ell_val, const oint *ell_col,
                    oint width, oint ell_m, const double *csr_val, const oint *csr_row,
                    const oint *csr_col, const oint *map, const double *x, double beta, double *y);
@@ -239,6 +263,14 @@ int orc_dcg(oint n, int base, const oint *ptr, const oint *col, const double *va
 int orc_dgmres(oint n, int base, const oint *ptr, const oint *col, const double *val,
                const double *b, double *x, oint m, double rtol, double atol, oint maxit,
                int precond, double *rinfo);
+/* float twins, float arithmetic throughout (dots and norms included); pairwise = 1 sums every dot product and norm by
+ * recursive halving instead of front to back (the iteration margin of the GPU tests is the spread of the two) */
+int orc_scg(oint n, int base, const oint *ptr, const oint *col, const float *val,
+            const oint *idiag, const oint *iurow, const float *b, float *x, float rtol,
+            float atol, oint maxit, int precond, float *rinfo, int pairwise);
+int orc_sgmres(oint n, int base, const oint *ptr, const oint *col, const float *val,
+               const float *b, float *x, oint m, float rtol, float atol, oint maxit,
+               int precond, float *rinfo, int pairwise);
 
 /* ---- sp2m (C = A*B, both general CSR), level3/aoclsparse_csr2m.cpp:46-543 ------------ */
 /* stage 1: row_ptr_C (0-based, length m+1).  Returns nnz_C in *nnz_c. */
@@ -281,6 +313,8 @@ void orc_dbsrmv(double alpha, oint mb, oint dim, int base, const double *val, co
 /* forward SOR sweep (solvers/aoclsparse_sorv.hpp:78-113, :212-226) */
 int orc_dsorv(oint n, int base, const oint *ptr, const oint *ind, const double *val, double omega, double alpha,
               double *x, const double *b);
+int orc_ssorv(oint n, int base, const oint *ptr, const oint *ind, const float *val, float omega, float alpha,
+              float *x, const float *b);
 
 #ifdef __cplusplus
 }

@@ -592,9 +592,7 @@ def test_trsv_strided_and_float():
     xf = np.zeros(m, np.float32)
     assert P.strsv(P.OP_NONE, 1.0, Af, dl, bf, xf) == 0
     o = oracle.dcsr_optimize(m, m, len(v), 0, rp, ci, v)
-    xo = np.zeros(m, np.float32)
-    st = oracle.lib().orc_strsv_l(ctypes.c_float(1.0), m, 0, P._ptr(vf), P._ptr(ci), P._ptr(rp),
-                                  P._ptr(o["idiag"]), P._ptr(bf), 1, P._ptr(xo), 1, 0)
+    st, xo = oracle.strsv("l", 1.0, m, 0, vf, ci, rp, o["idiag"], bf, False)
     assert st == 0 and np.array_equal(xf, xo)
 
 
@@ -3393,6 +3391,16 @@ def test_sorv_kats_and_bit_exact_sweeps(kats):
         assert np.linalg.norm(D @ x - b) <= 1e-10 * np.linalg.norm(b)
         xf, bf = x0.astype(np.float32), b.astype(np.float32)
         Af = P.Matrix(base, n, n, rp2, ci2, v2.astype(np.float32))
-        assert L.aoclsparse_ssorv(0, d.h, Af.h, 0.7, 1.0, P._ptr(xf), P._ptr(bf)) == 0
+        # float: the kernel's statement is one serial chain per row, so the float restatement's bits, host and device vectors
+        for omega, alpha in ((0.7, 1.0), (1.3, -0.5), (1.0, 0.0)):
+            st, want = oracle.ssorv(n, base, rp2, ci2, v2.astype(np.float32), omega, alpha, xf, bf)
+            xs = xf.copy()
+            assert st == 0 and L.aoclsparse_ssorv(0, d.h, Af.h, omega, alpha, P._ptr(xs), P._ptr(bf)) == 0
+            assert np.array_equal(xs.view(np.uint32), want.view(np.uint32)), (base, omega, alpha)
+            xd, bd = dev(xf), dev(bf)
+            assert L.aoclsparse_ssorv(0, d.h, Af.h, omega, alpha, ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(bd.data_ptr())) == 0
+            torch.cuda.synchronize()
+            assert np.array_equal(xd.cpu().numpy().view(np.uint32), want.view(np.uint32)), (base, omega, alpha, "device")
         st, want = oracle.dsorv(n, base, rp2, ci2, v2, 0.7, 1.0, x0, b)
-        assert np.allclose(xf, want, rtol=0, atol=64 * EPS32 * max(1.0, np.abs(want).max()))
+        st, got = oracle.ssorv(n, base, rp2, ci2, v2.astype(np.float32), 0.7, 1.0, xf, bf)
+        assert np.allclose(got, want, rtol=0, atol=64 * EPS32 * max(1.0, np.abs(want).max()))  # and the float chain is that sweep

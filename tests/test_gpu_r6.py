@@ -177,9 +177,8 @@ def test_two_level_trsv_float_strided_and_trsm(forced_chunks):
     bf = np.random.default_rng(6).uniform(-1, 1, m).astype(np.float32)
     for unit in (True, False):
         d = P.Descr(mtype=P.TYPE_TRIANGULAR, fill=P.FILL_LOWER, diag=P.DIAG_UNIT if unit else P.DIAG_NON_UNIT)
-        xo = np.zeros(m, np.float32)
-        assert oracle.lib().orc_strsv_l(ctypes.c_float(1.0), m, 0, P._ptr(vf), P._ptr(ci), P._ptr(rp), P._ptr(o["idiag"]), P._ptr(bf), 1,
-                                        P._ptr(xo), 1, 1 if unit else 0) == 0
+        st, xo = oracle.strsv("l", 1.0, m, 0, vf, ci, rp, o["idiag"], bf, unit)
+        assert st == 0
         with trsv_schedule(P, 5):
             xd = torch.zeros(m, dtype=torch.float32, device="cuda")
             assert P.strsv(P.OP_NONE, 1.0, Af, d, dev(bf), xd) == 0

@@ -4,7 +4,6 @@ types, both real precisions, every compiled shape (blocks of <= 5 rows with <= 1
 registers; larger: row by row from LDS), blocks of mixed sizes, rows too long for a block (the kernel's tail loop),
 NaN / Inf / NOT-READY-tag propagation.  Bar: bit-exact (same chain order per row).  That the block schedule is the one
 that ran is checked through its diagnostic trace in a subprocess (the C ABI is frozen: there is no query for it)."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -206,12 +205,10 @@ def test_block_strsv_float_bit_exact():
     o = oracle.dcsr_optimize(m, m, len(v), 0, rp, ci, v)
     A = P.Matrix(0, m, m, rp, ci, vf)
     bf = np.random.default_rng(6).uniform(-1, 1, m).astype(np.float32)
-    for fill, fn, iend in ((P.FILL_LOWER, "orc_strsv_l", o["idiag"]), (P.FILL_UPPER, "orc_strsv_u", o["iurow"])):
+    for fill, kind, iend in ((P.FILL_LOWER, "l", o["idiag"]), (P.FILL_UPPER, "u", o["iurow"])):
         for unit in (True, False):
             d = P.Descr(mtype=P.TYPE_TRIANGULAR, fill=fill, diag=P.DIAG_UNIT if unit else P.DIAG_NON_UNIT)
-            xo = np.zeros(m, np.float32)
-            st = getattr(oracle.lib(), fn)(ctypes.c_float(1.0), m, 0, P._ptr(vf), P._ptr(ci), P._ptr(rp), P._ptr(iend),
-                                           P._ptr(bf), 1, P._ptr(xo), 1, 1 if unit else 0)
+            st, xo = oracle.strsv(kind, 1.0, m, 0, vf, ci, rp, iend, bf, unit)
             assert st == 0
             xd = torch.zeros(m, dtype=torch.float32, device="cuda")
             assert P.strsv(P.OP_NONE, 1.0, A, d, dev(bf), xd) == 0
