@@ -100,6 +100,10 @@ SIGNATURES = {
     "aoclsparse_export_dcsr": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I),
                                        POINTER(_P), POINTER(_P), POINTER(_P)]),
     "aoclsparse_destroy": (c_int, [POINTER(_P)]),
+    "aoclsparse_create_stcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "aoclsparse_create_dtcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "aoclsparse_create_ctcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "aoclsparse_create_ztcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "aoclsparse_sset_value": (c_int, [_P, _I, _I, c_float]),
     "aoclsparse_dset_value": (c_int, [_P, _I, _I, c_double]),
     "aoclsparse_supdate_values": (c_int, [_P, _I, _P]),
@@ -558,6 +562,29 @@ class Matrix:
         lv = c_int32(-2)
         assert lib().aoclsparse_mi355_get_trsv_levels(self.h, fill, op, byref(lv)) == 0
         return lv.value
+
+
+class TcsrMatrix(Matrix):
+    """aoclsparse_matrix over a lower triangle L (diagonal last in every row) and an upper triangle U (diagonal first); keeps the
+    six aliased numpy arrays alive.  float32 / float64 / complex64 / complex128 values."""
+
+    def __init__(self, base, m, ptr_l, col_l, val_l, ptr_u, col_u, val_u, nnz=None):
+        import numpy as np
+
+        self.ptr_l, self.ptr_u = (np.ascontiguousarray(a, dtype=np.int32) for a in (ptr_l, ptr_u))
+        self.col_l, self.col_u = (np.ascontiguousarray(a, dtype=np.int32) for a in (col_l, col_u))
+        self.val_l = np.ascontiguousarray(val_l)
+        self.val_u = np.ascontiguousarray(val_u, dtype=self.val_l.dtype)
+        create = {np.dtype(np.float32): "s", np.dtype(np.float64): "d", np.dtype(np.complex64): "c", np.dtype(np.complex128): "z"}
+        fn = getattr(lib(), "aoclsparse_create_%stcsr" % create[self.val_l.dtype])
+        self.double = self.val_l.dtype == np.float64
+        self.row_ptr = self.col_ind = self.val = None
+        self.m = self.n = m
+        self.base = base
+        self.nnz = int(self.ptr_l[m]) + int(self.ptr_u[m]) - 2 * base - m if nnz is None else nnz
+        self.h = c_void_p()
+        self.status = fn(byref(self.h), base, m, m, self.nnz, _ptr(self.ptr_l), _ptr(self.ptr_u), _ptr(self.col_l),
+                         _ptr(self.col_u), _ptr(self.val_l), _ptr(self.val_u))
 
 
 def scalar(v, double=True):

@@ -52,6 +52,15 @@ aoclsparse_status cmv_t(aoclsparse_operation op, const cplx<R> *alpha, aoclspars
     const bool herm = descr->type == aoclsparse_matrix_type_hermitian;
     if((sym || herm) && A->m != A->n)
         return aoclsparse_status_invalid_size;
+    if(A->input_format == aoclsparse_tcsr_mat)
+    {
+        // level2/aoclsparse_tcsr.hpp:97-183: no general product for complex values (:113-118); a symmetric / Hermitian /
+        // triangular one runs on the triangle the fill mode names, the conjugate forms of a triangle are refused (:178-183)
+        if(descr->type == aoclsparse_matrix_type_general
+           || (descr->type == aoclsparse_matrix_type_triangular && op == aoclsparse_operation_conjugate_transpose))
+            return aoclsparse_status_not_implemented;
+        return cmv_t<R>(op, alpha, tcsr_triangle(A, descr->fill_mode), descr, x, beta, y, vt);
+    }
     if(A->input_format != aoclsparse_csr_mat)
         return aoclsparse_status_not_implemented;
 

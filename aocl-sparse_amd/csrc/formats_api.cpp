@@ -210,6 +210,59 @@ aoclsparse_status create_coo(aoclsparse_matrix *mat, aoclsparse_index_base base,
     return aoclsparse_status_success;
 }
 
+// extra/aoclsparse_auxiliary.hpp:54-193, checks in the same order.  The handle keeps no CSR of its own: each triangle becomes a CSR
+// handle over the caller's arrays (internal.hpp: tcsr_tri), which is all the solves and the one-triangle products need.
+aoclsparse_status create_tcsr(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N,
+                              aoclsparse_int nnz, aoclsparse_int *row_ptr_L, aoclsparse_int *row_ptr_U, aoclsparse_int *col_idx_L,
+                              aoclsparse_int *col_idx_U, void *val_L, void *val_U, aoclsparse_matrix_data_type vt)
+{
+    if(!mat)
+        return aoclsparse_status_invalid_pointer;
+    *mat = nullptr;
+    if(!row_ptr_L || !row_ptr_U || !col_idx_L || !col_idx_U || !val_L || !val_U)
+        return aoclsparse_status_invalid_pointer;
+    if(base != aoclsparse_index_base_one && base != aoclsparse_index_base_zero)
+        return aoclsparse_status_invalid_value;
+    if(M < 0 || N < 0 || nnz < 0)
+        return aoclsparse_status_invalid_size;
+    if(M != N) // square with a full diagonal only
+        return aoclsparse_status_invalid_size;
+    const aoclsparse_int lnnz = row_ptr_L[M] - base, unnz = row_ptr_U[M] - base;
+    if(nnz != lnnz + unnz - M)
+        return aoclsparse_status_invalid_size;
+    int  sort[2] = {0, 0};
+    bool full[2] = {false, false};
+    for(int t = 0; t < 2; t++) // L (shape 1: nothing right of the diagonal), then U (shape 2)
+    {
+        aoclsparse_status st = mat_check(M, N, t ? unnz : lnnz, t ? row_ptr_U : row_ptr_L, t ? col_idx_U : col_idx_L,
+                                         t ? val_U : val_L, t + 1, base, sort[t], full[t]);
+        if(st != aoclsparse_status_success)
+            return st;
+        if(sort[t] == 3)
+            return aoclsparse_status_unsorted_input;
+        if(!full[t])
+            return aoclsparse_status_invalid_value;
+    }
+    _aoclsparse_matrix *A = new(std::nothrow) _aoclsparse_matrix;
+    if(!A)
+        return aoclsparse_status_memory_error;
+    A->m = M, A->n = N, A->nnz = nnz, A->base = base, A->val_type = vt;
+    A->input_format = aoclsparse_tcsr_mat;
+    A->fulldiag = A->opt_csr_full_diag = A->optimized = true;
+    A->sort = (sort[0] == 2 || sort[1] == 2) ? 2 : 1;
+    aoclsparse_status st = alias_csr(&A->tcsr_tri[0], base, M, N, lnnz, row_ptr_L, col_idx_L, val_L, vt, sort[0], true);
+    if(st == aoclsparse_status_success)
+        st = alias_csr(&A->tcsr_tri[1], base, M, N, unnz, row_ptr_U, col_idx_U, val_U, vt, sort[1], true);
+    if(st != aoclsparse_status_success)
+    {
+        aoclsparse_matrix h = A;
+        aoclsparse_destroy(&h);
+        return st;
+    }
+    *mat = A;
+    return aoclsparse_status_success;
+}
+
 template <typename T>
 aoclsparse_status export_csc(const aoclsparse_matrix mat, aoclsparse_index_base *base, aoclsparse_int *m,
                              aoclsparse_int *n, aoclsparse_int *nnz, aoclsparse_int **col_ptr,
@@ -384,6 +437,35 @@ aoclsparse_status aoclsparse_create_scoo(aoclsparse_matrix *mat, const aoclspars
     return create_coo<float>(mat, base, M, N, nnz, row_ind, col_ind, val, aoclsparse_smat);
 }
 
+aoclsparse_status aoclsparse_create_stcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_int M,
+                                          const aoclsparse_int N, const aoclsparse_int nnz, aoclsparse_int *row_ptr_L,
+                                          aoclsparse_int *row_ptr_U, aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U,
+                                          float *val_L, float *val_U)
+{
+    return create_tcsr(mat, base, M, N, nnz, row_ptr_L, row_ptr_U, col_idx_L, col_idx_U, val_L, val_U, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_create_dtcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_int M,
+                                          const aoclsparse_int N, const aoclsparse_int nnz, aoclsparse_int *row_ptr_L,
+                                          aoclsparse_int *row_ptr_U, aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U,
+                                          double *val_L, double *val_U)
+{
+    return create_tcsr(mat, base, M, N, nnz, row_ptr_L, row_ptr_U, col_idx_L, col_idx_U, val_L, val_U, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_create_ctcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_int M,
+                                          const aoclsparse_int N, const aoclsparse_int nnz, aoclsparse_int *row_ptr_L,
+                                          aoclsparse_int *row_ptr_U, aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U,
+                                          aoclsparse_float_complex *val_L, aoclsparse_float_complex *val_U)
+{
+    return create_tcsr(mat, base, M, N, nnz, row_ptr_L, row_ptr_U, col_idx_L, col_idx_U, val_L, val_U, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_create_ztcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_int M,
+                                          const aoclsparse_int N, const aoclsparse_int nnz, aoclsparse_int *row_ptr_L,
+                                          aoclsparse_int *row_ptr_U, aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U,
+                                          aoclsparse_double_complex *val_L, aoclsparse_double_complex *val_U)
+{
+    return create_tcsr(mat, base, M, N, nnz, row_ptr_L, row_ptr_U, col_idx_L, col_idx_U, val_L, val_U, aoclsparse_zmat);
+}
+
 aoclsparse_status aoclsparse_create_ccsc(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
                                          aoclsparse_int N, aoclsparse_int nnz, aoclsparse_int *col_ptr,
                                          aoclsparse_int *row_idx, aoclsparse_float_complex *val)
@@ -464,7 +546,8 @@ aoclsparse_status aoclsparse_convert_csr(const aoclsparse_matrix src_mat, const 
     if(!src_mat || !dest_mat)
         return aoclsparse_status_invalid_pointer;
     *dest_mat = nullptr;
-    if(src_mat->input_format == aoclsparse_coo_mat ? !src_mat->coo_row : !src_mat->user.ptr)
+    if(src_mat->input_format == aoclsparse_coo_mat ? !src_mat->coo_row
+                                                   : (src_mat->input_format == aoclsparse_csr_mat && !src_mat->user.ptr))
         return aoclsparse_status_invalid_pointer;
     if(src_mat->input_format != aoclsparse_coo_mat && src_mat->input_format != aoclsparse_csr_mat)
         return aoclsparse_status_not_implemented;

@@ -653,6 +653,10 @@ struct _aoclsparse_matrix
     void           *csc_val = nullptr;
     aoclsparse_int *coo_row = nullptr, *coo_col = nullptr;
     void           *coo_val = nullptr;
+    // TCSR (input_format == aoclsparse_tcsr_mat, no CSR in `user`): [0] = L, [1] = U, each a CSR handle of its own that aliases the
+    // caller's three arrays of that triangle (L: the diagonal ends every row, U: it starts every row).  Every copy of the values --
+    // device mirrors, TRSV plans, symmetric / triangular expansions -- hangs on these two (drop_derived_state walks them)
+    aoclsparse_matrix tcsr_tri[2] = {nullptr, nullptr};
 
     // composite solvers (solvers_api.cpp): vector workspaces in HBM, and the ILU(0) factors
     // (solvers/aoclsparse_ilu.hpp:94-104, analysis.cpp:390-425): values on the user's pattern, kept
@@ -826,6 +830,15 @@ void drop_derived_state(aoclsparse_matrix A);
 aoclsparse_status coo_set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int col_idx, const void *val);
 void              csc_set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int col_idx, const void *val);
 aoclsparse_status csc_refresh_csr(aoclsparse_matrix A);
+// a handle over the caller's CSR arrays, nothing checked (the creators check first)
+aoclsparse_status alias_csr(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
+                            aoclsparse_int *row_ptr, aoclsparse_int *col_idx, void *val, aoclsparse_matrix_data_type vt, int sort,
+                            bool fulldiag);
+// the triangle of a TCSR handle that serves descriptors of this fill mode (L also for anything that is not `upper`)
+inline aoclsparse_matrix tcsr_triangle(const _aoclsparse_matrix *A, aoclsparse_fill_mode fill)
+{
+    return A->tcsr_tri[fill == aoclsparse_fill_mode_upper ? 1 : 0];
+}
 // allocates the ILU(0) value array as a copy of A's values (solvers_api.cpp; analysis.cpp:390-425)
 aoclsparse_status ilu_prepare(aoclsparse_matrix A);
 // builds A->trans (host transpose of the user CSR, 0-based) if absent
@@ -891,6 +904,10 @@ aoclsparse_status launch_blk_valoff(hipStream_t s, aoclsparse_int nblk, int rows
 aoclsparse_status launch_blkcsrmv(hipStream_t s, int base, double alpha, aoclsparse_int m, int rows, const uint8_t *masks,
                                   const double *val, const aoclsparse_int *col, const aoclsparse_int *row_ptr,
                                   const aoclsparse_int *valoff, const double *x, double beta, double *y);
+// y = alpha (L + U - D) x + beta y of a TCSR handle in the order of the reference's aoclsparse_dtcsrmv_avx2 (tcsr_kernels.hip)
+aoclsparse_status launch_tcsrmv(hipStream_t s, int base, double alpha, aoclsparse_int m, const double *val_l, const aoclsparse_int *col_l,
+                                const aoclsparse_int *ptr_l, const double *val_u, const aoclsparse_int *col_u, const aoclsparse_int *ptr_u,
+                                const double *x, double beta, double *y);
 template <typename T>
 aoclsparse_status launch_mergepath(hipStream_t s, int base, T alpha, aoclsparse_int ntiles, const aoclsparse_int *starts,
                                    const aoclsparse_int *first, const T *val, const aoclsparse_int *col,

@@ -327,6 +327,8 @@ aoclsparse_status csr_optimize(aoclsparse_matrix A)
     if(A->opt)
         return aoclsparse_status_success;
     HostCsr &u = A->user;
+    if(A->input_format == aoclsparse_tcsr_mat) // csr_util.hpp:804-805: no CSR among a TCSR handle's matrices (the solves and the
+        return aoclsparse_status_not_implemented; // one-triangle products come here with a triangle's own handle)
     if(!u.ptr || !u.ind || !u.val)
         return aoclsparse_status_invalid_pointer;
     try
@@ -1136,16 +1138,7 @@ static aoclsparse_status create_csr(aoclsparse_matrix *mat, aoclsparse_index_bas
     aoclsparse_status st = mat_check(M, N, nnz, row_ptr, col_idx, val, 0, base, sort, fulldiag);
     if(st != aoclsparse_status_success)
         return st;
-    _aoclsparse_matrix *A = new(std::nothrow) _aoclsparse_matrix;
-    if(!A)
-        return aoclsparse_status_memory_error;
-    A->m = M, A->n = N, A->nnz = nnz, A->base = base, A->val_type = vt;
-    A->sort = sort, A->fulldiag = fulldiag;
-    A->user.m = M, A->user.n = N, A->user.nnz = nnz, A->user.base = base;
-    A->user.ptr = row_ptr, A->user.ind = col_idx, A->user.val = val;
-    A->user.owned = false;
-    *mat          = A;
-    return aoclsparse_status_success;
+    return alias_csr(mat, base, M, N, nnz, row_ptr, col_idx, val, vt, sort, fulldiag);
 }
 
 aoclsparse_status aoclsparse_create_dcsr(aoclsparse_matrix *mat, aoclsparse_index_base base,
@@ -1188,6 +1181,9 @@ aoclsparse_status aoclsparse_destroy(aoclsparse_matrix *mat)
             (*mat)->user.owned = true; // sp2m results: the handle owns its CSR
         if((*mat)->ilu_factor)
             aoclsparse_destroy(&(*mat)->ilu_factor); // aliases ptr/ind/ilu_val: frees only its own plans
+        for(auto &t : (*mat)->tcsr_tri) // TCSR triangles alias the caller's arrays: only what the library built on them goes
+            if(t)
+                aoclsparse_destroy(&t);
         for(auto &r : (*mat)->replicas) // multi-device replicas alias the same host arrays: only their device side goes
             if(r)
                 aoclsparse_destroy(&r);
@@ -1287,6 +1283,9 @@ aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A)
     // every copy of the values (the one list: drop_derived_state) ...
     drop_derived_state(A);
     // ... and the structural plans of the device CSR, which a value change alone leaves valid
+    for(aoclsparse_matrix t : A->tcsr_tri)
+        if(t)
+            (void)aoclsparse_mi355_invalidate(t);
     for(SpmvPlan *p : {&A->plan_user, &A->plan_trans})
     {
         p->valid       = false; // row blocks
@@ -1306,10 +1305,32 @@ aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A)
 // deletes every derived copy.  Same here, device mirrors included: they are rebuilt lazily.
 namespace mi355
 {
+aoclsparse_status alias_csr(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
+                            aoclsparse_int *row_ptr, aoclsparse_int *col_idx, void *val, aoclsparse_matrix_data_type vt, int sort,
+                            bool fulldiag)
+{
+    _aoclsparse_matrix *A = new(std::nothrow) _aoclsparse_matrix;
+    if(!A)
+        return aoclsparse_status_memory_error;
+    A->m = M, A->n = N, A->nnz = nnz, A->base = base, A->val_type = vt;
+    A->sort = sort, A->fulldiag = fulldiag;
+    A->user.m = M, A->user.n = N, A->user.nnz = nnz, A->user.base = base;
+    A->user.ptr = row_ptr, A->user.ind = col_idx, A->user.val = val;
+    A->user.owned = false;
+    *mat          = A;
+    return aoclsparse_status_success;
+}
+
 // THE list of what holds A's values besides the caller's arrays (?set_value, ?update_values, aoclsparse_order_mat, the CSC refresh
 // and aoclsparse_mi355_invalidate all come here).  A copy added to the handle that holds values is dropped here, nowhere else.
 void drop_derived_state(aoclsparse_matrix A)
 {
+    for(aoclsparse_matrix t : A->tcsr_tri) // TCSR: everything that holds values hangs on the two triangle handles
+        if(t)
+        {
+            std::unique_lock<std::shared_mutex> w(t->guard);
+            drop_derived_state(t);
+        }
     if(A->opt != &A->user) // the clean copy of unsorted arrays / arrays that miss a diagonal entry
     {
         A->opt_copy.reset();
@@ -1339,14 +1360,16 @@ template <typename T>
 static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int col_idx, T val,
                                    aoclsparse_matrix_data_type vt)
 {
-    const bool coo = A && A->input_format == aoclsparse_coo_mat;
-    if(!A || (coo ? (!A->coo_row || !A->coo_col || !A->coo_val) : (!A->user.ptr || !A->user.ind || !A->user.val)))
+    const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && A->input_format == aoclsparse_tcsr_mat;
+    if(!A || (coo ? (!A->coo_row || !A->coo_col || !A->coo_val) : (!tcsr && (!A->user.ptr || !A->user.ind || !A->user.val))))
         return aoclsparse_status_invalid_pointer;
     const aoclsparse_int b = A->base;
     if(A->m + b <= row_idx || row_idx < b || A->n + b <= col_idx || col_idx < b)
         return aoclsparse_status_invalid_value;
     if(A->val_type != vt)
         return aoclsparse_status_wrong_type;
+    if(tcsr) // auxiliary.hpp:457-458: only CSR / CSC and COO have a setter
+        return aoclsparse_status_not_implemented;
     std::unique_lock<std::shared_mutex> w(A->guard);
     if(coo)
         return coo_set_value(A, row_idx, col_idx, &val);
@@ -1366,13 +1389,15 @@ static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, 
 template <typename T>
 static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, T *val, aoclsparse_matrix_data_type vt)
 {
-    const bool coo = A && A->input_format == aoclsparse_coo_mat;
-    if(!A || !val || (coo ? !A->coo_val : !A->user.ptr))
+    const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && A->input_format == aoclsparse_tcsr_mat;
+    if(!A || !val || (coo ? !A->coo_val : (!tcsr && !A->user.ptr)))
         return aoclsparse_status_invalid_pointer;
     if(len != A->nnz)
         return aoclsparse_status_invalid_size;
     if(A->val_type != vt)
         return aoclsparse_status_wrong_type;
+    if(tcsr) // auxiliary.hpp:255-256
+        return aoclsparse_status_not_implemented;
     if(!coo && !A->user.val)
         return aoclsparse_status_invalid_pointer;
     std::unique_lock<std::shared_mutex> w(A->guard);
@@ -1442,6 +1467,8 @@ aoclsparse_status aoclsparse_copy(const aoclsparse_matrix src, const aoclsparse_
         return aoclsparse_status_invalid_pointer;
     if(src->val_type < aoclsparse_dmat || src->val_type > aoclsparse_zmat)
         return aoclsparse_status_wrong_type;
+    if(src->input_format == aoclsparse_tcsr_mat) // auxiliary.cpp:1234-1235: only CSR / CSC and COO are copied
+        return aoclsparse_status_invalid_value;
     if(!src->user.ptr || !src->user.ind || !src->user.val)
         return aoclsparse_status_invalid_pointer;
     _aoclsparse_matrix *c = new(std::nothrow) _aoclsparse_matrix;
@@ -1477,7 +1504,7 @@ static aoclsparse_status set_hint(aoclsparse_matrix mat, hinted_action act, aocl
                                   const aoclsparse_mat_descr descr, aoclsparse_int ncalls,
                                   aoclsparse_int kid = -1)
 {
-    if(!mat || !mat->user.ptr || !descr)
+    if(!mat || (!mat->user.ptr && mat->input_format != aoclsparse_tcsr_mat) || !descr)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != aoclsparse_index_base_zero && descr->base != aoclsparse_index_base_one)
         return aoclsparse_status_invalid_value;
@@ -1502,6 +1529,12 @@ static aoclsparse_status set_hint(aoclsparse_matrix mat, hinted_action act, aocl
     {
         Hint h{act, get_doid(descr, trans), trans, descr->type, descr->fill_mode, ncalls, kid, false};
         mat->hints.insert(mat->hints.begin(), h); // newest first
+        // TCSR: the one-triangle products and the solves run on the triangle the fill mode names and read ITS list (a pinned kid)
+        if(mat->input_format == aoclsparse_tcsr_mat && descr->type != aoclsparse_matrix_type_general)
+        {
+            aoclsparse_matrix t = tcsr_triangle(mat, descr->fill_mode);
+            t->hints.insert(t->hints.begin(), h);
+        }
     }
     catch(const std::bad_alloc &)
     {
@@ -1587,6 +1620,9 @@ aoclsparse_status aoclsparse_set_memory_hint(aoclsparse_matrix mat, const aoclsp
     if(policy != aoclsparse_memory_usage_minimal && policy != aoclsparse_memory_usage_unrestricted)
         return aoclsparse_status_invalid_value;
     mat->mem_policy = policy;
+    for(aoclsparse_matrix t : mat->tcsr_tri) // the triangles of a TCSR handle build the plans: the policy is theirs too
+        if(t)
+            t->mem_policy = policy;
     return aoclsparse_status_success;
 }
 

@@ -17,6 +17,40 @@ extern "C" aoclsparse_status aoclsparse_optimize(aoclsparse_matrix A)
         return aoclsparse_status_invalid_pointer;
     if(A->m < 0 || A->n < 0 || A->nnz < 0)
         return aoclsparse_status_invalid_size;
+    if(A->input_format == aoclsparse_tcsr_mat)
+    {
+        // analysis.cpp:467-468: nothing to do on the host.  Here the hints put the triangles in HBM and build the TRSV plans ahead
+        // of the first call (skipped without a device and under aoclsparse_memory_usage_minimal, as below).
+        Runtime &rt = Runtime::get();
+        if(A->mem_policy == aoclsparse_memory_usage_unrestricted && A->m > 0 && rt.init() == aoclsparse_status_success)
+            for(Hint &h : A->hints)
+            {
+                if(h.optimized)
+                    continue;
+                aoclsparse_status st = aoclsparse_status_success;
+                if(h.act == action_mv && h.type == aoclsparse_matrix_type_general)
+                    for(aoclsparse_matrix t : A->tcsr_tri)
+                    {
+                        std::unique_lock<std::shared_mutex> w(t->guard);
+                        if(st == aoclsparse_status_success && !t->dev_user.valid)
+                            st = upload_csr(t->user, val_size(A->val_type), t->dev_user);
+                    }
+                else if((h.act == action_sv || h.act == action_sm_row || h.act == action_sm_col)
+                        && (h.type == aoclsparse_matrix_type_triangular || h.type == aoclsparse_matrix_type_symmetric))
+                {
+                    const aoclsparse_matrix t = tcsr_triangle(A, h.fill);
+                    st                        = csr_optimize(t);
+                    if(st == aoclsparse_status_success)
+                        st = ensure_trsv(t, h.fill == aoclsparse_fill_mode_upper, h.trans != aoclsparse_operation_none,
+                                         h.trans == aoclsparse_operation_conjugate_transpose, /*need_rows=*/false);
+                }
+                if(st != aoclsparse_status_success)
+                    return st;
+            }
+        for(Hint &h : A->hints)
+            h.optimized = true;
+        return aoclsparse_status_success;
+    }
     if(!A->user.ptr || !A->user.ind || !A->user.val)
         return aoclsparse_status_invalid_pointer;
 

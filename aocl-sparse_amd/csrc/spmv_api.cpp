@@ -211,6 +211,50 @@ aoclsparse_status scale_y(Runtime &rt, T *y, aoclsparse_int n, T beta)
 }
 
 // ---- handle path ---------------------------------------------------------------------------------
+// y = alpha (L + U - D) x + beta y on a TCSR handle (tcsr_kernels.hip): both triangles in HBM as the device mirrors of their own
+// handles, one launch on the runtime's stream
+aoclsparse_status tcsr_general_mv(Runtime &rt, aoclsparse_matrix A, double alpha, const double *x, double beta, double *y)
+{
+    // both mirrors stay valid from here to the launch: the shared locks are held across it, and an upload (exclusive) is followed by
+    // a fresh look under the shared locks, since aoclsparse_mi355_invalidate may have come between
+    aoclsparse_matrix                   tl = A->tcsr_tri[0], tu = A->tcsr_tri[1];
+    std::shared_lock<std::shared_mutex> rl(tl->guard), ru(tu->guard);
+    while(!tl->dev_user.valid || !tu->dev_user.valid)
+    {
+        rl.unlock(), ru.unlock();
+        for(aoclsparse_matrix tri : {tl, tu})
+        {
+            std::unique_lock<std::shared_mutex> w(tri->guard);
+            if(!tri->dev_user.valid)
+            {
+                aoclsparse_status su = upload_csr(tri->user, sizeof(double), tri->dev_user);
+                if(su != aoclsparse_status_success)
+                    return su;
+            }
+        }
+        rl.lock(), ru.lock();
+    }
+    const DeviceCsr *d[2] = {&tl->dev_user, &tu->dev_user};
+    Arg                                 ax, ay;
+    aoclsparse_status                   st = ax.in(rt, 3, x, sizeof(double) * (size_t)A->n, rt.is_device_pointer(x), true);
+    if(st != aoclsparse_status_success)
+        return st;
+    st = ay.in(rt, 4, y, sizeof(double) * (size_t)A->m, rt.is_device_pointer(y), beta != 0.0);
+    if(st != aoclsparse_status_success)
+        return st;
+    st = launch_tcsrmv(rt.stream(), A->base, alpha, A->m, d[0]->val.as<double>(), d[0]->ind.as<aoclsparse_int>(),
+                       d[0]->ptr.as<aoclsparse_int>(), d[1]->val.as<double>(), d[1]->ind.as<aoclsparse_int>(),
+                       d[1]->ptr.as<aoclsparse_int>(), static_cast<const double *>(ax.dev), beta, static_cast<double *>(ay.dev));
+    if(st != aoclsparse_status_success)
+        return st;
+    st = ay.out(rt);
+    if(st != aoclsparse_status_success)
+        return st;
+    if(ay.staged) // host-pointer semantics: result visible on return
+        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
+    return aoclsparse_status_success;
+}
+
 template <typename T>
 aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matrix A,
                        const aoclsparse_mat_descr descr, const T *x, const T *beta, T *y,
@@ -231,12 +275,23 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
     if((descr->type == aoclsparse_matrix_type_symmetric || descr->type == aoclsparse_matrix_type_hermitian)
        && A->m != A->n)
         return aoclsparse_status_invalid_size;
-    if(A->input_format != aoclsparse_csr_mat) // mv.cpp:96-97 (COO handles: convert with aoclsparse_convert_csr)
+    const bool tcsr = A->input_format == aoclsparse_tcsr_mat;
+    if(A->input_format != aoclsparse_csr_mat && !tcsr) // mv.cpp:96-97 (COO handles: convert with aoclsparse_convert_csr)
         return aoclsparse_status_not_implemented;
     if(op == aoclsparse_operation_conjugate_transpose)
         op = aoclsparse_operation_transpose;
     if(descr->type == aoclsparse_matrix_type_hermitian)
         return aoclsparse_status_not_implemented;
+    if(tcsr)
+    {
+        // level2/aoclsparse_tcsr.hpp:97-183, decided before the device is touched.  The general product exists for double and
+        // op = none only (:99-118); a symmetric or triangular one is the ordinary product on the triangle the fill mode names
+        // (:65-94): that triangle's own CSR handle serves it, with its derived operators and plans.
+        if(descr->type != aoclsparse_matrix_type_general)
+            return mv_t<T>(op, alpha, tcsr_triangle(A, descr->fill_mode), descr, x, beta, y, vt);
+        if(op != aoclsparse_operation_none || vt != aoclsparse_dmat)
+            return aoclsparse_status_not_implemented;
+    }
 
     Runtime          &rt = Runtime::get();
     aoclsparse_status st = rt.init();
@@ -249,6 +304,9 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
     // mv.cpp:116-121: empty matrix still scales y
     if(A->m == 0 || A->n == 0 || (A->nnz == 0 && descr->type == aoclsparse_matrix_type_general))
         return scale_y<T>(rt, y, op == aoclsparse_operation_none ? A->m : A->n, *beta);
+    if constexpr(std::is_same<T, double>::value)
+        if(tcsr)
+            return tcsr_general_mv(rt, A, *alpha, x, *beta, y);
 
     const doid     id  = get_doid(descr, op);
     aoclsparse_int kid = -1; // magic_box.hpp:34-53: first hint with matching action + doid
@@ -654,6 +712,15 @@ aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_matrix A, aocl
     const SpmvPlan                     &p  = tr ? A->plan_trans : A->plan_user;
     const DeviceCsr                    &d  = tr ? A->dev_trans : A->dev_user;
     std::memset(info, 0, sizeof(*info));
+    if(A->input_format == aoclsparse_tcsr_mat) // no plan: four lanes per row over the two triangles (tcsr_kernels.hip)
+    {
+        const aoclsparse_matrix l = A->tcsr_tri[0], u = A->tcsr_tri[1];
+        std::shared_lock<std::shared_mutex> rl(l->guard), ru(u->guard);
+        info->device_resident = l->dev_user.valid && u->dev_user.valid;
+        if(!tr && A->val_type == aoclsparse_dmat)
+            info->kernel = 5, info->order = 1, info->row_blocks = (A->m + 63) / 64;
+        return aoclsparse_status_success;
+    }
     info->device_resident = d.valid;
     if(!p.valid)
         return aoclsparse_status_success;

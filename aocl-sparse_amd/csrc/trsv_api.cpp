@@ -976,14 +976,15 @@ aoclsparse_status trsv_t(aoclsparse_operation trans, const T alpha, aoclsparse_m
     // trsv.cpp:59-113
     if(!A || !x || !b || !descr)
         return aoclsparse_status_invalid_pointer;
-    if(A->input_format != aoclsparse_csr_mat)
+    const bool tcsr = A->input_format == aoclsparse_tcsr_mat; // trsv.cpp:62-67: CSR / CSC and TCSR handles
+    if(A->input_format != aoclsparse_csr_mat && !tcsr)
         return aoclsparse_status_not_implemented;
     const aoclsparse_int m = A->m;
     if(m <= 0 || A->nnz <= 0)
         return aoclsparse_status_invalid_size;
     if(m != A->n || incb <= 0 || incx <= 0)
         return aoclsparse_status_invalid_value;
-    if(!A->user.ptr)
+    if(!tcsr && !A->user.ptr)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != A->base)
         return aoclsparse_status_invalid_value;
@@ -1000,6 +1001,11 @@ aoclsparse_status trsv_t(aoclsparse_operation trans, const T alpha, aoclsparse_m
         return aoclsparse_status_not_implemented;
     if(A->val_type != vt)
         return aoclsparse_status_wrong_type;
+    // trsv.cpp:158-176: a TCSR handle is solved on the triangle the fill mode names -- L with (ilrow, idiag, iurow) = (ptr_L,
+    // ptr_L[i + 1] - 1, ptr_L + 1), U with (ptr_U, ptr_U, ptr_U[i] + 1), which is what the clean-CSR step finds on that
+    // triangle's own handle; its plans, schedules and kernels are the CSR ones
+    if(tcsr)
+        A = tcsr_triangle(A, descr->fill_mode);
 
     // trsv.cpp:128-137: lazy clean CSR, then the rank check
     aoclsparse_status st = csr_optimize(A);
@@ -1028,11 +1034,12 @@ aoclsparse_status trsm_t(aoclsparse_operation trans, const T alpha, aoclsparse_m
 {
     if(!A || !X || !B || !descr)
         return aoclsparse_status_invalid_pointer;
-    if(!A->user.ptr)
+    const bool tcsr = A->input_format == aoclsparse_tcsr_mat; // trsm.hpp:62-67, 107-117
+    if(!tcsr && !A->user.ptr)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != A->base)
         return aoclsparse_status_invalid_value;
-    if(A->input_format != aoclsparse_csr_mat)
+    if(A->input_format != aoclsparse_csr_mat && !tcsr)
         return aoclsparse_status_not_implemented;
     const aoclsparse_int m = A->m;
     if(m < 0 || A->nnz < 0 || n < 0)
@@ -1054,6 +1061,8 @@ aoclsparse_status trsm_t(aoclsparse_operation trans, const T alpha, aoclsparse_m
         return aoclsparse_status_not_implemented;
     if(A->val_type != vt)
         return aoclsparse_status_wrong_type;
+    if(tcsr) // the triangle's own handle, as in trsv_t
+        A = tcsr_triangle(A, descr->fill_mode);
     aoclsparse_status st = csr_optimize(A);
     if(st != aoclsparse_status_success)
         return st;
@@ -1332,6 +1341,11 @@ aoclsparse_status aoclsparse_mi355_trsv_status(aoclsparse_matrix A)
 {
     if(!A)
         return aoclsparse_status_invalid_pointer;
+    if(A->input_format == aoclsparse_tcsr_mat) // the solves ran on the triangles' own handles: either word counts (both are read and cleared)
+    {
+        const aoclsparse_status l = aoclsparse_mi355_trsv_status(A->tcsr_tri[0]), u = aoclsparse_mi355_trsv_status(A->tcsr_tri[1]);
+        return l != aoclsparse_status_success ? l : u;
+    }
     if(A->trsv_timeout_host && *A->trsv_timeout_host)
     {
         *A->trsv_timeout_host = 0;
@@ -1345,6 +1359,8 @@ aoclsparse_status aoclsparse_mi355_get_trsv_levels(const aoclsparse_matrix A, ao
 {
     if(!A || !levels)
         return aoclsparse_status_invalid_pointer;
+    if(A->input_format == aoclsparse_tcsr_mat) // the plans live on the triangle's own handle
+        return aoclsparse_mi355_get_trsv_levels(tcsr_triangle(A, fill), fill, op, levels);
     std::shared_lock<std::shared_mutex> r(A->guard);
     const bool      up = fill == aoclsparse_fill_mode_upper;
     const bool      cj = op == aoclsparse_operation_conjugate_transpose && is_complex_type(A->val_type);
@@ -1358,6 +1374,8 @@ aoclsparse_status aoclsparse_mi355_get_trsv_info(const aoclsparse_matrix A, aocl
 {
     if(!A || !info)
         return aoclsparse_status_invalid_pointer;
+    if(A->input_format == aoclsparse_tcsr_mat)
+        return aoclsparse_mi355_get_trsv_info(tcsr_triangle(A, fill), fill, op, info);
     std::shared_lock<std::shared_mutex> r(A->guard);
     const bool      up = fill == aoclsparse_fill_mode_upper;
     const bool      cj = op == aoclsparse_operation_conjugate_transpose && is_complex_type(A->val_type);

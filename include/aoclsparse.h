@@ -69,7 +69,7 @@ typedef enum aoclsparse_matrix_data_type_ /* :191-197 */
     aoclsparse_zmat = 3
 } aoclsparse_matrix_data_type;
 
-typedef enum aoclsparse_matrix_format_type_ /* :214-239; only csr is produced here */
+typedef enum aoclsparse_matrix_format_type_ /* :214-239; csr, coo and tcsr handles are produced here */
 {
     aoclsparse_csr_mat           = 0,
     aoclsparse_ell_mat           = 1,
@@ -613,6 +613,35 @@ DLL_PUBLIC aoclsparse_status aoclsparse_dcsr2csc(aoclsparse_int m, aoclsparse_in
                                                  const aoclsparse_int *csr_col_ind, const double *csr_val,
                                                  aoclsparse_int *csc_row_ind, aoclsparse_int *csc_col_ptr,
                                                  double *csc_val);
+/* TCSR handles (aoclsparse_auxiliary.h:582-631): a square matrix with a full diagonal given as its lower triangle L (the diagonal
+ * ends every row) and its upper triangle U (the diagonal starts every row), nnz = nnz(L) + nnz(U) - M.  The six arrays are aliased,
+ * never freed.  ?mv, ?trsv and ?trsm (and their _kid / _strided forms) accept the handle; aoclsparse_dmv with a general descriptor
+ * and op = none runs in the order of the reference's TCSR kernel, every other executor answers as the reference does (not_implemented
+ * in almost all cases).  On a c / z handle a symmetric descriptor multiplies by the symmetric matrix (with op = conjugate transpose:
+ * by its conjugate) and a Hermitian descriptor by the Hermitian one, both built from the triangle the fill mode names exactly as
+ * for a CSR handle; the reference's TCSR dispatcher runs one Hermitian kernel for all of these (level2/aoclsparse_tcsr.hpp:119-146),
+ * so its symmetric answers differ.  Hints and aoclsparse_set_memory_hint given to the handle reach the triangle that serves them
+ * (a kid pinned with aoclsparse_set_mv_hint_kid for a symmetric / triangular descriptor is honoured). */
+DLL_PUBLIC aoclsparse_status aoclsparse_create_stcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, /* :582-592 */
+                                                     const aoclsparse_int M, const aoclsparse_int N, const aoclsparse_int nnz,
+                                                     aoclsparse_int *row_ptr_L, aoclsparse_int *row_ptr_U,
+                                                     aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U, float *val_L,
+                                                     float *val_U);
+DLL_PUBLIC aoclsparse_status aoclsparse_create_dtcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, /* :595-605 */
+                                                     const aoclsparse_int M, const aoclsparse_int N, const aoclsparse_int nnz,
+                                                     aoclsparse_int *row_ptr_L, aoclsparse_int *row_ptr_U,
+                                                     aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U, double *val_L,
+                                                     double *val_U);
+DLL_PUBLIC aoclsparse_status aoclsparse_create_ctcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, /* :608-618 */
+                                                     const aoclsparse_int M, const aoclsparse_int N, const aoclsparse_int nnz,
+                                                     aoclsparse_int *row_ptr_L, aoclsparse_int *row_ptr_U,
+                                                     aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U, aoclsparse_float_complex *val_L,
+                                                     aoclsparse_float_complex *val_U);
+DLL_PUBLIC aoclsparse_status aoclsparse_create_ztcsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, /* :621-631 */
+                                                     const aoclsparse_int M, const aoclsparse_int N, const aoclsparse_int nnz,
+                                                     aoclsparse_int *row_ptr_L, aoclsparse_int *row_ptr_U,
+                                                     aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U, aoclsparse_double_complex *val_L,
+                                                     aoclsparse_double_complex *val_U);
 /* complex twins of the above (aoclsparse_auxiliary.h:438-560,748-870; aoclsparse_convert.h:528-560) */
 DLL_PUBLIC aoclsparse_status aoclsparse_create_ccsc(aoclsparse_matrix *mat, aoclsparse_index_base base,
                                                     aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
