@@ -390,6 +390,7 @@ SIGNATURES = {
     "aoclsparse_mi355_export_diag": (c_int, [_P, POINTER(_P), POINTER(_P), POINTER(_I)]),
     "aoclsparse_mi355_get_spmv_info": (c_int, [_P, c_int, POINTER(SpmvInfo)]),
     "aoclsparse_mi355_get_sell_values": (c_int, [_P, c_int, POINTER(_I)]),
+    "aoclsparse_mi355_get_sell_packing": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_levels": (c_int, [_P, c_int, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_info": (c_int, [_P, c_int, c_int, POINTER(TrsvInfo)]),
     "aoclsparse_mi355_trsv_status": (c_int, [_P]),
@@ -552,6 +553,12 @@ class Matrix:
         n = _I(-1)
         assert lib().aoclsparse_mi355_get_sell_values(self.h, op, byref(n)) == 0
         return n.value
+
+    def sell_packing(self, op=OP_NONE):
+        """(index bits, word bytes, uniform slices) of the SELL-64 copy of op(A): 0, 0 when the cells hold bytes or values"""
+        b, w, u = _I(-1), _I(-1), _I(-1)
+        assert lib().aoclsparse_mi355_get_sell_packing(self.h, op, byref(b), byref(w), byref(u)) == 0
+        return b.value, w.value, u.value
 
     def trsv_info(self, fill, op=OP_NONE):
         info = TrsvInfo()

@@ -300,6 +300,11 @@ struct SellView
     const unsigned short *lead = nullptr;
     const void           *vtab = nullptr; // nullptr without a table
     const SellSliceDesc  *desc = nullptr; // nullptr when the plan has no slice records
+    // packed table indices (pbits > 0): cells holds one word of pbytes bytes per ROW, row i at i * pbytes, the index of cell q
+    // of the row at bit q * pbits; pbits = 0: one byte per cell (or the values)
+    int                   pbits = 0, pbytes = 0;
+    // one list of SELL_SHORT_WMAX columns per slice (mode 1 / 2 slices; -1 everywhere else); nullptr when the plan has none
+    const aoclsparse_int *ucol = nullptr;
 };
 
 // SELL-64 twin of a device CSR (matrix.cpp: build_sell; layout in sell_build_kernels.hip, products in sell_kernels.hip): built by
@@ -320,11 +325,17 @@ struct SellPlan
     DeviceBuffer   cptr, lead;
     // value table (sell_build_kernels.hip): ntab > 0 -> vidx holds one byte per cell (same cell order and offsets as val would) indexing
     // vtab, ntab values sorted by bit pattern, and val is not allocated; ntab = 0 -> the values are in val
-    int            ntab = 0;
-    DeviceBuffer   vtab, vidx;
+    // ... or, on a plan with slice records whose rows fit (widest slice x pbits <= 32): pidx holds one word of pbytes bytes per row
+    // with pbits bits per cell ((nslices + SELL_DESC_PAD) x 64 words, the padding 0) and vidx is not allocated either
+    int            ntab = 0, pbits = 0, pbytes = 0;
+    DeviceBuffer   vtab, vidx, pidx;
     // one 16-byte record per slice for the short-row kernel (SellSliceDesc; nslices + SELL_DESC_PAD of them), allocated only
     // when that kernel can serve the copy (pack 1, widest slice <= SELL_SHORT_WMAX, >= SELL_SHORT_MIN_SLICES slices)
     DeviceBuffer   desc;
+    // with slice records and shared lists: SELL_SHORT_WMAX columns per slice (nslices + SELL_DESC_PAD entries), the single list of
+    // a mode 1 / 2 slice, -1 elsewhere; uniform = how many slices have one
+    DeviceBuffer   ucol;
+    aoclsparse_int uniform = 0;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
@@ -337,7 +348,9 @@ struct SellPlan
         SellView v;
         v.m = m, v.nslices = nslices, v.pack = pack, v.max_width = max_width, v.ntab = ntab;
         v.slice_ptr = slice_ptr.as<long long>();
-        v.cells     = ntab ? vidx.ptr : val.ptr;
+        v.cells     = ntab ? (pbits ? pidx.ptr : vidx.ptr) : val.ptr;
+        v.pbits = ntab ? pbits : 0, v.pbytes = ntab ? pbytes : 0;
+        v.ucol = ucol.as<aoclsparse_int>();
         v.col = col.as<aoclsparse_int>(), v.rowlen = rowlen.as<aoclsparse_int>();
         v.cptr = shared ? cptr.as<long long>() : nullptr;
         v.lead = shared ? lead.as<unsigned short>() : nullptr;
@@ -883,9 +896,10 @@ aoclsparse_status launch_csrmv(hipStream_t s, int order, bool strict, int tile, 
 // the live row_ptr, computes its rows from the live arrays on a mismatch and sets *stale, a pinned host word)
 // SELL-64 plan kernels (sell_build_kernels.hip)
 // fills the cells, columns and row lengths of the copy v describes from d (values of vsize bytes; cells / col / rowlen are v's
-// arrays, writable); with a table (v.ntab > 0) the cells get one-byte indices into it instead of the values
+// arrays, writable); with a table (v.ntab > 0) the cells get one-byte indices into it instead of the values, or (v.pbits > 0) one
+// packed word per row; ucol (v.ucol, writable; preset to -1) gets the list of every mode 1 / 2 slice
 aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
-                                   aoclsparse_int *rowlen);
+                                   aoclsparse_int *rowlen, aoclsparse_int *ucol);
 // distinct bit patterns of n values of vsize (4 / 8) bytes on the device: *ntab of them; table = SELL_VTAB_MAX entries of vsize
 // bytes ready to upload, ascending by bit pattern, the unused ones 0; *ntab = 0 when there are more than SELL_VTAB_MAX
 constexpr int     SELL_VTAB_MAX = 256;

@@ -703,7 +703,8 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         return aoclsparse_status_success;
     sp.tried = true;
     sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
-    sp.vtab.release(), sp.vidx.release(), sp.desc.release();
+    sp.pbits = sp.pbytes = 0, sp.uniform = 0;
+    sp.vtab.release(), sp.vidx.release(), sp.pidx.release(), sp.desc.release(), sp.ucol.release();
     const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
         return aoclsparse_status_success;
@@ -733,6 +734,8 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         sptr[s + 1] = sptr[s] + 64LL * w;
     }
     const long long cells = sptr[nslices];
+    // slice records for the short-row kernel (sell_kernels.hip), where it can serve this copy
+    const bool records = pack == 1 && wmax >= 1 && wmax <= SELL_SHORT_WMAX && nslices >= SELL_SHORT_MIN_SLICES;
     // Padding budget: 1.35 cells per non-zero.  Round 1 set 1.15 from the two kernels' rates then (0.78 vs 0.66 of peak); the SELL
     // kernel has gained since.  Round-3 measurement on the unstructured flan-like variant (padding 1.21: tools/history/exp_r3_sellpad.sh,
     // profiles/r3/sell_padding_budget.txt): SELL-64 0.259 ms vs CSR-Adaptive 0.352 ms, i.e. break-even near 1.21 * 0.352 / 0.259 =
@@ -793,13 +796,28 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         if(st == aoclsparse_status_success && ntab > 0)
         {
             st = sp.vtab.upload(tab, vsize * (size_t)SELL_VTAB_MAX, rt.stream());
-            if(st == aoclsparse_status_success)
+            // With slice records the indices of a row are packed into ONE word where they fit: fields of 1 / 2 / 4 / 8 bits (the
+            // smallest that holds ntab - 1), cell q at bit q * bits, in the smallest word of 1 / 2 / 4 bytes that holds the widest
+            // slice; (nslices + SELL_DESC_PAD) x 64 words, addressed by row number alone.  Otherwise one byte per cell.
+            int bits = 1;
+            while((1 << bits) < ntab)
+                bits *= 2;
+            const int wbits = (int)wmax * bits;
+            if(st == aoclsparse_status_success && records && wbits <= 32)
+            {
+                sp.pbits  = bits;
+                sp.pbytes = wbits <= 8 ? 1 : (wbits <= 16 ? 2 : 4);
+                st        = sp.pidx.alloc(((size_t)nslices + SELL_DESC_PAD) * 64 * (size_t)sp.pbytes);
+            }
+            else if(st == aoclsparse_status_success)
                 st = sp.vidx.alloc((size_t)cells + SELL_CELL_PAD);
             if(st == aoclsparse_status_success)
             {
                 sp.ntab = ntab;
                 sp.val.release();
             }
+            else
+                sp.pbits = sp.pbytes = 0;
         }
         if(PhaseTimer::on())
             std::fprintf(stderr, "[mi355 timing] sell: %d distinct value patterns%s\n", ntab, ntab ? "" : " (more than 256, or none)");
@@ -814,14 +832,16 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         st = sp.rowlen.alloc(sizeof(aoclsparse_int) * (size_t)m);
     if(st != aoclsparse_status_success)
         return st;
-    if(sp.ntab)
+    if(sp.ntab && sp.pbits) // (the words of the padding slices; the rows behind m in the last slice are the fill kernel's)
+        MI355_HIP_TRY(hipMemsetAsync(sp.pidx.as<unsigned char>() + (size_t)nslices * 64 * (size_t)sp.pbytes, 0,
+                                     (size_t)SELL_DESC_PAD * 64 * (size_t)sp.pbytes, rt.stream()));
+    else if(sp.ntab)
         MI355_HIP_TRY(hipMemsetAsync(sp.vidx.as<unsigned char>() + cells, 0, SELL_CELL_PAD, rt.stream()));
     else
         MI355_HIP_TRY(hipMemsetAsync(sp.val.as<unsigned char>() + vsize * (size_t)cells, 0, vsize * SELL_CELL_PAD, rt.stream()));
     MI355_HIP_TRY(hipMemsetAsync(sp.col.as<aoclsparse_int>() + sp.ccells, 0xff, sizeof(aoclsparse_int) * SELL_CELL_PAD, rt.stream()));
-    // slice records for the short-row kernel (sell_kernels.hip), where it can serve this copy
     std::vector<SellSliceDesc> desc;
-    if(pack == 1 && wmax >= 1 && wmax <= SELL_SHORT_WMAX && nslices >= SELL_SHORT_MIN_SLICES)
+    if(records)
     {
         try
         {
@@ -835,10 +855,25 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         st = sp.desc.upload(desc.data(), sizeof(SellSliceDesc) * desc.size(), rt.stream());
         if(st != aoclsparse_status_success)
             return st;
+        // uniform column lists: a slice of mode 1 / 2 (full, one leader: sell_leaders_kernel) has ONE list, which the short-row
+        // kernel reads with a scalar load at 8 s -- no record needed; every other entry stays -1 (the fill kernel writes the lists).
+        // Only next to packed words: with values or one-byte indices in the cells the lists gained nothing for double and lost
+        // 4 - 6 % for float (profiles/r10/spw_sweep.txt, "ucol with values"), so those plans keep the kernels they had.
+        if(sp.shared && sp.pbits)
+        {
+            const size_t ubytes = sizeof(aoclsparse_int) * SELL_SHORT_WMAX * ((size_t)nslices + SELL_DESC_PAD);
+            st                  = sp.ucol.alloc(ubytes);
+            if(st != aoclsparse_status_success)
+                return st;
+            MI355_HIP_TRY(hipMemsetAsync(sp.ucol.ptr, 0xff, ubytes, rt.stream()));
+            for(aoclsparse_int s = 0; s < nslices; s++)
+                sp.uniform += (nlh[s] >> 8) == SELL_DESC_MODE_LANE_SHIFT || (nlh[s] >> 8) == SELL_DESC_MODE_ONE;
+        }
     }
     sp.nslices = nslices, sp.cells = cells, sp.pack = pack;
-    st = launch_sell_fill(rt.stream(), d, vsize, sp.view(m, plan.max_row_nnz), sp.ntab ? sp.vidx.ptr : sp.val.ptr, sp.col.as<aoclsparse_int>(),
-                          sp.rowlen.as<aoclsparse_int>());
+    const SellView view = sp.view(m, plan.max_row_nnz);
+    st = launch_sell_fill(rt.stream(), d, vsize, view, const_cast<void *>(view.cells), sp.col.as<aoclsparse_int>(),
+                          sp.rowlen.as<aoclsparse_int>(), sp.ucol.as<aoclsparse_int>());
     if(st != aoclsparse_status_success)
         return st;
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr / desc (host) are read by the uploads until here

@@ -298,6 +298,9 @@ __device__ __forceinline__ long long cell_of(int p, int k, int n = 64)
 }
 
 // SHARED: the columns go to the slice's lists (cptr, follow: see above), written by the first row of every list
+// pidx (pbits > 0): the table indices of a row go into ONE word of pbytes bytes at row * pbytes instead of sidx, cell p at bit
+// p * pbits; unused fields, padding cells and the rows behind m hold 0
+// ucol (SHARED): the list of a mode 1 / 2 slice is ALSO written to ucol[SELL_SHORT_WMAX s ..] (preset to -1 by the host)
 template <typename T, int PACK, bool SHARED>
 __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int base,
                                                         const aoclsparse_int *__restrict__ row_ptr,
@@ -308,7 +311,8 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
                                                         const unsigned short *__restrict__ follow, T *__restrict__ sval,
                                                         aoclsparse_int *__restrict__ scol,
                                                         aoclsparse_int *__restrict__ rowlen, unsigned char *__restrict__ sidx,
-                                                        const T *__restrict__ vtab, int ntab)
+                                                        const T *__restrict__ vtab, int ntab, unsigned char *__restrict__ pidx,
+                                                        int pbits, int pbytes, aoclsparse_int *__restrict__ ucol)
 {
     const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -319,10 +323,13 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
     const int       w  = (int)((slice_ptr[s + 1] - o0) >> 6);
     long long       c0 = 0;
     int             nl = 0;
+    bool            uni = false; // this lane writes the slice's uniform list
     if constexpr(SHARED)
     {
-        c0 = cptr[s] & SELL_CPTR_MASK;
-        nl = w > 0 ? (int)(((cptr[s + 1] & SELL_CPTR_MASK) - c0) / w) : 0;
+        const int mode = (int)(cptr[s] >> SELL_CPTR_MODE_SHIFT);
+        c0  = cptr[s] & SELL_CPTR_MASK;
+        nl  = w > 0 ? (int)(((cptr[s + 1] & SELL_CPTR_MASK) - c0) / w) : 0;
+        uni = ucol && lane == 0 && w <= SELL_SHORT_WMAX && (mode == SELL_DESC_MODE_LANE_SHIFT || mode == SELL_DESC_MODE_ONE);
     }
     int  b = 0, len = 0, k = 0;
     bool leader = !SHARED; // (own lists: every lane writes its columns, the padding rows behind m too)
@@ -337,25 +344,50 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
             leader = lane == 0 || (follow[i - 1] & 0xff) != k;
         }
     }
+    unsigned word = 0;
     for(int p = 0; p < w; p++)
     {
         const long long o  = o0 + cell_of<PACK>(p, lane);
         const bool      in = p < len;
-        fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
+        bool            packed = false;
+        if constexpr(std::is_floating_point_v<T>)
+            packed = pidx != nullptr;
+        if(packed)
+        {
+            if constexpr(std::is_floating_point_v<T>)
+                word |= in ? (unsigned)vtab_index(val[b + p], vtab, ntab) << (p * pbits) : 0u;
+        }
+        else
+            fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
         if(leader)
             scol[SHARED ? c0 + cell_of<PACK>(p, k, nl) : o] = in ? col[b + p] - base : -1;
+        if(uni)
+            ucol[(long long)s * SELL_SHORT_WMAX + p] = in ? col[b + p] - base : -1;
+    }
+    if(pidx) // (every lane of the slice: the rows behind m hold 0)
+    {
+        const long long row = (long long)s * 64 + lane;
+        if(pbytes == 1)
+            pidx[row] = (unsigned char)word;
+        else if(pbytes == 2)
+            reinterpret_cast<unsigned short *>(pidx)[row] = (unsigned short)word;
+        else
+            reinterpret_cast<unsigned *>(pidx)[row] = word;
     }
 }
 
 template <typename T>
-void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *cells, aoclsparse_int *scol, aoclsparse_int *rowlen)
+void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *cells, aoclsparse_int *scol, aoclsparse_int *rowlen,
+                  aoclsparse_int *ucol)
 {
     T             *sval = v.ntab ? nullptr : static_cast<T *>(cells);
-    unsigned char *sidx = v.ntab ? static_cast<unsigned char *>(cells) : nullptr;
+    unsigned char *sidx = v.ntab && !v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
+    unsigned char *pidx = v.ntab && v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
     auto           go   = [&](auto pack, auto shared) {
         hipLaunchKernelGGL((sell_fill_kernel<T, decltype(pack)::value, decltype(shared)::value>), dim3((v.nslices + 3) / 4), dim3(256),
                            0, s, v.m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.as<T>(), v.nslices,
-                           v.slice_ptr, v.cptr, v.lead, sval, scol, rowlen, sidx, static_cast<const T *>(v.vtab), v.ntab);
+                           v.slice_ptr, v.cptr, v.lead, sval, scol, rowlen, sidx, static_cast<const T *>(v.vtab), v.ntab, pidx, v.pbits,
+                           v.pbytes, ucol);
     };
     using P1 = std::integral_constant<int, 1>;
     using P4 = std::integral_constant<int, 4>;
@@ -368,17 +400,17 @@ void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *ce
 } // namespace
 
 aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
-                                   aoclsparse_int *rowlen)
+                                   aoclsparse_int *rowlen, aoclsparse_int *ucol)
 {
     if(v.nslices <= 0)
         return aoclsparse_status_success;
     // (the kernel only moves values: cfloat cells are filled as 8-byte doubles, cdouble cells need their own instantiation)
     if(vsize == sizeof(cdouble))
-        sell_fill_as<cdouble>(s, d, v, cells, col, rowlen);
+        sell_fill_as<cdouble>(s, d, v, cells, col, rowlen, ucol);
     else if(vsize == sizeof(float))
-        sell_fill_as<float>(s, d, v, cells, col, rowlen);
+        sell_fill_as<float>(s, d, v, cells, col, rowlen, ucol);
     else
-        sell_fill_as<double>(s, d, v, cells, col, rowlen);
+        sell_fill_as<double>(s, d, v, cells, col, rowlen, ucol);
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }

@@ -158,6 +158,28 @@ __device__ __forceinline__ T cell_value(R raw, const T *__restrict__ vtab)
     else
         return raw;
 }
+// Packed table indices (plans with slice records whose rows fit: build_sell): ONE word of 1 / 2 / 4 bytes per row, at row x bytes,
+// the index of cell q in the bits-wide field at bit q x bits.  The width is a run-time scalar, not a template argument.
+__device__ __forceinline__ int packed_index(unsigned word, int q, int bits)
+{
+    return (int)((word >> (q * bits)) & ((1u << bits) - 1u));
+}
+__device__ __forceinline__ unsigned packed_word(const void *__restrict__ words, long long row, int bytes)
+{
+    if(bytes == 1)
+        return static_cast<const unsigned char *>(words)[row];
+    if(bytes == 2)
+        return static_cast<const unsigned short *>(words)[row];
+    return static_cast<const unsigned *>(words)[row];
+}
+// the same without a branch on the width: the aligned dword that holds the word, shifted and masked (the words of a wavefront are
+// one line either way; the array is a multiple of 4 bytes long, build_sell pads it by whole slices)
+__device__ __forceinline__ unsigned packed_word_any(const void *__restrict__ words, long long row, int bytes)
+{
+    const long long a = row * bytes;
+    const unsigned  d = static_cast<const unsigned *>(words)[a >> 2];
+    return (d >> (((unsigned)a & 3u) * 8u)) & (0xffffffffu >> (32 - 8 * bytes));
+}
 // (shared column lists -- cptr, follow -- and the slice modes in cptr's top byte: sell_build_kernels.hip)
 // four adjacent cells of one lane as vector loads (PACK 4): 32 B of values (16 B for float), 16 B of columns
 __device__ __forceinline__ void load4(const double *p, double (&o)[4])
@@ -185,9 +207,10 @@ __device__ __forceinline__ void load4(const unsigned char *p, int (&o)[4])
 // loads the G cells p0 .. p0+G-1 of this lane (wave-uniform guards against the slice width w): stored S, loaded as R
 // (values, or table indices)
 // cs = lanes per column row: 64, or the slice's number of leaders when the column lists are shared
+// pbits > 0 (table indices, PACK 1): the row's indices are the pbits-wide fields of pw, nothing is read from v
 template <typename S, typename R, int PACK, int G>
 __device__ __forceinline__ void load_step(const S *v, const aoclsparse_int *c, int p0, int w, R (&vv)[G], int (&cc)[G],
-                                          int cs = 64)
+                                          int cs = 64, unsigned pw = 0, int pbits = 0)
 {
     if constexpr(PACK == 1)
     {
@@ -195,8 +218,11 @@ __device__ __forceinline__ void load_step(const S *v, const aoclsparse_int *c, i
         for(int q = 0; q < G; q++)
         {
             const bool ok = p0 + q < w;
-            vv[q]         = ok ? (R)v[(p0 + q) * 64] : R(0);
-            cc[q]         = ok ? c[(p0 + q) * cs] : -1;
+            if constexpr(std::is_same_v<R, int>)
+                vv[q] = ok ? (pbits ? packed_index(pw, p0 + q, pbits) : (R)v[(p0 + q) * 64]) : R(0);
+            else
+                vv[q] = ok ? (R)v[(p0 + q) * 64] : R(0);
+            cc[q] = ok ? c[(p0 + q) * cs] : -1;
         }
     }
     else
@@ -230,7 +256,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
                                                              const T *__restrict__ x, T beta, T *__restrict__ y,
                                                              bool nt, const long long *__restrict__ cptr = nullptr,
                                                              const unsigned short *__restrict__ follow = nullptr, int rev = 0,
-                                                             const T *__restrict__ vtab = nullptr)
+                                                             const T *__restrict__ vtab = nullptr, int pbits = 0, int pbytes = 0)
 {
     using S = typename SellCell<T, IDX>::src;
     using R = typename SellCell<T, IDX>::raw;
@@ -264,6 +290,24 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         c  = scol + c0 + (f & 0xff) * PACK;
         dl = f >> 8;
     }
+    // pbits > 0 (IDX, PACK 1: the plan has slice records, a pinned order or a transposed product came here): sval holds one
+    // packed word per row, read once; cell(p) is field p of it
+    [[maybe_unused]] unsigned pw = 0;
+    if constexpr(IDX && PACK == 1)
+    {
+        if(pbits)
+            pw = packed_word(sval, (long long)s * 64 + lane, pbytes);
+    }
+    else
+        pbits = 0;
+    auto cell = [&](int p) -> R {
+        if constexpr(IDX && PACK == 1)
+        {
+            if(pbits)
+                return packed_index(pw, p, pbits);
+        }
+        return (R)v[p * 64];
+    };
     T r = T(0);
     if constexpr(ORDER == 0 && PACK == 1)
     {
@@ -282,7 +326,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
             int           cc[W];
 #pragma unroll
             for(int q = 0; q < W; q++)
-                rr[q] = v[q * 64], cc[q] = c[q * cs];
+                rr[q] = cell(q), cc[q] = c[q * cs];
 #pragma unroll
             for(int q = 0; q < W; q++)
                 xx[q] = x[cc[q] >= 0 ? cc[q] + dl : 0], vv[q] = s_cj<CONJ>(cell_value<IDX>(rr[q], vtab));
@@ -301,7 +345,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         }
         for(; p + 4 <= w; p += 4)
         {
-            const R   r0 = v[(p + 0) * 64], r1 = v[(p + 1) * 64], r2 = v[(p + 2) * 64], r3 = v[(p + 3) * 64];
+            const R   r0 = cell(p + 0), r1 = cell(p + 1), r2 = cell(p + 2), r3 = cell(p + 3);
             const int c0 = c[(p + 0) * cs], c1 = c[(p + 1) * cs], c2 = c[(p + 2) * cs], c3 = c[(p + 3) * cs];
             // (a padding cell, -1, is never used, but its gather must stay inside x: index 0)
             const T   x0 = x[c0 >= 0 ? c0 + dl : 0], x1 = x[c1 >= 0 ? c1 + dl : 0], x2 = x[c2 >= 0 ? c2 + dl : 0],
@@ -315,7 +359,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         }
         for(; p < w; p++)
         {
-            const R   r0 = v[p * 64];
+            const R   r0 = cell(p);
             const int c0 = c[p * cs];
             const T   x0 = x[c0 >= 0 ? c0 + dl : 0], v0 = s_cj<CONJ>(cell_value<IDX>(r0, vtab));
             r = c0 >= 0 ? s_fma(v0, x0, r) : r;
@@ -336,7 +380,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         bool reduced = false;
         R    vn[G];
         int  cn[G];
-        load_step<S, R, PACK, G>(v, c, 0, w, vn, cn, cs);
+        load_step<S, R, PACK, G>(v, c, 0, w, vn, cn, cs, pw, pbits);
         for(int p0 = 0; p0 < w; p0 += G)
         {
             T   vv[G], xx[G];
@@ -346,7 +390,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
             for(int q = 0; q < G; q++)
                 vr[q] = vn[q], cc[q] = cn[q];
             if(p0 + G < w)
-                load_step<S, R, PACK, G>(v, c, p0 + G, w, vn, cn, cs);
+                load_step<S, R, PACK, G>(v, c, p0 + G, w, vn, cn, cs, pw, pbits);
             // (IDX: the table reads go out with the x gathers, after the next step's lines)
 #pragma unroll
             for(int q = 0; q < G; q++)
@@ -381,37 +425,46 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
 }
 
 // Short rows: matrices whose widest slice has WMAX <= 8 cells, scalar summation order, PACK 1, large launches.  A wavefront
-// takes SPW consecutive slices and walks them TOGETHER, with no branch and no loop on the common path, so that its life is four
-// dependent round trips whatever SPW is:
+// takes SPW consecutive slices and walks them TOGETHER, with no loop on the common path.  On a plan with uniform column lists
+// and packed table indices (UCOL, PK: a stencil with a value table, the headline) its life is THREE dependent round trips
+// whatever SPW is:
 //   1. the kernel arguments (one scalar batch: the sweep direction is the pair g0 / gstep, not a branch);
-//   2. the SPW slice records (SellSliceDesc, one wide scalar load: offsets, width, column stride, mode -- no slice_ptr / cptr
-//      pairs, no division);
-//   3. all SPW x WMAX value / column line loads (index clamped to the slice's own width, and to 0 for an EMPTY slice, which
-//      reads the padding cells behind the arrays: a narrower slice re-reads its last line and skips the FMA);
-//   4. all SPW x WMAX x gathers; then the chains and the stores.
-// Only a group with a mode-0 slice (lead[] says which list a lane follows: 2 slices in 64 on a stencil) takes a fifth, the lead[]
-// loads of the whole group, issued together in front of the line loads.
-// TAB: 0 = the cells hold values; 2 = one-byte indices into a table of <= 2 values, held in scalar registers and selected;
+//   2. one batch whose every address is a function of the slice number alone: the SPW slice records (SellSliceDesc, one wide
+//      scalar load), the SPW uniform column lists (ucol, 8 columns per slice, consecutive slices adjacent: one wide scalar load)
+//      and the SPW packed index words (one vector load per slice, one contiguous line per wavefront);
+//   3. all SPW x WMAX x gathers, each at a scalar base (x + column) plus the lane's shift; then the chains and the stores.
+// A slice of mode 1 / 2 (full, one leader: sell_leaders_kernel) has ONE column list, so its columns are wave-uniform: they live
+// in scalar registers and no vector load fetches them.  A group with a slice of any other mode (mode 0, lead[] says which list a
+// lane follows: 2 slices in 64 on a stencil; mode 3, lists not shared) takes ONE wave-uniform branch to the column lists in col,
+// as every group does without UCOL: there the life is four round trips (records -> value / column lines, index clamped to the
+// slice's own width, and to 0 for an EMPTY slice, which reads the padding cells behind the arrays -> gathers), five with lead[].
+// Without PK the value (or one-byte index) lines are SPW x WMAX vector loads behind the records.
+// TAB: 0 = the cells hold values; 2 = indices into a table of <= 2 values, held in scalar registers and selected;
 // 256 = indices into a table of <= SELL_VTAB_MAX values, copied to LDS once per workgroup (its load goes out with the records,
-// the barrier sits behind the line loads) -- no table read goes through the vector memory path.
-// The records, the padding cells and the table are padded at plan time (build_sell) so that nothing here needs a bound check:
-// SELL_DESC_PAD empty records behind the last slice, SELL_CELL_PAD cells, SELL_VTAB_MAX table entries.
-template <typename T, int WMAX, int WAVES, int SPW, bool CONJ, int TAB>
+// the barrier sits behind the gathers) -- no table read goes through the vector memory path.
+// PK (TAB != 0): sval holds one packed word per row (packed_index; TAB 2: always one byte, one bit per cell).
+// The records, the lists, the words, the padding cells and the table are padded at plan time (build_sell) so that nothing here
+// needs a bound check: SELL_DESC_PAD empty records / lists of -1 / zero words behind the last slice, SELL_CELL_PAD cells,
+// SELL_VTAB_MAX table entries.
+template <typename T, int WMAX, int WAVES, int SPW, bool CONJ, int TAB, bool UCOL, bool PK>
 __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_int m, aoclsparse_int nslices, int g0, int gstep,
                                                                    const uint4 *__restrict__ desc,
                                                                    const typename SellCell<T, TAB != 0>::src *__restrict__ sval,
                                                                    const aoclsparse_int *__restrict__ scol,
                                                                    const unsigned short *__restrict__ follow, T alpha,
                                                                    const T *__restrict__ x, T beta, T *__restrict__ y, bool nt,
-                                                                   const T *__restrict__ vtab)
+                                                                   const T *__restrict__ vtab, const aoclsparse_int *__restrict__ ucol,
+                                                                   int pbits, int pbytes)
 {
     using R = typename SellCell<T, TAB != 0>::raw;
     static_assert(WAVES * SPW <= SELL_DESC_PAD && 64 * WAVES == SELL_VTAB_MAX, "padding of the slice records / one table entry per lane");
+    static_assert(!PK || TAB != 0, "packed words hold table indices");
     // group g of WAVES x SPW slices; consecutive products of a handle ALTERNATE the direction (SellPlan::products): g0 = last
     // group, gstep = -1 on odd ones
     const int sb   = __builtin_amdgcn_readfirstlane(((g0 + gstep * (int)blockIdx.x) * WAVES + (int)(threadIdx.x >> 6)) * SPW);
     const int lane = threadIdx.x & 63;
     s_pin_arg(alpha), s_pin_arg(beta), s_pin_arg(y), s_pin_arg((int)nt), s_pin_arg(x), s_pin_arg(sval), s_pin_arg(scol), s_pin_arg(follow);
+    s_pin_arg(pbits), s_pin_arg(pbytes); // (not ucol / vtab: a pointer handed to an asm statement is no longer read with scalar loads)
     [[maybe_unused]] T t0, t1;
     if constexpr(TAB == 2)
         t0 = vtab[0], t1 = vtab[1];
@@ -421,77 +474,172 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
 #pragma unroll
     for(int u = 0; u < SPW; u++)
         d[u] = desc[sb + u];
-    int  f[SPW]; // list of this lane | column shift << 8
-    bool follows = false;
+    [[maybe_unused]] int uc[SPW][WMAX]; // the slices' uniform lists: scalars
+    if constexpr(UCOL)
+    {
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+#pragma unroll
+            for(int q = 0; q < WMAX; q++)
+                uc[u][q] = ucol[(sb + u) * SELL_SHORT_WMAX + q];
+    }
+    [[maybe_unused]] unsigned pw[SPW]; // the rows' packed index words
+    if constexpr(PK)
+    {
+        // (TAB 2: <= 8 cells of one bit, always a byte; else the width is a run-time scalar and the load has no branch)
+        const long long row = (long long)sb * 64 + lane;
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+            pw[u] = TAB == 2 ? packed_word(sval, row + 64 * u, 1) : packed_word_any(sval, row + 64 * u, pbytes);
+    }
+    int  mode[SPW];
+    bool lists = !UCOL; // the group reads its columns from the lists in col
 #pragma unroll
     for(int u = 0; u < SPW; u++)
     {
-        const int mode = (int)(d[u].w >> 16) & 0xff;
-        follows        = follows || mode == SELL_DESC_MODE_FOLLOW;
-        f[u]           = mode == SELL_DESC_MODE_LANE_SHIFT ? lane << 8 : (mode == SELL_DESC_MODE_OWN ? lane : 0);
+        mode[u] = (int)(d[u].w >> 16) & 0xff;
+        lists   = lists || !(mode[u] == SELL_DESC_MODE_LANE_SHIFT || mode[u] == SELL_DESC_MODE_ONE);
     }
-    if(follows) // wave-uniform
+    [[maybe_unused]] R rr[SPW][WMAX];
+    if constexpr(!PK)
     {
-        int ff[SPW];
 #pragma unroll
         for(int u = 0; u < SPW; u++)
-            ff[u] = follow[min((sb + u) * 64 + lane, (int)m - 1)];
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-            f[u] = ((int)(d[u].w >> 16) & 0xff) == SELL_DESC_MODE_FOLLOW ? ff[u] : f[u];
-    }
-    R   rr[SPW][WMAX];
-    int cc[SPW][WMAX];
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-    {
-        const long long o0 = (long long)d[u].x | (long long)(d[u].z & 0xffffu) << 32;
-        const long long c0 = (long long)d[u].y | (long long)(d[u].z >> 16) << 32;
-        const int       w = (int)(d[u].w & 0xffu), cs = (int)(d[u].w >> 8) & 0xff;
-        const auto     *v = sval + o0 + lane;
-        const aoclsparse_int *c = scol + c0 + (f[u] & 0xff);
-#pragma unroll
-        for(int q = 0; q < WMAX; q++)
         {
-            const int qq = max(min(q, w - 1), 0); // wave-uniform
-            rr[u][q]     = v[qq * 64];
-            cc[u][q]     = c[qq * cs];
+            const long long o0 = (long long)d[u].x | (long long)(d[u].z & 0xffffu) << 32;
+            const int       w  = (int)(d[u].w & 0xffu);
+            const auto     *v  = sval + o0 + lane;
+#pragma unroll
+            for(int q = 0; q < WMAX; q++)
+                rr[u][q] = v[max(min(q, w - 1), 0) * 64]; // (wave-uniform index)
         }
     }
-    __builtin_amdgcn_sched_barrier(0); // (every line load is issued before the first wait for one)
-    T vv[SPW][WMAX], xx[SPW][WMAX];
+    if constexpr(UCOL)
+    {
+        // the lists (and the two table entries) are in their scalar registers HERE: their loads go out with the records, in front of
+        // the branch, not inside the path that uses them (one more scalar round trip there); then the whole batch is issued
+        // before the branch
 #pragma unroll
-    for(int u = 0; u < SPW; u++)
+        for(int u = 0; u < SPW; u++)
 #pragma unroll
-        for(int q = 0; q < WMAX; q++) // (a padding cell, -1, is never used, but its gather must stay inside x: index 0)
-            xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + (f[u] >> 8) : 0];
+            for(int q = 0; q < WMAX; q++)
+                s_pin_arg(uc[u][q]);
+        if constexpr(TAB == 2)
+            s_pin_arg(t0), s_pin_arg(t1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    T        xx[SPW][WMAX];
+    unsigned okm[SPW]; // bit q: cell q of this lane's row is a cell of the matrix (inside the slice's width, no padding)
+    // the columns from the lists in col, as a lane finds them through the slice's mode; then the gathers
+    auto from_lists = [&]() {
+        int  f[SPW]; // list of this lane | column shift << 8
+        bool follows = false;
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+        {
+            follows = follows || mode[u] == SELL_DESC_MODE_FOLLOW;
+            f[u]    = mode[u] == SELL_DESC_MODE_LANE_SHIFT ? lane << 8 : (mode[u] == SELL_DESC_MODE_OWN ? lane : 0);
+        }
+        if(follows) // wave-uniform
+        {
+            int ff[SPW];
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+                ff[u] = follow[min((sb + u) * 64 + lane, (int)m - 1)];
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+                f[u] = mode[u] == SELL_DESC_MODE_FOLLOW ? ff[u] : f[u];
+        }
+        int cc[SPW][WMAX];
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+        {
+            const long long c0 = (long long)d[u].y | (long long)(d[u].z >> 16) << 32;
+            const int       w = (int)(d[u].w & 0xffu), cs = (int)(d[u].w >> 8) & 0xff;
+            const aoclsparse_int *c = scol + c0 + (f[u] & 0xff);
+#pragma unroll
+            for(int q = 0; q < WMAX; q++)
+                cc[u][q] = c[max(min(q, w - 1), 0) * cs]; // (wave-uniform index)
+        }
+        __builtin_amdgcn_sched_barrier(0); // (every line load is issued before the first wait for one)
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+        {
+            const int w = (int)(d[u].w & 0xffu);
+            okm[u]      = 0;
+#pragma unroll
+            for(int q = 0; q < WMAX; q++) // (a padding cell, -1, is never used, but its gather must stay inside x: index 0)
+            {
+                xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + (f[u] >> 8) : 0];
+                okm[u] |= (q < w && cc[u][q] >= 0) ? 1u << q : 0u;
+            }
+        }
+    };
+    if constexpr(UCOL)
+    {
+        if(__builtin_expect(lists, 0)) // wave-uniform
+            from_lists();
+        else
+        {
+            // every slice of the group has one list: a gather is a scalar base, x + column, plus the lane's shift (mode 1) in
+            // bytes -- no address arithmetic in vector registers.  An unused entry (-1) gathers at x + shift, which is inside x:
+            // a mode-1 slice has 64 distinct columns in its first cell, and the empty records behind the last slice are mode 2
+            // (no shift).  A mode 1 / 2 slice is full and its rows repeat one list: every row has exactly w cells, none padded.
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+            {
+                const unsigned sh = mode[u] == SELL_DESC_MODE_LANE_SHIFT ? (unsigned)lane * (unsigned)sizeof(T) : 0u;
+#pragma unroll
+                for(int q = 0; q < WMAX; q++)
+                {
+                    const T *xb = x + max(uc[u][q], 0);
+                    if constexpr(std::is_floating_point_v<T>)
+                    {
+                        // (the base stays a scalar pair, in the global address space: the load takes it as it is.  If a compiler
+                        // stops honouring this the base moves to vector registers: slower, the same loads, the same bits --
+                        // profiles/r10/isa_waits_after.txt is the check)
+                        using GT = const __attribute__((address_space(1))) T;
+                        using GC = const __attribute__((address_space(1))) char;
+                        GT *gb   = (GT *)xb;
+                        asm volatile("" : "+s"(gb));
+                        xx[u][q] = *(GT *)((GC *)gb + sh);
+                    }
+                    else
+                        xx[u][q] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(xb) + sh);
+                }
+                okm[u] = (1u << (d[u].w & 0xffu)) - 1u;
+            }
+        }
+    }
+    else
+        from_lists();
     [[maybe_unused]] __shared__ T ltab[TAB > 2 ? SELL_VTAB_MAX : 1];
     if constexpr(TAB > 2) // (behind the gathers: the barrier is waited for while they are in flight)
     {
         ltab[threadIdx.x] = t0;
         __syncthreads();
     }
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-#pragma unroll
-        for(int q = 0; q < WMAX; q++)
-        {
-            if constexpr(TAB == 0)
-                vv[u][q] = s_cj<CONJ>(rr[u][q]);
-            else if constexpr(TAB == 2)
-                vv[u][q] = rr[u][q] ? t1 : t0;
-            else
-                vv[u][q] = ltab[rr[u][q]];
-        }
     T r[SPW];
 #pragma unroll
     for(int u = 0; u < SPW; u++)
     {
-        const int w = (int)(d[u].w & 0xffu);
-        r[u]        = T(0);
+        r[u] = T(0);
 #pragma unroll
         for(int q = 0; q < WMAX; q++)
-            r[u] = (q < w && cc[u][q] >= 0) ? s_fma(vv[u][q], xx[u][q], r[u]) : r[u];
+        {
+            T vv;
+            if constexpr(TAB == 0)
+                vv = s_cj<CONJ>(rr[u][q]);
+            else if constexpr(TAB == 2 && PK)
+                vv = ((pw[u] >> q) & 1u) ? t1 : t0;
+            else if constexpr(TAB == 2)
+                vv = rr[u][q] ? t1 : t0;
+            else if constexpr(PK)
+                vv = ltab[packed_index(pw[u], q, pbits)];
+            else
+                vv = ltab[rr[u][q]];
+            r[u] = ((okm[u] >> q) & 1u) ? s_fma(vv, xx[u][q], r[u]) : r[u];
+        }
     }
 #pragma unroll
     for(int u = 0; u < SPW; u++)
@@ -527,14 +675,16 @@ bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T 
     constexpr bool       COMPLEX = !std::is_floating_point_v<T>;
     const aoclsparse_int m = v.m, nslices = v.nslices;
     // Slices per wavefront, by measurement (5-point Laplacians, cold products, one box, median of 20, ms; 1 / 2 / 4 slices per
-    // wavefront; profiles/r8/spw_sweep.txt, which also has the VGPRs and the occupancy of each variant):
+    // wavefront; profiles/r10/spw_sweep.txt, which also has the VGPRs and the occupancy of each variant; table = packed words and
+    // uniform lists, values = the cells hold values -- measured there WITH uniform lists, which lost and are not built for them):
     //                       4096^2 (262,144 slices)    3000^2 (140,625)          2000^2 (62,500)
-    //   double, table       0.1264 / 0.1204 / 0.1276   0.0729 / 0.0683 / 0.0722  0.0354 / 0.0333 / 0.0350
-    //   double, values      0.2025 / 0.2032 / 0.2073   0.1250 / 0.1252 / 0.1294  0.0686 / 0.0712 / 0.0739
-    //   float, table        0.1086 / 0.0747 / 0.0706   0.0590 / 0.0413 / 0.0415  0.0282 / 0.0218 / 0.0221
-    //   float, values       0.1289 / 0.1193 / 0.1234   0.0780 / 0.0803 / 0.0820  0.0418 / 0.0409 / 0.0422
-    // -> from 60,000 slices on: double with a table 2, float with a table 4, float values 2; double values stay at 1 (8-byte
-    // cells: the bytes in flight of ONE slice already fill the wave's share).  Not measured below 60,000 slices: 1.  Complex: 1.
+    //   double, table       0.0951 / 0.0816 / 0.0843   0.0498 / 0.0475 / 0.0485  0.0256 / 0.0239 / 0.0256
+    //   double, values      0.1741 / 0.1774 / 0.1811   0.0905 / 0.0943 / 0.0962  0.0421 / 0.0444 / 0.0470
+    //   float, table        0.0770 / 0.0538 / 0.0461   0.0394 / 0.0305 / 0.0292  0.0209 / 0.0168 / 0.0173
+    //   float, values       0.1028 / 0.0864 / 0.0887   0.0555 / 0.0533 / 0.0534  0.0275 / 0.0256 / 0.0276
+    // -> from 60,000 slices on: double with a table 2, float with a table 4 (2000^2: 2 and 4 within each other's spread), float
+    // values 2; double values stay at 1 (8-byte cells: the bytes in flight of ONE slice already fill the wave's share).  The same
+    // rule as before the packed words (profiles/r8/spw_sweep.txt).  Not measured below 60,000 slices: 1.  Complex: 1.
     int spw = 1;
     if constexpr(!COMPLEX)
     {
@@ -550,9 +700,30 @@ bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T 
     const uint4    *dp = reinterpret_cast<const uint4 *>(v.desc);
     const auto     *sval = static_cast<const typename SellCell<T, TAB != 0>::src *>(v.cells);
     const T        *vtab = static_cast<const T *>(v.vtab);
-#define MI355_SHORT_SPW(W, SPW)                                                                                                 \
-    hipLaunchKernelGGL((sell_mv_short_kernel<T, W, WAVES, SPW, CONJ, TAB>), grid, block, 0, s, m, nslices, g0, gstep, dp, sval, \
-                       v.col, v.lead, alpha, x, beta, y, nt, vtab)
+    if(TAB == 2 && !(v.pbits == 1 && v.pbytes == 1)) // (a plan with slice records and <= 2 table entries always packs)
+        return false;
+    // the kernel's path: PK when the plan's table indices are packed words (a table of two always is: <= 8 cells of one bit), UCOL
+    // when it also has uniform column lists (build_sell makes them next to packed words only)
+    auto launch = [&](auto wt, auto st, auto ut, auto pt) {
+        hipLaunchKernelGGL((sell_mv_short_kernel<T, decltype(wt)::value, WAVES, decltype(st)::value, CONJ, TAB, decltype(ut)::value, decltype(pt)::value>),
+                           grid, block, 0, s, m, nslices, g0, gstep, dp, sval, v.col, v.lead, alpha, x, beta, y, nt, vtab, v.ucol, v.pbits,
+                           v.pbytes);
+    };
+    auto path = [&](auto wt, auto st) {
+        if constexpr(TAB == 2)
+            v.ucol ? launch(wt, st, std::true_type{}, std::true_type{}) : launch(wt, st, std::false_type{}, std::true_type{});
+        else
+        {
+            if constexpr(TAB != 0)
+                if(v.pbits)
+                {
+                    v.ucol ? launch(wt, st, std::true_type{}, std::true_type{}) : launch(wt, st, std::false_type{}, std::true_type{});
+                    return;
+                }
+            launch(wt, st, std::false_type{}, std::false_type{}); // (values or one byte per cell: such a plan has no uniform lists)
+        }
+    };
+#define MI355_SHORT_SPW(W, SPW) path(std::integral_constant<int, W>{}, std::integral_constant<int, SPW>{})
 #define MI355_SHORT(W)                      \
     case W:                                 \
         if constexpr(!COMPLEX)              \
@@ -626,10 +797,11 @@ aoclsparse_status launch_sellmv(hipStream_t s, const SellView &v, int order, boo
         const T    *vtab  = static_cast<const T *>(v.vtab);
         if(v.nslices < 2048)
             hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 1, PACK, SHARED, CONJ, IDX>), dim3(v.nslices), dim3(64), 0, s, v.m, v.nslices,
-                               v.slice_ptr, cells, v.col, v.rowlen, alpha, x, beta, y, nt, v.cptr, v.lead, rev, vtab);
+                               v.slice_ptr, cells, v.col, v.rowlen, alpha, x, beta, y, nt, v.cptr, v.lead, rev, vtab, v.pbits, v.pbytes);
         else
             hipLaunchKernelGGL((sell_mv_kernel<T, ORDER, 2, PACK, SHARED, CONJ, IDX>), dim3((v.nslices + 1) / 2), dim3(128), 0, s, v.m,
-                               v.nslices, v.slice_ptr, cells, v.col, v.rowlen, alpha, x, beta, y, nt, v.cptr, v.lead, rev, vtab);
+                               v.nslices, v.slice_ptr, cells, v.col, v.rowlen, alpha, x, beta, y, nt, v.cptr, v.lead, rev, vtab, v.pbits,
+                               v.pbytes);
     };
     auto pick = [](bool b, auto f) { b ? f(std::true_type{}) : f(std::false_type{}); };
     using I0 = std::integral_constant<int, 0>;

@@ -772,4 +772,18 @@ aoclsparse_status aoclsparse_mi355_get_sell_values(const aoclsparse_matrix A, ao
     return aoclsparse_status_success;
 }
 
+aoclsparse_status aoclsparse_mi355_get_sell_packing(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *index_bits,
+                                                    aoclsparse_int *word_bytes, aoclsparse_int *uniform_slices)
+{
+    if(!A || !index_bits || !word_bytes || !uniform_slices)
+        return aoclsparse_status_invalid_pointer;
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
+    const bool packed = p.sell.valid && p.sell.ntab > 0 && p.sell.pbits > 0;
+    *index_bits       = packed ? p.sell.pbits : 0;
+    *word_bytes       = packed ? p.sell.pbytes : 0;
+    *uniform_slices   = p.sell.valid && p.sell.ucol.ptr ? p.sell.uniform : 0;
+    return aoclsparse_status_success;
+}
+
 } // extern "C"

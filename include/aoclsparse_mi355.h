@@ -50,7 +50,9 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_set_pointer_mode(aoclsparse_mi355_
  *                schedule (deep, narrow DAGs: a mesh numbered line by line); 0 never; 1 whenever the triangle has the shape the
  *                kernel serves.  Read when a TRSV plan is built.  Same bits on every schedule.
  *   sell_values  -1 (default): a SELL-64 copy of a real matrix with >= 2^17 non-zeros whose values take at most 256 distinct bit
- *                patterns stores one byte per cell, an index into a table of those patterns (aoclsparse_mi355_get_sell_values);
+ *                patterns stores indices into a table of those patterns instead (aoclsparse_mi355_get_sell_values): one byte
+ *                per cell, or -- a copy of short rows, where the indices of a row fit 32 bits -- one packed word of 1 / 2 / 4
+ *                bytes per row (aoclsparse_mi355_get_sell_packing);
  *                0 never (the values in the cells); 1 whenever there are at most 256 patterns, whatever the size.  Read when the
  *                SELL-64 copy is built.  Same bits either way: the table holds the values' exact bit patterns. */
 typedef enum aoclsparse_mi355_option_
@@ -242,6 +244,16 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_mat
  * reported. */
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_values(const aoclsparse_matrix A, aoclsparse_operation op,
                                                               aoclsparse_int *table_entries);
+/* How op(A)'s SELL-64 copy stores its table indices and its columns.  A copy with slice records (widest row <= 8 cells, >= 4096
+ * slices) packs the indices of a ROW into one word where they fit: fields of index_bits = 1 / 2 / 4 / 8 bits (the smallest that
+ * holds table_entries - 1), cell q of the row at bit q * index_bits, in a word of word_bytes = 1 / 2 / 4 bytes (the smallest
+ * that holds widest row * index_bits <= 32 bits); row i's word at i * word_bytes.  Both are 0 when the cells hold one byte per
+ * cell or the values.  uniform_slices = slices (64 full rows that share one column list, as it is or shifted by one per row) whose
+ * columns the short-row kernel reads as one scalar list per slice; 0 without packed words or shared lists.  Derived operators
+ * are not reported. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_packing(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                               aoclsparse_int *index_bits, aoclsparse_int *word_bytes,
+                                                               aoclsparse_int *uniform_slices);
 /* The plan behind mm_bell_xcd_chunk / the lattice sweep, computed from host arrays (no device involved; what aoclsparse_optimize runs on the
  * blocked-ELL copy's block columns): bcol = nbr x width block columns, ascending per block row, empty slots (-1) last; nbc = block columns of
  * the matrix.  forced: -2 automatic, -1 the lattice sweep whenever a lattice is found, 0 launch order, c >= 1 chunks of c block rows.
