@@ -482,7 +482,7 @@ constexpr int MM_DESCENDING = 0x40000000;
 constexpr int MM_DEAL       = 0x20000000; // the chunk of the word counts blocks per XCD TURN (chunks dealt round-robin), not per XCD
 int  &mm_direction_word();
 
-// TRSV plan of one (triangle, op) pair (trsv_api.cpp / trsv_kernels.hip): the strict triangle
+// TRSV plan of one (triangle, op) pair (trsv_plan.cpp / trsv_kernels.hip): the strict triangle
 // re-laid out in LEVEL ORDER.  Position k holds row rowmap[k]; its entries sit at
 // [pptr[k], pptr[k+1]) of pind/pval already in the order the reference's chain consumes them, so
 // a level is one contiguous slab of HBM and every kernel walks forward.
@@ -537,6 +537,9 @@ constexpr int trsv_chunk_slots(int bs, int ext)
     return ((160 * 1024 - 16 - (TRSV_CHUNK_WAVES - 1) * (trsv_chunk_pcap(bs, ext) * 8 + 9 * ext * 4) - 65 * 8) / 8) / 256 * 256;
 }
 constexpr int TRSV_CHUNK_ROWS = trsv_chunk_slots(5, 16); // the largest of the four shapes
+// the compiled shape (rows per block, external dependencies) that holds a plan's largest block / external list
+constexpr int trsv_chunk_bs(int max_rows) { return max_rows <= 5 ? 5 : TRSV_CHUNK_LANES; }
+constexpr int trsv_chunk_ext(int max_ext) { return max_ext <= 16 ? 16 : TRSV_BLK_EXT; }
 struct TrsvChunkPlan
 {
     bool           tried = false, valid = false;
@@ -546,7 +549,7 @@ struct TrsvChunkPlan
 };
 struct TrsvBlockPlan
 {
-    double         slice_fan_in = 0.0; // producer slices a slice of 64 blocks waits for, on average (trsv_api.cpp: the slice width)
+    double         slice_fan_in = 0.0; // producer slices a slice of 64 blocks waits for, on average (trsv_plan.cpp: the slice width)
     TrsvChunkPlan  chunk;
     bool           tried = false, valid = false;
     bool           front = false; // a row's chain starts with the rows of its own block (U), instead of ending with them
@@ -637,7 +640,7 @@ struct _aoclsparse_matrix
     // device side; guarded by `guard` (executors take it shared, builders exclusive)
     mi355::DeviceCsr dev_user, dev_trans;
     mi355::SpmvPlan  plan_user, plan_trans;
-    mi355::TrsvPlan  trsv_plan[6]; // index: (upper?2:0) + (transpose?1:0); complex op = H: 4 + (upper?1:0)
+    mi355::TrsvPlan  trsv_plan[6]; // index: trsv_plan_index (trsv_schedule.hpp)
     mi355::DeviceBuffer dev_diag; // diagonal values of the clean CSR (length min(m,n))
     mi355::DeviceBuffer trsv_scratch; // ticket (one per right-hand side) + timeout words of the sync-free solve
     mi355::DeviceBuffer trsv_xp; // solution(s) in level order, m x nrhs (stream-ordered reuse)
@@ -871,7 +874,7 @@ aoclsparse_status ensure_spmv(aoclsparse_matrix A, bool transposed, DeviceCsr *&
 // symmetric expansion / triangular slice of the clean CSR as a general device CSR (derived.cpp)
 aoclsparse_status ensure_derived(aoclsparse_matrix A, aoclsparse_matrix_type type, aoclsparse_fill_mode fill,
                                  aoclsparse_diag_type diag, bool transposed, Derived *&out);
-// clean CSR on the device + level sets of one triangle (trsv_api.cpp)
+// clean CSR on the device + level sets of one triangle (trsv_plan.cpp)
 // need_rows: also the level-ordered row layout (TrsvPlan::rows_valid); false = only what the automatic schedule needs
 aoclsparse_status ensure_trsv(aoclsparse_matrix A, bool upper, bool transposed, bool conj = false, bool need_rows = true);
 // SELL-64 copy of d (row_ptr_host = the host row pointer d mirrors); leaves plan.sell.valid false when the
@@ -1016,8 +1019,9 @@ aoclsparse_status launch_lincomb(hipStream_t s, int sign, aoclsparse_int n, int 
 
 // TRSV on the level-ordered layout (trsv_kernels.hip).
 // schedule 0: one launch per level; 1: hybrid (narrow level runs inside one workgroup); 2: sync-free, a lane per
-// position; 3: sync-free, a level slice per wavefront (single right-hand side; falls back to 2 otherwise);
-// 4: sync-free, a lane per BLOCK of chained rows (plan.blk, real types, one right-hand side; falls back to 3 / 2).
+// position; 3: sync-free, a level slice per wavefront (single right-hand side); 4: sync-free, a lane per BLOCK of chained
+// rows (plan.blk, real types); 5: chunks of blocks (plan.blk.chunk).  The schedule is the one resolve_trsv_schedule
+// (trsv_schedule.hpp) returned: the launcher replaces nothing, what the plan cannot serve is an internal error.
 // csrmm with beta == 0: false (default) = C is read and multiplied by zero as in every reference kernel (NaN / Inf in C
 // propagate); true = C is overwritten without being read (BLAS semantics, a third less traffic at 256 columns).  One word for the
 // process (aoclsparse_mi355_set_csrmm_beta0_overwrite; AOCLSPARSE_MI355_CSRMM_BETA0_OVERWRITE seeds it once, on first touch).

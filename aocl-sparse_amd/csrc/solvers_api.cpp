@@ -5,7 +5,7 @@
 // chained on the library stream under a DeviceScope, and only the results travel back.
 //   symgs : solvers/aoclsparse_symgs.hpp:62-258 (algorithm), :264-394 (checks)
 //   ilu   : solvers/aoclsparse_ilu.hpp:33-139, solvers/aoclsparse_ilu0.hpp:34-199, analysis.cpp:390-425
-#include "internal.hpp"
+#include "trsv_schedule.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -214,7 +214,7 @@ aoclsparse_status sorv_t(aoclsparse_sor_type sor_type, const aoclsparse_mat_desc
     MI355_HIP_TRY(hipMemcpyAsync(A->work[0].ptr, vx.dev, sizeof(T) * (size_t)m, hipMemcpyDeviceToDevice, s));
     {
         std::shared_lock<std::shared_mutex> r(A->guard);
-        const TrsvPlan                     &tp = A->trsv_plan[0];
+        const TrsvPlan                     &tp = A->trsv_plan[trsv_plan_index(false, false, false)];
         const aoclsparse_int               *rows = tp.rowmap.as<aoclsparse_int>();
         for(aoclsparse_int l = 0; l < tp.nlevels; l++)
             MI355_TRY(launch_sorv_level<T>(s, rows + tp.level_ptr[l], tp.level_ptr[l + 1] - tp.level_ptr[l], d->base,

@@ -6,7 +6,7 @@
 // lane as the reference's chain  xi = alpha*b_i; xi = fma(-a_ij, x_j, xi) in the reference's order;
 // xi /= d, so x is bit-identical to ref_trsv_l / _u / _lth / _uth (kid 0) whatever the schedule.
 //
-// Data layout (built once per (fill, op) by trsv_api.cpp): the strict triangle re-laid out in level
+// Data layout (built once per (fill, op) by trsv_plan.cpp): the strict triangle re-laid out in level
 // order.  Position k holds row rowmap[k]; its entries are [pptr[k], pptr[k+1]) of pind (POSITION of the
 // row depended on) / pval, stored in chain order (L: left to right; U: left to right; L^T: descending source row, as the column sweep of
 // ref_trsv_lth applies them; U^T: ascending).  A level is a contiguous slab, so per-level traffic is
@@ -1816,7 +1816,357 @@ __global__ __launch_bounds__(64 * TRSV_CHUNK_WAVES) void trsv_chunk_kernel(
         __hip_atomic_store(timeout_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// scratch: nrhs ticket words followed by one timeout word (zeroed here for the sync-free schedule)
+#define MI355_TRY(expr)                       \
+    do                                        \
+    {                                         \
+        aoclsparse_status st__ = (expr);      \
+        if(st__ != aoclsparse_status_success) \
+            return st__;                      \
+    } while(0)
+
+// ---- launchers: one function per schedule ---------------------------------------------------------------------------------
+// What a schedule's launcher needs, filled once by launch_trsv.  The schedule was decided by resolve_trsv_schedule
+// (trsv_schedule.hpp): a launcher only checks that the plan it is handed can serve it.
+template <typename T>
+struct TrsvLaunch
+{
+    hipStream_t     s;
+    const TrsvPlan &plan;
+    aoclsparse_int  m;
+    // the level-ordered row layout, or -- when only the block plan was built (TrsvPlan::rows_valid == false) -- the block
+    // plan's layout: also a topological order of the rows, which is all the lane-per-position kernel (schedule 2) needs
+    const aoclsparse_int *rowmap, *pptr, *pind;
+    const T              *pval;
+    const T              *diag, *b;
+    T                    *x, *xp;
+    unsigned int         *scratch; // nrhs ticket words, one timeout word, then (block schedule) the per-level counters
+    unsigned int         *timeout_word; // the handle's pinned word, or nullptr: the one in scratch
+    T                     alpha;
+    bool                  unit;
+    aoclsparse_int        nrhs;
+    long long             b_off, x_off;
+    aoclsparse_int        incb, incx;
+    int                   kt_bits; // 0 = the reference chain (ref_trsv_*); 256 / 512 = the KT kernels' order (kid 1/2 / 3)
+
+    long long     total() const { return (long long)m * nrhs; }
+    unsigned int *tmo() const { return timeout_word ? timeout_word : scratch + nrhs; }
+    RhsGeom       geom() const { return RhsGeom{b_off, x_off, incb, incx, 0}; }
+    // (several right-hand sides: the column is grid dimension x, the slice / chunk y <= 65,535; index arithmetic in int)
+    dim3 grid(aoclsparse_int n) const { return nrhs > 1 ? dim3((unsigned)nrhs, (unsigned)n) : dim3((unsigned)n); }
+    bool fits_grid(aoclsparse_int n) const { return nrhs == 1 || (n <= 65535 && total() + TRSV_XP_PAD < (1LL << 31)); }
+    // sync-free schedules: reset the first `words` of scratch, tag xp as not ready (zero_at: the slot that always holds 0)
+    aoclsparse_status reset(size_t words, long long zero_at = -1) const
+    {
+        MI355_HIP_TRY(hipMemsetAsync(scratch, 0, words * sizeof(unsigned int), s));
+        hipLaunchKernelGGL((trsv_fill_tag_kernel<T>), dim3((unsigned)((total() + 255) / 256)), dim3(256), 0, s, xp, total(), zero_at);
+        return aoclsparse_status_success;
+    }
+};
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// f(std::true_type / std::false_type) for a run-time flag
+template <typename F>
+static aoclsparse_status with_flag(bool flag, F &&f)
+{
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// f(int_c<TSZ>): the KT width in elements of T (0 = the reference chain) for the level and lane-per-position kernels
+template <typename T, typename F>
+static void with_kt_width(int kt_bits, F &&f)
+{
+    constexpr int T256 = std::is_same<T, double>::value ? 4 : 8;
+    kt_bits == 0 ? f(int_c<0>{}) : kt_bits == 256 ? f(int_c<T256>{}) : f(int_c<2 * T256>{});
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (kernel, device) pair: raised once for each, remembered in one bit
+// per device of a word per kernel (a device beyond the word is raised on every launch).
+template <auto Kernel>
+static aoclsparse_status raise_lds_limit(int bytes)
+{
+    static std::atomic<unsigned long long> raised{0};
+    int                                    dev = 0;
+    if(hipGetDevice(&dev) != hipSuccess)
+        return aoclsparse_status_internal_error;
+    const unsigned long long bit = dev < 64 ? 1ull << dev : 0ull;
+    if(raised.load(std::memory_order_acquire) & bit)
+        return aoclsparse_status_success;
+    if(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return aoclsparse_status_internal_error;
+    raised.fetch_or(bit, std::memory_order_release);
+    return aoclsparse_status_success;
+}
+
+// diagnostics: AOCLSPARSE_MI355_TRSV_TRACE=<file> makes the block and chunk kernels record clocks; `records` of `width` 64-bit
+// words each, or nullptr (no trace asked for, or no memory for it)
+static const char *trsv_trace_path()
+{
+    static const char *path = getenv("AOCLSPARSE_MI355_TRSV_TRACE");
+    return path;
+}
+static unsigned long long *trace_alloc(bool wanted, size_t width, size_t records)
+{
+    unsigned long long *trace = nullptr;
+    if(wanted && trsv_trace_path() && hipMalloc(&trace, sizeof(unsigned long long) * width * records) != hipSuccess)
+        trace = nullptr;
+    return trace;
+}
+// ... and after the launch: wait for the solve, write the records to the file, say what they belong to, free them
+template <typename... Args>
+static void trace_dump(hipStream_t s, unsigned long long *trace, size_t width, size_t records, const char *fmt, Args... args)
+{
+    if(!trace)
+        return;
+    std::vector<unsigned long long> host(width * records);
+    if(hipStreamSynchronize(s) == hipSuccess
+       && hipMemcpy(host.data(), trace, sizeof(unsigned long long) * host.size(), hipMemcpyDeviceToHost) == hipSuccess)
+        if(FILE *f = fopen(trsv_trace_path(), "wb"))
+        {
+            fwrite(host.data(), sizeof(unsigned long long), host.size(), f);
+            fclose(f);
+        }
+    fprintf(stderr, fmt, args...);
+    (void)hipFree(trace);
+}
+
+// one level, chip wide (schedules 0 and 1)
+template <typename T>
+static void launch_level(const TrsvLaunch<T> &a, aoclsparse_int l)
+{
+    const aoclsparse_int first = a.plan.level_ptr[l], count = a.plan.level_ptr[l + 1] - first;
+    const int            bs = count >= 256 ? 256 : 64;
+    for(aoclsparse_int c0 = 0; c0 < a.nrhs; c0 += 65535)
+    {
+        const int nc = a.nrhs - c0 < 65535 ? a.nrhs - c0 : 65535;
+        with_kt_width<T>(a.kt_bits, [&](auto tsz) {
+            constexpr int TSZ = decltype(tsz)::value;
+            hipLaunchKernelGGL((trsv_level_kernel<T, TSZ>), dim3((count + bs - 1) / bs, nc), dim3(bs), 0, a.s, first, count, a.m,
+                               a.rowmap, a.pptr, a.pind, a.pval, a.diag, a.b + c0 * a.b_off, a.xp + (size_t)c0 * a.m,
+                               a.x + c0 * a.x_off, a.alpha, (int)a.unit, a.geom());
+        });
+    }
+}
+
+// schedule 0: one launch per level
+template <typename T>
+static aoclsparse_status launch_levels(const TrsvLaunch<T> &a)
+{
+    if(!a.plan.rows_valid)
+        return aoclsparse_status_internal_error; // the caller asks for the row layout before choosing this (trsv_schedule.hpp)
+    for(aoclsparse_int l = 0; l < a.plan.nlevels; l++)
+        launch_level(a, l);
+    return aoclsparse_status_success;
+}
+
+// schedule 1: runs of narrow levels inside one workgroup (single right-hand side, unit stride, the reference chain)
+template <typename T>
+static aoclsparse_status launch_hybrid(const TrsvLaunch<T> &a)
+{
+    if(!a.plan.rows_valid || a.nrhs != 1 || a.incb != 1 || a.incx != 1 || a.kt_bits != 0)
+        return aoclsparse_status_internal_error;
+    for(const TrsvSegment &sg : a.plan.segments)
+    {
+        if(sg.narrow)
+            hipLaunchKernelGGL((trsv_multilevel_kernel<T>), dim3(1), dim3(TRSV_NARROW), 0, a.s, sg.l0, sg.l1,
+                               a.plan.levels.template as<aoclsparse_int>(), a.rowmap, a.pptr, a.pind, a.pval, a.diag, a.b, a.xp, a.x,
+                               a.alpha, (int)a.unit);
+        else
+            for(aoclsparse_int l = sg.l0; l < sg.l1; l++)
+                launch_level(a, l);
+    }
+    return aoclsparse_status_success;
+}
+
+// schedule 2: sync-free, a lane per position; one launch over all right-hand sides
+template <typename T>
+static aoclsparse_status launch_lane_per_position(const TrsvLaunch<T> &a)
+{
+    MI355_TRY(a.reset((size_t)a.nrhs + 1));
+    const bool     wide = (long long)a.plan.nnz_tri > 10LL * a.m;
+    const unsigned nblk = (unsigned)((a.m + (wide ? 511 : 1023)) / (wide ? 512 : 1024));
+    for(aoclsparse_int c0 = 0; c0 < a.nrhs; c0 += 65535)
+    {
+        const int nc    = a.nrhs - c0 < 65535 ? a.nrhs - c0 : 65535;
+        RhsGeom   g     = a.geom();
+        g.cols_fast     = nc > 1 && nblk <= 65535u;
+        const dim3 grid = g.cols_fast ? dim3(nc, nblk) : dim3(nblk, nc);
+        with_kt_width<T>(a.kt_bits, [&](auto tsz) {
+            constexpr int TSZ = decltype(tsz)::value;
+            auto          go  = [&](auto block_tag, auto pf_tag) {
+                constexpr int BLOCK = decltype(block_tag)::value, PF = decltype(pf_tag)::value;
+                hipLaunchKernelGGL((trsv_syncfree_kernel<T, BLOCK, PF, TSZ>), grid, dim3(BLOCK), 0, a.s, a.m, a.rowmap, a.pptr, a.pind,
+                                   a.pval, a.diag, a.b + c0 * a.b_off, a.xp + (size_t)c0 * a.m, a.x + c0 * a.x_off, a.alpha,
+                                   (int)a.unit, a.scratch + c0, a.tmo(), g);
+            };
+            wide ? go(int_c<512>{}, int_c<20>{}) : go(int_c<1024>{}, int_c<12>{});
+        });
+    }
+    return aoclsparse_status_success;
+}
+
+// schedule 3: sync-free, one level slice per wavefront (single right-hand side, the reference chain)
+template <typename T>
+static aoclsparse_status launch_slices(const TrsvLaunch<T> &a)
+{
+    if(!a.plan.rows_valid || a.plan.nslices <= 0 || a.nrhs != 1 || a.kt_bits != 0)
+        return aoclsparse_status_internal_error;
+    MI355_TRY(a.reset(2));
+    constexpr int  WV   = 16; // slices per workgroup (4 / 8 measured slower: 2.02 / 1.90 vs 1.69 ms, round 2: not compiled)
+    const unsigned nblk = (unsigned)((a.plan.nslices + WV - 1) / WV);
+    auto           go   = [&](auto pf_tag) {
+        constexpr int PF = decltype(pf_tag)::value;
+        hipLaunchKernelGGL((trsv_slice_kernel<T, WV, PF>), dim3(nblk), dim3(64 * WV), 0, a.s, a.m, a.plan.nslices,
+                           a.plan.slices.template as<aoclsparse_int>(), a.rowmap, a.pptr, a.pind, a.pval, a.diag, a.b, a.xp, a.x,
+                           a.alpha, (int)a.unit, a.scratch, a.tmo(), (int)a.incb, (int)a.incx);
+    };
+    (long long)a.plan.nnz_tri > 10LL * a.m ? go(int_c<20>{}) : go(int_c<8>{});
+    return aoclsparse_status_success;
+}
+
+// The block and chunk kernels are compiled for a few shapes (BS rows per block, EXT external dependencies: their loops are
+// unrolled); the plan's largest block / external list picks one.  f(int_c<BS>, int_c<EXT>).
+template <typename F>
+static aoclsparse_status with_block_shape(const TrsvBlockPlan &bp, F &&f)
+{
+    const bool small_ext = bp.max_ext <= 16, small_bs = bp.max_rows <= 5;
+    return small_ext && small_bs            ? f(int_c<5>{}, int_c<16>{})
+           : bp.max_ext <= 20 && small_bs   ? f(int_c<5>{}, int_c<20>{})
+           : small_ext                      ? f(int_c<TRSV_BLK_ROWS>{}, int_c<16>{})
+           : small_bs                       ? f(int_c<5>{}, int_c<TRSV_BLK_EXT>{})
+                                            : f(int_c<TRSV_BLK_ROWS>{}, int_c<TRSV_BLK_EXT>{});
+}
+template <typename F>
+static aoclsparse_status with_chunk_shape(const TrsvBlockPlan &bp, F &&f)
+{
+    return with_flag(trsv_chunk_bs(bp.max_rows) == 5, [&](auto small_bs) {
+        return with_flag(trsv_chunk_ext(bp.max_ext) == 16, [&](auto small_ext) {
+            return f(int_c<decltype(small_bs)::value ? 5 : TRSV_CHUNK_LANES>{}, int_c<decltype(small_ext)::value ? 16 : TRSV_BLK_EXT>{});
+        });
+    });
+}
+
+constexpr int TRSV_BLK_GATE = 2; // a wavefront starts looking at its dependencies when the block level two below is complete
+
+// schedule 4, the reference chain: trsv_block_kernel
+template <typename T>
+static aoclsparse_status launch_block_chain(const TrsvLaunch<T> &a, unsigned long long *trace)
+{
+    const TrsvBlockPlan &bp = a.plan.blk;
+    return with_block_shape(bp, [&](auto bs_tag, auto ext_tag) {
+        return with_flag(bp.front, [&](auto front_tag) {
+            constexpr int  BS = decltype(bs_tag)::value, EXT = decltype(ext_tag)::value;
+            constexpr bool FRONT = decltype(front_tag)::value;
+            // (the small shapes hold the block in registers and use no LDS)
+            constexpr size_t lds = trsv_blk_slots(BS, EXT) <= TRSV_BLK_REG_SLOTS ? 0 : sizeof(T) * 64 * (size_t)trsv_blk_slots(BS, EXT);
+            static_assert(lds <= 160 * 1024, "LDS of one CU");
+            auto go = [&](auto trace_tag) {
+                constexpr bool TRACE = decltype(trace_tag)::value;
+                if(lds > 64 * 1024)
+                    MI355_TRY((raise_lds_limit<&trsv_block_kernel<T, BS, EXT, FRONT, TRACE>>(160 * 1024)));
+                hipLaunchKernelGGL((trsv_block_kernel<T, BS, EXT, FRONT, TRACE>), a.grid(bp.nslices), dim3(64), lds, a.s, a.m, bp.nslices,
+                                   bp.slices.template as<aoclsparse_int>(), bp.bfirst.template as<aoclsparse_int>(),
+                                   bp.rowmap.template as<aoclsparse_int>(), bp.pptr.template as<aoclsparse_int>(),
+                                   bp.pind.template as<aoclsparse_int>(), bp.pval.template as<T>(), a.diag, a.b, a.xp, a.x, a.alpha,
+                                   (int)a.unit, a.scratch, a.tmo(), (int)a.incb, (int)a.incx, trace, a.scratch + a.nrhs + 1,
+                                   TRSV_BLK_GATE, (int)a.nrhs, a.b_off, a.x_off, (int)bp.nlevels);
+                return aoclsparse_status_success;
+            };
+            if constexpr(std::is_same<T, double>::value) // the traced build exists for double only
+                if(trace)
+                    return go(std::true_type{});
+            return go(std::false_type{});
+        });
+    });
+}
+
+// schedule 4, the KT orders: trsv_block_kt_kernel (run-time KT loops, every block in LDS)
+template <typename T>
+static aoclsparse_status launch_block_kt(const TrsvLaunch<T> &a, unsigned long long *trace)
+{
+    const TrsvBlockPlan &bp = a.plan.blk;
+    if(bp.max_rows > TRSV_BLK_ROWS)
+        return aoclsparse_status_internal_error; // (the plan never builds larger blocks)
+    constexpr int    T256   = std::is_same<T, double>::value ? 4 : 8;
+    constexpr size_t kt_lds = sizeof(T) * 64 * (size_t)(TRSV_BLK_NV + TRSV_BLK_EXT + TRSV_BLK_ROWS);
+    auto             go     = [&](auto tsz_tag) {
+        return with_flag(bp.front, [&](auto front_tag) {
+            constexpr int  TSZ = decltype(tsz_tag)::value;
+            constexpr bool FR  = decltype(front_tag)::value;
+            MI355_TRY((raise_lds_limit<&trsv_block_kt_kernel<T, TSZ, FR>>((int)kt_lds)));
+            hipLaunchKernelGGL((trsv_block_kt_kernel<T, TSZ, FR>), a.grid(bp.nslices), dim3(64), kt_lds, a.s, a.m, bp.nslices,
+                               bp.slices.template as<aoclsparse_int>(), bp.bfirst.template as<aoclsparse_int>(),
+                               bp.rowmap.template as<aoclsparse_int>(), bp.pptr.template as<aoclsparse_int>(),
+                               bp.pind.template as<aoclsparse_int>(), bp.pval.template as<T>(), a.diag, a.b, a.xp, a.x, a.alpha,
+                               (int)a.unit, a.scratch, a.tmo(), (int)a.incb, (int)a.incx, a.scratch + a.nrhs + 1, TRSV_BLK_GATE,
+                               (int)a.nrhs, a.b_off, a.x_off, (int)bp.nlevels, trace);
+            return aoclsparse_status_success;
+        });
+    };
+    return a.kt_bits == 256 ? go(int_c<T256>{}) : go(int_c<2 * T256>{});
+}
+
+// schedule 4: sync-free, one lane per block of chained rows (plan.blk has its own level-ordered copy of the triangle)
+template <typename T>
+static aoclsparse_status launch_blocks(const TrsvLaunch<T> &a)
+{
+    const TrsvBlockPlan &bp = a.plan.blk;
+    if(!bp.valid || !a.fits_grid(bp.nslices))
+        return aoclsparse_status_internal_error;
+    // scratch: one ticket per column, the timeout word, then one finished-slices counter per (column, block level)
+    MI355_TRY(a.reset((size_t)a.nrhs + 1 + (size_t)a.nrhs * bp.nlevels, a.total() + TRSV_XP_PAD - 1));
+    // the trace: per slice, the 100 MHz clock after the ticket, when the dependencies were all in, at the end, the slice's block
+    // level, after the LDS reads, after the external FMAs (6 x u64 per slice; tools/trsv_trace.py)
+    unsigned long long     *trace = trace_alloc(std::is_same<T, double>::value, 6, (size_t)bp.nslices);
+    const aoclsparse_status st    = a.kt_bits != 0 ? launch_block_kt(a, trace) : launch_block_chain(a, trace);
+    trace_dump(a.s, trace, 6, (size_t)bp.nslices, "[trsv trace] blocks %d slices %d levels %d max_rows %d max_ext %d\n", (int)bp.nblocks,
+               (int)bp.nslices, (int)bp.nlevels, bp.max_rows, bp.max_ext);
+    return st;
+}
+
+// schedule 5: two levels, a workgroup per chunk of consecutive blocks, hand-offs inside a chunk through LDS (trsv_chunk_kernel;
+// the reference chain only)
+template <typename T>
+static aoclsparse_status launch_chunks(const TrsvLaunch<T> &a)
+{
+    const TrsvBlockPlan &bp = a.plan.blk;
+    const TrsvChunkPlan &cp = bp.chunk;
+    if(!bp.valid || !cp.valid || a.kt_bits != 0 || !a.fits_grid(cp.nchunks))
+        return aoclsparse_status_internal_error;
+    MI355_TRY(a.reset((size_t)a.nrhs + 1));
+    static const int dbg = getenv("AOCLSPARSE_MI355_TRSV_DBG") ? atoi(getenv("AOCLSPARSE_MI355_TRSV_DBG")) : 0;
+    // the trace: per step, the 100 MHz clock when its wavefront took it, when its first look at the dependencies had landed, when
+    // all of them were in, at the end; then per step its chunk and block level (tools/trsv_chunk_trace.py)
+    unsigned long long     *trace = trace_alloc(a.nrhs == 1, 8, (size_t)cp.nsteps);
+    const aoclsparse_status st    = with_chunk_shape(bp, [&](auto bs_tag, auto ext_tag) {
+        constexpr int BS = decltype(bs_tag)::value, EXT = decltype(ext_tag)::value;
+        const size_t  stage_bytes = (size_t)(TRSV_CHUNK_WAVES - 1) * ((size_t)trsv_chunk_pcap(BS, EXT) * sizeof(T) + 9 * (size_t)EXT * 4);
+        const size_t  lds         = 16 + stage_bytes + sizeof(typename tag<T>::bits) * ((size_t)cp.max_rows + 1 + 64);
+        if(lds > 160 * 1024)
+            return aoclsparse_status_internal_error; // (the plan caps a chunk's rows)
+        return with_flag(a.unit, [&](auto unit_tag) {
+            return with_flag(bp.front, [&](auto front_tag) {
+                constexpr bool UNIT = decltype(unit_tag)::value, FRONT = decltype(front_tag)::value;
+                MI355_TRY((raise_lds_limit<&trsv_chunk_kernel<T, EXT, BS, UNIT, FRONT>>(160 * 1024)));
+                hipLaunchKernelGGL((trsv_chunk_kernel<T, EXT, BS, UNIT, FRONT>), a.grid(cp.nchunks), dim3(64 * TRSV_CHUNK_WAVES), lds, a.s,
+                                   a.m, std::max<aoclsparse_int>(a.plan.nnz_tri, 1), cp.nchunks,
+                                   reinterpret_cast<const int4 *>(cp.steps.template as<aoclsparse_int>()),
+                                   cp.cptr.template as<aoclsparse_int>(), bp.rowmap.template as<aoclsparse_int>(),
+                                   bp.pptr.template as<aoclsparse_int>(), bp.pval.template as<T>(), cp.eptr.template as<aoclsparse_int>(),
+                                   cp.cind.template as<aoclsparse_int>(), cp.hind.template as<aoclsparse_int>(), a.diag, a.b, a.xp, a.x,
+                                   a.alpha, a.scratch, a.tmo(), (int)a.incb, (int)a.incx, (int)a.nrhs, a.b_off, a.x_off, trace, dbg);
+                return aoclsparse_status_success;
+            });
+        });
+    });
+    trace_dump(a.s, trace, 8, (size_t)cp.nsteps, "[trsv chunk trace] chunks %d steps %d lds slots %d model %.1f us (block schedule %.1f us)\n",
+               (int)cp.nchunks, (int)cp.nsteps, (int)cp.max_rows, cp.model_us, cp.model_block_us);
+    return st;
+}
+
+// `schedule` is what resolve_trsv_schedule returned for this plan and these arguments: one that the plan cannot serve (4 without
+// a block plan, 0 / 1 / 3 without the row layout, 5 with kt_bits, ...) is an internal error here, never replaced by another.
 template <typename T>
 aoclsparse_status launch_trsv(hipStream_t s, int schedule, bool unit, T alpha, aoclsparse_int m,
                               const TrsvPlan &plan, const T *diag, const T *b, T *x, T *xp, unsigned int *scratch,
@@ -1825,324 +2175,28 @@ aoclsparse_status launch_trsv(hipStream_t s, int schedule, bool unit, T alpha, a
 {
     if(m <= 0 || nrhs <= 0)
         return aoclsparse_status_success;
-    // kt_bits: 0 = the reference chain (ref_trsv_*); 256 / 512 = the KT kernels' order for that vector width (kid 1/2 / 3).
-    // Served by trsv_block_kt_kernel when the triangle has a block plan (schedule 4), else by the per-level launches and the
-    // lane-per-position sync-free kernel.
-    constexpr int T256 = std::is_same<T, double>::value ? 4 : 8;
-    if(kt_bits != 0 && kt_bits != 256 && kt_bits != 512)
+    if((kt_bits != 0 && kt_bits != 256 && kt_bits != 512) || (!plan.rows_valid && !plan.blk.valid))
         return aoclsparse_status_internal_error;
-    // (the block plan serves the KT orders through trsv_block_kt_kernel; without it: per-level launches or lane per position)
-    if(kt_bits != 0 && schedule == 5)
-        schedule = 4; // (the two-level kernel serves the reference chain only)
-    if(kt_bits != 0 && schedule != 0 && !(schedule == 4 && plan.blk.valid))
-        schedule = 2;
-    // the level-ordered row layout, or -- when only the block plan was built (TrsvPlan::rows_valid == false) -- the block
-    // plan's layout: also a topological order of the rows, which is all the lane-per-position kernel (schedule 2) needs
-    const bool            rows   = plan.rows_valid;
-    const aoclsparse_int *rowmap = rows ? plan.rowmap.as<aoclsparse_int>() : plan.blk.rowmap.as<aoclsparse_int>();
-    const aoclsparse_int *pptr   = rows ? plan.pptr.as<aoclsparse_int>() : plan.blk.pptr.as<aoclsparse_int>();
-    const aoclsparse_int *pind   = rows ? plan.pind.as<aoclsparse_int>() : plan.blk.pind.as<aoclsparse_int>();
-    const T              *pval   = rows ? plan.pval.as<T>() : plan.blk.pval.as<T>();
-    if(!rows && !plan.blk.valid)
-        return aoclsparse_status_internal_error;
-    RhsGeom               g{b_off, x_off, incb, incx, 0};
-    if(schedule == 1 && (nrhs != 1 || incb != 1 || incx != 1))
-        schedule = 2; // the single-workgroup runs of the hybrid schedule are single-RHS, unit stride
-    // (several right-hand sides: the column is grid dimension x, the slice y <= 65,535; index arithmetic in int)
-    if(schedule == 5
-       && (!plan.blk.valid || !plan.blk.chunk.valid || kt_bits != 0
-           || (nrhs > 1 && (plan.blk.chunk.nchunks > 65535 || (long long)m * nrhs + TRSV_XP_PAD >= (1LL << 31)))))
-        schedule = 4;
-    if(schedule == 4
-       && (!plan.blk.valid || (nrhs > 1 && (plan.blk.nslices > 65535 || (long long)m * nrhs + TRSV_XP_PAD >= (1LL << 31)))))
-        schedule = 3;
-    if(schedule == 3 && (nrhs != 1 || plan.nslices <= 0 || !rows))
-        schedule = 2; // the slice kernel is single-RHS; trsm keeps the lane-per-position kernel
-    if((schedule == 0 || schedule == 1) && !rows)
-        return aoclsparse_status_internal_error; // the caller asks for the row layout before choosing these (trsv_api.cpp)
-    auto level_launch = [&](aoclsparse_int l) {
-        const aoclsparse_int first = plan.level_ptr[l], count = plan.level_ptr[l + 1] - first;
-        const int            bs = count >= 256 ? 256 : 64;
-        for(aoclsparse_int c0 = 0; c0 < nrhs; c0 += 65535)
-        {
-            const int nc = nrhs - c0 < 65535 ? nrhs - c0 : 65535;
-#define MI355_LEVEL_ARGS first, count, m, rowmap, pptr, pind, pval, diag, b + c0 * b_off, xp + (size_t)c0 * m, x + c0 * x_off, alpha, (int)unit, g
-            if(kt_bits == 0)
-                hipLaunchKernelGGL((trsv_level_kernel<T, 0>), dim3((count + bs - 1) / bs, nc), dim3(bs), 0, s, MI355_LEVEL_ARGS);
-            else if(kt_bits == 256)
-                hipLaunchKernelGGL((trsv_level_kernel<T, T256>), dim3((count + bs - 1) / bs, nc), dim3(bs), 0, s, MI355_LEVEL_ARGS);
-            else
-                hipLaunchKernelGGL((trsv_level_kernel<T, 2 * T256>), dim3((count + bs - 1) / bs, nc), dim3(bs), 0, s, MI355_LEVEL_ARGS);
-#undef MI355_LEVEL_ARGS
-        }
-    };
-    if(schedule == 0)
+    const bool            rows = plan.rows_valid;
+    const TrsvBlockPlan  &bp   = plan.blk;
+    const TrsvLaunch<T>   a{s, plan, m,
+                          rows ? plan.rowmap.as<aoclsparse_int>() : bp.rowmap.as<aoclsparse_int>(),
+                          rows ? plan.pptr.as<aoclsparse_int>() : bp.pptr.as<aoclsparse_int>(),
+                          rows ? plan.pind.as<aoclsparse_int>() : bp.pind.as<aoclsparse_int>(),
+                          rows ? plan.pval.as<T>() : bp.pval.as<T>(),
+                          diag, b, x, xp, scratch, timeout_word, alpha, unit, nrhs, b_off, x_off, incb, incx, kt_bits};
+    aoclsparse_status st = aoclsparse_status_internal_error;
+    switch(schedule)
     {
-        for(aoclsparse_int l = 0; l < plan.nlevels; l++)
-            level_launch(l);
+    case 0: st = launch_levels(a); break;
+    case 1: st = launch_hybrid(a); break;
+    case 2: st = launch_lane_per_position(a); break;
+    case 3: st = launch_slices(a); break;
+    case 4: st = launch_blocks(a); break;
+    case 5: st = launch_chunks(a); break;
     }
-    else if(schedule == 1)
-    {
-        for(const TrsvSegment &sg : plan.segments)
-        {
-            if(sg.narrow)
-                hipLaunchKernelGGL((trsv_multilevel_kernel<T>), dim3(1), dim3(TRSV_NARROW), 0, s, sg.l0, sg.l1,
-                                   plan.levels.as<aoclsparse_int>(), rowmap, pptr, pind, pval, diag, b, xp, x, alpha,
-                                   (int)unit);
-            else
-                for(aoclsparse_int l = sg.l0; l < sg.l1; l++)
-                    level_launch(l);
-        }
-    }
-    else if(schedule == 4)
-    {
-        // sync-free, one lane per block of chained rows (plan.blk has its own level-ordered copy of the triangle)
-        const TrsvBlockPlan &bp = plan.blk;
-        // scratch: one ticket per column, the timeout word, then one finished-slices counter per (column, block level)
-        const long long total = (long long)m * nrhs;
-        MI355_HIP_TRY(hipMemsetAsync(scratch, 0, ((size_t)nrhs + 1 + (size_t)nrhs * bp.nlevels) * sizeof(unsigned int), s));
-        hipLaunchKernelGGL((trsv_fill_tag_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, xp, total,
-                           total + TRSV_XP_PAD - 1);
-        constexpr int gate = 2; // a wavefront starts looking at its dependencies when the block level two below is complete
-        // diagnostic: AOCLSPARSE_MI355_TRSV_TRACE=<file> dumps, per slice, the 100 MHz clock after the ticket, when the
-        // dependencies were all in, at the end, the slice's block level, after the LDS reads, after the external FMAs (6 x u64 per slice; tools/trsv_trace.py)
-        static const char  *trace_path = getenv("AOCLSPARSE_MI355_TRSV_TRACE");
-        unsigned long long *trace      = nullptr;
-        if(trace_path && std::is_same<T, double>::value
-           && hipMalloc(&trace, sizeof(unsigned long long) * 6 * (size_t)bp.nslices) != hipSuccess)
-            trace = nullptr;
-        aoclsparse_status lst = aoclsparse_status_success;
-        if(kt_bits != 0)
-        {
-            if(bp.max_rows > TRSV_BLK_ROWS)
-                return aoclsparse_status_internal_error; // (the plan never builds larger blocks)
-            const dim3 grid = nrhs > 1 ? dim3((unsigned)nrhs, (unsigned)bp.nslices) : dim3((unsigned)bp.nslices);
-#define MI355_BLKKT_ARGS                                                                                                      \
-    m, bp.nslices, bp.slices.as<aoclsparse_int>(), bp.bfirst.as<aoclsparse_int>(), bp.rowmap.as<aoclsparse_int>(),              \
-        bp.pptr.as<aoclsparse_int>(), bp.pind.as<aoclsparse_int>(), bp.pval.as<T>(), diag, b, xp, x, alpha, (int)unit, scratch,   \
-        timeout_word ? timeout_word : scratch + nrhs, (int)incb, (int)incx, scratch + nrhs + 1, gate, (int)nrhs, b_off, x_off,     \
-        (int)bp.nlevels, trace
-            constexpr size_t kt_lds = sizeof(T) * 64 * (size_t)(TRSV_BLK_NV + TRSV_BLK_EXT + TRSV_BLK_ROWS);
-            auto go_kt = [&](auto tsz_tag, auto front_tag) {
-                constexpr int  TSZ = decltype(tsz_tag)::value;
-                constexpr bool FR  = decltype(front_tag)::value;
-                static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&trsv_block_kt_kernel<T, TSZ, FR>),
-                                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kt_lds);
-                if(raised != hipSuccess)
-                    return aoclsparse_status_internal_error;
-                hipLaunchKernelGGL((trsv_block_kt_kernel<T, TSZ, FR>), grid, dim3(64), kt_lds, s, MI355_BLKKT_ARGS);
-                return aoclsparse_status_success;
-            };
-            if(kt_bits == 256)
-                lst = bp.front ? go_kt(std::integral_constant<int, T256>{}, std::true_type{})
-                               : go_kt(std::integral_constant<int, T256>{}, std::false_type{});
-            else
-                lst = bp.front ? go_kt(std::integral_constant<int, 2 * T256>{}, std::true_type{})
-                               : go_kt(std::integral_constant<int, 2 * T256>{}, std::false_type{});
-            if(lst != aoclsparse_status_success)
-                return lst;
-#undef MI355_BLKKT_ARGS
-            MI355_HIP_TRY(hipGetLastError());
-        }
-        else
-        {
-        auto go_form = [&](auto bs_tag, auto ext_tag, auto front_tag) {
-            constexpr int    BS = decltype(bs_tag)::value, EXT = decltype(ext_tag)::value;
-            constexpr bool   FRONT = decltype(front_tag)::value;
-            // (the small shapes hold the block in registers and use no LDS)
-            constexpr size_t need = trsv_blk_slots(BS, EXT) <= TRSV_BLK_REG_SLOTS ? 0 : sizeof(T) * 64 * (size_t)trsv_blk_slots(BS, EXT);
-            static_assert(need <= 160 * 1024, "LDS of one CU");
-            const size_t     lds  = std::min<size_t>(need, 160 * 1024);
-            if(lds > 64 * 1024)
-            {
-                static const hipError_t raised = hipFuncSetAttribute(
-                    reinterpret_cast<const void *>(&trsv_block_kernel<T, BS, EXT, FRONT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if(raised != hipSuccess)
-                    return aoclsparse_status_internal_error;
-            }
-            const dim3 grid = nrhs > 1 ? dim3((unsigned)nrhs, (unsigned)bp.nslices) : dim3((unsigned)bp.nslices);
-#define MI355_BLK_ARGS                                                                                                       \
-    m, bp.nslices, bp.slices.as<aoclsparse_int>(), bp.bfirst.as<aoclsparse_int>(), bp.rowmap.as<aoclsparse_int>(),              \
-        bp.pptr.as<aoclsparse_int>(), bp.pind.as<aoclsparse_int>(), bp.pval.as<T>(), diag, b, xp, x, alpha, (int)unit, scratch,   \
-        timeout_word ? timeout_word : scratch + nrhs, (int)incb, (int)incx, trace, scratch + nrhs + 1, gate, (int)nrhs, b_off,     \
-        x_off, (int)bp.nlevels
-            if constexpr(std::is_same<T, double>::value) // the traced build exists for double only
-            {
-                if(trace)
-                {
-                    if(lds > 64 * 1024)
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&trsv_block_kernel<T, BS, EXT, FRONT, true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    hipLaunchKernelGGL((trsv_block_kernel<T, BS, EXT, FRONT, true>), grid, dim3(64), lds, s, MI355_BLK_ARGS);
-                    return aoclsparse_status_success;
-                }
-            }
-            hipLaunchKernelGGL((trsv_block_kernel<T, BS, EXT, FRONT>), grid, dim3(64), lds, s, MI355_BLK_ARGS);
-#undef MI355_BLK_ARGS
-            return aoclsparse_status_success;
-        };
-        auto go = [&](auto bs_tag, auto ext_tag) {
-            return bp.front ? go_form(bs_tag, ext_tag, std::true_type{}) : go_form(bs_tag, ext_tag, std::false_type{});
-        };
-        using std::integral_constant;
-        // shapes by the plan's largest block / external list (the loops over rows and external entries are unrolled)
-        const bool small_ext = bp.max_ext <= 16, small_bs = bp.max_rows <= 5;
-        lst = small_ext && small_bs ? go(integral_constant<int, 5>{}, integral_constant<int, 16>{})
-              : bp.max_ext <= 20 && small_bs ? go(integral_constant<int, 5>{}, integral_constant<int, 20>{})
-              : small_ext           ? go(integral_constant<int, TRSV_BLK_ROWS>{}, integral_constant<int, 16>{})
-              : small_bs            ? go(integral_constant<int, 5>{}, integral_constant<int, TRSV_BLK_EXT>{})
-                                    : go(integral_constant<int, TRSV_BLK_ROWS>{}, integral_constant<int, TRSV_BLK_EXT>{});
-        }
-        if(trace)
-        {
-            std::vector<unsigned long long> host(6 * (size_t)bp.nslices);
-            if(hipStreamSynchronize(s) == hipSuccess
-               && hipMemcpy(host.data(), trace, sizeof(unsigned long long) * host.size(), hipMemcpyDeviceToHost) == hipSuccess)
-                if(FILE *f = fopen(trace_path, "wb"))
-                {
-                    fwrite(host.data(), sizeof(unsigned long long), host.size(), f);
-                    fclose(f);
-                }
-            fprintf(stderr, "[trsv trace] blocks %d slices %d levels %d max_rows %d max_ext %d\n", (int)bp.nblocks, (int)bp.nslices,
-                    (int)bp.nlevels, bp.max_rows, bp.max_ext);
-            (void)hipFree(trace);
-        }
-        if(lst != aoclsparse_status_success)
-            return lst;
-    }
-    else if(schedule == 5)
-    {
-        // two levels: a workgroup per chunk of consecutive blocks, hand-offs inside a chunk through LDS (trsv_chunk_kernel)
-        const TrsvBlockPlan &bp = plan.blk;
-        const TrsvChunkPlan &cp = bp.chunk;
-        const long long      total = (long long)m * nrhs;
-        MI355_HIP_TRY(hipMemsetAsync(scratch, 0, ((size_t)nrhs + 1) * sizeof(unsigned int), s));
-        hipLaunchKernelGGL((trsv_fill_tag_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, xp, total);
-        const bool   small_ext5 = bp.max_ext <= 16, small_bs5 = bp.max_rows <= 5;
-        const size_t stage_bytes = (size_t)(TRSV_CHUNK_WAVES - 1)
-                               * ((size_t)trsv_chunk_pcap(small_bs5 ? 5 : TRSV_CHUNK_LANES, small_ext5 ? 16 : TRSV_BLK_EXT) * sizeof(T)
-                                  + 9 * (size_t)(small_ext5 ? 16 : TRSV_BLK_EXT) * 4);
-        const size_t lds = 16 + stage_bytes + sizeof(typename tag<T>::bits) * ((size_t)cp.max_rows + 1 + 64);
-        if(lds > 160 * 1024)
-            return aoclsparse_status_internal_error; // (the plan caps a chunk's rows)
-        // diagnostic: AOCLSPARSE_MI355_TRSV_TRACE=<file> dumps, per step, the 100 MHz clock when its wavefront took it, when its first
-        // look at the dependencies had landed, when all of them were in, at the end; then per step its chunk and block level
-        // (tools/trsv_chunk_trace.py)
-        static const int    dbg5        = getenv("AOCLSPARSE_MI355_TRSV_DBG") ? atoi(getenv("AOCLSPARSE_MI355_TRSV_DBG")) : 0;
-        static const char  *trace_path5 = getenv("AOCLSPARSE_MI355_TRSV_TRACE");
-        unsigned long long *trace5      = nullptr;
-        if(trace_path5 && nrhs == 1 && hipMalloc(&trace5, sizeof(unsigned long long) * 8 * (size_t)cp.nsteps) != hipSuccess)
-            trace5 = nullptr;
-        auto go_form = [&](auto ext_tag, auto bs_tag, auto unit_tag, auto front_tag) {
-            constexpr int  EXT = decltype(ext_tag)::value, BS = decltype(bs_tag)::value;
-            constexpr bool UNIT = decltype(unit_tag)::value, FRONT = decltype(front_tag)::value;
-            static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&trsv_chunk_kernel<T, EXT, BS, UNIT, FRONT>),
-                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if(raised != hipSuccess)
-                return aoclsparse_status_internal_error;
-            const dim3 grid = nrhs > 1 ? dim3((unsigned)nrhs, (unsigned)cp.nchunks) : dim3((unsigned)cp.nchunks);
-            hipLaunchKernelGGL((trsv_chunk_kernel<T, EXT, BS, UNIT, FRONT>), grid, dim3(64 * TRSV_CHUNK_WAVES), lds, s, m,
-                               std::max<aoclsparse_int>(plan.nnz_tri, 1), cp.nchunks,
-                               reinterpret_cast<const int4 *>(cp.steps.as<aoclsparse_int>()), cp.cptr.as<aoclsparse_int>(),
-                               bp.rowmap.as<aoclsparse_int>(), bp.pptr.as<aoclsparse_int>(), bp.pval.as<T>(),
-                               cp.eptr.as<aoclsparse_int>(), cp.cind.as<aoclsparse_int>(), cp.hind.as<aoclsparse_int>(), diag, b, xp, x,
-                               alpha, scratch, timeout_word ? timeout_word : scratch + nrhs, (int)incb, (int)incx, (int)nrhs, b_off,
-                               x_off, trace5, dbg5);
-            return aoclsparse_status_success;
-        };
-        auto go = [&](auto ext_tag, auto bs_tag) {
-            if(bp.front)
-                return unit ? go_form(ext_tag, bs_tag, std::true_type{}, std::true_type{})
-                            : go_form(ext_tag, bs_tag, std::false_type{}, std::true_type{});
-            return unit ? go_form(ext_tag, bs_tag, std::true_type{}, std::false_type{})
-                        : go_form(ext_tag, bs_tag, std::false_type{}, std::false_type{});
-        };
-        using std::integral_constant;
-        const bool              small_ext = bp.max_ext <= 16, small_bs = bp.max_rows <= 5;
-        const aoclsparse_status lst
-            = small_ext && small_bs ? go(integral_constant<int, 16>{}, integral_constant<int, 5>{})
-              : small_ext           ? go(integral_constant<int, 16>{}, integral_constant<int, TRSV_CHUNK_LANES>{})
-              : small_bs            ? go(integral_constant<int, TRSV_BLK_EXT>{}, integral_constant<int, 5>{})
-                                    : go(integral_constant<int, TRSV_BLK_EXT>{}, integral_constant<int, TRSV_CHUNK_LANES>{});
-        if(trace5)
-        {
-            std::vector<unsigned long long> host(8 * (size_t)cp.nsteps);
-            if(hipStreamSynchronize(s) == hipSuccess
-               && hipMemcpy(host.data(), trace5, sizeof(unsigned long long) * host.size(), hipMemcpyDeviceToHost) == hipSuccess)
-                if(FILE *f = fopen(trace_path5, "wb"))
-                {
-                    fwrite(host.data(), sizeof(unsigned long long), host.size(), f);
-                    fclose(f);
-                }
-            fprintf(stderr, "[trsv chunk trace] chunks %d steps %d lds slots %d model %.1f us (block schedule %.1f us)\n", (int)cp.nchunks,
-                    (int)cp.nsteps, (int)cp.max_rows, cp.model_us, cp.model_block_us);
-            (void)hipFree(trace5);
-        }
-        if(lst != aoclsparse_status_success)
-            return lst;
-    }
-    else if(schedule == 3)
-    {
-        // sync-free, one level slice per wavefront (single right-hand side)
-        MI355_HIP_TRY(hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned int), s));
-        hipLaunchKernelGGL((trsv_fill_tag_kernel<T>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, xp, (long long)m);
-        const bool  wide = (long long)plan.nnz_tri > 10LL * m;
-        constexpr int wv = 16; // slices per workgroup (4 / 8 measured slower: 2.02 / 1.90 vs 1.69 ms, round 2)
-        const aoclsparse_int *sl = plan.slices.as<aoclsparse_int>();
-        auto go = [&](auto wv_tag, auto pf_tag) {
-            constexpr int WV = decltype(wv_tag)::value, PF = decltype(pf_tag)::value;
-            const unsigned nblk = (unsigned)((plan.nslices + WV - 1) / WV);
-            hipLaunchKernelGGL((trsv_slice_kernel<T, WV, PF>), dim3(nblk), dim3(64 * WV), 0, s, m, plan.nslices, sl, rowmap,
-                               pptr, pind, pval, diag, b, xp, x, alpha, (int)unit, scratch, timeout_word ? timeout_word : scratch + 1,
-                               (int)incb, (int)incx);
-        };
-        using I4 = std::integral_constant<int, 4>;
-        using I8 = std::integral_constant<int, 8>;
-        using I16 = std::integral_constant<int, 16>;
-        using PW = std::integral_constant<int, 20>;
-        using PN = std::integral_constant<int, 8>;
-        if(wide)
-            wv == 4 ? go(I4{}, PW{}) : wv == 8 ? go(I8{}, PW{}) : go(I16{}, PW{});
-        else
-            wv == 4 ? go(I4{}, PN{}) : wv == 8 ? go(I8{}, PN{}) : go(I16{}, PN{});
-    }
-    else
-    {
-        // sync-free: tag xp, reset tickets + timeout word, one launch over all right-hand sides
-        MI355_HIP_TRY(hipMemsetAsync(scratch, 0, ((size_t)nrhs + 1) * sizeof(unsigned int), s));
-        const long long total = (long long)m * nrhs;
-        hipLaunchKernelGGL((trsv_fill_tag_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, xp,
-                           total);
-        unsigned int *tmo = timeout_word ? timeout_word : scratch + nrhs;
-        for(aoclsparse_int c0 = 0; c0 < nrhs; c0 += 65535)
-        {
-            const int nc = nrhs - c0 < 65535 ? nrhs - c0 : 65535;
-            const bool     wide = (long long)plan.nnz_tri > 10LL * m;
-            const unsigned nblk = (unsigned)((m + (wide ? 511 : 1023)) / (wide ? 512 : 1024));
-            g.cols_fast         = nc > 1 && nblk <= 65535u;
-            const dim3 grid     = g.cols_fast ? dim3(nc, nblk) : dim3(nblk, nc);
-#define MI355_SF_ARGS m, rowmap, pptr, pind, pval, diag, b + c0 * b_off, xp + (size_t)c0 * m, x + c0 * x_off, alpha, (int)unit, scratch + c0, tmo, g
-            if(kt_bits == 256)
-            {
-                if(wide)
-                    hipLaunchKernelGGL((trsv_syncfree_kernel<T, 512, 20, T256>), grid, dim3(512), 0, s, MI355_SF_ARGS);
-                else
-                    hipLaunchKernelGGL((trsv_syncfree_kernel<T, 1024, 12, T256>), grid, dim3(1024), 0, s, MI355_SF_ARGS);
-            }
-            else if(kt_bits == 512)
-            {
-                if(wide)
-                    hipLaunchKernelGGL((trsv_syncfree_kernel<T, 512, 20, 2 * T256>), grid, dim3(512), 0, s, MI355_SF_ARGS);
-                else
-                    hipLaunchKernelGGL((trsv_syncfree_kernel<T, 1024, 12, 2 * T256>), grid, dim3(1024), 0, s, MI355_SF_ARGS);
-            }
-            else if(wide)
-                hipLaunchKernelGGL((trsv_syncfree_kernel<T, 512, 20>), grid, dim3(512), 0, s, MI355_SF_ARGS);
-            else
-                hipLaunchKernelGGL((trsv_syncfree_kernel<T, 1024, 12>), grid, dim3(1024), 0, s, MI355_SF_ARGS);
-#undef MI355_SF_ARGS
-        }
-    }
+    if(st != aoclsparse_status_success)
+        return st;
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }

@@ -276,7 +276,10 @@ typedef struct aoclsparse_mi355_trsv_info_
     aoclsparse_int blocks, block_levels; /* blocks of chained rows (0: no block plan) and their dependency levels */
     aoclsparse_int chunks, steps, lds_slots; /* two-level schedule (0: not built): chunks of consecutive blocks, steps, LDS words of the largest chunk */
     aoclsparse_int model_chunk_us, model_block_us; /* plan-time estimates of the two-level / the lane-per-block schedule */
-    aoclsparse_int schedule; /* the schedule a solve with the reference chain runs now (set_trsv_schedule included) */
+    /* what a single-RHS, unit-stride, kid-0 solve runs now (set_trsv_schedule included): the schedule the solve itself resolves,
+     * every fallback applied (4 forced on a triangle without a block plan reads 3 or 2); other strides, right-hand sides or kids
+     * may run another one */
+    aoclsparse_int schedule;
     aoclsparse_int slices, slice_fan_in_permille; /* lane-per-block schedule: wavefronts (slices of <= 64 blocks of one level; 32 where
                                                      1000 * the producer slices a slice of 64 waits for, on average, exceeds 8000) */
 } aoclsparse_mi355_trsv_info;

@@ -527,7 +527,7 @@ def test_row_group_csrmm_with_the_groups_band_dealt_to_the_xcds_same_bits(which)
 def test_lane_per_block_trsv_on_an_irregular_numbering_narrow_slices_and_sorted_levels():
     """The shell-like mesh with a tenth of its couplings dropped and its nodes renumbered at random inside windows of 256 (a small
     instance of the unstructured stand-in): 5-row blocks on up to 20 dependencies, slices that wait for many producer slices -- the plan
-    then packs 32 blocks per wavefront and orders the blocks of a level by their last dependency (trsv_api.cpp).  None of that may touch
+    then packs 32 blocks per wavefront and orders the blocks of a level by their last dependency (trsv_plan.cpp).  None of that may touch
     a row's chain: ref_trsv_*'s bits (trsv_kr.hpp:57-75) on every triangle, unit and non-unit, on the lane-per-block schedule, on the
     automatic one, and with a pinned KT kid."""
     from test_gpu_trsv_blocks import VARIANTS

@@ -425,3 +425,77 @@ def test_block_chains_under_random_symmetric_permutations(seed):
         assert np.array_equal(got, ref), (seed, what, int((got != ref).sum()))
 
     solve_all(m, Ap.indptr.astype(np.int32), Ap.indices.astype(np.int32), Ap.data.copy(), same)
+
+
+# --------------------------------------------------------------------------------------------------
+# the reported schedule is the one that runs (triangles without a block plan)
+# --------------------------------------------------------------------------------------------------
+def level_slices(m, rp, ci, upper):
+    """(levels, level slices of <= 64 rows) of the strict lower / upper triangle of a sorted CSR pattern"""
+    level = np.zeros(m, dtype=np.int64)
+    for i in (range(m - 1, -1, -1) if upper else range(m)):
+        cols = ci[rp[i]:rp[i + 1]]
+        deps = cols[cols > i] if upper else cols[cols < i]
+        level[i] = level[deps].max() + 1 if len(deps) else 0
+    width = np.bincount(level)
+    return len(width), int(((width + 63) // 64).sum())
+
+
+@pytest.fixture(scope="module")
+def unblocked():
+    """the ILU(0) factor of the 40 x 40 5-point Laplacian (79 levels in 79 slices, 79 * 16 <= m: packed) and a 200-row unit-lower
+    bidiagonal (200 levels of one row: not packed); neither has chains to block.  The oracle's solutions, checked on the CPU."""
+    from util import laplace5
+
+    m, rp, ci, v = laplace5(40)
+    st, lu, _ = oracle.dilu0(m, 0, rp, ci, v)
+    assert st == 0 and m == 1600
+    assert level_slices(m, rp, ci, False) == (79, 79) and level_slices(m, rp, ci, True) == (79, 79)
+    o = oracle.dcsr_optimize(m, m, len(lu), 0, rp, ci, lu)
+    b = np.random.default_rng(21).uniform(-1, 1, m)
+    st_l, xl = oracle.dtrsv("l", 1.0, m, 0, lu, ci, rp, o["idiag"], b, True)
+    st_u, xu = oracle.dtrsv("u", 1.0, m, 0, lu, ci, rp, o["iurow"], b, False)
+    assert st_l == 0 and st_u == 0 and np.isfinite(xl).all() and np.isfinite(xu).all()
+    n = 200
+    brp = np.concatenate([[0], np.arange(1, 2 * n, 2)]).astype(np.int32)
+    bci = np.concatenate([[0], np.stack([np.arange(n - 1), np.arange(1, n)], axis=1).ravel()]).astype(np.int32)
+    bv = np.ones(2 * n - 1)
+    bv[1::2] = np.random.default_rng(22).uniform(-1, 1, n - 1)
+    assert level_slices(n, brp, bci, False) == (200, 200)
+    bo = oracle.dcsr_optimize(n, n, len(bv), 0, brp, bci, bv)
+    bb = np.random.default_rng(23).uniform(-1, 1, n)
+    st_b, xb = oracle.dtrsv("l", 1.0, n, 0, bv, bci, brp, bo["idiag"], bb, True)
+    assert st_b == 0 and np.isfinite(xb).all()
+    return {"lap": (m, rp, ci, lu, b, xl, xu), "bidiag": (n, brp, bci, bv, bb, xb)}
+
+
+def solve_and_report(A, m, fill, unit, b):
+    d = P.Descr(mtype=P.TYPE_TRIANGULAR, fill=fill, diag=P.DIAG_UNIT if unit else P.DIAG_NON_UNIT)
+    x = dev(np.full(m, 7.0))
+    assert P.dtrsv(P.OP_NONE, 1.0, A, d, dev(b), x) == 0
+    torch.cuda.synchronize()
+    assert L.aoclsparse_mi355_trsv_status(A.h) == 0
+    info = A.trsv_info(fill)
+    print("trsv_info: levels %d blocks %d slices %d schedule %d" % (info.levels, info.blocks, info.slices, info.schedule))
+    return x.cpu().numpy(), info
+
+
+def test_reported_schedule_is_the_resolved_one_without_a_block_plan(unblocked):
+    """aoclsparse_mi355_get_trsv_info reports what a single-RHS, unit-stride, kid-0 solve runs: the slice kernel (3) on a packed
+    triangle without a block plan -- automatic, and with the block schedule (4) forced --, the lane-per-position kernel (2) on
+    a deep chain; the bits of the serial chain either way."""
+    from util import trsv_schedule
+
+    m, rp, ci, lu, b, xl, xu = unblocked["lap"]
+    A = P.Matrix(0, m, m, rp, ci, lu)
+    x, info = solve_and_report(A, m, P.FILL_LOWER, True, b)
+    assert np.array_equal(x, xl) and (info.levels, info.blocks, info.schedule) == (79, 0, 3), info.schedule
+    x, info = solve_and_report(A, m, P.FILL_UPPER, False, b)
+    assert np.array_equal(x, xu) and (info.levels, info.blocks, info.schedule) == (79, 0, 3), info.schedule
+    with trsv_schedule(P, 4):
+        x, info = solve_and_report(A, m, P.FILL_LOWER, True, b)
+    assert np.array_equal(x, xl) and info.schedule == 3, info.schedule
+    n, brp, bci, bv, bb, xb = unblocked["bidiag"]
+    B = P.Matrix(0, n, n, brp, bci, bv)
+    x, info = solve_and_report(B, n, P.FILL_LOWER, True, bb)
+    assert np.array_equal(x, xb) and (info.levels, info.blocks, info.schedule) == (200, 0, 2), info.schedule
