@@ -104,6 +104,13 @@ SIGNATURES = {
     "aoclsparse_create_dtcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "aoclsparse_create_ctcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "aoclsparse_create_ztcsr": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "aoclsparse_create_sbsr": (c_int, [POINTER(_P), c_int, c_int, _I, _I, _I, _P, _P, _P, ctypes.c_bool]),
+    "aoclsparse_create_dbsr": (c_int, [POINTER(_P), c_int, c_int, _I, _I, _I, _P, _P, _P, ctypes.c_bool]),
+    "aoclsparse_create_cbsr": (c_int, [POINTER(_P), c_int, c_int, _I, _I, _I, _P, _P, _P, ctypes.c_bool]),
+    "aoclsparse_create_zbsr": (c_int, [POINTER(_P), c_int, c_int, _I, _I, _I, _P, _P, _P, ctypes.c_bool]),
+    "aoclsparse_convert_bsr": (c_int, [_P, _I, c_int, c_int, POINTER(_P)]),
+    "aoclsparse_mi355_export_bsr": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P),
+                                            POINTER(_P), POINTER(_P), POINTER(_I)]),
     "aoclsparse_sset_value": (c_int, [_P, _I, _I, c_float]),
     "aoclsparse_dset_value": (c_int, [_P, _I, _I, c_double]),
     "aoclsparse_supdate_values": (c_int, [_P, _I, _P]),
@@ -592,6 +599,77 @@ class TcsrMatrix(Matrix):
         self.h = c_void_p()
         self.status = fn(byref(self.h), base, m, m, self.nnz, _ptr(self.ptr_l), _ptr(self.ptr_u), _ptr(self.col_l),
                          _ptr(self.col_u), _ptr(self.val_l), _ptr(self.val_u))
+
+
+class BsrMatrix(Matrix):
+    """aoclsparse_matrix over BSR arrays: bM x bN blocks of block_dim x block_dim values (order: ORDER_ROW / ORDER_COLUMN inside a
+    block); keeps the three aliased numpy arrays alive.  float32 / float64 / complex64 / complex128 values."""
+
+    def __init__(self, base, order, bm, bn, block_dim, row_ptr, col_ind, val, fast_check=False):
+        import numpy as np
+
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        self.col_ind = np.ascontiguousarray(col_ind, dtype=np.int32)
+        self.val = np.ascontiguousarray(val)
+        create = {np.dtype(np.float32): "s", np.dtype(np.float64): "d", np.dtype(np.complex64): "c", np.dtype(np.complex128): "z"}
+        fn = getattr(lib(), "aoclsparse_create_%sbsr" % create[self.val.dtype])
+        self.double = self.val.dtype == np.float64
+        self.base, self.order, self.bm, self.bn, self.block_dim = base, order, bm, bn, block_dim
+        self.m, self.n = bm * block_dim, bn * block_dim
+        self.nnz = (int(self.row_ptr[bm]) - base) * block_dim * block_dim if len(self.row_ptr) > bm >= 0 else 0
+        self.h = c_void_p()
+        self.status = fn(byref(self.h), base, order, bm, bn, block_dim, _ptr(self.row_ptr), _ptr(self.col_ind), _ptr(self.val),
+                         fast_check)
+
+    @classmethod
+    def from_handle(cls, h, dtype):
+        """wrap a BSR handle the library made (aoclsparse_convert_bsr); the arrays are views of the handle's own"""
+        self = cls.__new__(cls)
+        self.h, self.status = h, 0
+        self._view(dtype)
+        return self
+
+    def _view(self, dtype):
+        import numpy as np
+
+        e = self.export_bsr(dtype)
+        self.base, self.order, self.bm, self.bn, self.block_dim = e["base"], e["order"], e["bm"], e["bn"], e["block_dim"]
+        self.row_ptr, self.col_ind, self.val = e["row_ptr"], e["col_ind"], e["val"]
+        self.m, self.n, self.nnz = self.bm * self.block_dim, self.bn * self.block_dim, len(self.val)
+        self.double = np.dtype(dtype) == np.float64
+
+    def export_bsr(self, dtype=None):
+        """aoclsparse_mi355_export_bsr: the arrays as the handle holds them (numpy views, not copies)"""
+        import numpy as np
+
+        base, order, internal = c_int(), c_int(), _I()
+        bm, bn, dim = _I(), _I(), _I()
+        p, c, v = c_void_p(), c_void_p(), c_void_p()
+        st = lib().aoclsparse_mi355_export_bsr(self.h, byref(base), byref(order), byref(bm), byref(bn), byref(dim), byref(p),
+                                               byref(c), byref(v), byref(internal))
+        if st != 0:
+            raise RuntimeError("aoclsparse_mi355_export_bsr -> %s" % STATUS.get(st, st))
+        dtype = np.dtype(self.val.dtype if dtype is None else dtype)
+        ptr = np.ctypeslib.as_array(ctypes.cast(p, POINTER(_I)), shape=(bm.value + 1,))
+        nb = int(ptr[bm.value]) - base.value
+        cells = nb * dim.value * dim.value
+        col = np.ctypeslib.as_array(ctypes.cast(c, POINTER(_I)), shape=(nb,)) if nb else np.zeros(0, np.int32)
+        if cells:
+            raw = (ctypes.c_char * (cells * dtype.itemsize)).from_address(v.value)
+            val = np.frombuffer(raw, dtype=dtype)
+        else:
+            val = np.zeros(0, dtype)
+        return dict(base=base.value, order=order.value, bm=bm.value, bn=bn.value, block_dim=dim.value, row_ptr=ptr, col_ind=col,
+                    val=val, is_internal=internal.value)
+
+
+def convert_bsr(A, block_dim, order, op, dtype=None):
+    """aoclsparse_convert_bsr of a CSR-input handle -> (status, BsrMatrix or None); the new handle owns its arrays"""
+    h = c_void_p()
+    st = lib().aoclsparse_convert_bsr(A.h, block_dim, order, op, byref(h))
+    if st != 0:
+        return st, None
+    return st, BsrMatrix.from_handle(h, A.val.dtype if dtype is None else dtype)
 
 
 def scalar(v, double=True):

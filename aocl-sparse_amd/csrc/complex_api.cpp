@@ -61,14 +61,25 @@ aoclsparse_status cmv_t(aoclsparse_operation op, const cplx<R> *alpha, aoclspars
             return aoclsparse_status_not_implemented;
         return cmv_t<R>(op, alpha, tcsr_triangle(A, descr->fill_mode), descr, x, beta, y, vt);
     }
-    if(A->input_format != aoclsparse_csr_mat)
+    const bool bsr = A->input_format == aoclsparse_bsr_mat;
+    if(A->input_format != aoclsparse_csr_mat && !bsr)
+        return aoclsparse_status_not_implemented;
+    const bool empty = A->m == 0 || A->n == 0 || (A->nnz == 0 && descr->type == aoclsparse_matrix_type_general);
+    // A BSR handle that is not empty, decided before the device is touched: only a matrix whose effective doid is gn is found for
+    // it (magic_box.hpp:103-107), so every transposed, symmetric, Hermitian or triangular product ends in the default of
+    // mv.cpp:344-345, and only column-major blocks have a kernel (mv.cpp:325-329)
+    if(bsr && !empty
+       && (descr->type != aoclsparse_matrix_type_general || op != aoclsparse_operation_none
+           || A->bsr_order != aoclsparse_order_column))
         return aoclsparse_status_not_implemented;
 
     Runtime &rt = Runtime::get();
     MI355_TRY(rt.init());
     std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
     const bool                            tr = op != aoclsparse_operation_none;
-    if(A->m == 0 || A->n == 0 || (A->nnz == 0 && descr->type == aoclsparse_matrix_type_general))
+    if(bsr && !empty) // mv.cpp:331-342 with the handle's own base (:165): one chain per scalar row (bsr_complex_kernels.hip)
+        return bsr_handle_mv<C>(rt, A, *alpha, x, *beta, y);
+    if(empty)
     {
         const aoclsparse_int dim = tr ? A->n : A->m; // mv.cpp:116-121: an empty matrix still scales y
         StagedArg            ay;

@@ -1,5 +1,6 @@
 // dia_bsr_api.cpp -- the DIA and BSR raw-array routines: aoclsparse_csr2dia_ndiag, aoclsparse_?csr2dia,
-// aoclsparse_?diamv(_kid), aoclsparse_csr2bsr_nnz, aoclsparse_?csr2bsr, aoclsparse_?bsrmv.
+// aoclsparse_?diamv(_kid), aoclsparse_csr2bsr_nnz, aoclsparse_?csr2bsr, aoclsparse_?bsrmv; and the product of a BSR handle
+// (bsr_handle_mv, reached from aoclsparse_?mv).
 //
 // Conversions are host routines (the reference's are serial host loops over host arrays; a conversion is done once):
 // conversion/aoclsparse_convert.cpp:510-566 (ndiag), conversion/aoclsparse_convert.hpp:291-387 (csr2dia),
@@ -9,6 +10,7 @@
 #include "internal.hpp"
 
 #include <algorithm>
+#include <shared_mutex>
 #include <vector>
 
 using namespace mi355;
@@ -286,6 +288,72 @@ aoclsparse_status bsrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
 }
 
 } // namespace
+
+namespace mi355
+{
+namespace
+{
+inline bool is_zero(float v) { return v == 0.0f; }
+inline bool is_zero(double v) { return v == 0.0; }
+template <typename R>
+inline bool is_zero(cplx<R> v)
+{
+    return v.re == R(0) && v.im == R(0);
+}
+inline aoclsparse_status launch_bsr_any(hipStream_t s, float alpha, aoclsparse_int mb, aoclsparse_int dim, int base, const float *val,
+                                        const aoclsparse_int *col, const aoclsparse_int *ptr, const float *x, float beta, float *y)
+{
+    return launch_bsrmv<float>(s, alpha, mb, dim, base, val, col, ptr, x, beta, y);
+}
+inline aoclsparse_status launch_bsr_any(hipStream_t s, double alpha, aoclsparse_int mb, aoclsparse_int dim, int base, const double *val,
+                                        const aoclsparse_int *col, const aoclsparse_int *ptr, const double *x, double beta, double *y)
+{
+    return launch_bsrmv<double>(s, alpha, mb, dim, base, val, col, ptr, x, beta, y);
+}
+template <typename R>
+inline aoclsparse_status launch_bsr_any(hipStream_t s, cplx<R> alpha, aoclsparse_int mb, aoclsparse_int dim, int base,
+                                        const cplx<R> *val, const aoclsparse_int *col, const aoclsparse_int *ptr, const cplx<R> *x,
+                                        cplx<R> beta, cplx<R> *y)
+{
+    return launch_cbsrmv<R>(s, alpha, mb, dim, base, val, col, ptr, x, beta, y);
+}
+} // namespace
+
+template <typename T>
+aoclsparse_status bsr_handle_mv(Runtime &rt, aoclsparse_matrix A, T alpha, const T *x, T beta, T *y)
+{
+    // the mirror stays valid from here to the launch: the shared lock is held across it, and an upload (exclusive) is followed by a
+    // fresh look under the shared lock, since aoclsparse_mi355_invalidate may have come between
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    while(!A->dev_bsr.valid)
+    {
+        r.unlock();
+        aoclsparse_status su = ensure_bsr_mirror(A);
+        if(su != aoclsparse_status_success)
+            return su;
+        r.lock();
+    }
+    const DeviceCsr  &d = A->dev_bsr;
+    StagedArg         ax, ay;
+    aoclsparse_status st = ax.in(rt, 3, x, sizeof(T) * (size_t)A->n, true);
+    if(st == aoclsparse_status_success)
+        st = ay.in(rt, 4, y, sizeof(T) * (size_t)A->m, !is_zero(beta)); // y is not read when beta == 0
+    if(st == aoclsparse_status_success)
+        st = launch_bsr_any(rt.stream(), alpha, d.m, A->bsr_dim, d.base, d.val.as<T>(), d.ind.as<aoclsparse_int>(),
+                            d.ptr.as<aoclsparse_int>(), static_cast<const T *>(ax.dev), beta, static_cast<T *>(ay.dev));
+    if(st == aoclsparse_status_success)
+        st = ay.out(rt);
+    if(st != aoclsparse_status_success)
+        return st;
+    if(ay.staged) // host-pointer semantics: result visible on return
+        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
+    return aoclsparse_status_success;
+}
+template aoclsparse_status bsr_handle_mv<float>(Runtime &, aoclsparse_matrix, float, const float *, float, float *);
+template aoclsparse_status bsr_handle_mv<double>(Runtime &, aoclsparse_matrix, double, const double *, double, double *);
+template aoclsparse_status bsr_handle_mv<cfloat>(Runtime &, aoclsparse_matrix, cfloat, const cfloat *, cfloat, cfloat *);
+template aoclsparse_status bsr_handle_mv<cdouble>(Runtime &, aoclsparse_matrix, cdouble, const cdouble *, cdouble, cdouble *);
+} // namespace mi355
 
 extern "C" {
 

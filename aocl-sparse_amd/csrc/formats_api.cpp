@@ -263,6 +263,117 @@ aoclsparse_status create_tcsr(aoclsparse_matrix *mat, aoclsparse_index_base base
     return aoclsparse_status_success;
 }
 
+// create/aoclsparse_create.cpp:116-190, checks in the same order; the matrix check runs on the block pattern.  The three arrays
+// are aliased (internal.hpp: bsr), the block order is stored as given.
+aoclsparse_status create_bsr(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_order order, aoclsparse_int bM,
+                             aoclsparse_int bN, aoclsparse_int block_dim, aoclsparse_int *row_ptr, aoclsparse_int *col_idx, void *val,
+                             bool fast_chck, aoclsparse_matrix_data_type vt)
+{
+    if(!mat || !row_ptr)
+        return aoclsparse_status_invalid_pointer;
+    *mat = nullptr;
+    if(block_dim <= 0)
+        return aoclsparse_status_invalid_value;
+    if(bM < 0)
+        return aoclsparse_status_invalid_size;
+    const aoclsparse_int bnnz = row_ptr[bM] - base;
+    int                  sort = 0;
+    bool                 fulldiag = false;
+    if(fast_chck) // analysis/aoclsparse_csr_util.cpp:142-188: pointers, sizes and the two ends of row_ptr; indices and order unlooked at
+    {
+        if(!col_idx || !val)
+            return aoclsparse_status_invalid_pointer;
+        if(bN < 0 || bnnz < 0)
+            return aoclsparse_status_invalid_size;
+        if(row_ptr[0] != base)
+            return aoclsparse_status_invalid_value;
+    }
+    else
+    {
+        aoclsparse_status st = mat_check(bM, bN, bnnz, row_ptr, col_idx, val, 0, base, sort, fulldiag);
+        if(st != aoclsparse_status_success)
+            return st;
+    }
+    _aoclsparse_matrix *A = new(std::nothrow) _aoclsparse_matrix;
+    if(!A)
+        return aoclsparse_status_memory_error;
+    A->m = bM * block_dim, A->n = bN * block_dim, A->nnz = bnnz * block_dim * block_dim;
+    A->base = base, A->val_type = vt, A->sort = sort, A->fulldiag = false;
+    A->input_format = aoclsparse_bsr_mat;
+    A->bsr.m = bM, A->bsr.n = bN, A->bsr.nnz = bnnz, A->bsr.base = base;
+    A->bsr.ptr = row_ptr, A->bsr.ind = col_idx, A->bsr.val = val;
+    A->bsr.owned = false;
+    A->bsr_dim = block_dim, A->bsr_order = order;
+    *mat = A;
+    return aoclsparse_status_success;
+}
+
+// conversion/aoclsparse_convert.cpp:1218-1428: the counting and filling routines are the raw-array ones (dia_bsr_api.cpp), the
+// value storage starts as zeros so that the cells of a block without an entry, and the padding past m and n, are zero
+template <typename T, typename CT>
+aoclsparse_status convert_bsr(const aoclsparse_matrix src, aoclsparse_int block_dim, aoclsparse_order block_order,
+                              aoclsparse_operation op, aoclsparse_matrix *dest,
+                              aoclsparse_status (*fill)(aoclsparse_int, aoclsparse_int, const aoclsparse_mat_descr,
+                                                        const aoclsparse_order, const CT *, const aoclsparse_int *,
+                                                        const aoclsparse_int *, aoclsparse_int, CT *, aoclsparse_int *,
+                                                        aoclsparse_int *))
+{
+    if(!src->user.ptr) // :1230-1232
+        return aoclsparse_status_invalid_pointer;
+    aoclsparse_matrix tmp = nullptr; // the (conjugate) transpose, through aoclsparse_convert_csr
+    if(op != aoclsparse_operation_none)
+        MI355_TRY(aoclsparse_convert_csr(src, op, &tmp));
+    const _aoclsparse_matrix *in = tmp ? tmp : src;
+    const aoclsparse_int      mb = (in->m + block_dim - 1) / block_dim, nb = (in->n + block_dim - 1) / block_dim;
+    _aoclsparse_mat_descr     descr;
+    descr.base = src->base;
+    _aoclsparse_matrix *D = new(std::nothrow) _aoclsparse_matrix;
+    aoclsparse_status   st = D ? aoclsparse_status_success : aoclsparse_status_memory_error;
+    aoclsparse_int      bnnz = 0;
+    if(st == aoclsparse_status_success)
+    {
+        D->bsr.owned = true; // from here on aoclsparse_destroy frees what has been allocated
+        D->bsr.ptr   = new(std::nothrow) aoclsparse_int[(size_t)mb + 1];
+        if(!D->bsr.ptr)
+            st = aoclsparse_status_memory_error;
+    }
+    if(st == aoclsparse_status_success)
+    {
+        std::fill(D->bsr.ptr, D->bsr.ptr + mb + 1, (aoclsparse_int)src->base); // (the count of an m = 0 or n = 0 source writes nothing)
+        st = aoclsparse_csr2bsr_nnz(in->m, in->n, &descr, in->user.ptr, in->user.ind, block_dim, D->bsr.ptr, &bnnz);
+    }
+    if(st == aoclsparse_status_success)
+    {
+        const size_t cells = (size_t)bnnz * (size_t)block_dim * (size_t)block_dim;
+        D->bsr.ind         = new(std::nothrow) aoclsparse_int[std::max<size_t>((size_t)bnnz, 1)];
+        D->bsr.val         = ::operator new(sizeof(T) * std::max<size_t>(cells, 1), std::nothrow);
+        if(!D->bsr.ind || !D->bsr.val)
+            st = aoclsparse_status_memory_error;
+        else
+        {
+            std::memset(D->bsr.val, 0, sizeof(T) * cells);
+            st = fill(in->m, in->n, &descr, block_order, static_cast<const CT *>(in->user.val), in->user.ptr, in->user.ind,
+                      block_dim, static_cast<CT *>(D->bsr.val), D->bsr.ptr, D->bsr.ind);
+        }
+    }
+    if(tmp)
+        aoclsparse_destroy(&tmp);
+    if(st != aoclsparse_status_success)
+    {
+        aoclsparse_matrix h = D;
+        aoclsparse_destroy(&h);
+        return st;
+    }
+    // :1419-1424: the padded dimensions
+    D->m = mb * block_dim, D->n = nb * block_dim, D->nnz = bnnz * block_dim * block_dim;
+    D->base = src->base, D->val_type = src->val_type;
+    D->input_format = aoclsparse_bsr_mat;
+    D->bsr.m = mb, D->bsr.n = nb, D->bsr.nnz = bnnz, D->bsr.base = src->base;
+    D->bsr_dim = block_dim, D->bsr_order = block_order;
+    *dest = D;
+    return aoclsparse_status_success;
+}
+
 template <typename T>
 aoclsparse_status export_csc(const aoclsparse_matrix mat, aoclsparse_index_base *base, aoclsparse_int *m,
                              aoclsparse_int *n, aoclsparse_int *nnz, aoclsparse_int **col_ptr,
@@ -399,6 +510,21 @@ void csc_set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int c
         }
 }
 
+aoclsparse_status ensure_bsr_mirror(aoclsparse_matrix A)
+{
+    {
+        std::shared_lock<std::shared_mutex> r(A->guard);
+        if(A->dev_bsr.valid)
+            return aoclsparse_status_success;
+    }
+    std::unique_lock<std::shared_mutex> w(A->guard);
+    if(A->dev_bsr.valid)
+        return aoclsparse_status_success;
+    if(!A->bsr.ptr || !A->bsr.ind || !A->bsr.val)
+        return aoclsparse_status_invalid_pointer;
+    return upload_csr(A->bsr, val_size(A->val_type) * (size_t)A->bsr_dim * (size_t)A->bsr_dim, A->dev_bsr);
+}
+
 aoclsparse_status csc_refresh_csr(aoclsparse_matrix A)
 {
     return dispatch_value_type(A->val_type, [&](auto tag) {
@@ -464,6 +590,81 @@ aoclsparse_status aoclsparse_create_ztcsr(aoclsparse_matrix *mat, const aoclspar
                                           aoclsparse_double_complex *val_L, aoclsparse_double_complex *val_U)
 {
     return create_tcsr(mat, base, M, N, nnz, row_ptr_L, row_ptr_U, col_idx_L, col_idx_U, val_L, val_U, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_create_sbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_order order,
+                                         const aoclsparse_int bM, const aoclsparse_int bN, const aoclsparse_int block_dim,
+                                         aoclsparse_int *row_ptr, aoclsparse_int *col_idx, float *val,
+                                         bool fast_chck)
+{
+    return create_bsr(mat, base, order, bM, bN, block_dim, row_ptr, col_idx, val, fast_chck, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_create_dbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_order order,
+                                         const aoclsparse_int bM, const aoclsparse_int bN, const aoclsparse_int block_dim,
+                                         aoclsparse_int *row_ptr, aoclsparse_int *col_idx, double *val,
+                                         bool fast_chck)
+{
+    return create_bsr(mat, base, order, bM, bN, block_dim, row_ptr, col_idx, val, fast_chck, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_create_cbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_order order,
+                                         const aoclsparse_int bM, const aoclsparse_int bN, const aoclsparse_int block_dim,
+                                         aoclsparse_int *row_ptr, aoclsparse_int *col_idx, aoclsparse_float_complex *val,
+                                         bool fast_chck)
+{
+    return create_bsr(mat, base, order, bM, bN, block_dim, row_ptr, col_idx, val, fast_chck, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_create_zbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base, const aoclsparse_order order,
+                                         const aoclsparse_int bM, const aoclsparse_int bN, const aoclsparse_int block_dim,
+                                         aoclsparse_int *row_ptr, aoclsparse_int *col_idx, aoclsparse_double_complex *val,
+                                         bool fast_chck)
+{
+    return create_bsr(mat, base, order, bM, bN, block_dim, row_ptr, col_idx, val, fast_chck, aoclsparse_zmat);
+}
+
+// conversion/aoclsparse_convert.cpp:1431-1476
+aoclsparse_status aoclsparse_convert_bsr(const aoclsparse_matrix src_mat, aoclsparse_int block_dim, aoclsparse_order block_order,
+                                         aoclsparse_operation op, aoclsparse_matrix *dest_mat)
+{
+    if(!src_mat || !dest_mat)
+        return aoclsparse_status_invalid_pointer;
+    if(block_dim <= 0)
+        return aoclsparse_status_invalid_value;
+    if(block_order != aoclsparse_order_row && block_order != aoclsparse_order_column)
+        return aoclsparse_status_invalid_value;
+    if(op != aoclsparse_operation_none && op != aoclsparse_operation_transpose && op != aoclsparse_operation_conjugate_transpose)
+        return aoclsparse_status_not_implemented;
+    *dest_mat = nullptr;
+    if(src_mat->input_format != aoclsparse_csr_mat)
+        return aoclsparse_status_not_implemented;
+    switch(src_mat->val_type)
+    {
+    case aoclsparse_smat:
+        return convert_bsr<float, float>(src_mat, block_dim, block_order, op, dest_mat, aoclsparse_scsr2bsr);
+    case aoclsparse_dmat:
+        return convert_bsr<double, double>(src_mat, block_dim, block_order, op, dest_mat, aoclsparse_dcsr2bsr);
+    case aoclsparse_cmat:
+        return convert_bsr<cfloat, aoclsparse_float_complex>(src_mat, block_dim, block_order, op, dest_mat, aoclsparse_ccsr2bsr);
+    case aoclsparse_zmat:
+        return convert_bsr<cdouble, aoclsparse_double_complex>(src_mat, block_dim, block_order, op, dest_mat, aoclsparse_zcsr2bsr);
+    default:
+        return aoclsparse_status_invalid_value;
+    }
+}
+
+aoclsparse_status aoclsparse_mi355_export_bsr(const aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_order *order,
+                                              aoclsparse_int *bM, aoclsparse_int *bN, aoclsparse_int *block_dim,
+                                              aoclsparse_int **row_ptr, aoclsparse_int **col_idx, void **val,
+                                              aoclsparse_int *is_internal)
+{
+    if(!A || !base || !order || !bM || !bN || !block_dim || !row_ptr || !col_idx || !val)
+        return aoclsparse_status_invalid_pointer;
+    if(A->input_format != aoclsparse_bsr_mat)
+        return aoclsparse_status_invalid_value;
+    *base = A->base, *order = A->bsr_order, *bM = A->bsr.m, *bN = A->bsr.n, *block_dim = A->bsr_dim;
+    *row_ptr = A->bsr.ptr, *col_idx = A->bsr.ind, *val = A->bsr.val;
+    if(is_internal)
+        *is_internal = A->bsr.owned;
+    return aoclsparse_status_success;
 }
 
 aoclsparse_status aoclsparse_create_ccsc(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,

@@ -673,6 +673,14 @@ struct _aoclsparse_matrix
     // caller's three arrays of that triangle (L: the diagonal ends every row, U: it starts every row).  Every copy of the values --
     // device mirrors, TRSV plans, symmetric / triangular expansions -- hangs on these two (drop_derived_state walks them)
     aoclsparse_matrix tcsr_tri[2] = {nullptr, nullptr};
+    // BSR (input_format == aoclsparse_bsr_mat, no CSR in `user`): the block pattern as a CSR of bM x bN blocks (`bsr`: m = bM,
+    // n = bN, nnz = blocks) whose value array holds bsr_dim^2 values per block in bsr_order.  The arrays are the caller's
+    // (aoclsparse_create_?bsr) or owned (aoclsparse_convert_bsr: bsr.owned).  dev_bsr is their one mirror in HBM, uploaded at the
+    // first product and dropped by drop_derived_state
+    mi355::HostCsr   bsr;
+    aoclsparse_int   bsr_dim   = 0;
+    aoclsparse_order bsr_order = aoclsparse_order_column;
+    mi355::DeviceCsr dev_bsr;
 
     // composite solvers (solvers_api.cpp): vector workspaces in HBM, and the ILU(0) factors
     // (solvers/aoclsparse_ilu.hpp:94-104, analysis.cpp:390-425): values on the user's pattern, kept
@@ -855,6 +863,12 @@ inline aoclsparse_matrix tcsr_triangle(const _aoclsparse_matrix *A, aoclsparse_f
 {
     return A->tcsr_tri[fill == aoclsparse_fill_mode_upper ? 1 : 0];
 }
+// TCSR and BSR handles hold valid arrays of their own format and no CSR in `user`: a null user.ptr is no missing pointer there,
+// the format checks that follow decide
+inline bool holds_no_csr(const _aoclsparse_matrix *A)
+{
+    return A->input_format == aoclsparse_tcsr_mat || A->input_format == aoclsparse_bsr_mat;
+}
 // allocates the ILU(0) value array as a copy of A's values (solvers_api.cpp; analysis.cpp:390-425)
 aoclsparse_status ilu_prepare(aoclsparse_matrix A);
 // builds A->trans (host transpose of the user CSR, 0-based) if absent
@@ -925,6 +939,21 @@ aoclsparse_status launch_blkcsrmv(hipStream_t s, int base, double alpha, aoclspa
 aoclsparse_status launch_tcsrmv(hipStream_t s, int base, double alpha, aoclsparse_int m, const double *val_l, const aoclsparse_int *col_l,
                                 const aoclsparse_int *ptr_l, const double *val_u, const aoclsparse_int *col_u, const aoclsparse_int *ptr_u,
                                 const double *x, double beta, double *y);
+// y = alpha A x + beta y for BSR arrays with column-major blocks, one lane per scalar row in the reference's chain order: real
+// values (dia_bsr_kernels.hip) and complex ones (bsr_complex_kernels.hip)
+template <typename T>
+aoclsparse_status launch_bsrmv(hipStream_t s, T alpha, aoclsparse_int mb, aoclsparse_int dim, int base, const T *val,
+                               const aoclsparse_int *col, const aoclsparse_int *row_ptr, const T *x, T beta, T *y);
+template <typename R>
+aoclsparse_status launch_cbsrmv(hipStream_t s, cplx<R> alpha, aoclsparse_int mb, aoclsparse_int dim, int base, const cplx<R> *val,
+                                const aoclsparse_int *col, const aoclsparse_int *row_ptr, const cplx<R> *x, cplx<R> beta,
+                                cplx<R> *y);
+// the mirror of a BSR handle's arrays in HBM, uploaded if absent (formats_api.cpp); call without A->guard held
+aoclsparse_status ensure_bsr_mirror(aoclsparse_matrix A);
+// y = alpha A x + beta y on a BSR handle with column-major blocks (dia_bsr_api.cpp): T = float / double / cfloat / cdouble, x and y
+// host or device memory, the matrix read from the handle's mirror.  The caller has initialised the runtime and holds its stage lock
+template <typename T>
+aoclsparse_status bsr_handle_mv(Runtime &rt, aoclsparse_matrix A, T alpha, const T *x, T beta, T *y);
 template <typename T>
 aoclsparse_status launch_mergepath(hipStream_t s, int base, T alpha, aoclsparse_int ntiles, const aoclsparse_int *starts,
                                    const aoclsparse_int *first, const T *val, const aoclsparse_int *col,

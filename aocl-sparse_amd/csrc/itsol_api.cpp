@@ -856,10 +856,10 @@ aoclsparse_status solve_direct(Solver<T> *S, aoclsparse_int n, aoclsparse_matrix
         return aoclsparse_status_invalid_pointer;
     for(int i = 0; i < 100; i++)
         rinfo[i] = T(0);
-    // A TCSR handle holds no CSR for aoclsparse_csr_csc_optimize to find (solvers/aoclsparse_itsol_functions.hpp:591 ->
+    // A TCSR or BSR handle holds no CSR for aoclsparse_csr_csc_optimize to find (solvers/aoclsparse_itsol_functions.hpp:591 ->
     // analysis/aoclsparse_csr_util.hpp:804-805): not_implemented, as csr_optimize below would answer.  Decided here, before the
     // device is touched, once the argument checks that come first have passed.
-    if(n >= 0 && b && mat && descr && mat->val_type == vt && mat->input_format == aoclsparse_tcsr_mat)
+    if(n >= 0 && b && mat && descr && mat->val_type == vt && holds_no_csr(mat))
         return aoclsparse_status_not_implemented;
     MI355_TRY(set_rhs(*S, n, b, true));
     MI355_TRY(S->init());
@@ -1558,10 +1558,10 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
         return aoclsparse_status_invalid_pointer;
     for(int i = 0; i < 100; i++)
         rinfo[i] = R(0);
-    // A TCSR handle holds no CSR for aoclsparse_csr_csc_optimize to find (solvers/aoclsparse_itsol_functions.hpp:591 ->
+    // A TCSR or BSR handle holds no CSR for aoclsparse_csr_csc_optimize to find (solvers/aoclsparse_itsol_functions.hpp:591 ->
     // analysis/aoclsparse_csr_util.hpp:804-805): not_implemented, as csr_optimize below would answer.  Decided here, before the
     // device is touched, once the argument checks that come first have passed.
-    if(n >= 0 && b && mat && descr && mat->val_type == vt && mat->input_format == aoclsparse_tcsr_mat)
+    if(n >= 0 && b && mat && descr && mat->val_type == vt && holds_no_csr(mat))
         return aoclsparse_status_not_implemented;
     MI355_TRY(cset_rhs(*S, n, b, true));
     MI355_TRY(S->init());

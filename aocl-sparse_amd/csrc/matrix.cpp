@@ -327,8 +327,8 @@ aoclsparse_status csr_optimize(aoclsparse_matrix A)
     if(A->opt)
         return aoclsparse_status_success;
     HostCsr &u = A->user;
-    if(A->input_format == aoclsparse_tcsr_mat) // csr_util.hpp:804-805: no CSR among a TCSR handle's matrices (the solves and the
-        return aoclsparse_status_not_implemented; // one-triangle products come here with a triangle's own handle)
+    if(holds_no_csr(A)) // csr_util.hpp:804-805: no CSR among the matrices of a TCSR or BSR handle (the solves and the
+        return aoclsparse_status_not_implemented; // one-triangle products come here with a TCSR triangle's own handle)
     if(!u.ptr || !u.ind || !u.val)
         return aoclsparse_status_invalid_pointer;
     try
@@ -1379,6 +1379,7 @@ void drop_derived_state(aoclsparse_matrix A)
             aoclsparse_destroy(&r);
     A->replicas_cloned = 0;
     A->dev_user.valid = A->dev_trans.valid = false; // device CSRs; row-block plans stay valid: structure is unchanged
+    A->dev_bsr.valid = false; // the mirror of a BSR handle's arrays
     A->plan_user.sell.valid = A->plan_user.sell.tried = false; // the SELL copies hold values: rebuilt on optimize
     A->plan_trans.sell.valid = A->plan_trans.sell.tried = false;
     // ... and so does the blocked-ELL copy of csrmm (round 6: it was left standing, and a product after aoclsparse_?set_value /
@@ -1395,7 +1396,7 @@ template <typename T>
 static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int col_idx, T val,
                                    aoclsparse_matrix_data_type vt)
 {
-    const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && A->input_format == aoclsparse_tcsr_mat;
+    const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && holds_no_csr(A); // (or BSR: the same answers)
     if(!A || (coo ? (!A->coo_row || !A->coo_col || !A->coo_val) : (!tcsr && (!A->user.ptr || !A->user.ind || !A->user.val))))
         return aoclsparse_status_invalid_pointer;
     const aoclsparse_int b = A->base;
@@ -1403,7 +1404,7 @@ static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, 
         return aoclsparse_status_invalid_value;
     if(A->val_type != vt)
         return aoclsparse_status_wrong_type;
-    if(tcsr) // auxiliary.hpp:457-458: only CSR / CSC and COO have a setter
+    if(tcsr) // auxiliary.hpp:457-458: only CSR / CSC and COO have a setter (TCSR and BSR handles)
         return aoclsparse_status_not_implemented;
     std::unique_lock<std::shared_mutex> w(A->guard);
     if(coo)
@@ -1424,7 +1425,7 @@ static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, 
 template <typename T>
 static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, T *val, aoclsparse_matrix_data_type vt)
 {
-    const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && A->input_format == aoclsparse_tcsr_mat;
+    const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && holds_no_csr(A); // (or BSR: the same answers)
     if(!A || !val || (coo ? !A->coo_val : (!tcsr && !A->user.ptr)))
         return aoclsparse_status_invalid_pointer;
     if(len != A->nnz)
@@ -1502,7 +1503,7 @@ aoclsparse_status aoclsparse_copy(const aoclsparse_matrix src, const aoclsparse_
         return aoclsparse_status_invalid_pointer;
     if(src->val_type < aoclsparse_dmat || src->val_type > aoclsparse_zmat)
         return aoclsparse_status_wrong_type;
-    if(src->input_format == aoclsparse_tcsr_mat) // auxiliary.cpp:1234-1235: only CSR / CSC and COO are copied
+    if(holds_no_csr(src)) // auxiliary.cpp:1234-1235: only CSR / CSC and COO are copied
         return aoclsparse_status_invalid_value;
     if(!src->user.ptr || !src->user.ind || !src->user.val)
         return aoclsparse_status_invalid_pointer;
@@ -1539,7 +1540,7 @@ static aoclsparse_status set_hint(aoclsparse_matrix mat, hinted_action act, aocl
                                   const aoclsparse_mat_descr descr, aoclsparse_int ncalls,
                                   aoclsparse_int kid = -1)
 {
-    if(!mat || (!mat->user.ptr && mat->input_format != aoclsparse_tcsr_mat) || !descr)
+    if(!mat || (!mat->user.ptr && !holds_no_csr(mat)) || !descr)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != aoclsparse_index_base_zero && descr->base != aoclsparse_index_base_one)
         return aoclsparse_status_invalid_value;

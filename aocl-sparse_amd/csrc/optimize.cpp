@@ -51,6 +51,8 @@ extern "C" aoclsparse_status aoclsparse_optimize(aoclsparse_matrix A)
             h.optimized = true;
         return aoclsparse_status_success;
     }
+    if(A->input_format == aoclsparse_bsr_mat) // analysis.cpp:472-474: the first matrix of a BSR handle is no CSR.  Its mirror goes
+        return aoclsparse_status_not_implemented; // to HBM at the first product
     if(!A->user.ptr || !A->user.ind || !A->user.val)
         return aoclsparse_status_invalid_pointer;
 

@@ -240,7 +240,7 @@ aoclsparse_status symgs_t(aoclsparse_operation trans, aoclsparse_matrix A, const
         return aoclsparse_status_invalid_pointer;
     if(!A || !descr)
         return aoclsparse_status_invalid_pointer;
-    if(!A->user.ptr && A->input_format != aoclsparse_tcsr_mat) // (a TCSR handle holds valid arrays: refused below)
+    if(!A->user.ptr && !holds_no_csr(A)) // (a TCSR or BSR handle holds valid arrays: refused below)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != A->base)
         return aoclsparse_status_invalid_value;
@@ -456,7 +456,7 @@ aoclsparse_status ilu_smoother_t(aoclsparse_operation op, aoclsparse_matrix A, c
         return aoclsparse_status_invalid_pointer;
     if(!x || !b || !precond_csr_val)
         return aoclsparse_status_invalid_pointer;
-    if(!A->user.ptr && A->input_format != aoclsparse_tcsr_mat) // (a TCSR handle holds valid arrays: refused below)
+    if(!A->user.ptr && !holds_no_csr(A)) // (a TCSR or BSR handle holds valid arrays: refused below)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != A->base)
         return aoclsparse_status_invalid_value;

@@ -275,8 +275,8 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
     if((descr->type == aoclsparse_matrix_type_symmetric || descr->type == aoclsparse_matrix_type_hermitian)
        && A->m != A->n)
         return aoclsparse_status_invalid_size;
-    const bool tcsr = A->input_format == aoclsparse_tcsr_mat;
-    if(A->input_format != aoclsparse_csr_mat && !tcsr) // mv.cpp:96-97 (COO handles: convert with aoclsparse_convert_csr)
+    const bool tcsr = A->input_format == aoclsparse_tcsr_mat, bsr = A->input_format == aoclsparse_bsr_mat;
+    if(A->input_format != aoclsparse_csr_mat && !tcsr && !bsr) // mv.cpp:96-97 (COO handles: convert with aoclsparse_convert_csr)
         return aoclsparse_status_not_implemented;
     if(op == aoclsparse_operation_conjugate_transpose)
         op = aoclsparse_operation_transpose;
@@ -292,6 +292,15 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
         if(op != aoclsparse_operation_none || vt != aoclsparse_dmat)
             return aoclsparse_status_not_implemented;
     }
+    // mv.cpp:116-121: empty matrix still scales y
+    const bool empty = A->m == 0 || A->n == 0 || (A->nnz == 0 && descr->type == aoclsparse_matrix_type_general);
+    // A BSR handle that is not empty, decided before the device is touched: only a matrix whose effective doid is gn is found for
+    // it (magic_box.hpp:103-107), so every transposed, symmetric or triangular product ends in the default of mv.cpp:344-345,
+    // and only column-major blocks have a kernel (mv.cpp:325-329)
+    if(bsr && !empty
+       && (descr->type != aoclsparse_matrix_type_general || op != aoclsparse_operation_none
+           || A->bsr_order != aoclsparse_order_column))
+        return aoclsparse_status_not_implemented;
 
     Runtime          &rt = Runtime::get();
     aoclsparse_status st = rt.init();
@@ -301,9 +310,10 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
     if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
         sl.lock();
 
-    // mv.cpp:116-121: empty matrix still scales y
-    if(A->m == 0 || A->n == 0 || (A->nnz == 0 && descr->type == aoclsparse_matrix_type_general))
+    if(empty)
         return scale_y<T>(rt, y, op == aoclsparse_operation_none ? A->m : A->n, *beta);
+    if(bsr) // mv.cpp:331-342 with the handle's own base (:165); launch_bsrmv keeps the reference's chain per scalar row
+        return bsr_handle_mv<T>(rt, A, *alpha, x, *beta, y);
     if constexpr(std::is_same<T, double>::value)
         if(tcsr)
             return tcsr_general_mv(rt, A, *alpha, x, *beta, y);
@@ -712,6 +722,13 @@ aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_matrix A, aocl
     const SpmvPlan                     &p  = tr ? A->plan_trans : A->plan_user;
     const DeviceCsr                    &d  = tr ? A->dev_trans : A->dev_user;
     std::memset(info, 0, sizeof(*info));
+    if(A->input_format == aoclsparse_bsr_mat) // no plan: one lane per scalar row (dia_bsr_kernels.hip, bsr_complex_kernels.hip)
+    {
+        info->device_resident = A->dev_bsr.valid;
+        if(!tr && A->bsr_order == aoclsparse_order_column)
+            info->kernel = 6, info->order = 0, info->row_blocks = (aoclsparse_int)(((long long)A->m + 255) / 256);
+        return aoclsparse_status_success;
+    }
     if(A->input_format == aoclsparse_tcsr_mat) // no plan: four lanes per row over the two triangles (tcsr_kernels.hip)
     {
         const aoclsparse_matrix l = A->tcsr_tri[0], u = A->tcsr_tri[1];

@@ -234,7 +234,7 @@ aoclsparse_status trsm_t(aoclsparse_operation trans, const T alpha, aoclsparse_m
     if(!A || !X || !B || !descr)
         return aoclsparse_status_invalid_pointer;
     const bool tcsr = A->input_format == aoclsparse_tcsr_mat; // trsm.hpp:62-67, 107-117
-    if(!tcsr && !A->user.ptr)
+    if(!holds_no_csr(A) && !A->user.ptr)
         return aoclsparse_status_invalid_pointer;
     if(descr->base != A->base)
         return aoclsparse_status_invalid_value;

@@ -69,7 +69,7 @@ typedef enum aoclsparse_matrix_data_type_ /* :191-197 */
     aoclsparse_zmat = 3
 } aoclsparse_matrix_data_type;
 
-typedef enum aoclsparse_matrix_format_type_ /* :214-239; csr, coo and tcsr handles are produced here */
+typedef enum aoclsparse_matrix_format_type_ /* :214-239; csr, coo, tcsr and bsr handles are produced here */
 {
     aoclsparse_csr_mat           = 0,
     aoclsparse_ell_mat           = 1,
@@ -642,6 +642,35 @@ DLL_PUBLIC aoclsparse_status aoclsparse_create_ztcsr(aoclsparse_matrix *mat, con
                                                      aoclsparse_int *row_ptr_L, aoclsparse_int *row_ptr_U,
                                                      aoclsparse_int *col_idx_L, aoclsparse_int *col_idx_U, aoclsparse_double_complex *val_L,
                                                      aoclsparse_double_complex *val_U);
+/* BSR handles (aoclsparse_auxiliary.h:440-532): bM x bN blocks of block_dim x block_dim values each, stored like a CSR of blocks;
+ * `order` says how the values of a block are laid out.  The three arrays are aliased, never copied on the host and never freed.
+ * The checks run on the block pattern (fast_chck = true: pointers, sizes and the ends of row_ptr only); the handle reports
+ * m = bM * block_dim, n = bN * block_dim, nnz = blocks * block_dim^2.  aoclsparse_?mv / ?dotmv with a general descriptor and
+ * op = none run on a handle with column-major blocks, for all four value types, from a mirror of the arrays in HBM (uploaded at the
+ * first product; after changing values in place call aoclsparse_mi355_invalidate).  Row-major blocks, every other descriptor or
+ * operation and every other executor answer as the reference does (not_implemented in almost all cases). */
+DLL_PUBLIC aoclsparse_status aoclsparse_create_sbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base,
+                                                    const aoclsparse_order order, const aoclsparse_int bM, const aoclsparse_int bN,
+                                                    const aoclsparse_int block_dim, aoclsparse_int *row_ptr,
+                                                    aoclsparse_int *col_idx, float *val, bool fast_chck);
+DLL_PUBLIC aoclsparse_status aoclsparse_create_dbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base,
+                                                    const aoclsparse_order order, const aoclsparse_int bM, const aoclsparse_int bN,
+                                                    const aoclsparse_int block_dim, aoclsparse_int *row_ptr,
+                                                    aoclsparse_int *col_idx, double *val, bool fast_chck);
+DLL_PUBLIC aoclsparse_status aoclsparse_create_cbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base,
+                                                    const aoclsparse_order order, const aoclsparse_int bM, const aoclsparse_int bN,
+                                                    const aoclsparse_int block_dim, aoclsparse_int *row_ptr,
+                                                    aoclsparse_int *col_idx, aoclsparse_float_complex *val, bool fast_chck);
+DLL_PUBLIC aoclsparse_status aoclsparse_create_zbsr(aoclsparse_matrix *mat, const aoclsparse_index_base base,
+                                                    const aoclsparse_order order, const aoclsparse_int bM, const aoclsparse_int bN,
+                                                    const aoclsparse_int block_dim, aoclsparse_int *row_ptr,
+                                                    aoclsparse_int *col_idx, aoclsparse_double_complex *val, bool fast_chck);
+/* aoclsparse_convert.h:664-691: a new BSR handle from a handle created from CSR arrays, optionally (conjugate) transposed first.
+ * The new handle owns its arrays (free it with aoclsparse_destroy), keeps the source's base and value type and has the padded
+ * dimensions ceil(m / block_dim) * block_dim by ceil(n / block_dim) * block_dim; cells without an entry are zero. */
+DLL_PUBLIC aoclsparse_status aoclsparse_convert_bsr(const aoclsparse_matrix src_mat, aoclsparse_int block_dim,
+                                                    aoclsparse_order block_order, aoclsparse_operation op,
+                                                    aoclsparse_matrix *dest_mat);
 /* complex twins of the above (aoclsparse_auxiliary.h:438-560,748-870; aoclsparse_convert.h:528-560) */
 DLL_PUBLIC aoclsparse_status aoclsparse_create_ccsc(aoclsparse_matrix *mat, aoclsparse_index_base base,
                                                     aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,

@@ -212,15 +212,22 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_diag(const aoclsparse_matri
                                                           aoclsparse_int        **idiag,
                                                           aoclsparse_int        **iurow,
                                                           aoclsparse_int         *is_internal);
+/* The arrays of a BSR handle as it holds them (aoclsparse_create_?bsr: the caller's own, is_internal = 0; aoclsparse_convert_bsr:
+ * owned by the handle, is_internal = 1), read-only: the counterpart of the reference-internal aoclsparse::bsr the unit tests
+ * inspect (tests/unit_tests/bsr_convert_tests.cpp).  invalid_value for a handle of another format. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_bsr(const aoclsparse_matrix A, aoclsparse_index_base *base,
+                                                         aoclsparse_order *order, aoclsparse_int *bM, aoclsparse_int *bN,
+                                                         aoclsparse_int *block_dim, aoclsparse_int **row_ptr,
+                                                         aoclsparse_int **col_idx, void **val, aoclsparse_int *is_internal);
 typedef struct aoclsparse_mi355_spmv_info_
 {
-    aoclsparse_int kernel; /* 0 none yet, 1 csr-adaptive stream, 2 merge-path (scalar order, no pinned kid; else 1), 3 SELL-64 (mv hint + optimize), 4 SELL-64 with one column list per run of rows that share it, 5 TCSR handle: four lanes per row over both triangles (double, op = none) */
+    aoclsparse_int kernel; /* 0 none yet, 1 csr-adaptive stream, 2 merge-path (scalar order, no pinned kid; else 1), 3 SELL-64 (mv hint + optimize), 4 SELL-64 with one column list per run of rows that share it, 5 TCSR handle: four lanes per row over both triangles (double, op = none), 6 BSR handle: one lane per scalar row (column-major blocks, op = none) */
     aoclsparse_int order; /* 0 scalar chain (kid 0), 1 4-lane (kid 1/2), 2 8-lane (kid 3) */
     aoclsparse_int row_blocks; /* workgroups per launch */
     aoclsparse_int tile; /* non-zeros staged in LDS per workgroup */
     aoclsparse_int long_rows; /* rows longer than one LDS tile */
     aoclsparse_int max_row_nnz;
-    aoclsparse_int device_resident; /* 1 once the CSR arrays are in HBM */
+    aoclsparse_int device_resident; /* 1 once the CSR arrays (the BSR arrays of a BSR handle) are in HBM */
     aoclsparse_int sell_slices; /* SELL-64: 64-row slices (0 otherwise) */
     long long      stored_cells; /* SELL-64: value cells stored, padding included (kernel 4 stores fewer column cells) */
     aoclsparse_int mm_groups; /* row-major csrmm: row groups (runs of rows with one column pattern) in use, else 0 */
