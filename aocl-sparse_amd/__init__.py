@@ -265,6 +265,14 @@ SIGNATURES = {
     "aoclsparse_spmm": (c_int, [c_int, _P, _P, POINTER(_P)]),
     "aoclsparse_dcsr2m": (c_int, [c_int, _P, _P, c_int, _P, _P, c_int, POINTER(_P)]),
     "aoclsparse_scsr2m": (c_int, [c_int, _P, _P, c_int, _P, _P, c_int, POINTER(_P)]),
+    "aoclsparse_ssyrkd": (c_int, [c_int, _P, c_float, c_float, _P, c_int, _I]),
+    "aoclsparse_ssyprd": (c_int, [c_int, _P, _P, c_int, _I, c_float, c_float, _P, c_int, _I]),
+    "aoclsparse_dsyrkd": (c_int, [c_int, _P, c_double, c_double, _P, c_int, _I]),
+    "aoclsparse_dsyprd": (c_int, [c_int, _P, _P, c_int, _I, c_double, c_double, _P, c_int, _I]),
+    "aoclsparse_csyrkd": (c_int, [c_int, _P, CFloat, CFloat, _P, c_int, _I]),
+    "aoclsparse_csyprd": (c_int, [c_int, _P, _P, c_int, _I, CFloat, CFloat, _P, c_int, _I]),
+    "aoclsparse_zsyrkd": (c_int, [c_int, _P, CDouble, CDouble, _P, c_int, _I]),
+    "aoclsparse_zsyprd": (c_int, [c_int, _P, _P, c_int, _I, CDouble, CDouble, _P, c_int, _I]),
     "aoclsparse_ssp2md": (c_int, [c_int, _P, _P, c_int, _P, _P, c_float, c_float, _P, c_int, _I]),
     "aoclsparse_sspmmd": (c_int, [c_int, _P, _P, c_int, _P, _I]),
     "aoclsparse_scsr2dense": (c_int, [_I, _I, _P, _P, _P, _P, _P, _I, c_int]),

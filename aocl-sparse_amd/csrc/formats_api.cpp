@@ -168,7 +168,8 @@ aoclsparse_status create_csc(aoclsparse_matrix *mat, aoclsparse_index_base base,
     bool fulldiag = false;
     // the CSC arrays are checked as the CSR of the N x M transpose (auxiliary.cpp: create_csc_t)
     MI355_TRY(mat_check(N, M, nnz, col_ptr, row_idx, val, 0, base, sort, fulldiag));
-    aoclsparse_matrix A = nullptr;
+    const int         csc_sort = sort; // of the caller's arrays: what the reference's ?syrkd asks about (sy_dense_api.cpp)
+    aoclsparse_matrix A        = nullptr;
     MI355_TRY(new_owned_csr(&A, M, N, nnz, base, vt));
     aoclsparse_status st = csr2csc<T>(N, M, nnz, base, base, col_ptr, row_idx, val, A->user.ind, A->user.ptr,
                                       static_cast<T *>(A->user.val));
@@ -181,6 +182,7 @@ aoclsparse_status create_csc(aoclsparse_matrix *mat, aoclsparse_index_base base,
     if(mat_check(M, N, nnz, A->user.ptr, A->user.ind, A->user.val, 0, base, sort, fulldiag) == aoclsparse_status_success)
         A->sort = sort, A->fulldiag = fulldiag;
     A->csc_ptr = col_ptr, A->csc_ind = row_idx, A->csc_val = val; // for export_?csc / order_mat / mutation
+    A->csc_sort = csc_sort;
     *mat = A;
     return aoclsparse_status_success;
 }

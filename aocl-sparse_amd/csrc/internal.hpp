@@ -662,11 +662,15 @@ struct _aoclsparse_matrix
 
     // sp2m stage-1 state (C handles own their arrays)
     bool owns_user_arrays = false;
+    // does a row of the user CSR hold a column twice?  -1: not looked at yet (sy_dense_api.cpp looks once; the pattern of a
+    // handle never changes)
+    std::atomic<int> repeated_cols{-1};
 
     // other input formats (formats_api.cpp): the caller's CSC arrays of a handle created from CSC (its CSR
     // lives in `user`, owned), or the caller's COO arrays (input_format == aoclsparse_coo_mat, no CSR)
     aoclsparse_int *csc_ptr = nullptr, *csc_ind = nullptr;
     void           *csc_val = nullptr;
+    int             csc_sort = 0; // sort class of those CSC arrays (`sort` is the class of the CSR in `user`)
     aoclsparse_int *coo_row = nullptr, *coo_col = nullptr;
     void           *coo_val = nullptr;
     // TCSR (input_format == aoclsparse_tcsr_mat, no CSR in `user`): [0] = L, [1] = U, each a CSR handle of its own that aliases the
@@ -1197,6 +1201,24 @@ aoclsparse_status launch_csradd(hipStream_t s, bool fill, aoclsparse_int m, int 
                                 const aoclsparse_int *ind_a, const T *val_a, bool conj_a, T alpha, int base_b,
                                 const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b, const T *val_b, int base_c,
                                 const aoclsparse_int *ptr_c, aoclsparse_int *cnt_or_ind_c, T *val_c);
+// sy_dense_kernels.hip: the symmetric products with a dense result (?syrkd, ?syprd); only C's upper triangle is touched
+constexpr int    SY_SERIAL  = 1; // syrkd: a row of the handle repeats a column -- one lane walks the rows of W
+constexpr int    SY_ORDERED = 2; // syrkd: walk X's rows by ascending column (op = none on rows that are not sorted)
+constexpr size_t SY_LDS_MAX = 128 * 1024; // syprd stage 2 keeps a row of the scratch in LDS up to this size
+template <typename T>
+aoclsparse_status launch_sy_scale_upper(hipStream_t s, T *C, aoclsparse_int n, long long ld, bool rowmajor, T beta,
+                                        bool zero);
+// X = the CSR whose row i lists the rows of M that hold column i (M's transpose), W = M
+template <typename T>
+aoclsparse_status launch_syrkd(hipStream_t s, aoclsparse_int mc, int base_x, const aoclsparse_int *ptr_x,
+                               const aoclsparse_int *ind_x, const T *val_x, bool conj_x, int base_w,
+                               const aoclsparse_int *ptr_w, const aoclsparse_int *ind_w, const T *val_w, bool conj_w,
+                               T alpha, T *C, long long rs, long long cs, int flags);
+// scratch: mc x nin values; beta_mode: 0 C starts at zero, 1 at C, 2 at beta*C
+template <typename T>
+aoclsparse_status launch_syprd(hipStream_t s, aoclsparse_int mc, aoclsparse_int nin, int base, const aoclsparse_int *ptr,
+                               const aoclsparse_int *ind, const T *val, bool conj_1, bool conj_2, T alpha, const T *B,
+                               long long ldb, bool rowmajor, T *scratch, T beta, int beta_mode, T *C, long long rs, long long cs);
 // a new handle that owns host CSR arrays (sp2m_api.cpp); row_ptr copied when given, else filled with `base`
 aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz,
                                  aoclsparse_matrix_data_type vt, const aoclsparse_int *row_ptr,

@@ -1011,6 +1011,40 @@ DLL_PUBLIC aoclsparse_status aoclsparse_scsr2m(aoclsparse_operation       trans_
                                                const aoclsparse_request   request,
                                                aoclsparse_matrix         *csrC);
 
+/* ---- symmetric products with a dense result ----------------------------------------------------------------
+ * Replaces library/include/aoclsparse_functions.h:2969-3014 (?syprd: C = alpha*A*B*A^H + beta*C for op = none,
+ * alpha*A^H*B*A + beta*C otherwise; B dense Hermitian, only its upper triangle is read) and :3178-3217 (?syrkd:
+ * C = alpha*A*A^H + beta*C for op = none, alpha*A^H*A + beta*C otherwise).  Only the upper triangle of C is read and
+ * written.  The complex ?syrkd take the real parts of alpha and beta.  B / C may be host or device memory. */
+DLL_PUBLIC aoclsparse_status aoclsparse_ssyprd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               const float *B, const aoclsparse_order orderB, const aoclsparse_int ldb,
+                                               const float alpha, const float beta, float *C,
+                                               const aoclsparse_order orderC, const aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_dsyprd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               const double *B, const aoclsparse_order orderB, const aoclsparse_int ldb,
+                                               const double alpha, const double beta, double *C,
+                                               const aoclsparse_order orderC, const aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_csyprd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               const aoclsparse_float_complex *B, const aoclsparse_order orderB, const aoclsparse_int ldb,
+                                               const aoclsparse_float_complex alpha, const aoclsparse_float_complex beta, aoclsparse_float_complex *C,
+                                               const aoclsparse_order orderC, const aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_zsyprd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               const aoclsparse_double_complex *B, const aoclsparse_order orderB, const aoclsparse_int ldb,
+                                               const aoclsparse_double_complex alpha, const aoclsparse_double_complex beta, aoclsparse_double_complex *C,
+                                               const aoclsparse_order orderC, const aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_ssyrkd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               float alpha, float beta, float *C,
+                                               const aoclsparse_order layout, aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_dsyrkd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               double alpha, double beta, double *C,
+                                               const aoclsparse_order layout, aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_csyrkd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               aoclsparse_float_complex alpha, aoclsparse_float_complex beta, aoclsparse_float_complex *C,
+                                               const aoclsparse_order layout, aoclsparse_int ldc);
+DLL_PUBLIC aoclsparse_status aoclsparse_zsyrkd(const aoclsparse_operation op, const aoclsparse_matrix A,
+                                               aoclsparse_double_complex alpha, aoclsparse_double_complex beta, aoclsparse_double_complex *C,
+                                               const aoclsparse_order layout, aoclsparse_int ldc);
+
 /* ---- sparse x sparse with a dense result, CSR -> dense, sparse sum ------------------------------------------
  * Replaces library/include/aoclsparse_functions.h:2546-2586 (?spmmd), :2674-2720 (?sp2md), :2856-2882 (?add) and
  * library/include/aoclsparse_convert.h:566-610 (?csr2dense).  C / A may be host or device memory. */

@@ -24,6 +24,7 @@ L = pkg.lib()
 ap = argparse.ArgumentParser()
 ap.add_argument("--what", default="spmv,csrmm,trsv,cg,next,wider,setup,pcie")
 ap.add_argument("--small", action="store_true", help="skip the two 50-120 M nnz stand-ins")
+ap.add_argument("--sy-out", default=os.path.join(ROOT, "profiles", "r12", "sy_dense_cold.json"), help="where --what sy writes its record")
 args = ap.parse_args()
 what = set(args.what.split(","))
 dev = torch.device("cuda", 0)
@@ -479,3 +480,49 @@ if "pcie" in what:
     dt = time.perf_counter() - t
     emit(kind="pcie-inclusive", workload="aoclsparse_dcsrmv, ALL arrays on the host (matrix re-sent every call)",
          ms=round(dt * 1e3, 3), gflops=round(2.0 * nnz / dt / 1e9, 2), equal_to_handle_path=bool(np.array_equal(yh, yh2)))
+
+if "sy" in what:
+    # the dense symmetric products next to what a caller could do before them (not in the default list: --what sy).  Cold: 1 GiB
+    # read between two calls (bench.timed_cold).  Byte model: the upper triangle of C written once (4 m (m + 1) B; + the same
+    # read when beta != 0), 12 B per entry of A and of its transpose; syprd adds B read once and the scratch written and read once.
+    from bench import timed_cold
+
+    L.aoclsparse_mi355_set_pointer_mode(pkg.PTR_DEVICE)
+    g = 96
+    m, rp, ci, v = entry.laplace5(g)
+    nnz = len(v)
+    A = pkg.Matrix(0, m, m, rp, ci, v)
+    flush = torch.ones(1 << 27, dtype=torch.float64, device=dev)
+    Cd = torch.zeros(m * m, dtype=torch.float64, device=dev)
+    half = 4 * m * (m + 1)
+    a = (m, m, 0, rp, ci, v)
+    legs = {}
+
+    def leg(name, fn, nbytes, **kw):
+        laps = np.array(timed_cold(pkg, fn, 20, flush))
+        legs[name] = dict(ms=round(float(np.median(laps)), 4), min_ms=round(float(laps.min()), 4), max_ms=round(float(laps.max()), 4),
+                          model_bytes=nbytes, frac_of_8TBs=round(nbytes / float(np.median(laps)) / 1e6 / 8000, 4), **kw)
+        emit(kind="sy", op=name, system="5-pt Laplacian grid %d^2, dense C %d^2" % (g, m), **legs[name])
+
+    fn = lambda: L.aoclsparse_dsyrkd(pkg.OP_TRANSPOSE, A.h, 1.0, 0.0, pkg._ptr(Cd), pkg.ORDER_ROW, m)
+    assert fn() == 0
+    want = oracle.dsp2md(a, True, a, False, 1.0, 0.0, np.zeros(m * m), True, m).reshape(m, m)
+    got = Cd.cpu().numpy().reshape(m, m)
+    iu = np.triu_indices(m)
+    leg("dsyrkd op=T", fn, half + 24 * nnz, bit_exact_upper=bool(np.array_equal(got[iu], want[iu])))
+    fn = lambda: L.aoclsparse_dsp2md(pkg.OP_TRANSPOSE, d0.h, A.h, pkg.OP_NONE, d0.h, A.h, 1.0, 0.0, pkg._ptr(Cd), pkg.ORDER_ROW, m)
+    assert fn() == 0
+    leg("dsp2md(A^T, A)", fn, 8 * m * m + 24 * nnz, bit_exact=bool(np.array_equal(Cd.cpu().numpy().reshape(m, m), want)))
+    rng = np.random.default_rng(12)
+    P_ = rng.uniform(-0.01, 0.01, (m, m))
+    Bd = torch.from_numpy(np.eye(m) + (P_ + P_.T) / 2).to(dev)
+    del P_
+    fn = lambda: L.aoclsparse_dsyprd(pkg.OP_NONE, A.h, pkg._ptr(Bd), pkg.ORDER_ROW, m, 1.0, 0.0, pkg._ptr(Cd), pkg.ORDER_ROW, m)
+    assert fn() == 0
+    # sp2md multiplies two SPARSE matrices, so the triple product with a dense B cannot be finished by hand from it: the two stage
+    # times come from a kernel trace of this leg (rocprofv3 --kernel-trace --stats)
+    leg("dsyprd op=N", fn, half + 12 * nnz + half + 2 * 8 * m * m)
+    out = args.sy_out
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(gpu=torch.cuda.get_device_name(0), grid=g, m=m, nnz=nnz, reps=20, cold="1 GiB read between calls", legs=legs), f, indent=1)
