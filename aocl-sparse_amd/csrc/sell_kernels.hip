@@ -424,20 +424,34 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_kernel(aoclsparse_int m, a
         s_store(y + i, s_finish(r, alpha, beta, y + i), nt);
 }
 
+// N adjacent rows of x or y in one lane, aligned as ONE element (the operands and x + column are no better)
+template <typename T, int N>
+using SellRows = T __attribute__((ext_vector_type(N), aligned(sizeof(T))));
+
 // Short rows: matrices whose widest slice has WMAX <= 8 cells, scalar summation order, PACK 1, large launches.  A wavefront
 // takes SPW consecutive slices and walks them TOGETHER, with no loop on the common path.  On a plan with uniform column lists
 // and packed table indices (UCOL, PK: a stencil with a value table, the headline) its life is THREE dependent round trips
 // whatever SPW is:
 //   1. the kernel arguments (one scalar batch: the sweep direction is the pair g0 / gstep, not a branch);
-//   2. one batch whose every address is a function of the slice number alone: the SPW slice records (SellSliceDesc, one wide
-//      scalar load), the SPW uniform column lists (ucol, 8 columns per slice, consecutive slices adjacent: one wide scalar load)
-//      and the SPW packed index words (one vector load per slice, one contiguous line per wavefront);
-//   3. all SPW x WMAX x gathers, each at a scalar base (x + column) plus the lane's shift; then the chains and the stores.
+//   2. one scalar batch whose every address is a function of the slice number alone: the SPW slice records (SellSliceDesc, one
+//      wide scalar load) and the SPW uniform column lists (ucol, 8 columns per slice, consecutive slices adjacent: one wide
+//      scalar load);
+//   3. the packed index words (one contiguous line per slice) and all the x gathers, each at a scalar base (x + column) plus the
+//      lane's offset; then the chains and the stores.
 // A slice of mode 1 / 2 (full, one leader: sell_leaders_kernel) has ONE column list, so its columns are wave-uniform: they live
 // in scalar registers and no vector load fetches them.  A group with a slice of any other mode (mode 0, lead[] says which list a
 // lane follows: 2 slices in 64 on a stencil; mode 3, lists not shared) takes ONE wave-uniform branch to the column lists in col,
 // as every group does without UCOL: there the life is four round trips (records -> value / column lines, index clamped to the
 // slice's own width, and to 0 for an EMPTY slice, which reads the padding cells behind the arrays -> gathers), five with lead[].
+// A RUN (double, UCOL, PK, SPW > 1): the group's SPW slices are all mode 1, of one width, and every list continues the list
+// before it (column + 64 in every used cell), so row j of the group's 64 SPW rows reads x[column_q + j] with ONE base per cell.
+// Then lane l owns the SPW CONSECUTIVE rows SPW l .. SPW l + SPW - 1 instead of row l of every slice: one gather per cell of
+// SPW elements per lane (16 bytes at the shipped SPW of 2), one load of the lane's SPW adjacent word bytes, one
+// store of y -- 7 vector memory instructions on the headline instead of 14; the same three round trips, the same
+// bytes, each row's chain as before.  The test is scalar compares on the records and lists of the batch; it is the third outcome
+// of the wave-uniform decision (lists in col / uniform by slice / run), and the packed words are loaded behind it, by the
+// mapping it chose.  x + column, x and y are aligned as elements only: the vector type says so.  Words of more than one byte
+// per row (pbytes > 1) stay on the mapping by slice.
 // Without PK the value (or one-byte index) lines are SPW x WMAX vector loads behind the records.
 // TAB: 0 = the cells hold values; 2 = indices into a table of <= 2 values, held in scalar registers and selected;
 // 256 = indices into a table of <= SELL_VTAB_MAX values, copied to LDS once per workgroup (its load goes out with the records,
@@ -457,6 +471,10 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
                                                                    int pbits, int pbytes)
 {
     using R = typename SellCell<T, TAB != 0>::raw;
+    // the mapping of a run (below): double, several slices per wavefront, uniform lists and packed words.  (Float was built and
+    // measured with it -- 28 -> 7 vector memory instructions per wavefront and the same time, DESIGN.md 5.1 -- and keeps the
+    // mapping by slice; the code below is written for any real type and any SPW > 1.)
+    constexpr bool WIDE = UCOL && PK && SPW > 1 && std::is_same_v<T, double>;
     static_assert(WAVES * SPW <= SELL_DESC_PAD && 64 * WAVES == SELL_VTAB_MAX, "padding of the slice records / one table entry per lane");
     static_assert(!PK || TAB != 0, "packed words hold table indices");
     // group g of WAVES x SPW slices; consecutive products of a handle ALTERNATE the direction (SellPlan::products): g0 = last
@@ -483,15 +501,21 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
             for(int q = 0; q < WMAX; q++)
                 uc[u][q] = ucol[(sb + u) * SELL_SHORT_WMAX + q];
     }
-    [[maybe_unused]] unsigned pw[SPW]; // the rows' packed index words
-    if constexpr(PK)
-    {
-        // (TAB 2: <= 8 cells of one bit, always a byte; else the width is a run-time scalar and the load has no branch)
-        const long long row = (long long)sb * 64 + lane;
+    // the rows' packed index words.  Kernels without the run mapping load them HERE, with the records; the others behind the
+    // decision, which says whose rows they are
+    [[maybe_unused]] unsigned pw[SPW];
+    auto words_by_slice = [&]() {
+        if constexpr(PK)
+        {
+            // (TAB 2: <= 8 cells of one bit, always a byte; else the width is a run-time scalar and the load has no branch)
+            const long long row = (long long)sb * 64 + lane;
 #pragma unroll
-        for(int u = 0; u < SPW; u++)
-            pw[u] = TAB == 2 ? packed_word(sval, row + 64 * u, 1) : packed_word_any(sval, row + 64 * u, pbytes);
-    }
+            for(int u = 0; u < SPW; u++)
+                pw[u] = TAB == 2 ? packed_word(sval, row + 64 * u, 1) : packed_word_any(sval, row + 64 * u, pbytes);
+        }
+    };
+    if constexpr(!WIDE)
+        words_by_slice();
     int  mode[SPW];
     bool lists = !UCOL; // the group reads its columns from the lists in col
 #pragma unroll
@@ -524,9 +548,38 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
 #pragma unroll
             for(int q = 0; q < WMAX; q++)
                 s_pin_arg(uc[u][q]);
+        if constexpr(WIDE)
+        {
+            // all four words of every record too: the run test reads only w, and the compiler would otherwise fetch x / y / z
+            // (offsets, needed by the lists in col alone) behind the test -- a fourth round trip on that path
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+                s_pin_arg(d[u].x), s_pin_arg(d[u].y), s_pin_arg(d[u].z), s_pin_arg(d[u].w);
+        }
         if constexpr(TAB == 2)
             s_pin_arg(t0), s_pin_arg(t1);
         __builtin_amdgcn_sched_barrier(0);
+    }
+    // A RUN: the group's SPW slices are all mode 1, of one width, and each list continues the list before it (column + 64 in
+    // every used cell): row j of the group's 64 SPW rows reads x[uc[0][q] + j].  Scalar compares on what the batch above brought.
+    // Words of more than one byte per row stay on the mapping by slice.
+    [[maybe_unused]] bool run = false;
+    if constexpr(WIDE)
+    {
+        // (one word of differences, no branch per compare: mode and width are bits 0 .. 7 and 16 .. 23 of w)
+        const int w0  = (int)(d[0].w & 0xffu);
+        unsigned  dif = (d[0].w ^ ((unsigned)SELL_DESC_MODE_LANE_SHIFT << 16)) & 0xff0000u;
+        if constexpr(TAB != 2)
+            dif |= (unsigned)(pbytes - 1);
+#pragma unroll
+        for(int u = 1; u < SPW; u++)
+        {
+            dif |= (d[u].w ^ d[0].w) & 0xff00ffu;
+#pragma unroll
+            for(int q = 0; q < WMAX; q++)
+                dif |= q < w0 ? (unsigned)(uc[u][q] - uc[0][q] - 64 * u) : 0u;
+        }
+        run = dif == 0u;
     }
     T        xx[SPW][WMAX];
     unsigned okm[SPW]; // bit q: cell q of this lane's row is a cell of the matrix (inside the slice's width, no padding)
@@ -578,9 +631,43 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
     if constexpr(UCOL)
     {
         if(__builtin_expect(lists, 0)) // wave-uniform
+        {
+            if constexpr(WIDE)
+                words_by_slice();
             from_lists();
+        }
+        else if(WIDE && __builtin_expect(run, 1)) // wave-uniform
+        {
+            // lane l owns the SPW CONSECUTIVE rows SPW l .. SPW l + SPW - 1 of the group: xx[u] / pw[u] / r[u] are row SPW l + u.
+            // One gather per cell, SPW elements (16 bytes) per lane at the scalar base x + column (element-aligned only: column
+            // i - 1 is odd); one load of the lane's SPW adjacent word bytes.  An unused entry (-1) gathers at x + the lane's
+            // offset: inside x, a run has 64 SPW distinct columns in its first cell.
+            if constexpr(WIDE)
+            {
+                using RowVec = SellRows<T, SPW>;
+                using PW = std::conditional_t<SPW == 2, unsigned short, unsigned>;
+                const unsigned word = *reinterpret_cast<const PW *>(reinterpret_cast<const unsigned char *>(sval) + (long long)sb * 64 + SPW * lane);
+#pragma unroll
+                for(int u = 0; u < SPW; u++)
+                    pw[u] = (word >> (8 * u)) & 0xffu, okm[u] = (1u << (d[0].w & 0xffu)) - 1u;
+                using GV = const __attribute__((address_space(1))) RowVec;
+                using GC = const __attribute__((address_space(1))) char;
+#pragma unroll
+                for(int q = 0; q < WMAX; q++)
+                {
+                    GC *gb = (GC *)(x + max(uc[0][q], 0));
+                    asm volatile("" : "+s"(gb)); // (the base stays a scalar pair: as on the path below)
+                    const RowVec xv = *(GV *)(gb + (unsigned)lane * (unsigned)sizeof(RowVec));
+#pragma unroll
+                    for(int u = 0; u < SPW; u++)
+                        xx[u][q] = xv[u];
+                }
+            }
+        }
         else
         {
+            if constexpr(WIDE)
+                words_by_slice();
             // every slice of the group has one list: a gather is a scalar base, x + column, plus the lane's shift (mode 1) in
             // bytes -- no address arithmetic in vector registers.  An unused entry (-1) gathers at x + shift, which is inside x:
             // a mode-1 slice has 64 distinct columns in its first cell, and the empty records behind the last slice are mode 2
@@ -644,6 +731,28 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
 #pragma unroll
     for(int u = 0; u < SPW; u++)
         s_pin(r[u]); // (every load above is issued before the first guarded store)
+    if constexpr(WIDE)
+    {
+        if(__builtin_expect(run, 1)) // the lane's SPW rows are adjacent, inside m (mode 1 slices are full): one store
+        {
+            using RowVec = SellRows<T, SPW>;
+            RowVec *yp = reinterpret_cast<RowVec *>(y + (long long)sb * 64 + SPW * lane);
+            RowVec  yv = {};
+            if(beta != T(0))
+                yv = *yp;
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+            {
+                const T yu = yv[u];
+                yv[u]      = s_finish(r[u], alpha, beta, &yu);
+            }
+            if(nt)
+                __builtin_nontemporal_store(yv, yp);
+            else
+                *yp = yv;
+            return;
+        }
+    }
 #pragma unroll
     for(int u = 0; u < SPW; u++)
     {
