@@ -273,6 +273,8 @@ SIGNATURES = {
     "aoclsparse_csyprd": (c_int, [c_int, _P, _P, c_int, _I, CFloat, CFloat, _P, c_int, _I]),
     "aoclsparse_zsyrkd": (c_int, [c_int, _P, CDouble, CDouble, _P, c_int, _I]),
     "aoclsparse_zsyprd": (c_int, [c_int, _P, _P, c_int, _I, CDouble, CDouble, _P, c_int, _I]),
+    "aoclsparse_syrk": (c_int, [c_int, _P, POINTER(_P)]),
+    "aoclsparse_sypr": (c_int, [c_int, _P, _P, _P, POINTER(_P), c_int]),
     "aoclsparse_ssp2md": (c_int, [c_int, _P, _P, c_int, _P, _P, c_float, c_float, _P, c_int, _I]),
     "aoclsparse_sspmmd": (c_int, [c_int, _P, _P, c_int, _P, _I]),
     "aoclsparse_scsr2dense": (c_int, [_I, _I, _P, _P, _P, _P, _P, _I, c_int]),

@@ -22,6 +22,7 @@
 #include <exception>
 #include <memory>
 #include <mutex>
+#include <functional>
 #include <new>
 #include <shared_mutex>
 #include <system_error>
@@ -780,7 +781,7 @@ private:
     std::atomic<bool> inited_{false}; // set (release) after init_status_ / device / events are written
     aoclsparse_status init_status_ = aoclsparse_status_success;
     hipStream_t  stream_ = nullptr;
-    DeviceBuffer stage_[48]; // 0-7: csrmv / mv / trsv / dotmv, 8-15: ELL family and BLKCSR (ell_api.cpp, blk_api.cpp), 16-39: sp2m (sp2m_api.cpp),
+    DeviceBuffer stage_[48]; // 0-7: csrmv / mv / trsv / dotmv, 8-15: ELL family and BLKCSR (ell_api.cpp, blk_api.cpp), 16-39 and 46: sp2m, syrk, sypr (SPG_SLOT_*),
                              // 40-45: the temporaries of the device transpose (transpose_kernels.hip; sp2m transposes operands while its own slots are in use)
 };
 
@@ -1223,6 +1224,91 @@ aoclsparse_status launch_syprd(hipStream_t s, aoclsparse_int mc, aoclsparse_int 
 aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz,
                                  aoclsparse_matrix_data_type vt, const aoclsparse_int *row_ptr,
                                  aoclsparse_index_base base = aoclsparse_index_base_zero);
+
+// ---- one first-touch product D = X * Y on the device (sp2m_api.cpp; kernels: spgemm_kernels.hip) ----------------------------------
+// What aoclsparse_sp2m, aoclsparse_syrk and aoclsparse_sypr share: the upper bound of every row's list, the bins, the count pass
+// with its prefix sum and the fill pass.  X and Y are CSR arrays in HBM (any base), D is 0-based.  Staging slots 16-39 and 46 of the
+// runtime belong to these three entry points; the caller holds the runtime's stage lock from analyse() to the last pass.
+enum
+{
+    SPG_SLOT_XP = 16, // operands that no handle keeps resident: X (ptr, ind, val), then Y
+    SPG_SLOT_XI,
+    SPG_SLOT_XV,
+    SPG_SLOT_YP,
+    SPG_SLOT_YI,
+    SPG_SLOT_YV,
+    SPG_SLOT_CNT, // the list size of every row: the counts themselves
+    SPG_SLOT_ORDER_COUNT,
+    SPG_SLOT_ORDER_FILL,
+    SPG_SLOT_HEAVY_COUNT,
+    SPG_SLOT_HEAVY_FILL,
+    SPG_SLOT_G_KEY,
+    SPG_SLOT_G_POS,
+    SPG_SLOT_G_LIST,
+    SPG_SLOT_G_ACC,
+    SPG_SLOT_CAP,
+    SPG_SLOT_SMALL,
+    SPG_SLOT_SCAN,
+    SPG_SLOT_HEAVY_KEYS,
+    SPG_SLOT_TP, // sypr: the intermediate product T = sym(B) * A (ptr, ind, val), which never leaves HBM
+    SPG_SLOT_TI,
+    SPG_SLOT_TV,
+    SPG_SLOT_CP, // syrk / sypr: the result before it goes to the handle's host arrays (ptr, ind; val: SPG_SLOT_CV)
+    SPG_SLOT_CI,
+    SPG_SLOT_END,
+    SPG_SLOT_CV = 46
+};
+static_assert(SPG_SLOT_END <= 40, "Runtime::stage_: slots 40-45 belong to the device transpose");
+struct SpgDevOp
+{
+    const aoclsparse_int *ptr = nullptr, *ind = nullptr;
+    const void           *val = nullptr;
+    int                   base = 0;
+};
+template <typename T>
+struct SpgProduct
+{
+    Runtime       &rt;
+    aoclsparse_int m = 0, n = 0; // D is m x n
+    SpgDevOp       x, y;
+    bool           conj_x = false, conj_y = false;
+    bool           upper  = false; // row i of D keeps the columns >= i only (spgemm_hash_kernel, UPPER)
+    std::function<void(const char *)> phase; // diagnostic hook: called after every step with its name
+
+    explicit SpgProduct(Runtime &r)
+        : rt(r)
+    {
+    }
+    // the upper bound of every row's list; clears the word the passes raise when a row does not fit what it was given
+    aoclsparse_status analyse();
+    // count pass and prefix sum: d_ptr[0..m] (device) = D's row pointer, *d_total (device) = its last entry in 64 bits
+    aoclsparse_status count(aoclsparse_int *d_ptr, long long **d_total);
+    // instead of count(): the counts that a row pointer from elsewhere (a finalize call) implies
+    aoclsparse_status counts_from(const aoclsparse_int *d_ptr);
+    // fill pass; the counts of count() / counts_from() are checked against the upper bounds first (invalid_value)
+    aoclsparse_status fill(const aoclsparse_int *d_ptr, aoclsparse_int *d_ind, T *d_val);
+    // device word, nonzero once a row ended short of, or beyond, its segment
+    const unsigned int *bad_word() const
+    {
+        return d_bad;
+    }
+
+private:
+    struct Binned;
+    int          *d_cap = nullptr, *d_key = nullptr;
+    unsigned int *d_hist = nullptr, *d_cursor = nullptr, *d_bad = nullptr;
+    aoclsparse_status bin_rows(Binned &bn, bool for_fill, const int *key, const int *limit);
+    aoclsparse_status run_pass(bool pass_fill, Binned &bn, const aoclsparse_int *ptr_c, aoclsparse_int *out_i, T *out_v);
+};
+// the dense-row path of aoclsparse_syrk (spgemm_kernels.hip: aat_dense_row_kernel): the upper triangle of A * A^H for a short, wide
+// A (syrk.hpp:46-113).  (ptr_s, ind_s, val_s): A with every row sorted by column and one entry per column (repeats
+// summed), 0-based -- the searchable form of the reference's dense row.  Count pass: cnt[i]; fill pass: ind_c (in base_c) / val_c
+// at the 0-based ptr_c.
+template <typename T>
+aoclsparse_status launch_aat_dense_row(hipStream_t s, bool fill, aoclsparse_int m, int base_a, const aoclsparse_int *ptr_a,
+                                       const aoclsparse_int *ind_a, const T *val_a, const aoclsparse_int *ptr_s,
+                                       const aoclsparse_int *ind_s, const T *val_s, const aoclsparse_int *ptr_c, int *cnt,
+                                       int base_c, aoclsparse_int *ind_c, T *val_c);
 
 // level1_kernels.hip: sparse-vector operations
 constexpr int L1_DOT_PARTIALS = 1024;

@@ -26,13 +26,13 @@ aoclsparse_status launch_spgemm_heavy(hipStream_t s, bool fill, aoclsparse_int n
                                       int *g_list, T *g_acc, int base_a, const aoclsparse_int *ptr_a, const aoclsparse_int *ind_a,
                                       const T *val_a, int base_b, const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b,
                                       const T *val_b, const aoclsparse_int *ptr_c, aoclsparse_int *cnt_or_ind_c, T *val_c,
-                                      bool conj_a, bool conj_b, unsigned int *bad);
+                                      bool conj_a, bool conj_b, bool upper, unsigned int *bad);
 template <typename T>
 aoclsparse_status launch_spgemm_bin(hipStream_t s, bool fill, int bin, aoclsparse_int nrows, const aoclsparse_int *rows, int base_a,
                                     const aoclsparse_int *ptr_a, const aoclsparse_int *ind_a, const T *val_a, int base_b,
                                     const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b, const T *val_b,
                                     const aoclsparse_int *ptr_c, aoclsparse_int *cnt_or_ind_c, T *val_c, bool conj_a, bool conj_b,
-                                    unsigned int *bad);
+                                    bool upper, unsigned int *bad);
 
 aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz,
                                  aoclsparse_matrix_data_type vt, const aoclsparse_int *row_ptr, aoclsparse_index_base base)
@@ -60,6 +60,196 @@ aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclspa
     *C = c;
     return aoclsparse_status_success;
 }
+
+// the rows of a product grouped by the bin of spgemm_hash_kernel that serves them (device arrays: staging slots of the runtime,
+// grown on demand and reused by the next product -- a hipMalloc / hipFree pair per temporary cost more than the kernels)
+template <typename T>
+struct SpgProduct<T>::Binned
+{
+    aoclsparse_int        bounds[SPGEMM_BINS + 1] = {};
+    const aoclsparse_int *d_order = nullptr; // null: one bin holds every row (no list needed)
+    // the rows of the last bin (tables in a global slab), in batches whose tables fit SPG_SLAB_SLOTS: batch b = records
+    // [batch[b], batch[b + 1]) with offsets that start at 0
+    std::vector<SpgHeavy>       heavy;
+    std::vector<aoclsparse_int> batch;
+    long long                   slots = 0, entries = 0; // of the largest batch
+    const SpgHeavy             *d_heavy = nullptr;
+};
+constexpr long long SPG_SLAB_SLOTS = 1LL << 28; // 1 GiB of keys (and of slots in the fill pass) per batch
+
+// ---- analysis on the device: the upper bound of every row's list, the bins, the rows of every bin (spgemm_kernels.hip) ----
+template <typename T>
+aoclsparse_status SpgProduct<T>::analyse()
+{
+    void             *p_cap = nullptr, *p_key = nullptr, *p_small = nullptr;
+    aoclsparse_status st    = rt.staging(SPG_SLOT_CAP, sizeof(int) * (size_t)m, &p_cap);
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_CNT, sizeof(int) * (size_t)m, &p_key);
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_SMALL, 256, &p_small);
+    if(st == aoclsparse_status_success)
+        st = launch_spg_bounds(rt.stream(), m, n, x.base, x.ptr, x.ind, y.ptr, static_cast<int *>(p_cap));
+    if(st != aoclsparse_status_success)
+        return st;
+    d_cap = static_cast<int *>(p_cap), d_key = static_cast<int *>(p_key);
+    d_hist = static_cast<unsigned int *>(p_small), d_cursor = d_hist + 16, d_bad = d_hist + 32;
+    MI355_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), rt.stream())); // raised by a row whose list does not fit what it was given
+    return aoclsparse_status_success;
+}
+
+// key = the size of every row's list (count pass: d_cap; fill pass: the exact counts, checked against d_cap)
+template <typename T>
+aoclsparse_status SpgProduct<T>::bin_rows(Binned &bn, bool for_fill, const int *key, const int *limit)
+{
+    hipStream_t       s  = rt.stream();
+    aoclsparse_status rc = launch_spg_hist(s, m, key, limit, for_fill, d_hist);
+    if(rc != aoclsparse_status_success)
+        return rc;
+    unsigned int hist[SPGEMM_BINS + 1];
+    MI355_HIP_TRY(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if(hist[SPGEMM_BINS])
+        return aoclsparse_status_invalid_value; // a row_ptr that is not this product's (csr2m.cpp:397-399 checks dimensions only)
+    bn.bounds[0] = 0;
+    bool one_bin = false;
+    for(int b = 0; b < SPGEMM_BINS; b++)
+    {
+        bn.bounds[b + 1] = bn.bounds[b] + (aoclsparse_int)hist[b];
+        one_bin |= (aoclsparse_int)hist[b] == m;
+    }
+    const aoclsparse_int nheavy = (aoclsparse_int)hist[SPGEMM_BINS - 1];
+    if(one_bin && nheavy == 0)
+        return aoclsparse_status_success; // (no list: workgroup g serves row g)
+    void *po = nullptr;
+    rc       = rt.staging(for_fill ? SPG_SLOT_ORDER_FILL : SPG_SLOT_ORDER_COUNT, sizeof(aoclsparse_int) * (size_t)m, &po);
+    if(rc == aoclsparse_status_success)
+        rc = launch_spg_order(s, m, key, for_fill, bn.bounds, d_cursor, static_cast<aoclsparse_int *>(po));
+    if(rc != aoclsparse_status_success)
+        return rc;
+    bn.d_order = static_cast<const aoclsparse_int *>(po);
+    if(nheavy == 0)
+        return rc;
+    // the rows of the last bin: ids and list sizes to the host, slab offsets back (few rows: the dense ones of a power-law matrix)
+    void *pk = nullptr;
+    rc       = rt.staging(SPG_SLOT_HEAVY_KEYS, sizeof(int) * (size_t)nheavy, &pk);
+    if(rc == aoclsparse_status_success)
+        rc = launch_spg_gather(s, nheavy, bn.d_order + bn.bounds[SPGEMM_BINS - 1], key, static_cast<int *>(pk));
+    if(rc != aoclsparse_status_success)
+        return rc;
+    std::vector<aoclsparse_int> ids((size_t)nheavy);
+    std::vector<int>            caps((size_t)nheavy);
+    MI355_HIP_TRY(hipMemcpyAsync(ids.data(), bn.d_order + bn.bounds[SPGEMM_BINS - 1], sizeof(aoclsparse_int) * (size_t)nheavy,
+                                 hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipMemcpyAsync(caps.data(), pk, sizeof(int) * (size_t)nheavy, hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    std::vector<std::pair<aoclsparse_int, int>> rows((size_t)nheavy);
+    for(aoclsparse_int j = 0; j < nheavy; j++)
+        rows[(size_t)j] = {ids[(size_t)j], caps[(size_t)j]};
+    std::sort(rows.begin(), rows.end()); // (the device appends them in arrival order)
+    bn.heavy.reserve((size_t)nheavy);
+    long long hs = 0, cs = 0;
+    bn.batch.push_back(0);
+    for(const auto &r : rows)
+    {
+        const long long cap = r.second;
+        if(cap > (1LL << 29))
+            return aoclsparse_status_memory_error;
+        int logh = 6;
+        while((1LL << logh) < 2 * cap)
+            logh++;
+        if(hs + (1LL << logh) > SPG_SLAB_SLOTS && hs > 0)
+        {
+            bn.batch.push_back((aoclsparse_int)bn.heavy.size());
+            hs = cs = 0;
+        }
+        bn.heavy.push_back(SpgHeavy{r.first, logh, hs, cs});
+        hs += 1LL << logh, cs += cap;
+        bn.slots = std::max(bn.slots, hs), bn.entries = std::max(bn.entries, cs);
+    }
+    bn.batch.push_back((aoclsparse_int)bn.heavy.size());
+    void *ph = nullptr;
+    rc       = rt.staging(for_fill ? SPG_SLOT_HEAVY_FILL : SPG_SLOT_HEAVY_COUNT, sizeof(SpgHeavy) * bn.heavy.size(), &ph);
+    if(rc == aoclsparse_status_success)
+        rc = rt.h2d(ph, bn.heavy.data(), sizeof(SpgHeavy) * bn.heavy.size());
+    bn.d_heavy = static_cast<const SpgHeavy *>(ph);
+    return rc;
+}
+
+template <typename T>
+aoclsparse_status SpgProduct<T>::run_pass(bool pass_fill, Binned &bn, const aoclsparse_int *ptr_c, aoclsparse_int *out_i, T *out_v)
+{
+    hipStream_t       s  = rt.stream();
+    const T          *xv = static_cast<const T *>(x.val), *yv = static_cast<const T *>(y.val);
+    aoclsparse_status rc = aoclsparse_status_success;
+    for(int b = 0; b < SPGEMM_BINS - 1 && rc == aoclsparse_status_success; b++)
+        rc = launch_spgemm_bin<T>(s, pass_fill, b, bn.bounds[b + 1] - bn.bounds[b], bn.d_order ? bn.d_order + bn.bounds[b] : nullptr,
+                                  x.base, x.ptr, x.ind, xv, y.base, y.ptr, y.ind, yv, ptr_c, out_i, out_v, conj_x, conj_y, upper,
+                                  d_bad);
+    if(rc != aoclsparse_status_success || bn.heavy.empty())
+        return rc;
+    void *gk = nullptr, *gp = nullptr, *gl = nullptr, *ga = nullptr;
+    rc       = rt.staging(SPG_SLOT_G_KEY, sizeof(int) * (size_t)bn.slots, &gk);
+    if(pass_fill)
+    {
+        if(rc == aoclsparse_status_success)
+            rc = rt.staging(SPG_SLOT_G_POS, sizeof(int) * (size_t)bn.slots, &gp);
+        if(rc == aoclsparse_status_success)
+            rc = rt.staging(SPG_SLOT_G_LIST, sizeof(int) * (size_t)bn.entries, &gl);
+        if(rc == aoclsparse_status_success)
+            rc = rt.staging(SPG_SLOT_G_ACC, sizeof(T) * (size_t)bn.entries, &ga);
+    }
+    for(size_t b = 0; b + 1 < bn.batch.size() && rc == aoclsparse_status_success; b++) // (stream order: a batch reuses the slab)
+        rc = launch_spgemm_heavy<T>(s, pass_fill, bn.batch[b + 1] - bn.batch[b], bn.d_heavy + bn.batch[b], static_cast<int *>(gk),
+                                    static_cast<int *>(gp), static_cast<int *>(gl), static_cast<T *>(ga), x.base, x.ptr, x.ind, xv,
+                                    y.base, y.ptr, y.ind, yv, ptr_c, out_i, out_v, conj_x, conj_y, upper, d_bad);
+    return rc;
+}
+
+template <typename T>
+aoclsparse_status SpgProduct<T>::count(aoclsparse_int *d_ptr, long long **d_total)
+{
+    Binned            by_bound;
+    aoclsparse_status st = bin_rows(by_bound, false, d_cap, nullptr);
+    if(phase)
+        phase("count: bins");
+    if(st == aoclsparse_status_success)
+        st = run_pass(false, by_bound, nullptr, d_key, nullptr);
+    if(st != aoclsparse_status_success)
+        return st;
+    if(phase)
+        phase("count: kernels");
+    // row_ptr of D = prefix sum of the counts, on the device (64-bit sums: a product of more than 2^31 - 1 entries is refused by the
+    // caller, csr2m.cpp:221-236)
+    void *p_scan = nullptr;
+    st           = rt.staging(SPG_SLOT_SCAN, spg_scan_scratch_bytes(m), &p_scan);
+    if(st == aoclsparse_status_success)
+        st = launch_spg_scan(rt.stream(), m, d_key, d_ptr, static_cast<long long *>(p_scan), d_total);
+    return st;
+}
+
+template <typename T>
+aoclsparse_status SpgProduct<T>::counts_from(const aoclsparse_int *d_ptr)
+{
+    return launch_spg_diff(rt.stream(), m, d_ptr, d_key);
+}
+
+template <typename T>
+aoclsparse_status SpgProduct<T>::fill(const aoclsparse_int *d_ptr, aoclsparse_int *d_ind, T *d_val)
+{
+    // rows binned by their exact count, checked against the upper bounds on the device (bin_rows)
+    Binned            by_count;
+    aoclsparse_status st = bin_rows(by_count, true, d_key, d_cap);
+    if(phase)
+        phase("fill: bins");
+    if(st == aoclsparse_status_success)
+        st = run_pass(true, by_count, d_ptr, d_ind, d_val);
+    return st;
+}
+
+template struct SpgProduct<double>;
+template struct SpgProduct<float>;
+template struct SpgProduct<cdouble>;
+template struct SpgProduct<cfloat>;
 }
 
 namespace
@@ -108,46 +298,6 @@ void transpose_of(const Operand<T> &a, Operand<T> &t)
         t.optr[j] += b;
     t.ptr = t.optr.data(), t.ind = t.oind.data(), t.val = t.oval.data();
 }
-
-// the rows of a product grouped by the bin of spgemm_hash_kernel that serves them (device arrays: staging slots of the runtime,
-// grown on demand and reused by the next product -- a hipMalloc / hipFree pair per temporary cost more than the kernels)
-struct Binned
-{
-    aoclsparse_int        bounds[SPGEMM_BINS + 1] = {};
-    const aoclsparse_int *d_order = nullptr; // null: one bin holds every row (no list needed)
-    // the rows of the last bin (tables in a global slab), in batches whose tables fit SPG_SLAB_SLOTS: batch b = records
-    // [batch[b], batch[b + 1]) with offsets that start at 0
-    std::vector<SpgHeavy>       heavy;
-    std::vector<aoclsparse_int> batch;
-    long long                   slots = 0, entries = 0; // of the largest batch
-    const SpgHeavy             *d_heavy = nullptr;
-};
-constexpr long long SPG_SLAB_SLOTS = 1LL << 28; // 1 GiB of keys (and of slots in the fill pass) per batch
-enum
-{
-    SLOT_XP = 16,
-    SLOT_XI,
-    SLOT_XV,
-    SLOT_YP,
-    SLOT_YI,
-    SLOT_YV,
-    SLOT_CNT,
-    SLOT_ORDER_COUNT,
-    SLOT_ORDER_FILL,
-    SLOT_HEAVY_COUNT,
-    SLOT_HEAVY_FILL,
-    SLOT_G_KEY,
-    SLOT_G_POS,
-    SLOT_G_LIST,
-    SLOT_G_ACC,
-    SLOT_CAP,
-    SLOT_SMALL,
-    SLOT_SCAN,
-    SLOT_HEAVY_KEYS,
-    SLOT_END
-};
-static_assert(SLOT_END <= 40, "Runtime::stage_ is too small");
-constexpr int SLOT_KEY = SLOT_CNT; // the list size of every row: the counts themselves
 
 template <typename T>
 aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr descrA, const aoclsparse_matrix A,
@@ -315,154 +465,37 @@ aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr de
             dv.ptr = static_cast<const aoclsparse_int *>(pp), dv.ind = static_cast<const aoclsparse_int *>(pi), dv.val = pv;
             return rc;
         };
-        st = send(X, HX, dx, SLOT_XP);
+        st = send(X, HX, dx, SPG_SLOT_XP);
         if(st == aoclsparse_status_success)
         {
             if(Y->ptr == X->ptr && Y->ind == X->ind && Y->val == X->val)
                 dy = dx;
             else
-                st = send(Y, HY, dy, SLOT_YP);
+                st = send(Y, HY, dy, SPG_SLOT_YP);
         }
         if(st != aoclsparse_status_success)
             return st;
         phase("operands to the device");
-        // ---- analysis on the device: the upper bound of every row's list, the bins, the rows of every bin (spgemm_kernels.hip) ----
-        void *p_cap = nullptr, *p_key = nullptr, *p_small = nullptr;
-        st          = rt.staging(SLOT_CAP, sizeof(int) * (size_t)m, &p_cap);
-        if(st == aoclsparse_status_success)
-            st = rt.staging(SLOT_KEY, sizeof(int) * (size_t)m, &p_key);
-        if(st == aoclsparse_status_success)
-            st = rt.staging(SLOT_SMALL, 256, &p_small);
-        if(st == aoclsparse_status_success)
-            st = launch_spg_bounds(s, m, n, X->base, dx.ptr, dx.ind, dy.ptr, static_cast<int *>(p_cap));
+        // ---- the product itself: upper bounds, bins, count pass, prefix sum, fill pass (SpgProduct above) ----
+        SpgProduct<T> prod(rt);
+        prod.m = m, prod.n = n;
+        prod.x = SpgDevOp{dx.ptr, dx.ind, dx.val, (int)X->base}, prod.y = SpgDevOp{dy.ptr, dy.ind, dy.val, (int)Y->base};
+        prod.conj_x = conj_x, prod.conj_y = conj_y;
+        if(trace)
+            prod.phase = phase;
+        st = prod.analyse();
         if(st != aoclsparse_status_success)
             return st;
-        int          *d_cap  = static_cast<int *>(p_cap);
-        unsigned int *d_hist = static_cast<unsigned int *>(p_small), *d_cursor = d_hist + 16, *d_bad = d_hist + 32;
-        MI355_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), s)); // raised by a row whose list does not fit what it was given
-        // key = the size of every row's list (count pass: d_cap; fill pass: the exact counts, checked against d_cap)
-        auto bin_rows = [&](Binned &bn, bool for_fill, const int *key, const int *limit) -> aoclsparse_status {
-            aoclsparse_status rc = launch_spg_hist(s, m, key, limit, for_fill, d_hist);
-            if(rc != aoclsparse_status_success)
-                return rc;
-            unsigned int hist[SPGEMM_BINS + 1];
-            MI355_HIP_TRY(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, s));
-            MI355_HIP_TRY(hipStreamSynchronize(s));
-            if(hist[SPGEMM_BINS])
-                return aoclsparse_status_invalid_value; // a row_ptr that is not this product's (csr2m.cpp:397-399 checks dimensions only)
-            bn.bounds[0] = 0;
-            bool one_bin = false;
-            for(int b = 0; b < SPGEMM_BINS; b++)
-            {
-                bn.bounds[b + 1] = bn.bounds[b] + (aoclsparse_int)hist[b];
-                one_bin |= (aoclsparse_int)hist[b] == m;
-            }
-            const aoclsparse_int nheavy = (aoclsparse_int)hist[SPGEMM_BINS - 1];
-            if(one_bin && nheavy == 0)
-                return aoclsparse_status_success; // (no list: workgroup g serves row g)
-            void *po = nullptr;
-            rc       = rt.staging(for_fill ? SLOT_ORDER_FILL : SLOT_ORDER_COUNT, sizeof(aoclsparse_int) * (size_t)m, &po);
-            if(rc == aoclsparse_status_success)
-                rc = launch_spg_order(s, m, key, for_fill, bn.bounds, d_cursor, static_cast<aoclsparse_int *>(po));
-            if(rc != aoclsparse_status_success)
-                return rc;
-            bn.d_order = static_cast<const aoclsparse_int *>(po);
-            if(nheavy == 0)
-                return rc;
-            // the rows of the last bin: ids and list sizes to the host, slab offsets back (few rows: the dense ones of a power-law matrix)
-            void *pk = nullptr;
-            rc       = rt.staging(SLOT_HEAVY_KEYS, sizeof(int) * (size_t)nheavy, &pk);
-            if(rc == aoclsparse_status_success)
-                rc = launch_spg_gather(s, nheavy, bn.d_order + bn.bounds[SPGEMM_BINS - 1], key, static_cast<int *>(pk));
-            if(rc != aoclsparse_status_success)
-                return rc;
-            std::vector<aoclsparse_int> ids((size_t)nheavy);
-            std::vector<int>            caps((size_t)nheavy);
-            MI355_HIP_TRY(hipMemcpyAsync(ids.data(), bn.d_order + bn.bounds[SPGEMM_BINS - 1], sizeof(aoclsparse_int) * (size_t)nheavy,
-                                         hipMemcpyDeviceToHost, s));
-            MI355_HIP_TRY(hipMemcpyAsync(caps.data(), pk, sizeof(int) * (size_t)nheavy, hipMemcpyDeviceToHost, s));
-            MI355_HIP_TRY(hipStreamSynchronize(s));
-            std::vector<std::pair<aoclsparse_int, int>> rows((size_t)nheavy);
-            for(aoclsparse_int j = 0; j < nheavy; j++)
-                rows[(size_t)j] = {ids[(size_t)j], caps[(size_t)j]};
-            std::sort(rows.begin(), rows.end()); // (the device appends them in arrival order)
-            bn.heavy.reserve((size_t)nheavy);
-            long long hs = 0, cs = 0;
-            bn.batch.push_back(0);
-            for(const auto &r : rows)
-            {
-                const long long cap = r.second;
-                if(cap > (1LL << 29))
-                    return aoclsparse_status_memory_error;
-                int logh = 6;
-                while((1LL << logh) < 2 * cap)
-                    logh++;
-                if(hs + (1LL << logh) > SPG_SLAB_SLOTS && hs > 0)
-                {
-                    bn.batch.push_back((aoclsparse_int)bn.heavy.size());
-                    hs = cs = 0;
-                }
-                bn.heavy.push_back(SpgHeavy{r.first, logh, hs, cs});
-                hs += 1LL << logh, cs += cap;
-                bn.slots = std::max(bn.slots, hs), bn.entries = std::max(bn.entries, cs);
-            }
-            bn.batch.push_back((aoclsparse_int)bn.heavy.size());
-            void *ph = nullptr;
-            rc       = rt.staging(for_fill ? SLOT_HEAVY_FILL : SLOT_HEAVY_COUNT, sizeof(SpgHeavy) * bn.heavy.size(), &ph);
-            if(rc == aoclsparse_status_success)
-                rc = rt.h2d(ph, bn.heavy.data(), sizeof(SpgHeavy) * bn.heavy.size());
-            bn.d_heavy = static_cast<const SpgHeavy *>(ph);
-            return rc;
-        };
         phase("upper bounds (device)");
-        auto run_pass = [&](bool pass_fill, Binned &bn, const aoclsparse_int *ptr_c, aoclsparse_int *out_i, T *out_v) -> aoclsparse_status {
-            aoclsparse_status rc = aoclsparse_status_success;
-            for(int b = 0; b < SPGEMM_BINS - 1 && rc == aoclsparse_status_success; b++)
-                rc = launch_spgemm_bin<T>(s, pass_fill, b, bn.bounds[b + 1] - bn.bounds[b], bn.d_order ? bn.d_order + bn.bounds[b] : nullptr,
-                                          X->base, dx.ptr, dx.ind, static_cast<const T *>(dx.val), Y->base, dy.ptr, dy.ind,
-                                          static_cast<const T *>(dy.val), ptr_c, out_i, out_v, conj_x, conj_y, d_bad);
-            if(rc != aoclsparse_status_success || bn.heavy.empty())
-                return rc;
-            void *gk = nullptr, *gp = nullptr, *gl = nullptr, *ga = nullptr;
-            rc       = rt.staging(SLOT_G_KEY, sizeof(int) * (size_t)bn.slots, &gk);
-            if(pass_fill)
-            {
-                if(rc == aoclsparse_status_success)
-                    rc = rt.staging(SLOT_G_POS, sizeof(int) * (size_t)bn.slots, &gp);
-                if(rc == aoclsparse_status_success)
-                    rc = rt.staging(SLOT_G_LIST, sizeof(int) * (size_t)bn.entries, &gl);
-                if(rc == aoclsparse_status_success)
-                    rc = rt.staging(SLOT_G_ACC, sizeof(T) * (size_t)bn.entries, &ga);
-            }
-            for(size_t b = 0; b + 1 < bn.batch.size() && rc == aoclsparse_status_success; b++) // (stream order: a batch reuses the slab)
-                rc = launch_spgemm_heavy<T>(s, pass_fill, bn.batch[b + 1] - bn.batch[b], bn.d_heavy + bn.batch[b], static_cast<int *>(gk),
-                                            static_cast<int *>(gp), static_cast<int *>(gl), static_cast<T *>(ga), X->base, dx.ptr, dx.ind,
-                                            static_cast<const T *>(dx.val), Y->base, dy.ptr, dy.ind, static_cast<const T *>(dy.val), ptr_c,
-                                            out_i, out_v, conj_x, conj_y, d_bad);
-            return rc;
-        };
 
         bool ptr_on_device = false; // d_cptr holds D's row_ptr (a full computation goes from the count pass to the fill pass in HBM)
         if(count)
         {
-            Binned by_bound;
-            st = bin_rows(by_bound, false, d_cap, nullptr);
-            phase("count: bins");
-            if(st == aoclsparse_status_success)
-                st = run_pass(false, by_bound, nullptr, static_cast<aoclsparse_int *>(p_key), nullptr);
-            if(st != aoclsparse_status_success)
-                return st;
-            phase("count: kernels");
-            // row_ptr of D = prefix sum of the counts, on the device; the host needs the total now (to allocate) and the array itself
-            // for the handle (64-bit sums: a product of more than 2^31 - 1 entries is refused, csr2m.cpp:221-236)
-            void      *p_scan = nullptr;
+            // the host needs the total now (to allocate) and the array itself for the handle
             long long *d_total = nullptr, total = 0;
-            st = rt.staging(SLOT_SCAN, spg_scan_scratch_bytes(m), &p_scan);
+            st = d_cptr.alloc(sizeof(aoclsparse_int) * ((size_t)m + 1));
             if(st == aoclsparse_status_success)
-                st = d_cptr.alloc(sizeof(aoclsparse_int) * ((size_t)m + 1));
-            if(st == aoclsparse_status_success)
-                st = launch_spg_scan(s, m, static_cast<const int *>(p_key), d_cptr.as<aoclsparse_int>(), static_cast<long long *>(p_scan),
-                                     &d_total);
+                st = prod.count(d_cptr.as<aoclsparse_int>(), &d_total);
             if(st != aoclsparse_status_success)
                 return st;
             std::vector<aoclsparse_int> cptr((size_t)m + 1);
@@ -515,20 +548,15 @@ aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr de
             {
                 st = d_cptr.upload(d->ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), s);
                 if(st == aoclsparse_status_success)
-                    st = launch_spg_diff(s, m, d_cptr.as<aoclsparse_int>(), static_cast<int *>(p_key));
+                    st = prod.counts_from(d_cptr.as<aoclsparse_int>());
                 if(st != aoclsparse_status_success)
                     return st;
             }
-            Binned by_count;
-            st = bin_rows(by_count, true, static_cast<const int *>(p_key), d_cap);
-            if(st == aoclsparse_status_success)
-                st = d_ci.alloc(sizeof(aoclsparse_int) * (size_t)std::max(nnz_c, 1));
+            st = d_ci.alloc(sizeof(aoclsparse_int) * (size_t)std::max(nnz_c, 1));
             if(st == aoclsparse_status_success)
                 st = d_cv.alloc(sizeof(T) * (size_t)std::max(nnz_c, 1));
-            if(st != aoclsparse_status_success)
-                return st;
-            phase("fill: bins, buffers");
-            st = run_pass(true, by_count, d_cptr.as<aoclsparse_int>(), d_ci.as<aoclsparse_int>(), d_cv.as<T>());
+            if(st == aoclsparse_status_success)
+                st = prod.fill(d_cptr.as<aoclsparse_int>(), d_ci.as<aoclsparse_int>(), d_cv.as<T>());
             if(st != aoclsparse_status_success)
                 return st;
             unsigned int bad = 0;
@@ -537,7 +565,7 @@ aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr de
                 // finalize-only call: the row_ptr is whatever the caller's handle holds.  The verdict of the device checks is read
                 // BEFORE anything of *C is touched, so a refused call (the row_ptr of another product) leaves the caller's handle --
                 // its arrays, its device copy, its plans -- exactly as it was
-                MI355_HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+                MI355_HIP_TRY(hipMemcpyAsync(&bad, prod.bad_word(), sizeof(bad), hipMemcpyDeviceToHost, s));
                 MI355_HIP_TRY(hipStreamSynchronize(s));
                 if(bad)
                     return aoclsparse_status_invalid_value;
@@ -569,7 +597,7 @@ aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr de
             MI355_HIP_TRY(e1);
             MI355_HIP_TRY(hipMemcpyAsync(d->val, d_cv.ptr, sizeof(T) * (size_t)nnz_c, hipMemcpyDeviceToHost, s));
             if(ptr_on_device) // (full computation: the counts are this product's own, the word is read with the result)
-                MI355_HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+                MI355_HIP_TRY(hipMemcpyAsync(&bad, prod.bad_word(), sizeof(bad), hipMemcpyDeviceToHost, s));
             MI355_HIP_TRY(hipStreamSynchronize(s));
             if(bad) // the row_ptr of *C is not the one stage 1 of THIS product returned (a row ended short of, or beyond, its segment)
                 return aoclsparse_status_invalid_value;

@@ -20,6 +20,9 @@
 // allocates C; stage 2 writes col_ind / val of C at row_ptr_C.  Integer output is bit-exact, fp output
 // bit-identical to the reference's single-thread order.
 //
+// aoclsparse_syrk / aoclsparse_sypr run the same kernel with UPPER = true (only the columns >= i of row i are built) on operands the
+// host lays out in the reference's walk order (sy_sparse_api.cpp); the dense-row path of syrk is aat_dense_row_kernel below.
+//
 // Bound: neither HBM nor MFMA -- irregular, latency/instruction bound; algorithmic traffic is
 // 12 B per entry of A and of the touched B rows + 12 B per entry of C.
 #include "internal.hpp"
@@ -132,7 +135,10 @@ __device__ __forceinline__ void spg_sync()
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 }
 
-template <typename T, bool FILL, int G, int LOGH, int NG, bool GLOBAL>
+//
+// UPPER (syrk / sypr, sypr.hpp:71-73 BUILD_ONLY_U): row i of C keeps the columns >= i only; the entries of B's rows left of that
+// are passed over in both passes (they still take part in the strictly-increasing test, which is about B's row, not about C's).
+template <typename T, bool FILL, int G, int LOGH, int NG, bool GLOBAL, bool UPPER>
 __global__ __launch_bounds__(G *NG) void spgemm_hash_kernel(aoclsparse_int nrows, const aoclsparse_int *__restrict__ rows,
                                                            const SpgHeavy *__restrict__ heavy, int *g_key, int *g_pos, int *g_list,
                                                            T *g_acc, int base_a, const aoclsparse_int *__restrict__ ptr_a,
@@ -226,12 +232,13 @@ __global__ __launch_bounds__(G *NG) void spgemm_hash_kernel(aoclsparse_int nrows
                     prev = carry;
                 carry = __shfl(c, G - 1, G);
                 const unsigned long long bad = spg_group_bits<G>(__ballot(valid && c <= prev), wgrp);
+                const bool               use = valid && (!UPPER || c >= i);
                 if(!bad)
                 {
                     // distinct columns: look up together, append the new ones in lane order
                     int      pos = -1;
                     unsigned h   = hash(c);
-                    if(valid)
+                    if(use)
                         for(;;)
                         {
                             const int key = spg_key<GLOBAL>(&hkey[h]);
@@ -244,7 +251,7 @@ __global__ __launch_bounds__(G *NG) void spgemm_hash_kernel(aoclsparse_int nrows
                             }
                             h = (h + 1) & hmask;
                         }
-                    const bool               isnew = valid && pos < 0;
+                    const bool               isnew = use && pos < 0;
                     const unsigned long long nm    = spg_group_bits<G>(__ballot(isnew), wgrp);
                     if(len + __popcll(nm) > limit) // (uniform inside the group)
                     {
@@ -269,7 +276,7 @@ __global__ __launch_bounds__(G *NG) void spgemm_hash_kernel(aoclsparse_int nrows
                     }
                     else if constexpr(FILL)
                     {
-                        if(valid)
+                        if(use)
                             acc[pos] = sp_fma(va, vb, acc[pos]); // csr2m.cpp:498, contracted
                     }
                     len += __popcll(nm);
@@ -281,6 +288,9 @@ __global__ __launch_bounds__(G *NG) void spgemm_hash_kernel(aoclsparse_int nrows
                     for(int q = 0; q < nv; q++)
                     {
                         const int cq = __shfl(c, q, G);
+                        if constexpr(UPPER)
+                            if(cq < i) // (uniform inside the group)
+                                continue;
                         T         vq = T(0);
                         if constexpr(FILL)
                             vq = spg_shfl(vb, q, G);
@@ -351,14 +361,22 @@ aoclsparse_status launch_spgemm_bin(hipStream_t s, bool fill, int bin, aoclspars
                                     const aoclsparse_int *ptr_a, const aoclsparse_int *ind_a, const T *val_a, int base_b,
                                     const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b, const T *val_b,
                                     const aoclsparse_int *ptr_c, aoclsparse_int *cnt_or_ind_c, T *val_c, bool conj_a, bool conj_b,
-                                    unsigned int *bad)
+                                    bool upper, unsigned int *bad)
 {
     if(nrows <= 0)
         return aoclsparse_status_success;
-#define MI355_SPG(F, G, LOGH, NG)                                                                                               \
-    hipLaunchKernelGGL((spgemm_hash_kernel<T, F, G, LOGH, NG, false>), dim3((unsigned)((nrows + NG - 1) / NG)), dim3(G * NG), 0, s, \
+#define MI355_SPG_U(F, G, LOGH, NG, U)                                                                                             \
+    hipLaunchKernelGGL((spgemm_hash_kernel<T, F, G, LOGH, NG, false, U>), dim3((unsigned)((nrows + NG - 1) / NG)), dim3(G * NG), 0, s, \
                        nrows, rows, (const SpgHeavy *)nullptr, (int *)nullptr, (int *)nullptr, (int *)nullptr, (T *)nullptr, base_a, \
                        ptr_a, ind_a, val_a, base_b, ptr_b, ind_b, val_b, ptr_c, cnt_or_ind_c, val_c, conj_a, conj_b, bad)
+#define MI355_SPG(F, G, LOGH, NG)             \
+    do                                        \
+    {                                         \
+        if(upper)                             \
+            MI355_SPG_U(F, G, LOGH, NG, true);  \
+        else                                  \
+            MI355_SPG_U(F, G, LOGH, NG, false); \
+    } while(0)
     if(fill)
     {
         switch(bin)
@@ -381,6 +399,7 @@ aoclsparse_status launch_spgemm_bin(hipStream_t s, bool fill, int bin, aoclspars
         }
     }
 #undef MI355_SPG
+#undef MI355_SPG_U
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }
@@ -391,18 +410,23 @@ aoclsparse_status launch_spgemm_heavy(hipStream_t s, bool fill, aoclsparse_int n
                                       int *g_list, T *g_acc, int base_a, const aoclsparse_int *ptr_a, const aoclsparse_int *ind_a,
                                       const T *val_a, int base_b, const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b,
                                       const T *val_b, const aoclsparse_int *ptr_c, aoclsparse_int *cnt_or_ind_c, T *val_c,
-                                      bool conj_a, bool conj_b, unsigned int *bad)
+                                      bool conj_a, bool conj_b, bool upper, unsigned int *bad)
 {
     if(nrows <= 0)
         return aoclsparse_status_success;
-    if(fill)
-        hipLaunchKernelGGL((spgemm_hash_kernel<T, true, 64, 0, 1, true>), dim3((unsigned)nrows), dim3(64), 0, s, nrows,
-                           (const aoclsparse_int *)nullptr, heavy, g_key, g_pos, g_list, g_acc, base_a, ptr_a, ind_a, val_a, base_b,
-                           ptr_b, ind_b, val_b, ptr_c, cnt_or_ind_c, val_c, conj_a, conj_b, bad);
+#define MI355_SPG_HEAVY(F, U)                                                                                                    \
+    hipLaunchKernelGGL((spgemm_hash_kernel<T, F, 64, 0, 1, true, U>), dim3((unsigned)nrows), dim3(64), 0, s, nrows,                \
+                       (const aoclsparse_int *)nullptr, heavy, g_key, g_pos, g_list, g_acc, base_a, ptr_a, ind_a, val_a, base_b, \
+                       ptr_b, ind_b, val_b, ptr_c, cnt_or_ind_c, val_c, conj_a, conj_b, bad)
+    if(fill && upper)
+        MI355_SPG_HEAVY(true, true);
+    else if(fill)
+        MI355_SPG_HEAVY(true, false);
+    else if(upper)
+        MI355_SPG_HEAVY(false, true);
     else
-        hipLaunchKernelGGL((spgemm_hash_kernel<T, false, 64, 0, 1, true>), dim3((unsigned)nrows), dim3(64), 0, s, nrows,
-                           (const aoclsparse_int *)nullptr, heavy, g_key, g_pos, g_list, g_acc, base_a, ptr_a, ind_a, val_a, base_b,
-                           ptr_b, ind_b, val_b, ptr_c, cnt_or_ind_c, val_c, conj_a, conj_b, bad);
+        MI355_SPG_HEAVY(false, false);
+#undef MI355_SPG_HEAVY
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }
@@ -695,16 +719,126 @@ int spgemm_bin_of(long long entries, bool fill)
     return SPGEMM_BINS - 1; // tables in the global slab
 }
 
+// ---- aoclsparse_syrk, dense-row path: the upper triangle of A * A^H for a short, wide A (syrk.hpp:46-113) ---------------------------
+// The reference scatters row i of A into a dense row of length n (:92-93) and, for
+// j = i .. m - 1, adds trow[col] * conj(val) over the entries of row j in stored order, entries whose column row i does not hold
+// included (their product is a signed zero); elements that sum to exactly zero are dropped (:101-106).  n is unbounded on this path
+// (m < 3,000, nnz <= 10 m, m < n), so the dense row is replaced by a search: (ptr_s, ind_s, val_s) is A with every row sorted by
+// column, one entry per column (built on the host: at most 30,000 entries; sy_sparse_api.cpp says what a repeated column becomes), and
+// trow[col] is a binary search in row i of it.  One workgroup per row i of C, one thread per j, 256 columns at a time; the kept elements of a chunk take their
+// places by ballot rank, so j ascends as in the reference.  Count pass: cnt[i]; fill pass: the same sums again, written at ptr_c[i].
+__device__ __forceinline__ bool sp_nonzero(double v)
+{
+    return v != 0.0;
+}
+__device__ __forceinline__ bool sp_nonzero(float v)
+{
+    return v != 0.0f;
+}
+template <typename R>
+__device__ __forceinline__ bool sp_nonzero(cplx<R> v)
+{
+    return v.re != R(0) || v.im != R(0);
+}
+
+template <typename T, bool FILL>
+__global__ __launch_bounds__(256) void aat_dense_row_kernel(aoclsparse_int m, int base_a, const aoclsparse_int *__restrict__ ptr_a,
+                                                            const aoclsparse_int *__restrict__ ind_a, const T *__restrict__ val_a,
+                                                            const aoclsparse_int *__restrict__ ptr_s,
+                                                            const aoclsparse_int *__restrict__ ind_s, const T *__restrict__ val_s,
+                                                            const aoclsparse_int *__restrict__ ptr_c, int *__restrict__ cnt,
+                                                            int base_c, aoclsparse_int *__restrict__ ind_c, T *__restrict__ val_c)
+{
+    __shared__ int wave_n[4];
+    const int      i    = blockIdx.x;
+    const int      lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int      sb = ptr_s[i], se = ptr_s[i + 1];
+    int            run = 0, end = 0; // elements kept so far (fill pass: the next free place of the row, and the row's end)
+    if constexpr(FILL)
+        run = ptr_c[i], end = ptr_c[i + 1];
+    for(int j0 = i; j0 < m; j0 += 256) // (uniform trip count: every thread meets the barriers)
+    {
+        const int j = j0 + (int)threadIdx.x;
+        T         c = T(0);
+        if(j < m)
+            for(int k = ptr_a[j] - base_a; k < ptr_a[j + 1] - base_a; k++)
+            {
+                const int col = ind_a[k] - base_a;
+                int       lo = sb, hi = se;
+                while(lo < hi)
+                {
+                    const int mid = (lo + hi) >> 1;
+                    if(ind_s[mid] < col)
+                        lo = mid + 1;
+                    else
+                        hi = mid;
+                }
+                T t = T(0);
+                if(lo < se && ind_s[lo] == col)
+                    t = val_s[lo];
+                c = sp_fma(t, sp_conj(val_a[k], true), c); // syrk.hpp:99
+            }
+        const bool               keep = j < m && sp_nonzero(c);
+        const unsigned long long mk   = __ballot(keep);
+        if(lane == 0)
+            wave_n[w] = __popcll(mk);
+        __syncthreads();
+        int before = 0, all = 0;
+        for(int u = 0; u < 4; u++)
+        {
+            const int nu = wave_n[u];
+            before += u < w ? nu : 0;
+            all += nu;
+        }
+        if constexpr(FILL)
+        {
+            const int at = run + before + __popcll(mk & ((1ull << lane) - 1ull));
+            if(keep && at < end) // (the counts are this call's own: `at < end` always holds)
+            {
+                ind_c[at] = j + base_c;
+                val_c[at] = c;
+            }
+        }
+        run += all;
+        __syncthreads(); // (wave_n is written again by the next chunk)
+    }
+    if constexpr(!FILL)
+        if(threadIdx.x == 0)
+            cnt[i] = run;
+}
+
+template <typename T>
+aoclsparse_status launch_aat_dense_row(hipStream_t s, bool fill, aoclsparse_int m, int base_a, const aoclsparse_int *ptr_a,
+                                       const aoclsparse_int *ind_a, const T *val_a, const aoclsparse_int *ptr_s,
+                                       const aoclsparse_int *ind_s, const T *val_s, const aoclsparse_int *ptr_c, int *cnt,
+                                       int base_c, aoclsparse_int *ind_c, T *val_c)
+{
+    if(m <= 0)
+        return aoclsparse_status_success;
+    if(fill)
+        hipLaunchKernelGGL((aat_dense_row_kernel<T, true>), dim3((unsigned)m), dim3(256), 0, s, m, base_a, ptr_a, ind_a, val_a, ptr_s,
+                           ind_s, val_s, ptr_c, cnt, base_c, ind_c, val_c);
+    else
+        hipLaunchKernelGGL((aat_dense_row_kernel<T, false>), dim3((unsigned)m), dim3(256), 0, s, m, base_a, ptr_a, ind_a, val_a, ptr_s,
+                           ind_s, val_s, ptr_c, cnt, base_c, ind_c, val_c);
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
 #define MI355_SPGEMM_INST(T)                                                                                        \
     template aoclsparse_status launch_spgemm_bin<T>(hipStream_t, bool, int, aoclsparse_int, const aoclsparse_int *, int, \
                                                     const aoclsparse_int *, const aoclsparse_int *, const T *, int, \
                                                     const aoclsparse_int *, const aoclsparse_int *, const T *,      \
-                                                    const aoclsparse_int *, aoclsparse_int *, T *, bool, bool,      \
+                                                    const aoclsparse_int *, aoclsparse_int *, T *, bool, bool, bool, \
                                                     unsigned int *);                                                \
     template aoclsparse_status launch_spgemm_heavy<T>(hipStream_t, bool, aoclsparse_int, const SpgHeavy *, int *, int *, int *, T *, \
                                                       int, const aoclsparse_int *, const aoclsparse_int *, const T *, int,          \
                                                       const aoclsparse_int *, const aoclsparse_int *, const T *,                    \
-                                                      const aoclsparse_int *, aoclsparse_int *, T *, bool, bool, unsigned int *);
+                                                      const aoclsparse_int *, aoclsparse_int *, T *, bool, bool, bool, unsigned int *); \
+    template aoclsparse_status launch_aat_dense_row<T>(hipStream_t, bool, aoclsparse_int, int, const aoclsparse_int *,              \
+                                                       const aoclsparse_int *, const T *, const aoclsparse_int *,                   \
+                                                       const aoclsparse_int *, const T *, const aoclsparse_int *, int *, int,       \
+                                                       aoclsparse_int *, T *);
 MI355_SPGEMM_INST(double)
 MI355_SPGEMM_INST(float)
 MI355_SPGEMM_INST(cdouble)

@@ -1045,6 +1045,17 @@ DLL_PUBLIC aoclsparse_status aoclsparse_zsyrkd(const aoclsparse_operation op, co
                                                aoclsparse_double_complex alpha, aoclsparse_double_complex beta, aoclsparse_double_complex *C,
                                                const aoclsparse_order layout, aoclsparse_int ldc);
 
+/* ---- symmetric products with a sparse result -----------------------------------------------------------------
+ * Replaces library/include/aoclsparse_functions.h:2379 (syrk: *C = the upper triangle of A*A^H for op = none, of A^H*A
+ * otherwise, a new CSR handle in A's index base) and :3096 (sypr: *C = the upper triangle of op(A)*B*op(A)^H, zero-based;
+ * B symmetric / Hermitian, of which only the triangle descrB->fill_mode names is read; request as for aoclsparse_sp2m).
+ * Both dispatch on the handles' value type.  C's arrays are host arrays owned by the handle (aoclsparse_export_?csr,
+ * aoclsparse_destroy).  Complex types with op = transpose: not_implemented. */
+DLL_PUBLIC aoclsparse_status aoclsparse_syrk(const aoclsparse_operation opA, const aoclsparse_matrix A, aoclsparse_matrix *C);
+DLL_PUBLIC aoclsparse_status aoclsparse_sypr(aoclsparse_operation opA, const aoclsparse_matrix A, const aoclsparse_matrix B,
+                                             const aoclsparse_mat_descr descrB, aoclsparse_matrix *C,
+                                             const aoclsparse_request request);
+
 /* ---- sparse x sparse with a dense result, CSR -> dense, sparse sum ------------------------------------------
  * Replaces library/include/aoclsparse_functions.h:2546-2586 (?spmmd), :2674-2720 (?sp2md), :2856-2882 (?add) and
  * library/include/aoclsparse_convert.h:566-610 (?csr2dense).  C / A may be host or device memory. */

@@ -25,6 +25,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--what", default="spmv,csrmm,trsv,cg,next,wider,setup,pcie")
 ap.add_argument("--small", action="store_true", help="skip the two 50-120 M nnz stand-ins")
 ap.add_argument("--sy-out", default=os.path.join(ROOT, "profiles", "r12", "sy_dense_cold.json"), help="where --what sy writes its record")
+ap.add_argument("--sysparse-out", default=os.path.join(ROOT, "profiles", "r14", "sy_sparse_cold.json"),
+                help="where --what sysparse writes its record")
+ap.add_argument("--sysparse-grid", type=int, default=1000, help="grid side of the Laplacian of --what sysparse")
 args = ap.parse_args()
 what = set(args.what.split(","))
 dev = torch.device("cuda", 0)
@@ -526,3 +529,72 @@ if "sy" in what:
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(dict(gpu=torch.cuda.get_device_name(0), grid=g, m=m, nnz=nnz, reps=20, cold="1 GiB read between calls", legs=legs), f, indent=1)
+
+if "sysparse" in what:
+    # aoclsparse_syrk / aoclsparse_sypr next to the call that gave the same entries before them: aoclsparse_sp2m(T, A, N, A), which
+    # builds both triangles of A^T A (not in the default list: --what sysparse).  Cold as above (bench.timed_cold); the events sit
+    # around the whole call, so the host side of a call -- the linked-list walk of syrk / sypr, the analysis, the copy of C into
+    # the handle's host arrays -- is inside the figure.  Every call makes a new C; the one before is destroyed at the start of the
+    # next call, inside its figure, for all three legs alike.
+    from ctypes import POINTER, byref, c_byte, c_int, c_void_p, cast
+
+    from bench import timed_cold
+
+    g = args.sysparse_grid
+    m, rp, ci, v = entry.laplace5(g)
+    nnz = len(v)
+    A = pkg.Matrix(0, m, m, rp, ci, v)
+    Bm = pkg.Matrix(0, m, m, rp.copy(), ci.copy(), v.copy())
+    dB = pkg.Descr(0, pkg.TYPE_SYMMETRIC, pkg.FILL_LOWER)
+    flush = torch.ones(1 << 27, dtype=torch.float64, device=dev)
+    last = c_void_p()
+
+    def fresh():
+        if last:
+            L.aoclsparse_destroy(byref(last))
+        return byref(last)
+
+    def exported():
+        base, mm, nn, nz = c_int(), c_int(), c_int(), c_int()
+        p, i, x = c_void_p(), c_void_p(), c_void_p()
+        assert L.aoclsparse_export_dcsr(last, byref(base), byref(mm), byref(nn), byref(nz), byref(p), byref(i), byref(x)) == 0
+        arr = lambda q, count, dt: np.frombuffer(cast(q, POINTER(c_byte * (count * np.dtype(dt).itemsize))).contents, dt).copy()
+        return arr(p, mm.value + 1, np.int32), arr(i, nz.value, np.int32), arr(x, nz.value, np.float64)
+
+    def keyed(ptr, ind, val, upper):
+        rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+        keep = ind >= rows if upper else np.ones(len(ind), bool)
+        key = rows[keep] * m + ind[keep]
+        order = np.argsort(key, kind="stable")
+        return key[order], val[keep][order]
+
+    legs = {}
+    reps = 10
+
+    def leg(name, fn, **kw):
+        laps = np.array(timed_cold(pkg, fn, reps, flush))
+        legs[name] = dict(ms=round(float(np.median(laps)), 3), min_ms=round(float(laps.min()), 3), max_ms=round(float(laps.max()), 3), **kw)
+        emit(kind="sysparse", op=name, system="5-pt Laplacian grid %d^2" % g, **legs[name])
+
+    fn = lambda: L.aoclsparse_sp2m(pkg.OP_TRANSPOSE, d0.h, A.h, pkg.OP_NONE, d0.h, A.h, pkg.STAGE_FULL, fresh())
+    assert fn() == 0
+    full = exported()
+    want = keyed(*full, True)
+    leg("sp2m(T, A, N, A)", fn, nnz_c=int(len(full[1])))
+    fn = lambda: L.aoclsparse_syrk(pkg.OP_TRANSPOSE, A.h, fresh())
+    assert fn() == 0
+    up = exported()
+    got = keyed(*up, False)
+    # (the Laplacian's entries are small integers: every sum is exact, whatever its order)
+    same = bool(np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and (up[1] >= np.repeat(np.arange(m), np.diff(up[0]))).all())
+    leg("syrk op=T", fn, nnz_c=int(len(up[1])), equals_upper_triangle_of_sp2m=same)
+    fn = lambda: L.aoclsparse_sypr(pkg.OP_TRANSPOSE, A.h, Bm.h, dB.h, fresh(), pkg.STAGE_FULL)
+    assert fn() == 0
+    leg("sypr op=T", fn, nnz_c=int(len(exported()[1])))
+    fresh()
+    out = args.sysparse_out
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(gpu=torch.cuda.get_device_name(0), grid=g, m=m, nnz=nnz, reps=reps, cold="1 GiB read between calls",
+                       timed="hipEvents around the whole call: host walk, analysis and the copy of C to the host included", legs=legs),
+                  f, indent=1)
