@@ -28,7 +28,9 @@
 #include <limits>
 #include <map>
 #include <complex>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace mi355;
@@ -285,32 +287,61 @@ void lartg(T f, T g, T &c, T &s, T &r)
     }
 }
 
-template <typename T>
-struct Solver
+// ---- value types ---------------------------------------------------------------------------------------
+// V is the vector element type of a handle: double, float, cdouble or cfloat.  real_t<V> is the type of its norms, tolerances and
+// rinfo, public_t<V> the (layout-identical) type the C interface and the user callbacks name, type_tag<V> what the handle and the
+// matrix carry.
+template <typename V>
+struct real_of
+{
+    using type = V;
+};
+template <typename R>
+struct real_of<cplx<R>>
+{
+    using type = R;
+};
+template <typename V>
+using real_t = typename real_of<V>::type;
+template <typename V>
+using public_t = std::conditional_t<std::is_same_v<V, cdouble>, aoclsparse_double_complex,
+                                    std::conditional_t<std::is_same_v<V, cfloat>, aoclsparse_float_complex, V>>;
+template <typename V>
+constexpr aoclsparse_matrix_data_type type_tag = std::is_same_v<V, double>    ? aoclsparse_dmat
+                                                 : std::is_same_v<V, float>   ? aoclsparse_smat
+                                                 : std::is_same_v<V, cdouble> ? aoclsparse_zmat
+                                                                              : aoclsparse_cmat;
+
+// ---- solver state --------------------------------------------------------------------------------------
+// What a solver holds whatever its value type (the workspaces are untyped); the handle owns one of these.
+struct SolverBase
 {
     aoclsparse_int n = 0;
-    bool           have_b = false, pinned = false, solving = false;
-    int            method = solver_cg;
+    bool           have_b = false, pinned = false, solving = false, x_dirty = false;
+    int            method = solver_cg, stage = CG_ENTRY, precond = 0;
     Options        opts;
-    VBuf           b, xshadow, red_partial, red_out, coef;
-    // CG (cg_data, aoclsparse_itsol_data.hpp:96-111)
-    VBuf           r, z, p, q, y;
+    VBuf           b, xshadow, red_partial, red_out;
+    VBuf           r, z, p, q, symgs_y; // CG (cg_data, aoclsparse_itsol_data.hpp:96-111) and the scratch of its built-in SymGS
+    VBuf           v, zz; // GMRES (gmres_data, :127-143)
+    aoclsparse_int niter = 0, maxit = 0, j = 0, restart = 0;
+    virtual ~SolverBase() = default;
+};
+
+// Arith<V>: the scalars of the recurrences, the GMRES host arrays and the two state machines in the arithmetic of V.  The primary
+// template is the real one; Arith<cplx<R>> follows below.  Each offers alloc_gmres_host(m) to the shared life cycle of Solver<V>.
+template <typename T>
+struct Arith : SolverBase
+{
     T              alpha = 0, rz = 0, beta = 0, rnorm2 = 0, bnorm2 = 0, brtol = 0, rtol = 0, atol = 0;
     T              rr_last = 0; // r.r of the current residual (what z.r is when there is no preconditioner)
-    int            stage = CG_ENTRY;
-    aoclsparse_int niter = 0, maxit = 0;
-    int            precond = 0;
-    // GMRES (gmres_data, :127-143)
-    VBuf              v, zz;
-    std::vector<T>    h, g, s, c;
-    aoclsparse_int    j = 0, restart = 0;
-    bool              x_dirty = false;
+    VBuf           coef;
+    std::vector<T> h, g, s, c;
 
-    void free_solver_data() // aoclsparse_itsol_data_free(itsol, true)
+    aoclsparse_status alloc_gmres_host(long long m) // may throw std::bad_alloc
     {
-        r.release(), z.release(), p.release(), q.release(), y.release(), v.release(), zz.release();
-        h.clear(), g.clear(), s.clear(), c.clear();
-        stage = CG_ENTRY, niter = 0, j = 0;
+        h.assign((size_t)(m * m), T(0)), g.assign((size_t)m + 1, T(0));
+        c.assign((size_t)m, T(0)), s.assign((size_t)m, T(0));
+        return coef.alloc(sizeof(T) * (size_t)(m + 1), false);
     }
 
     // ---- reductions: result read back through a pinned-free plain copy ----
@@ -328,57 +359,6 @@ struct Solver
         T d = 0;
         MI355_TRY(dots(rt, 1, a, 0, a, &d));
         out = std::sqrt(d);
-        return aoclsparse_status_success;
-    }
-
-    aoclsparse_status init() // aoclsparse_itsol_solver_init (:335-384)
-    {
-        method = opts.reg["iterative method"].key;
-        if(method == solver_cg)
-        {
-            const size_t nb = sizeof(T) * (size_t)n;
-            MI355_TRY(r.alloc(nb, pinned));
-            MI355_TRY(z.alloc(nb, pinned));
-            MI355_TRY(p.alloc(nb, pinned));
-            MI355_TRY(q.alloc(nb, pinned));
-            stage    = CG_ENTRY;
-            precond = opts.reg["cg preconditioner"].key;
-            rtol    = (T)opts.reg["cg rel tolerance"].rval;
-            atol    = (T)opts.reg["cg abs tolerance"].rval;
-            maxit   = (aoclsparse_int)opts.reg["cg iteration limit"].ival;
-        }
-        else
-        {
-            if(v.ptr == nullptr)
-            {
-                restart           = (aoclsparse_int)opts.reg["gmres restart iterations"].ival;
-                const long long m = restart;
-                if((m + 1) * (long long)n > std::numeric_limits<aoclsparse_int>::max()
-                   || m * m > std::numeric_limits<aoclsparse_int>::max())
-                    return aoclsparse_status_invalid_size; // :106-112
-                const size_t kb = sizeof(T) * (size_t)(m + 1) * (size_t)n;
-                MI355_TRY(v.alloc(kb, pinned));
-                MI355_TRY(zz.alloc(kb, pinned));
-                MI355_HIP_TRY(hipMemset(v.ptr, 0, kb));
-                MI355_HIP_TRY(hipMemset(zz.ptr, 0, kb));
-                try
-                {
-                    h.assign((size_t)(m * m), T(0)), g.assign((size_t)m + 1, T(0));
-                    c.assign((size_t)m, T(0)), s.assign((size_t)m, T(0));
-                }
-                catch(const std::bad_alloc &)
-                {
-                    return aoclsparse_status_memory_error;
-                }
-                MI355_TRY(coef.alloc(sizeof(T) * (size_t)(m + 1), false));
-                niter = 0, j = 0;
-            }
-            stage    = GM_ENTRY;
-            precond = opts.reg["gmres preconditioner"].key;
-            rtol    = (T)opts.reg["gmres rel tolerance"].rval;
-            atol    = (T)opts.reg["gmres abs tolerance"].rval;
-            maxit   = (aoclsparse_int)opts.reg["gmres iteration limit"].ival;
-        }
         return aoclsparse_status_success;
     }
 
@@ -693,297 +673,9 @@ struct Solver
         } while(loop);
         return exit_status;
     }
-
-    // aoclsparse_itsol_rci_solve (:481-553); x must be addressable by the GPU
-    aoclsparse_status rci(Runtime &rt, aoclsparse_itsol_rci_job *ircomm, T **u, T **vv, T *x, T *rinfo)
-    {
-        aoclsparse_status st;
-        if(!solving)
-        {
-            st = init();
-            if(st != aoclsparse_status_success)
-            {
-                *ircomm = aoclsparse_rci_stop;
-                return st;
-            }
-            solving     = true;
-            opts.locked = true;
-        }
-        st = method == solver_cg ? cg_step(rt, ircomm, u, vv, x, rinfo) : gmres_step(rt, ircomm, u, vv, x, rinfo);
-        if(st != aoclsparse_status_success)
-            *ircomm = aoclsparse_rci_stop;
-        if(*ircomm == aoclsparse_rci_stop)
-        {
-            solving     = false;
-            opts.locked = false;
-        }
-        return st;
-    }
 };
 
-// aoclsparse_itsol_rci_input (:294-330)
-template <typename T>
-aoclsparse_status set_rhs(Solver<T> &S, aoclsparse_int n, const T *b, bool force_device)
-{
-    if(n < 0)
-        return aoclsparse_status_invalid_value;
-    if(!b)
-        return aoclsparse_status_invalid_pointer;
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    S.free_solver_data();
-    const bool bdev = rt.is_device_pointer(b);
-    S.pinned        = !force_device && !bdev;
-    S.n             = n;
-    MI355_TRY(S.b.alloc(sizeof(T) * (size_t)n, S.pinned));
-    if(n > 0)
-        MI355_HIP_TRY(hipMemcpy(S.b.ptr, b, sizeof(T) * (size_t)n, hipMemcpyDefault));
-    S.have_b  = true;
-    S.solving = false;
-    return aoclsparse_status_success;
-}
-
-// public RCI step: with host workspaces x is shadowed in pinned memory and synchronised around the step
-template <typename T>
-aoclsparse_status rci_public(Solver<T> *S, aoclsparse_itsol_rci_job *ircomm, T **u, T **v, T *x, T *rinfo)
-{
-    if(!ircomm)
-        return aoclsparse_status_invalid_pointer;
-    if(!S)
-    {
-        *ircomm = aoclsparse_rci_stop;
-        return aoclsparse_status_internal_error;
-    }
-    if(!u || !v || !x || !rinfo)
-    {
-        *ircomm = aoclsparse_rci_stop;
-        return aoclsparse_status_invalid_pointer;
-    }
-    if(!S->have_b)
-    {
-        *ircomm = aoclsparse_rci_stop;
-        return aoclsparse_status_invalid_pointer; // rci_input was never called (the reference dereferences b)
-    }
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    T *xd = x;
-    if(S->pinned)
-    {
-        const bool starting = !S->solving;
-        MI355_TRY(S->xshadow.alloc(sizeof(T) * (size_t)S->n, true));
-        xd = S->xshadow.template as<T>();
-        if(starting)
-            std::memcpy(xd, x, sizeof(T) * (size_t)S->n);
-    }
-    S->x_dirty                 = false;
-    const aoclsparse_status st = S->rci(rt, ircomm, u, v, xd, rinfo);
-    if(S->pinned)
-    {
-        (void)hipStreamSynchronize(rt.stream()); // the caller reads u / v / x from the CPU next
-        if(S->x_dirty)
-            std::memcpy(x, xd, sizeof(T) * (size_t)S->n);
-        if(u && *u == xd)
-            *u = x; // GMRES hands x itself out as the mv operand
-    }
-    return st;
-}
-
-// typed access to the executors
-inline aoclsparse_status exec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const double *x, double *y)
-{
-    const double one = 1.0, zero = 0.0;
-    return aoclsparse_dmv(aoclsparse_operation_none, &one, A, d, x, &zero, y);
-}
-inline aoclsparse_status exec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const float *x, float *y)
-{
-    const float one = 1.0f, zero = 0.0f;
-    return aoclsparse_smv(aoclsparse_operation_none, &one, A, d, x, &zero, y);
-}
-inline aoclsparse_status exec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
-                                   const double *b, double *x)
-{
-    return aoclsparse_dtrsv(op, 1.0, A, d, b, x);
-}
-inline aoclsparse_status exec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
-                                   const float *b, float *x)
-{
-    return aoclsparse_strsv(op, 1.0f, A, d, b, x);
-}
-inline aoclsparse_status exec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, double *x, const double *b)
-{
-    double *f = nullptr;
-    return aoclsparse_dilu_smoother(aoclsparse_operation_none, A, d, &f, nullptr, x, b);
-}
-inline aoclsparse_status exec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, float *x, const float *b)
-{
-    float *f = nullptr;
-    return aoclsparse_silu_smoother(aoclsparse_operation_none, A, d, &f, nullptr, x, b);
-}
-
-// the built-in SymGS preconditioner of CG (aoclsparse_itsol_symgs, :390-479): (L+D) y = r, y := D y, (U+D) z = y
-template <typename T>
-aoclsparse_status precond_symgs(Runtime &rt, aoclsparse_matrix A, const aoclsparse_mat_descr descr, const T *r, T *y,
-                                T *z)
-{
-    if(descr->type != aoclsparse_matrix_type_general && descr->type != aoclsparse_matrix_type_symmetric)
-        return aoclsparse_status_invalid_value;
-    if(descr->diag_type == aoclsparse_diag_type_zero)
-        return aoclsparse_status_invalid_value;
-    _aoclsparse_mat_descr d = *descr;
-    d.type                  = aoclsparse_matrix_type_triangular;
-    const bool lower_direct = descr->type == aoclsparse_matrix_type_general || descr->fill_mode == aoclsparse_fill_mode_lower;
-    d.fill_mode             = lower_direct ? aoclsparse_fill_mode_lower : aoclsparse_fill_mode_upper;
-    MI355_TRY(exec_trsv(lower_direct ? aoclsparse_operation_none : aoclsparse_operation_transpose, A, &d, r, y));
-    if(descr->diag_type == aoclsparse_diag_type_non_unit)
-        MI355_TRY(launch_vec_mul<T>(rt.stream(), A->m, A->dev_diag.as<T>(), y)); // diagonal of the clean CSR
-    const bool upper_direct = descr->type == aoclsparse_matrix_type_general || descr->fill_mode == aoclsparse_fill_mode_upper;
-    d.fill_mode             = upper_direct ? aoclsparse_fill_mode_upper : aoclsparse_fill_mode_lower;
-    MI355_TRY(exec_trsv(upper_direct ? aoclsparse_operation_none : aoclsparse_operation_transpose, A, &d, y, z));
-    return aoclsparse_status_success;
-}
-
-// aoclsparse_itsol_solve + aoclsparse_cg_solve / aoclsparse_gmres_solve (:556-630, :1369-1619)
-template <typename T>
-aoclsparse_status solve_direct(Solver<T> *S, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
-                               const T *b, T *x, T *rinfo,
-                               aoclsparse_int precond(aoclsparse_int, aoclsparse_int, const T *, T *, void *),
-                               aoclsparse_int monit(aoclsparse_int, const T *, const T *, T *, void *), void *udata,
-                               aoclsparse_matrix_data_type vt)
-{
-    if(!S)
-        return aoclsparse_status_internal_error;
-    if(!x || !rinfo)
-        return aoclsparse_status_invalid_pointer;
-    for(int i = 0; i < 100; i++)
-        rinfo[i] = T(0);
-    // A TCSR or BSR handle holds no CSR for aoclsparse_csr_csc_optimize to find (solvers/aoclsparse_itsol_functions.hpp:591 ->
-    // analysis/aoclsparse_csr_util.hpp:804-805): not_implemented, as csr_optimize below would answer.  Decided here, before the
-    // device is touched, once the argument checks that come first have passed.
-    if(n >= 0 && b && mat && descr && mat->val_type == vt && holds_no_csr(mat))
-        return aoclsparse_status_not_implemented;
-    MI355_TRY(set_rhs(*S, n, b, true));
-    MI355_TRY(S->init());
-    if(!mat || !descr)
-        return aoclsparse_status_invalid_pointer;
-    if(mat->val_type != vt)
-        return aoclsparse_status_wrong_type;
-    MI355_TRY(csr_optimize(mat));
-    Runtime &rt = Runtime::get();
-
-    if(mat->m != n || mat->n != n)
-        return aoclsparse_status_invalid_size;
-    if(S->method == solver_cg)
-    {
-        if(descr->type != aoclsparse_matrix_type_symmetric || descr->fill_mode != aoclsparse_fill_mode_lower)
-            return aoclsparse_status_invalid_value;
-        if(S->precond == 1 && !precond)
-            return aoclsparse_status_invalid_pointer;
-        if(S->precond == 3)
-        {
-            if((!mat->opt_csr_full_diag && descr->diag_type != aoclsparse_diag_type_unit)
-               || descr->diag_type == aoclsparse_diag_type_zero)
-                return aoclsparse_status_invalid_value;
-            MI355_TRY(S->y.alloc(sizeof(T) * (size_t)n, false));
-        }
-    }
-    else if(S->precond == 1 && !precond)
-        return aoclsparse_status_invalid_pointer;
-
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    // x in HBM for the whole solve
-    const bool xdev = rt.is_device_pointer(x);
-    T         *xd   = x;
-    if(!xdev)
-    {
-        MI355_TRY(S->xshadow.alloc(sizeof(T) * (size_t)n, false));
-        xd = S->xshadow.template as<T>();
-        MI355_HIP_TRY(hipMemcpy(xd, x, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    std::vector<T> hu, hv; // host copies for user callbacks
-    if(precond || monit)
-    {
-        try
-        {
-            hu.resize((size_t)n), hv.resize((size_t)n);
-        }
-        catch(const std::bad_alloc &)
-        {
-            return aoclsparse_status_memory_error;
-        }
-    }
-    auto to_host = [&](std::vector<T> &h, const T *d) -> aoclsparse_status {
-        MI355_HIP_TRY(hipMemcpyAsync(h.data(), d, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, rt.stream()));
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-        return aoclsparse_status_success;
-    };
-
-    S->solving     = true;
-    S->opts.locked = true;
-    aoclsparse_itsol_rci_job ircomm = aoclsparse_rci_start;
-    T                       *u = nullptr, *v = nullptr;
-    aoclsparse_status        exit_status = aoclsparse_status_success, st;
-    auto finish = [&](aoclsparse_status code) {
-        S->solving     = false;
-        S->opts.locked = false;
-        if(!xdev)
-            (void)hipMemcpy(x, xd, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost);
-        return code;
-    };
-    DeviceScope scope;
-    while(ircomm != aoclsparse_rci_stop)
-    {
-        exit_status = S->rci(rt, &ircomm, &u, &v, xd, rinfo);
-        if(exit_status != aoclsparse_status_success && ircomm != aoclsparse_rci_stop)
-            return finish(exit_status);
-        switch(ircomm)
-        {
-        case aoclsparse_rci_mv:
-            if(exec_mv(mat, descr, u, v) != aoclsparse_status_success)
-                return finish(aoclsparse_status_internal_error);
-            break;
-        case aoclsparse_rci_precond:
-            if(S->precond == 1)
-            {
-                st = to_host(hu, u);
-                if(st != aoclsparse_status_success)
-                    return finish(st);
-                if(precond(0, n, hu.data(), hv.data(), udata) != 0)
-                    ircomm = aoclsparse_rci_interrupt;
-                if(hipMemcpy(v, hv.data(), sizeof(T) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
-                    return finish(aoclsparse_status_internal_error);
-            }
-            else if(S->method == solver_cg && S->precond == 3)
-            {
-                if(precond_symgs<T>(rt, mat, descr, u, S->y.template as<T>(), v) != aoclsparse_status_success)
-                    return finish(aoclsparse_status_internal_error);
-            }
-            else if(S->method == solver_gmres && S->precond == 2)
-                (void)exec_ilu(mat, descr, v, u); // status ignored by the reference as well (:1589-1594)
-            else if(launch_vec_copy<T>(rt.stream(), n, u, v) != aoclsparse_status_success)
-                return finish(aoclsparse_status_internal_error);
-            break;
-        case aoclsparse_rci_stopping_criterion:
-            if(monit)
-            {
-                // CG hands the residual out as u (v = nullptr); GMRES leaves the last operands.  The callback
-                // gets host copies: (x, r) here, which is what its documented signature promises.
-                st = to_host(hu, xd);
-                if(st == aoclsparse_status_success && S->method == solver_cg)
-                    st = to_host(hv, S->r.template as<T>());
-                if(st != aoclsparse_status_success)
-                    return finish(st);
-                if(monit(n, hu.data(), S->method == solver_cg ? hv.data() : nullptr, rinfo, udata) != 0)
-                    ircomm = aoclsparse_rci_interrupt;
-            }
-            break;
-        default:
-            break;
-        }
-    }
-    return finish(exit_status);
-}
-
-// ==== complex handles (aoclsparse_itsol_{c,z}_*) ==========================================================
+// ==== complex arithmetic (aoclsparse_itsol_{c,z}_*) =======================================================
 // The same two state machines with complex vectors (itsol_functions.hpp is one template over T).  CG: the products
 // r.z and p.q are the UNCONJUGATED sums the reference forms (:786-812), i.e. the conjugate-orthogonal CG for complex
 // SYMMETRIC matrices; norms and tolerances are real (tolerance_t<T>).  GMRES deviates on purpose: the reference stores
@@ -993,8 +685,8 @@ aoclsparse_status solve_direct(Solver<T> *S, aoclsparse_int n, aoclsparse_matrix
 // ILU(0)); restated literally it diverges on a general complex matrix.  Here h(i,j) = v_i^H w, the rotation is
 // [c s; -conj(s) c] from ?lartg on (h(j,j), |w|) and x += sum y_i v_i, which reproduces the reference wherever it
 // converges.  Vector steps are the generic complex kernels of complex_kernels.hip, one reduction read back per
-// scalar: correctness path, not tuned.  Preconditioners: none, user, ILU(0) for GMRES; the built-in
-// SymGS of CG is not offered for complex handles (not_implemented).
+// scalar: correctness path, not tuned.  Preconditioners as for real handles: none, user, the built-in
+// SymGS for CG and ILU(0) for GMRES.
 template <typename R>
 void clartg(std::complex<R> f, std::complex<R> g, R &c, std::complex<R> &s, std::complex<R> &r)
 {
@@ -1031,30 +723,24 @@ void clartg(std::complex<R> f, std::complex<R> g, R &c, std::complex<R> &s, std:
 }
 
 template <typename R>
-struct CSolver
+struct Arith<cplx<R>> : SolverBase
 {
     using C  = cplx<R>;
     using Cs = std::complex<R>;
-    aoclsparse_int n = 0;
-    bool           have_b = false, pinned = false, solving = false, x_dirty = false;
-    int            method = solver_cg, stage = CG_ENTRY, precond = 0;
-    Options        opts;
-    VBuf           b, xshadow, red_partial, red_out, r, z, p, q, v, zz, symgs_y;
-    Cs             alpha = 0, rz = 0, beta = 0;
-    R              rnorm2 = 0, bnorm2 = 0, brtol = 0, rtol = 0, atol = 0;
-    aoclsparse_int niter = 0, maxit = 0, j = 0, restart = 0;
+    Cs              alpha = 0, rz = 0, beta = 0;
+    R               rnorm2 = 0, bnorm2 = 0, brtol = 0, rtol = 0, atol = 0;
     std::vector<Cs> h, g, s;
     std::vector<R>  c;
 
+    aoclsparse_status alloc_gmres_host(long long m) // may throw std::bad_alloc
+    {
+        h.assign((size_t)(m * m), Cs(0)), g.assign((size_t)m + 1, Cs(0));
+        s.assign((size_t)m, Cs(0)), c.assign((size_t)m, R(0));
+        return aoclsparse_status_success;
+    }
     static C dev(Cs v)
     {
         return C(v.real(), v.imag());
-    }
-    void free_solver_data()
-    {
-        r.release(), z.release(), p.release(), q.release(), v.release(), zz.release();
-        h.clear(), g.clear(), s.clear(), c.clear();
-        stage = CG_ENTRY, niter = 0, j = 0;
     }
     aoclsparse_status dot(Runtime &rt, const C *x, const C *y, bool conj_x, Cs &out)
     {
@@ -1077,53 +763,6 @@ struct CSolver
     aoclsparse_status axpby(Runtime &rt, Cs a, const C *x, Cs bb, const C *y, C *w)
     {
         return launch_caxpby<R>(rt.stream(), n, dev(a), x, dev(bb), y, w);
-    }
-    aoclsparse_status init()
-    {
-        method = opts.reg["iterative method"].key;
-        const size_t nb = sizeof(C) * (size_t)n;
-        if(method == solver_cg)
-        {
-            MI355_TRY(r.alloc(nb, pinned));
-            MI355_TRY(z.alloc(nb, pinned));
-            MI355_TRY(p.alloc(nb, pinned));
-            MI355_TRY(q.alloc(nb, pinned));
-            stage    = CG_ENTRY;
-            precond = opts.reg["cg preconditioner"].key;
-            rtol = (R)opts.reg["cg rel tolerance"].rval, atol = (R)opts.reg["cg abs tolerance"].rval;
-            maxit = (aoclsparse_int)opts.reg["cg iteration limit"].ival;
-        }
-        else
-        {
-            if(v.ptr == nullptr)
-            {
-                restart           = (aoclsparse_int)opts.reg["gmres restart iterations"].ival;
-                const long long m = restart;
-                if((m + 1) * (long long)n > std::numeric_limits<aoclsparse_int>::max()
-                   || m * m > std::numeric_limits<aoclsparse_int>::max())
-                    return aoclsparse_status_invalid_size;
-                const size_t kb = nb * (size_t)(m + 1);
-                MI355_TRY(v.alloc(kb, pinned));
-                MI355_TRY(zz.alloc(kb, pinned));
-                MI355_HIP_TRY(hipMemset(v.ptr, 0, kb));
-                MI355_HIP_TRY(hipMemset(zz.ptr, 0, kb));
-                try
-                {
-                    h.assign((size_t)(m * m), Cs(0)), g.assign((size_t)m + 1, Cs(0));
-                    s.assign((size_t)m, Cs(0)), c.assign((size_t)m, R(0));
-                }
-                catch(const std::bad_alloc &)
-                {
-                    return aoclsparse_status_memory_error;
-                }
-                niter = 0, j = 0;
-            }
-            stage    = GM_ENTRY;
-            precond = opts.reg["gmres preconditioner"].key;
-            rtol = (R)opts.reg["gmres rel tolerance"].rval, atol = (R)opts.reg["gmres abs tolerance"].rval;
-            maxit = (aoclsparse_int)opts.reg["gmres iteration limit"].ival;
-        }
-        return aoclsparse_status_success;
     }
     static bool tiny(Cs v)
     {
@@ -1391,11 +1030,68 @@ struct CSolver
         } while(loop);
         return exit_status;
     }
+};
 
-    aoclsparse_status rci(Runtime &rt, aoclsparse_itsol_rci_job *ircomm, C **u, C **vv, C *x, R *rinfo)
+// ---- life cycle, the same for every value type -----------------------------------------------------------
+template <typename V>
+struct Solver : Arith<V>
+{
+    using R = real_t<V>;
+
+    void free_solver_data() // aoclsparse_itsol_data_free(itsol, true)
+    {
+        for(VBuf *w : {&this->r, &this->z, &this->p, &this->q, &this->symgs_y, &this->v, &this->zz})
+            w->release();
+        this->h.clear(), this->g.clear(), this->s.clear(), this->c.clear();
+        this->stage = CG_ENTRY, this->niter = 0, this->j = 0;
+    }
+
+    aoclsparse_status init() // aoclsparse_itsol_solver_init (:335-384)
+    {
+        auto &reg        = this->opts.reg;
+        this->method     = reg["iterative method"].key;
+        const bool   cg  = this->method == solver_cg;
+        const size_t nb  = sizeof(V) * (size_t)this->n;
+        if(cg)
+        {
+            for(VBuf *w : {&this->r, &this->z, &this->p, &this->q})
+                MI355_TRY(w->alloc(nb, this->pinned));
+        }
+        else if(this->v.ptr == nullptr)
+        {
+            this->restart     = (aoclsparse_int)reg["gmres restart iterations"].ival;
+            const long long m = this->restart;
+            if((m + 1) * (long long)this->n > std::numeric_limits<aoclsparse_int>::max()
+               || m * m > std::numeric_limits<aoclsparse_int>::max())
+                return aoclsparse_status_invalid_size; // :106-112
+            const size_t kb = nb * (size_t)(m + 1);
+            MI355_TRY(this->v.alloc(kb, this->pinned));
+            MI355_TRY(this->zz.alloc(kb, this->pinned));
+            MI355_HIP_TRY(hipMemset(this->v.ptr, 0, kb));
+            MI355_HIP_TRY(hipMemset(this->zz.ptr, 0, kb));
+            try
+            {
+                MI355_TRY(this->alloc_gmres_host(m));
+            }
+            catch(const std::bad_alloc &)
+            {
+                return aoclsparse_status_memory_error;
+            }
+            this->niter = 0, this->j = 0;
+        }
+        this->stage   = cg ? (int)CG_ENTRY : (int)GM_ENTRY;
+        this->precond = reg[cg ? "cg preconditioner" : "gmres preconditioner"].key;
+        this->rtol    = (R)reg[cg ? "cg rel tolerance" : "gmres rel tolerance"].rval;
+        this->atol    = (R)reg[cg ? "cg abs tolerance" : "gmres abs tolerance"].rval;
+        this->maxit   = (aoclsparse_int)reg[cg ? "cg iteration limit" : "gmres iteration limit"].ival;
+        return aoclsparse_status_success;
+    }
+
+    // aoclsparse_itsol_rci_solve (:481-553); x must be addressable by the GPU
+    aoclsparse_status rci(Runtime &rt, aoclsparse_itsol_rci_job *ircomm, V **u, V **vv, V *x, R *rinfo)
     {
         aoclsparse_status st;
-        if(!solving)
+        if(!this->solving)
         {
             st = init();
             if(st != aoclsparse_status_success)
@@ -1403,19 +1099,20 @@ struct CSolver
                 *ircomm = aoclsparse_rci_stop;
                 return st;
             }
-            solving = true, opts.locked = true;
+            this->solving = true, this->opts.locked = true;
         }
-        st = method == solver_cg ? cg_step(rt, ircomm, u, vv, x, rinfo) : gmres_step(rt, ircomm, u, vv, x, rinfo);
+        st = this->method == solver_cg ? this->cg_step(rt, ircomm, u, vv, x, rinfo) : this->gmres_step(rt, ircomm, u, vv, x, rinfo);
         if(st != aoclsparse_status_success)
             *ircomm = aoclsparse_rci_stop;
         if(*ircomm == aoclsparse_rci_stop)
-            solving = false, opts.locked = false;
+            this->solving = false, this->opts.locked = false;
         return st;
     }
 };
 
-template <typename R>
-aoclsparse_status cset_rhs(CSolver<R> &S, aoclsparse_int n, const cplx<R> *b, bool force_device)
+// aoclsparse_itsol_rci_input (:294-330)
+template <typename V>
+aoclsparse_status set_rhs(Solver<V> &S, aoclsparse_int n, const V *b, bool force_device)
 {
     if(n < 0)
         return aoclsparse_status_invalid_value;
@@ -1424,20 +1121,21 @@ aoclsparse_status cset_rhs(CSolver<R> &S, aoclsparse_int n, const cplx<R> *b, bo
     Runtime &rt = Runtime::get();
     MI355_TRY(rt.init());
     S.free_solver_data();
-    S.pinned = !force_device && !rt.is_device_pointer(b);
-    S.n      = n;
-    MI355_TRY(S.b.alloc(sizeof(cplx<R>) * (size_t)n, S.pinned));
+    const bool bdev = rt.is_device_pointer(b);
+    S.pinned        = !force_device && !bdev;
+    S.n             = n;
+    MI355_TRY(S.b.alloc(sizeof(V) * (size_t)n, S.pinned));
     if(n > 0)
-        MI355_HIP_TRY(hipMemcpy(S.b.ptr, b, sizeof(cplx<R>) * (size_t)n, hipMemcpyDefault));
-    S.have_b = true, S.solving = false;
+        MI355_HIP_TRY(hipMemcpy(S.b.ptr, b, sizeof(V) * (size_t)n, hipMemcpyDefault));
+    S.have_b  = true;
+    S.solving = false;
     return aoclsparse_status_success;
 }
 
-template <typename R>
-aoclsparse_status crci_public(CSolver<R> *S, aoclsparse_itsol_rci_job *ircomm, cplx<R> **u, cplx<R> **v, cplx<R> *x,
-                              R *rinfo)
+// public RCI step: with host workspaces x is shadowed in pinned memory and synchronised around the step
+template <typename V>
+aoclsparse_status rci_public(Solver<V> *S, aoclsparse_itsol_rci_job *ircomm, V **u, V **v, V *x, real_t<V> *rinfo)
 {
-    using C = cplx<R>;
     if(!ircomm)
         return aoclsparse_status_invalid_pointer;
     if(!S)
@@ -1453,77 +1151,127 @@ aoclsparse_status crci_public(CSolver<R> *S, aoclsparse_itsol_rci_job *ircomm, c
     if(!S->have_b)
     {
         *ircomm = aoclsparse_rci_stop;
-        return aoclsparse_status_invalid_pointer;
+        return aoclsparse_status_invalid_pointer; // rci_input was never called (the reference dereferences b)
     }
     Runtime &rt = Runtime::get();
     MI355_TRY(rt.init());
-    C *xd = x;
+    V *xd = x;
     if(S->pinned)
     {
         const bool starting = !S->solving;
-        MI355_TRY(S->xshadow.alloc(sizeof(C) * (size_t)S->n, true));
-        xd = S->xshadow.template as<C>();
+        MI355_TRY(S->xshadow.alloc(sizeof(V) * (size_t)S->n, true));
+        xd = S->xshadow.template as<V>();
         if(starting)
-            std::memcpy(xd, x, sizeof(C) * (size_t)S->n);
+            std::memcpy(xd, x, sizeof(V) * (size_t)S->n);
     }
     S->x_dirty                 = false;
     const aoclsparse_status st = S->rci(rt, ircomm, u, v, xd, rinfo);
     if(S->pinned)
     {
-        (void)hipStreamSynchronize(rt.stream());
+        (void)hipStreamSynchronize(rt.stream()); // the caller reads u / v / x from the CPU next
         if(S->x_dirty)
-            std::memcpy(x, xd, sizeof(C) * (size_t)S->n);
+            std::memcpy(x, xd, sizeof(V) * (size_t)S->n);
         if(*u == xd)
-            *u = x;
+            *u = x; // GMRES hands x itself out as the mv operand
     }
     return st;
 }
 
-template <typename R>
-aoclsparse_status cexec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const cplx<R> *x, cplx<R> *y);
-template <>
-aoclsparse_status cexec_mv<double>(aoclsparse_matrix A, const aoclsparse_mat_descr d, const cdouble *x, cdouble *y)
+// typed access to the executors and to the two vector steps the drivers launch themselves
+inline aoclsparse_status exec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const double *x, double *y)
+{
+    const double one = 1.0, zero = 0.0;
+    return aoclsparse_dmv(aoclsparse_operation_none, &one, A, d, x, &zero, y);
+}
+inline aoclsparse_status exec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const float *x, float *y)
+{
+    const float one = 1.0f, zero = 0.0f;
+    return aoclsparse_smv(aoclsparse_operation_none, &one, A, d, x, &zero, y);
+}
+inline aoclsparse_status exec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
+                                   const double *b, double *x)
+{
+    return aoclsparse_dtrsv(op, 1.0, A, d, b, x);
+}
+inline aoclsparse_status exec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
+                                   const float *b, float *x)
+{
+    return aoclsparse_strsv(op, 1.0f, A, d, b, x);
+}
+inline aoclsparse_status exec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, double *x, const double *b)
+{
+    double *f = nullptr;
+    return aoclsparse_dilu_smoother(aoclsparse_operation_none, A, d, &f, nullptr, x, b);
+}
+inline aoclsparse_status exec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, float *x, const float *b)
+{
+    float *f = nullptr;
+    return aoclsparse_silu_smoother(aoclsparse_operation_none, A, d, &f, nullptr, x, b);
+}
+
+inline aoclsparse_status exec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const cdouble *x, cdouble *y)
 {
     const aoclsparse_double_complex one{1.0, 0.0}, zero{0.0, 0.0};
     return aoclsparse_zmv(aoclsparse_operation_none, &one, A, d, reinterpret_cast<const aoclsparse_double_complex *>(x), &zero,
                           reinterpret_cast<aoclsparse_double_complex *>(y));
 }
-template <>
-aoclsparse_status cexec_mv<float>(aoclsparse_matrix A, const aoclsparse_mat_descr d, const cfloat *x, cfloat *y)
+inline aoclsparse_status exec_mv(aoclsparse_matrix A, const aoclsparse_mat_descr d, const cfloat *x, cfloat *y)
 {
     const aoclsparse_float_complex one{1.0f, 0.0f}, zero{0.0f, 0.0f};
     return aoclsparse_cmv(aoclsparse_operation_none, &one, A, d, reinterpret_cast<const aoclsparse_float_complex *>(x), &zero,
                           reinterpret_cast<aoclsparse_float_complex *>(y));
 }
-inline aoclsparse_status cexec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, cdouble *x, const cdouble *b)
+inline aoclsparse_status exec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
+                                   const cdouble *b, cdouble *x)
+{
+    return aoclsparse_ztrsv(op, aoclsparse_double_complex{1.0, 0.0}, A, d, reinterpret_cast<const aoclsparse_double_complex *>(b),
+                            reinterpret_cast<aoclsparse_double_complex *>(x));
+}
+inline aoclsparse_status exec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
+                                   const cfloat *b, cfloat *x)
+{
+    return aoclsparse_ctrsv(op, aoclsparse_float_complex{1.0f, 0.0f}, A, d, reinterpret_cast<const aoclsparse_float_complex *>(b),
+                            reinterpret_cast<aoclsparse_float_complex *>(x));
+}
+inline aoclsparse_status exec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, cdouble *x, const cdouble *b)
 {
     aoclsparse_double_complex *f = nullptr;
     return aoclsparse_zilu_smoother(aoclsparse_operation_none, A, d, &f, nullptr, reinterpret_cast<aoclsparse_double_complex *>(x),
                                     reinterpret_cast<const aoclsparse_double_complex *>(b));
 }
-inline aoclsparse_status cexec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, cfloat *x, const cfloat *b)
+inline aoclsparse_status exec_ilu(aoclsparse_matrix A, const aoclsparse_mat_descr d, cfloat *x, const cfloat *b)
 {
     aoclsparse_float_complex *f = nullptr;
     return aoclsparse_cilu_smoother(aoclsparse_operation_none, A, d, &f, nullptr, reinterpret_cast<aoclsparse_float_complex *>(x),
                                     reinterpret_cast<const aoclsparse_float_complex *>(b));
 }
 
-inline aoclsparse_status cexec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
-                                    const cdouble *b, cdouble *x)
+// v = u
+template <typename T>
+aoclsparse_status vec_copy(hipStream_t s, aoclsparse_int n, const T *u, T *v)
 {
-    return aoclsparse_ztrsv(op, aoclsparse_double_complex{1.0, 0.0}, A, d, reinterpret_cast<const aoclsparse_double_complex *>(b),
-                            reinterpret_cast<aoclsparse_double_complex *>(x));
+    return launch_vec_copy<T>(s, n, u, v);
 }
-inline aoclsparse_status cexec_trsv(aoclsparse_operation op, aoclsparse_matrix A, const aoclsparse_mat_descr d,
-                                    const cfloat *b, cfloat *x)
-{
-    return aoclsparse_ctrsv(op, aoclsparse_float_complex{1.0f, 0.0f}, A, d, reinterpret_cast<const aoclsparse_float_complex *>(b),
-                            reinterpret_cast<aoclsparse_float_complex *>(x));
-}
-// the built-in SymGS preconditioner of CG for complex handles: precond_symgs with complex solves and scale
 template <typename R>
-aoclsparse_status cprecond_symgs(Runtime &rt, aoclsparse_matrix A, const aoclsparse_mat_descr descr, const cplx<R> *r,
-                                 cplx<R> *y, cplx<R> *z)
+aoclsparse_status vec_copy(hipStream_t s, aoclsparse_int n, const cplx<R> *u, cplx<R> *v)
+{
+    return launch_caxpby<R>(s, n, cplx<R>(R(1), R(0)), u, cplx<R>(R(0), R(0)), nullptr, v);
+}
+// y := d .* y
+template <typename T>
+aoclsparse_status vec_mul(hipStream_t s, aoclsparse_int n, const T *d, T *y)
+{
+    return launch_vec_mul<T>(s, n, d, y);
+}
+template <typename R>
+aoclsparse_status vec_mul(hipStream_t s, aoclsparse_int n, const cplx<R> *d, cplx<R> *y)
+{
+    return launch_cvec_mul<R>(s, n, d, y);
+}
+
+// the built-in SymGS preconditioner of CG (aoclsparse_itsol_symgs, :390-479): (L+D) y = r, y := D y, (U+D) z = y
+template <typename V>
+aoclsparse_status precond_symgs(Runtime &rt, aoclsparse_matrix A, const aoclsparse_mat_descr descr, const V *r, V *y, V *z)
 {
     if(descr->type != aoclsparse_matrix_type_general && descr->type != aoclsparse_matrix_type_symmetric)
         return aoclsparse_status_invalid_value;
@@ -1533,37 +1281,40 @@ aoclsparse_status cprecond_symgs(Runtime &rt, aoclsparse_matrix A, const aoclspa
     d.type                  = aoclsparse_matrix_type_triangular;
     const bool lower_direct = descr->type == aoclsparse_matrix_type_general || descr->fill_mode == aoclsparse_fill_mode_lower;
     d.fill_mode             = lower_direct ? aoclsparse_fill_mode_lower : aoclsparse_fill_mode_upper;
-    MI355_TRY(cexec_trsv(lower_direct ? aoclsparse_operation_none : aoclsparse_operation_transpose, A, &d, r, y));
+    MI355_TRY(exec_trsv(lower_direct ? aoclsparse_operation_none : aoclsparse_operation_transpose, A, &d, r, y));
     if(descr->diag_type == aoclsparse_diag_type_non_unit)
-        MI355_TRY(launch_cvec_mul<R>(rt.stream(), A->m, A->dev_diag.as<cplx<R>>(), y));
+        MI355_TRY(vec_mul(rt.stream(), A->m, A->dev_diag.as<V>(), y)); // diagonal of the clean CSR
     const bool upper_direct = descr->type == aoclsparse_matrix_type_general || descr->fill_mode == aoclsparse_fill_mode_upper;
     d.fill_mode             = upper_direct ? aoclsparse_fill_mode_upper : aoclsparse_fill_mode_lower;
-    MI355_TRY(cexec_trsv(upper_direct ? aoclsparse_operation_none : aoclsparse_operation_transpose, A, &d, y, z));
+    MI355_TRY(exec_trsv(upper_direct ? aoclsparse_operation_none : aoclsparse_operation_transpose, A, &d, y, z));
     return aoclsparse_status_success;
 }
 
-// aoclsparse_itsol_solve for complex handles: the loop of solve_direct with complex operands.  PT is the public complex
-// struct of the callbacks (layout-identical to cplx<R>).
-template <typename R, typename PT>
-aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
-                                const cplx<R> *b, cplx<R> *x, R *rinfo,
-                                aoclsparse_int precond(aoclsparse_int, aoclsparse_int, const PT *, PT *, void *),
-                                aoclsparse_int monit(aoclsparse_int, const PT *, const PT *, R *, void *), void *udata,
-                                aoclsparse_matrix_data_type vt)
+// the user callbacks of the direct interface, as the C interface declares them for a handle of value type V
+template <typename V>
+using precond_fn = aoclsparse_int(aoclsparse_int, aoclsparse_int, const public_t<V> *, public_t<V> *, void *);
+template <typename V>
+using monit_fn = aoclsparse_int(aoclsparse_int, const public_t<V> *, const public_t<V> *, real_t<V> *, void *);
+
+// aoclsparse_itsol_solve + aoclsparse_cg_solve / aoclsparse_gmres_solve (:556-630, :1369-1619)
+template <typename V>
+aoclsparse_status solve_direct(Solver<V> *S, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
+                               const V *b, V *x, real_t<V> *rinfo, precond_fn<V> *precond, monit_fn<V> *monit, void *udata)
 {
-    using C = cplx<R>;
+    using PT                             = public_t<V>; // what the callbacks call a V
+    const aoclsparse_matrix_data_type vt = type_tag<V>;
     if(!S)
         return aoclsparse_status_internal_error;
     if(!x || !rinfo)
         return aoclsparse_status_invalid_pointer;
     for(int i = 0; i < 100; i++)
-        rinfo[i] = R(0);
+        rinfo[i] = real_t<V>(0);
     // A TCSR or BSR handle holds no CSR for aoclsparse_csr_csc_optimize to find (solvers/aoclsparse_itsol_functions.hpp:591 ->
     // analysis/aoclsparse_csr_util.hpp:804-805): not_implemented, as csr_optimize below would answer.  Decided here, before the
     // device is touched, once the argument checks that come first have passed.
     if(n >= 0 && b && mat && descr && mat->val_type == vt && holds_no_csr(mat))
         return aoclsparse_status_not_implemented;
-    MI355_TRY(cset_rhs(*S, n, b, true));
+    MI355_TRY(set_rhs(*S, n, b, true));
     MI355_TRY(S->init());
     if(!mat || !descr)
         return aoclsparse_status_invalid_pointer;
@@ -1571,6 +1322,7 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
         return aoclsparse_status_wrong_type;
     MI355_TRY(csr_optimize(mat));
     Runtime &rt = Runtime::get();
+
     if(mat->m != n || mat->n != n)
         return aoclsparse_status_invalid_size;
     if(S->method == solver_cg)
@@ -1582,21 +1334,23 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
             if((!mat->opt_csr_full_diag && descr->diag_type != aoclsparse_diag_type_unit)
                || descr->diag_type == aoclsparse_diag_type_zero)
                 return aoclsparse_status_invalid_value;
-            MI355_TRY(S->symgs_y.alloc(sizeof(C) * (size_t)n, false));
+            MI355_TRY(S->symgs_y.alloc(sizeof(V) * (size_t)n, false));
         }
     }
     if(S->precond == 1 && !precond)
         return aoclsparse_status_invalid_pointer;
+
     std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    // x in HBM for the whole solve
     const bool xdev = rt.is_device_pointer(x);
-    C         *xd   = x;
+    V         *xd   = x;
     if(!xdev)
     {
-        MI355_TRY(S->xshadow.alloc(sizeof(C) * (size_t)n, false));
-        xd = S->xshadow.template as<C>();
-        MI355_HIP_TRY(hipMemcpy(xd, x, sizeof(C) * (size_t)n, hipMemcpyHostToDevice));
+        MI355_TRY(S->xshadow.alloc(sizeof(V) * (size_t)n, false));
+        xd = S->xshadow.template as<V>();
+        MI355_HIP_TRY(hipMemcpy(xd, x, sizeof(V) * (size_t)n, hipMemcpyHostToDevice));
     }
-    std::vector<C> hu, hv;
+    std::vector<V> hu, hv; // host copies for user callbacks
     if(precond || monit)
     {
         try
@@ -1608,19 +1362,22 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
             return aoclsparse_status_memory_error;
         }
     }
-    auto to_host = [&](std::vector<C> &hh, const C *d) -> aoclsparse_status {
-        MI355_HIP_TRY(hipMemcpyAsync(hh.data(), d, sizeof(C) * (size_t)n, hipMemcpyDeviceToHost, rt.stream()));
+    auto to_host = [&](std::vector<V> &h, const V *d) -> aoclsparse_status {
+        MI355_HIP_TRY(hipMemcpyAsync(h.data(), d, sizeof(V) * (size_t)n, hipMemcpyDeviceToHost, rt.stream()));
         MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
         return aoclsparse_status_success;
     };
-    S->solving = true, S->opts.locked = true;
+
+    S->solving     = true;
+    S->opts.locked = true;
     aoclsparse_itsol_rci_job ircomm = aoclsparse_rci_start;
-    C                       *u = nullptr, *v = nullptr;
+    V                       *u = nullptr, *v = nullptr;
     aoclsparse_status        exit_status = aoclsparse_status_success, st;
     auto finish = [&](aoclsparse_status code) {
-        S->solving = false, S->opts.locked = false;
+        S->solving     = false;
+        S->opts.locked = false;
         if(!xdev)
-            (void)hipMemcpy(x, xd, sizeof(C) * (size_t)n, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(x, xd, sizeof(V) * (size_t)n, hipMemcpyDeviceToHost);
         return code;
     };
     DeviceScope scope;
@@ -1632,7 +1389,7 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
         switch(ircomm)
         {
         case aoclsparse_rci_mv:
-            if(cexec_mv<R>(mat, descr, u, v) != aoclsparse_status_success)
+            if(exec_mv(mat, descr, u, v) != aoclsparse_status_success)
                 return finish(aoclsparse_status_internal_error);
             break;
         case aoclsparse_rci_precond:
@@ -1643,25 +1400,27 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
                     return finish(st);
                 if(precond(0, n, reinterpret_cast<const PT *>(hu.data()), reinterpret_cast<PT *>(hv.data()), udata) != 0)
                     ircomm = aoclsparse_rci_interrupt;
-                if(hipMemcpy(v, hv.data(), sizeof(C) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
+                if(hipMemcpy(v, hv.data(), sizeof(V) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
                     return finish(aoclsparse_status_internal_error);
             }
             else if(S->method == solver_cg && S->precond == 3)
             {
-                if(cprecond_symgs<R>(rt, mat, descr, u, S->symgs_y.template as<C>(), v) != aoclsparse_status_success)
+                if(precond_symgs<V>(rt, mat, descr, u, S->symgs_y.template as<V>(), v) != aoclsparse_status_success)
                     return finish(aoclsparse_status_internal_error);
             }
             else if(S->method == solver_gmres && S->precond == 2)
-                (void)cexec_ilu(mat, descr, v, u);
-            else if(S->axpby(rt, std::complex<R>(1), u, std::complex<R>(0), nullptr, v) != aoclsparse_status_success)
+                (void)exec_ilu(mat, descr, v, u); // status ignored by the reference as well (:1589-1594)
+            else if(vec_copy(rt.stream(), n, u, v) != aoclsparse_status_success)
                 return finish(aoclsparse_status_internal_error);
             break;
         case aoclsparse_rci_stopping_criterion:
             if(monit)
             {
+                // CG hands the residual out as u (v = nullptr); GMRES leaves the last operands.  The callback
+                // gets host copies: (x, r) here, which is what its documented signature promises.
                 st = to_host(hu, xd);
                 if(st == aoclsparse_status_success && S->method == solver_cg)
-                    st = to_host(hv, S->r.template as<C>());
+                    st = to_host(hv, S->r.template as<V>());
                 if(st != aoclsparse_status_success)
                     return finish(st);
                 if(monit(n, reinterpret_cast<const PT *>(hu.data()),
@@ -1682,51 +1441,97 @@ aoclsparse_status csolve_direct(CSolver<R> *S, aoclsparse_int n, aoclsparse_matr
 struct _aoclsparse_itsol_handle
 {
     aoclsparse_matrix_data_type type = aoclsparse_dmat;
-    Solver<float>              *s    = nullptr;
-    Solver<double>             *d    = nullptr;
-    CSolver<float>             *c    = nullptr;
-    CSolver<double>            *z    = nullptr;
+    std::unique_ptr<SolverBase> solver; // a Solver<V> of that value type
 };
+
+namespace
+{
+
+// ---- the typed entry points: handle checks and pointer casts, once ------------------------------------------------
+template <typename V>
+aoclsparse_status solver_of(aoclsparse_itsol_handle handle, Solver<V> *&S)
+{
+    if(!handle)
+        return aoclsparse_status_invalid_pointer;
+    if(handle->type != type_tag<V>)
+        return aoclsparse_status_wrong_type;
+    S = static_cast<Solver<V> *>(handle->solver.get());
+    return aoclsparse_status_success;
+}
+
+template <typename V>
+aoclsparse_status init(aoclsparse_itsol_handle *handle)
+{
+    if(!handle)
+        return aoclsparse_status_invalid_pointer;
+    try
+    {
+        *handle         = new _aoclsparse_itsol_handle;
+        (*handle)->type = type_tag<V>;
+        (*handle)->solver.reset(new Solver<V>);
+        register_options<real_t<V>>((*handle)->solver->opts);
+    }
+    catch(const std::bad_alloc &)
+    {
+        aoclsparse_itsol_destroy(handle);
+        return aoclsparse_status_memory_error;
+    }
+    return aoclsparse_status_success;
+}
+
+template <typename V>
+aoclsparse_status rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n, const public_t<V> *b)
+{
+    Solver<V> *S = nullptr;
+    MI355_TRY(solver_of(handle, S));
+    if(!S)
+        return aoclsparse_status_internal_error;
+    return set_rhs(*S, n, reinterpret_cast<const V *>(b), false);
+}
+
+template <typename V>
+aoclsparse_status rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm, public_t<V> **u, public_t<V> **v,
+                            public_t<V> *x, real_t<V> *rinfo)
+{
+    Solver<V> *S = nullptr;
+    MI355_TRY(solver_of(handle, S));
+    return rci_public(S, ircomm, reinterpret_cast<V **>(u), reinterpret_cast<V **>(v), reinterpret_cast<V *>(x), rinfo);
+}
+
+template <typename V>
+aoclsparse_status solve(aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
+                        const public_t<V> *b, public_t<V> *x, real_t<V> *rinfo, precond_fn<V> *precond, monit_fn<V> *monit,
+                        void *udata)
+{
+    Solver<V> *S = nullptr;
+    MI355_TRY(solver_of(handle, S));
+    return solve_direct(S, n, mat, descr, reinterpret_cast<const V *>(b), reinterpret_cast<V *>(x), rinfo, precond, monit, udata);
+}
+
+} // namespace
 
 extern "C" {
 
 void aoclsparse_itsol_handle_prn_options(aoclsparse_itsol_handle handle)
 {
-    if(!handle)
-        return;
-    if(handle->type == aoclsparse_dmat && handle->d)
-        handle->d->opts.print();
-    else if(handle->type == aoclsparse_smat && handle->s)
-        handle->s->opts.print();
-    else if(handle->type == aoclsparse_zmat && handle->z)
-        handle->z->opts.print();
-    else if(handle->type == aoclsparse_cmat && handle->c)
-        handle->c->opts.print();
+    if(handle && handle->solver)
+        handle->solver->opts.print();
 }
 
 aoclsparse_status aoclsparse_itsol_option_set(aoclsparse_itsol_handle handle, const char *option, const char *value)
 {
     if(!handle)
         return aoclsparse_status_invalid_pointer;
-    if(handle->type == aoclsparse_dmat)
-        return handle->d ? handle->d->opts.set(option, value) : aoclsparse_status_internal_error;
-    if(handle->type == aoclsparse_smat)
-        return handle->s ? handle->s->opts.set(option, value) : aoclsparse_status_internal_error;
-    if(handle->type == aoclsparse_zmat)
-        return handle->z ? handle->z->opts.set(option, value) : aoclsparse_status_internal_error;
-    if(handle->type == aoclsparse_cmat)
-        return handle->c ? handle->c->opts.set(option, value) : aoclsparse_status_internal_error;
-    return aoclsparse_status_invalid_value;
+    if(handle->type != aoclsparse_dmat && handle->type != aoclsparse_smat && handle->type != aoclsparse_zmat
+       && handle->type != aoclsparse_cmat)
+        return aoclsparse_status_invalid_value;
+    return handle->solver ? handle->solver->opts.set(option, value) : aoclsparse_status_internal_error;
 }
 
 void aoclsparse_itsol_destroy(aoclsparse_itsol_handle *handle)
 {
     if(handle && *handle)
     {
-        delete(*handle)->s;
-        delete(*handle)->d;
-        delete(*handle)->c;
-        delete(*handle)->z;
         delete *handle;
         *handle = nullptr;
     }
@@ -1734,203 +1539,88 @@ void aoclsparse_itsol_destroy(aoclsparse_itsol_handle *handle)
 
 aoclsparse_status aoclsparse_itsol_d_init(aoclsparse_itsol_handle *handle)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    try
-    {
-        *handle       = new _aoclsparse_itsol_handle;
-        (*handle)->type = aoclsparse_dmat;
-        (*handle)->d    = new Solver<double>;
-        register_options<double>((*handle)->d->opts);
-    }
-    catch(const std::bad_alloc &)
-    {
-        aoclsparse_itsol_destroy(handle);
-        return aoclsparse_status_memory_error;
-    }
-    return aoclsparse_status_success;
+    return init<double>(handle);
+}
+aoclsparse_status aoclsparse_itsol_d_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n, const double *b)
+{
+    return rci_input<double>(handle, n, b);
+}
+aoclsparse_status aoclsparse_itsol_d_rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm, double **u,
+                                               double **v, double *x, double rinfo[100])
+{
+    return rci_solve<double>(handle, ircomm, u, v, x, rinfo);
+}
+aoclsparse_status aoclsparse_itsol_d_solve(aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat,
+                                           const aoclsparse_mat_descr descr, const double *b, double *x, double rinfo[100],
+                                           precond_fn<double> *precond, monit_fn<double> *monit, void *udata)
+{
+    return solve<double>(handle, n, mat, descr, b, x, rinfo, precond, monit, udata);
 }
 
 aoclsparse_status aoclsparse_itsol_s_init(aoclsparse_itsol_handle *handle)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    try
-    {
-        *handle         = new _aoclsparse_itsol_handle;
-        (*handle)->type = aoclsparse_smat;
-        (*handle)->s    = new Solver<float>;
-        register_options<float>((*handle)->s->opts);
-    }
-    catch(const std::bad_alloc &)
-    {
-        aoclsparse_itsol_destroy(handle);
-        return aoclsparse_status_memory_error;
-    }
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_itsol_d_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n, const double *b)
-{
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_dmat)
-        return aoclsparse_status_wrong_type;
-    return set_rhs(*handle->d, n, b, false);
+    return init<float>(handle);
 }
 aoclsparse_status aoclsparse_itsol_s_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n, const float *b)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_smat)
-        return aoclsparse_status_wrong_type;
-    return set_rhs(*handle->s, n, b, false);
+    return rci_input<float>(handle, n, b);
 }
-
-aoclsparse_status aoclsparse_itsol_d_rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm,
-                                               double **u, double **v, double *x, double rinfo[100])
+aoclsparse_status aoclsparse_itsol_s_rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm, float **u,
+                                               float **v, float *x, float rinfo[100])
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_dmat)
-        return aoclsparse_status_wrong_type;
-    return rci_public(handle->d, ircomm, u, v, x, rinfo);
+    return rci_solve<float>(handle, ircomm, u, v, x, rinfo);
 }
-aoclsparse_status aoclsparse_itsol_s_rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm,
-                                               float **u, float **v, float *x, float rinfo[100])
+aoclsparse_status aoclsparse_itsol_s_solve(aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat,
+                                           const aoclsparse_mat_descr descr, const float *b, float *x, float rinfo[100],
+                                           precond_fn<float> *precond, monit_fn<float> *monit, void *udata)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_smat)
-        return aoclsparse_status_wrong_type;
-    return rci_public(handle->s, ircomm, u, v, x, rinfo);
-}
-
-aoclsparse_status aoclsparse_itsol_d_solve(
-    aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
-    const double *b, double *x, double rinfo[100],
-    aoclsparse_int precond(aoclsparse_int flag, aoclsparse_int n, const double *u, double *v, void *udata),
-    aoclsparse_int monit(aoclsparse_int n, const double *x, const double *r, double rinfo[100], void *udata),
-    void *udata)
-{
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_dmat)
-        return aoclsparse_status_wrong_type;
-    return solve_direct<double>(handle->d, n, mat, descr, b, x, rinfo, precond, monit, udata, aoclsparse_dmat);
-}
-aoclsparse_status aoclsparse_itsol_s_solve(
-    aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
-    const float *b, float *x, float rinfo[100],
-    aoclsparse_int precond(aoclsparse_int flag, aoclsparse_int n, const float *u, float *v, void *udata),
-    aoclsparse_int monit(aoclsparse_int n, const float *x, const float *r, float rinfo[100], void *udata),
-    void *udata)
-{
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_smat)
-        return aoclsparse_status_wrong_type;
-    return solve_direct<float>(handle->s, n, mat, descr, b, x, rinfo, precond, monit, udata, aoclsparse_smat);
+    return solve<float>(handle, n, mat, descr, b, x, rinfo, precond, monit, udata);
 }
 
 aoclsparse_status aoclsparse_itsol_z_init(aoclsparse_itsol_handle *handle)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    try
-    {
-        *handle         = new _aoclsparse_itsol_handle;
-        (*handle)->type = aoclsparse_zmat;
-        (*handle)->z    = new CSolver<double>;
-        register_options<double>((*handle)->z->opts);
-    }
-    catch(const std::bad_alloc &)
-    {
-        aoclsparse_itsol_destroy(handle);
-        return aoclsparse_status_memory_error;
-    }
-    return aoclsparse_status_success;
+    return init<cdouble>(handle);
 }
-aoclsparse_status aoclsparse_itsol_z_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n, const aoclsparse_double_complex *b)
+aoclsparse_status aoclsparse_itsol_z_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n,
+                                               const aoclsparse_double_complex *b)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_zmat)
-        return aoclsparse_status_wrong_type;
-    return cset_rhs(*handle->z, n, reinterpret_cast<const cplx<double> *>(b), false);
+    return rci_input<cdouble>(handle, n, b);
 }
 aoclsparse_status aoclsparse_itsol_z_rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm,
-                                               aoclsparse_double_complex **u, aoclsparse_double_complex **v, aoclsparse_double_complex *x, double rinfo[100])
+                                               aoclsparse_double_complex **u, aoclsparse_double_complex **v,
+                                               aoclsparse_double_complex *x, double rinfo[100])
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_zmat)
-        return aoclsparse_status_wrong_type;
-    return crci_public(handle->z, ircomm, reinterpret_cast<cplx<double> **>(u), reinterpret_cast<cplx<double> **>(v),
-                       reinterpret_cast<cplx<double> *>(x), rinfo);
+    return rci_solve<cdouble>(handle, ircomm, u, v, x, rinfo);
 }
-aoclsparse_status aoclsparse_itsol_z_solve(
-    aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
-    const aoclsparse_double_complex *b, aoclsparse_double_complex *x, double rinfo[100],
-    aoclsparse_int precond(aoclsparse_int flag, aoclsparse_int n, const aoclsparse_double_complex *u, aoclsparse_double_complex *v, void *udata),
-    aoclsparse_int monit(aoclsparse_int n, const aoclsparse_double_complex *x, const aoclsparse_double_complex *r, double rinfo[100], void *udata), void *udata)
+aoclsparse_status aoclsparse_itsol_z_solve(aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat,
+                                           const aoclsparse_mat_descr descr, const aoclsparse_double_complex *b,
+                                           aoclsparse_double_complex *x, double rinfo[100],
+                                           precond_fn<cdouble> *precond, monit_fn<cdouble> *monit, void *udata)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_zmat)
-        return aoclsparse_status_wrong_type;
-    return csolve_direct<double, aoclsparse_double_complex>(handle->z, n, mat, descr, reinterpret_cast<const cplx<double> *>(b),
-                                    reinterpret_cast<cplx<double> *>(x), rinfo, precond, monit, udata, aoclsparse_zmat);
+    return solve<cdouble>(handle, n, mat, descr, b, x, rinfo, precond, monit, udata);
 }
 
 aoclsparse_status aoclsparse_itsol_c_init(aoclsparse_itsol_handle *handle)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    try
-    {
-        *handle         = new _aoclsparse_itsol_handle;
-        (*handle)->type = aoclsparse_cmat;
-        (*handle)->c    = new CSolver<float>;
-        register_options<float>((*handle)->c->opts);
-    }
-    catch(const std::bad_alloc &)
-    {
-        aoclsparse_itsol_destroy(handle);
-        return aoclsparse_status_memory_error;
-    }
-    return aoclsparse_status_success;
+    return init<cfloat>(handle);
 }
-aoclsparse_status aoclsparse_itsol_c_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n, const aoclsparse_float_complex *b)
+aoclsparse_status aoclsparse_itsol_c_rci_input(aoclsparse_itsol_handle handle, aoclsparse_int n,
+                                               const aoclsparse_float_complex *b)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_cmat)
-        return aoclsparse_status_wrong_type;
-    return cset_rhs(*handle->c, n, reinterpret_cast<const cplx<float> *>(b), false);
+    return rci_input<cfloat>(handle, n, b);
 }
 aoclsparse_status aoclsparse_itsol_c_rci_solve(aoclsparse_itsol_handle handle, aoclsparse_itsol_rci_job *ircomm,
-                                               aoclsparse_float_complex **u, aoclsparse_float_complex **v, aoclsparse_float_complex *x, float rinfo[100])
+                                               aoclsparse_float_complex **u, aoclsparse_float_complex **v,
+                                               aoclsparse_float_complex *x, float rinfo[100])
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_cmat)
-        return aoclsparse_status_wrong_type;
-    return crci_public(handle->c, ircomm, reinterpret_cast<cplx<float> **>(u), reinterpret_cast<cplx<float> **>(v),
-                       reinterpret_cast<cplx<float> *>(x), rinfo);
+    return rci_solve<cfloat>(handle, ircomm, u, v, x, rinfo);
 }
-aoclsparse_status aoclsparse_itsol_c_solve(
-    aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat, const aoclsparse_mat_descr descr,
-    const aoclsparse_float_complex *b, aoclsparse_float_complex *x, float rinfo[100],
-    aoclsparse_int precond(aoclsparse_int flag, aoclsparse_int n, const aoclsparse_float_complex *u, aoclsparse_float_complex *v, void *udata),
-    aoclsparse_int monit(aoclsparse_int n, const aoclsparse_float_complex *x, const aoclsparse_float_complex *r, float rinfo[100], void *udata), void *udata)
+aoclsparse_status aoclsparse_itsol_c_solve(aoclsparse_itsol_handle handle, aoclsparse_int n, aoclsparse_matrix mat,
+                                           const aoclsparse_mat_descr descr, const aoclsparse_float_complex *b,
+                                           aoclsparse_float_complex *x, float rinfo[100],
+                                           precond_fn<cfloat> *precond, monit_fn<cfloat> *monit, void *udata)
 {
-    if(!handle)
-        return aoclsparse_status_invalid_pointer;
-    if(handle->type != aoclsparse_cmat)
-        return aoclsparse_status_wrong_type;
-    return csolve_direct<float, aoclsparse_float_complex>(handle->c, n, mat, descr, reinterpret_cast<const cplx<float> *>(b),
-                                    reinterpret_cast<cplx<float> *>(x), rinfo, precond, monit, udata, aoclsparse_cmat);
+    return solve<cfloat>(handle, n, mat, descr, b, x, rinfo, precond, monit, udata);
 }
 
 } // extern "C"

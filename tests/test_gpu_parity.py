@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 import oracle
-from util import (EPS32, EPS64, abs_row_sums, banded_rows, kt_lanes, laplace5, pkg, powerlaw_rows, random_csr,
-                  triangular_system, trsv_schedule)
+from util import (EPS32, EPS64, abs_row_sums, banded_rows, complex_itsol_systems, kt_lanes, laplace5, pkg, powerlaw_rows,
+                  random_csr, triangular_system, trsv_schedule)
+from util import cplx_tri_system as _cplx_tri_system
 
 pytestmark = pytest.mark.gpu
 
@@ -2461,22 +2462,6 @@ def test_complex_sp2m(prec):
     L.aoclsparse_destroy(ctypes.byref(hA)), L.aoclsparse_destroy(ctypes.byref(hB))
 
 
-def _cplx_tri_system(seed, n, dtype, base):
-    """sorted complex CSR with a dominant full diagonal, ~8 entries per row on both sides of it"""
-    rng = np.random.default_rng(seed)
-    dense = np.zeros((n, n), np.complex128)
-    for i in range(n):
-        cols = rng.choice(n, size=min(n, 8), replace=False)
-        dense[i, cols] = rng.uniform(-0.5, 0.5, len(cols)) + 1j * rng.uniform(-0.5, 0.5, len(cols))
-        dense[i, i] = (3.0 + rng.uniform(0, 1)) * np.exp(1j * rng.uniform(0, 2 * np.pi))
-    dense = dense.astype(dtype)
-    rows = [np.flatnonzero(dense[i]) for i in range(n)]
-    rp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32) + base
-    ci = (np.concatenate(rows) + base).astype(np.int32)
-    v = np.concatenate([dense[i, r] for i, r in enumerate(rows)]).astype(dtype)
-    return dense, rp, ci, v
-
-
 def _op_tri(dense, fill, diag, op):
     T = np.tril(dense) if fill == "lower" else np.triu(dense)
     if diag == "unit":
@@ -2644,16 +2629,7 @@ def test_complex_itsol_cg_and_gmres(prec):
     the RCI loop driven by hand gives the direct interface's bits."""
     dtype, rdtype, eps = (np.complex128, np.float64, EPS64) if prec == "z" else (np.complex64, np.float32, EPS32)
     fn = lambda stem: getattr(L, "aoclsparse_" + stem.replace("?", prec))
-    n = 200
-    rng = np.random.default_rng(8)
-    dense, rp, ci, v = _cplx_tri_system(55, n, dtype, 0)
-    # a spectrum in the right half plane (the generator's diagonal has random phases: eigenvalues all around the origin)
-    for i in range(n):
-        dgp = rp[i] + int(np.searchsorted(ci[rp[i]:rp[i + 1]], i))
-        v[dgp] = 4.0 + 0.5j * (1 + i % 3)
-        dense[i, i] = v[dgp]
-    D = dense.astype(np.complex128)
-    xs = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex128)
+    n, D, (rp, ci, v), S, (lrp, lci, lv), xs = complex_itsol_systems(dtype)
     tol = 1e-9 if prec == "z" else 2e-4
 
     def handle(method, extra=()):
@@ -2700,12 +2676,6 @@ def test_complex_itsol_cg_and_gmres(prec):
         L.aoclsparse_itsol_destroy(ctypes.byref(hh))
     L.aoclsparse_destroy(ctypes.byref(A))
     # ---- CG on the complex symmetric matrix S = tril + tril^T (lower triangle stored)
-    Ls = np.tril(D)
-    S = Ls + np.tril(D, -1).T
-    rows = [np.flatnonzero(Ls[i]) for i in range(n)]
-    lrp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
-    lci = np.concatenate(rows).astype(np.int32)
-    lv = np.concatenate([Ls[i, r] for i, r in enumerate(rows)]).astype(dtype)
     A = ctypes.c_void_p()
     assert fn("create_?csr")(ctypes.byref(A), 0, n, n, len(lv), P._ptr(lrp), P._ptr(lci), P._ptr(lv)) == 0
     ds = P.Descr(mtype=P.TYPE_SYMMETRIC, fill=P.FILL_LOWER)

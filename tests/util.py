@@ -97,6 +97,44 @@ def banded_rows(seed, m, n, per_row, base=0):
     return np.array(rp, np.int32) + base, np.array(ci, np.int32) + base, v
 
 
+def cplx_tri_system(seed, n, dtype, base):
+    """sorted complex CSR with a dominant full diagonal, ~8 entries per row on both sides of it"""
+    rng = np.random.default_rng(seed)
+    dense = np.zeros((n, n), np.complex128)
+    for i in range(n):
+        cols = rng.choice(n, size=min(n, 8), replace=False)
+        dense[i, cols] = rng.uniform(-0.5, 0.5, len(cols)) + 1j * rng.uniform(-0.5, 0.5, len(cols))
+        dense[i, i] = (3.0 + rng.uniform(0, 1)) * np.exp(1j * rng.uniform(0, 2 * np.pi))
+    dense = dense.astype(dtype)
+    rows = [np.flatnonzero(dense[i]) for i in range(n)]
+    rp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32) + base
+    ci = (np.concatenate(rows) + base).astype(np.int32)
+    v = np.concatenate([dense[i, r] for i, r in enumerate(rows)]).astype(dtype)
+    return dense, rp, ci, v
+
+
+def complex_itsol_systems(dtype, n=200):
+    """The two systems of the complex iterative-solver tests: a general matrix with its spectrum in the right half plane (for
+    GMRES) and the complex SYMMETRIC S = tril + tril^T of it, lower triangle stored (for CG), with the solution both share.
+    Returns n, D (dense, complex128), (rp, ci, v), S (dense), (lrp, lci, lv), xs."""
+    rng = np.random.default_rng(8)
+    dense, rp, ci, v = cplx_tri_system(55, n, dtype, 0)
+    # a spectrum in the right half plane (the generator's diagonal has random phases: eigenvalues all around the origin)
+    for i in range(n):
+        dgp = rp[i] + int(np.searchsorted(ci[rp[i]:rp[i + 1]], i))
+        v[dgp] = 4.0 + 0.5j * (1 + i % 3)
+        dense[i, i] = v[dgp]
+    D = dense.astype(np.complex128)
+    xs = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex128)
+    Ls = np.tril(D)
+    S = Ls + np.tril(D, -1).T
+    rows = [np.flatnonzero(Ls[i]) for i in range(n)]
+    lrp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    lci = np.concatenate(rows).astype(np.int32)
+    lv = np.concatenate([Ls[i, r] for i, r in enumerate(rows)]).astype(dtype)
+    return n, D, (rp, ci, v), S, (lrp, lci, lv), xs
+
+
 class beta0_overwrite:
     """with beta0_overwrite(P): ... -- csrmm with beta == 0 does not read C inside the block (the opt-in mode of
     aoclsparse_mi355_set_csrmm_beta0_overwrite); the default (C read and multiplied by zero, as the reference) is restored."""
