@@ -408,6 +408,7 @@ SIGNATURES = {
     "aoclsparse_mi355_get_spmv_info": (c_int, [_P, c_int, POINTER(SpmvInfo)]),
     "aoclsparse_mi355_get_sell_values": (c_int, [_P, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_sell_packing": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I)]),
+    "aoclsparse_mi355_get_sell_records": (c_int, [_P, c_int, POINTER(_I), POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_levels": (c_int, [_P, c_int, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_info": (c_int, [_P, c_int, c_int, POINTER(TrsvInfo)]),
     "aoclsparse_mi355_trsv_status": (c_int, [_P]),
@@ -576,6 +577,12 @@ class Matrix:
         b, w, u = _I(-1), _I(-1), _I(-1)
         assert lib().aoclsparse_mi355_get_sell_packing(self.h, op, byref(b), byref(w), byref(u)) == 0
         return b.value, w.value, u.value
+
+    def sell_records(self, op=OP_NONE):
+        """(slices whose record holds their rows' one packed word, those among them that are a shifted list with exception rows)"""
+        u, e = _I(-1), _I(-1)
+        assert lib().aoclsparse_mi355_get_sell_records(self.h, op, byref(u), byref(e)) == 0
+        return u.value, e.value
 
     def trsv_info(self, fill, op=OP_NONE):
         info = TrsvInfo()

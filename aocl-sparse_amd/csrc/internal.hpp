@@ -268,8 +268,19 @@ struct SellSliceDesc
 {
     uint32_t cell_lo, col_lo; // low words of the first value cell (slice_ptr[s]) and of the first column entry
     uint32_t hi; // bits 0-15: bits 32-47 of the value-cell offset; bits 16-31: those of the column offset
-    uint32_t wsm; // bits 0-7 width (cells per row), 8-15 column stride, 16-23 mode
+    uint32_t wsm; // bits 0-7 width (cells per row), 8-15 column stride, 16-23 mode, 24-31 flags (SELL_DESC_UWORD / _EXCEPT)
 };
+// Flags in the DEVICE copy of a record (sell_build_kernels.hip: sell_records_kernel writes them behind the fill pass; the host
+// function below never sets them).  Only on a plan with uniform lists and one-byte packed words, whose kernels (UCOL && PK) read
+// neither cell_lo nor the low half of hi: those bits then carry what the flags announce.
+//   SELL_DESC_UWORD:  all 64 rows of the (full, one-list) slice have the same packed word: cell_lo bits 0-7 hold it and the
+//                     kernel does not read the rows' words.
+//   SELL_DESC_EXCEPT: (always with UWORD) the slice is mode 0 in every other reader's eyes, but its rows are ONE list shifted by
+//                     lane of which at most two lanes omit cells: ucol holds the canonical list B (row of lane l: B + l), cell_lo
+//                     bits 8-15 / 16-23 = first exception lane / the mask of the canonical cells it has, bits 24-31 and hi bits
+//                     0-7 = the same for the second; lane 0xff = none.  The word sits at the CANONICAL cell positions.
+constexpr uint32_t       SELL_DESC_UWORD = 1u << 24, SELL_DESC_EXCEPT = 1u << 25;
+constexpr uint32_t       SELL_DESC_NO_LANE = 0xffu;
 // modes: 0 lead[row] = list | shift << 8; 1 one list, shift = lane; 2 one list, no shift; 3 list = lane, no shift (lists not shared)
 constexpr int            SELL_DESC_MODE_FOLLOW = 0, SELL_DESC_MODE_LANE_SHIFT = 1, SELL_DESC_MODE_ONE = 2, SELL_DESC_MODE_OWN = 3;
 // the general kernel reads the same mode (0 / 1 / 2) from the top byte of a slice's cptr word, the offset from the bits below
@@ -337,6 +348,8 @@ struct SellPlan
     // a mode 1 / 2 slice, -1 elsewhere; uniform = how many slices have one
     DeviceBuffer   ucol;
     aoclsparse_int uniform = 0;
+    // slices whose device record carries SELL_DESC_UWORD / SELL_DESC_EXCEPT (counted by the kernel that sets them)
+    aoclsparse_int uniform_words = 0, exceptions = 0;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
@@ -922,6 +935,11 @@ aoclsparse_status launch_csrmv(hipStream_t s, int order, bool strict, int tile, 
 // packed word per row; ucol (v.ucol, writable; preset to -1) gets the list of every mode 1 / 2 slice
 aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
                                    aoclsparse_int *rowlen, aoclsparse_int *ucol);
+// behind launch_sell_fill on the same stream, for a copy with uniform lists and one-byte packed words: sets SELL_DESC_UWORD /
+// SELL_DESC_EXCEPT in the device records (desc, nslices of them) and writes the canonical list of an exception slice to ucol;
+// counts (device, two words, zeroed here) receives how many slices got each flag.  d = the CSR the copy mirrors.
+aoclsparse_status launch_sell_records(hipStream_t s, const DeviceCsr &d, const SellView &v, SellSliceDesc *desc, aoclsparse_int *ucol,
+                                      unsigned *counts);
 // distinct bit patterns of n values of vsize (4 / 8) bytes on the device: *ntab of them; table = SELL_VTAB_MAX entries of vsize
 // bytes ready to upload, ascending by bit pattern, the unused ones 0; *ntab = 0 when there are more than SELL_VTAB_MAX
 constexpr int     SELL_VTAB_MAX = 256;

@@ -703,7 +703,7 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         return aoclsparse_status_success;
     sp.tried = true;
     sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
-    sp.pbits = sp.pbytes = 0, sp.uniform = 0;
+    sp.pbits = sp.pbytes = 0, sp.uniform = 0, sp.uniform_words = sp.exceptions = 0;
     sp.vtab.release(), sp.vidx.release(), sp.pidx.release(), sp.desc.release(), sp.ucol.release();
     const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
@@ -862,7 +862,9 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         if(sp.shared && sp.pbits)
         {
             const size_t ubytes = sizeof(aoclsparse_int) * SELL_SHORT_WMAX * ((size_t)nslices + SELL_DESC_PAD);
-            st                  = sp.ucol.alloc(ubytes);
+            // (+ two words behind the lists: the counters of sell_records_kernel, so that the plan makes no allocation of its own
+            // for them -- where later arrays lie in HBM moves the other SELL products by 2 - 3 %)
+            st                  = sp.ucol.alloc(ubytes + 2 * sizeof(unsigned));
             if(st != aoclsparse_status_success)
                 return st;
             MI355_HIP_TRY(hipMemsetAsync(sp.ucol.ptr, 0xff, ubytes, rt.stream()));
@@ -876,7 +878,19 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
                           sp.rowlen.as<aoclsparse_int>(), sp.ucol.as<aoclsparse_int>());
     if(st != aoclsparse_status_success)
         return st;
+    // what the records say beyond offsets and mode (uniform word, shifted list with exception lanes): written on the device,
+    // behind the fill pass whose words and lists it reads -- every rebuild after a value change passes here again
+    unsigned rc[2] = {0, 0};
+    if(sp.ucol.ptr && sp.pbytes == 1)
+    {
+        unsigned *rcount = reinterpret_cast<unsigned *>(sp.ucol.as<aoclsparse_int>() + SELL_SHORT_WMAX * ((size_t)nslices + SELL_DESC_PAD));
+        st = launch_sell_records(rt.stream(), d, view, sp.desc.as<SellSliceDesc>(), sp.ucol.as<aoclsparse_int>(), rcount);
+        if(st != aoclsparse_status_success)
+            return st;
+        MI355_HIP_TRY(hipMemcpyAsync(rc, rcount, sizeof(rc), hipMemcpyDeviceToHost, rt.stream()));
+    }
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr / desc (host) are read by the uploads until here
+    sp.uniform_words = (aoclsparse_int)rc[0], sp.exceptions = (aoclsparse_int)rc[1];
     sp.valid = sp.wanted = true;
     return aoclsparse_status_success;
 }

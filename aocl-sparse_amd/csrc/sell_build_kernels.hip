@@ -397,7 +397,118 @@ void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *ce
         v.pack == 4 ? go(P4{}, std::false_type{}) : go(P1{}, std::false_type{});
 }
 
+// ---- what a slice record says beyond offsets, width and mode (SELL_DESC_UWORD / SELL_DESC_EXCEPT, internal.hpp) ---------------
+// Behind the fill pass, on a copy with uniform lists and one-byte packed words; one wavefront per FULL slice.
+// Mode 1 / 2 (one list): the 64 words of the fill pass are compared; if they are one word the record carries it.
+// Mode 0 with a width: "one list shifted by lane, a few lanes omit a cell" (the first and last slice of a grid line):
+//   - canonical row = the lowest lane whose length is the slice width, B = its columns minus its lane;
+//   - every B[q] >= 0 and B[q] + 63 < n (every gather at B[q] + lane stays inside x; -1 stays ucol's "unused");
+//   - every row's columns are an in-order subsequence of B + lane (greedy match: the earliest match is as good as any);
+//   - at most two lanes are shorter than the width;
+//   - the rows' table indices, moved to the canonical positions of their cells, agree with the canonical row's word.
+// Then the record gets both flags, the word, the two (lane, mask of present canonical cells) pairs, and ucol gets B.  A slice
+// that fails any condition keeps its record and its ucol entries (-1) as the fill pass left them.
+__global__ __launch_bounds__(256) void sell_records_kernel(aoclsparse_int m, aoclsparse_int n, int base,
+                                                           const aoclsparse_int *__restrict__ row_ptr,
+                                                           const aoclsparse_int *__restrict__ col, aoclsparse_int nslices,
+                                                           SellSliceDesc *__restrict__ desc, const unsigned char *__restrict__ pidx,
+                                                           int pbits, aoclsparse_int *__restrict__ ucol, unsigned *__restrict__ counts)
+{
+    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if(s >= nslices || (long long)s * 64 + 63 >= m) // (wave-uniform: full slices only)
+        return;
+    const int      i    = s * 64 + lane;
+    const uint32_t wsm  = desc[s].wsm;
+    const int      w    = (int)(wsm & 0xffu), mode = (int)(wsm >> 16) & 0xff;
+    const unsigned own  = pidx[i]; // the row's word, fields at the row's own cell positions
+    if(w > SELL_SHORT_WMAX)
+        return;
+    if(mode == SELL_DESC_MODE_LANE_SHIFT || mode == SELL_DESC_MODE_ONE)
+    {
+        const unsigned w0 = (unsigned)__shfl((int)own, 0);
+        if(__builtin_amdgcn_ballot_w64(own != w0) != 0ull || lane != 0)
+            return;
+        desc[s].cell_lo = w0 | SELL_DESC_NO_LANE << 8 | SELL_DESC_NO_LANE << 24;
+        desc[s].hi &= 0xffff0000u;
+        desc[s].wsm = wsm | SELL_DESC_UWORD;
+        atomicAdd(counts, 1u);
+        return;
+    }
+    if(mode != SELL_DESC_MODE_FOLLOW || w < 1)
+        return;
+    const int                b = row_ptr[i] - base, len = row_ptr[i + 1] - base - b;
+    const unsigned long long shortb = __builtin_amdgcn_ballot_w64(len < w);
+    if(__builtin_popcountll(shortb) > 2) // (never all 64: w is the longest row's length)
+        return;
+    const int c  = __builtin_ctzll(~shortb); // canonical lane
+    const int bc = __shfl(b, c);
+    int       B[SELL_SHORT_WMAX];
+    bool      ok = true;
+#pragma unroll
+    for(int q = 0; q < SELL_SHORT_WMAX; q++)
+    {
+        B[q] = q < w ? col[bc + q] - base - c : 0;
+        ok   = ok && B[q] >= 0 && (long long)B[q] + 63 < (long long)n;
+    }
+    // this row against B + lane: mask = the canonical cells it has, cw = its index fields moved to their positions
+    const unsigned field = (1u << pbits) - 1u;
+    unsigned       mask = 0, cw = 0, fm = 0;
+    int            p = 0;
+#pragma unroll
+    for(int q = 0; q < SELL_SHORT_WMAX; q++)
+    {
+        const bool hit = q < w && p < len && col[b + min(p, max(len - 1, 0))] - base == B[q] + lane;
+        if(hit)
+        {
+            mask |= 1u << q, fm |= field << (q * pbits);
+            cw |= ((own >> (p * pbits)) & field) << (q * pbits);
+            p++;
+        }
+    }
+    ok               = ok && p == len;
+    const unsigned W = (unsigned)__shfl((int)cw, c);
+    ok               = ok && ((cw ^ W) & fm) == 0u;
+    if(__builtin_amdgcn_ballot_w64(!ok) != 0ull)
+        return;
+    unsigned la = SELL_DESC_NO_LANE, lb = SELL_DESC_NO_LANE, ma = 0, mb = 0;
+    if(shortb)
+    {
+        la = (unsigned)__builtin_ctzll(shortb);
+        ma = (unsigned)__shfl((int)mask, (int)la);
+        const unsigned long long rest = shortb & (shortb - 1ull);
+        if(rest)
+        {
+            lb = (unsigned)__builtin_ctzll(rest);
+            mb = (unsigned)__shfl((int)mask, (int)lb);
+        }
+    }
+    if(lane != 0)
+        return;
+#pragma unroll
+    for(int q = 0; q < SELL_SHORT_WMAX; q++)
+        if(q < w)
+            ucol[(long long)s * SELL_SHORT_WMAX + q] = B[q];
+    desc[s].cell_lo = (W & 0xffu) | la << 8 | ma << 16 | lb << 24;
+    desc[s].hi      = (desc[s].hi & 0xffff0000u) | mb;
+    desc[s].wsm     = wsm | SELL_DESC_UWORD | SELL_DESC_EXCEPT;
+    atomicAdd(counts, 1u);
+    atomicAdd(counts + 1, 1u);
+}
+
 } // namespace
+
+aoclsparse_status launch_sell_records(hipStream_t s, const DeviceCsr &d, const SellView &v, SellSliceDesc *desc, aoclsparse_int *ucol,
+                                      unsigned *counts)
+{
+    MI355_HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s));
+    if(v.nslices <= 0 || !desc || !ucol || !v.cells || v.pbits <= 0 || v.pbytes != 1)
+        return aoclsparse_status_success;
+    hipLaunchKernelGGL(sell_records_kernel, dim3((v.nslices + 3) / 4), dim3(256), 0, s, v.m, d.n, d.base, d.ptr.as<aoclsparse_int>(),
+                       d.ind.as<aoclsparse_int>(), v.nslices, desc, static_cast<const unsigned char *>(v.cells), v.pbits, ucol, counts);
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
 
 aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
                                    aoclsparse_int *rowlen, aoclsparse_int *ucol)

@@ -452,6 +452,14 @@ using SellRows = T __attribute__((ext_vector_type(N), aligned(sizeof(T))));
 // of the wave-uniform decision (lists in col / uniform by slice / run), and the packed words are loaded behind it, by the
 // mapping it chose.  x + column, x and y are aligned as elements only: the vector type says so.  Words of more than one byte
 // per row (pbytes > 1) stay on the mapping by slice.
+// RECORD FLAGS (UCOL, PK, one-byte words; internal.hpp: SELL_DESC_UWORD / SELL_DESC_EXCEPT, set at plan time by
+// sell_records_kernel): a slice whose 64 rows share one word has it in its record, and a group in which every slice does reads
+// no word at all (6 vector memory instructions in a run on the headline); a mode-0 slice that is one list shifted by lane of
+// which at most two lanes omit cells (the first and last slice of a grid line) counts as a shifted slice -- for the column
+// decision and the run test -- with its canonical list in ucol, and the two lanes get the mask of the cells they have instead of
+// the full one: the gather of an absent cell is issued (inside x by the plan's rule) and dropped by the chain's select, so each
+// row's chain is its own cells in its own order and the bits are unchanged.  A group that still reads the lists in col reads a
+// flagged slice as before (its rows' own words, follow[]).
 // Without PK the value (or one-byte index) lines are SPW x WMAX vector loads behind the records.
 // TAB: 0 = the cells hold values; 2 = indices into a table of <= 2 values, held in scalar registers and selected;
 // 256 = indices into a table of <= SELL_VTAB_MAX values, copied to LDS once per workgroup (its load goes out with the records,
@@ -475,6 +483,10 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
     // measured with it -- 28 -> 7 vector memory instructions per wavefront and the same time, DESIGN.md 5.1 -- and keeps the
     // mapping by slice; the code below is written for any real type and any SPW > 1.)
     constexpr bool WIDE = UCOL && PK && SPW > 1 && std::is_same_v<T, double>;
+    // what the records say beyond offsets and mode (plans with uniform lists and one-byte words: internal.hpp, SELL_DESC_UWORD /
+    // SELL_DESC_EXCEPT): a slice's rows share ONE word, held by the record; a mode-0 slice is one list shifted by lane in which
+    // two lanes at most omit cells -- it counts as shifted here, for the column decision and the run test
+    constexpr bool REC = UCOL && PK;
     static_assert(WAVES * SPW <= SELL_DESC_PAD && 64 * WAVES == SELL_VTAB_MAX, "padding of the slice records / one table entry per lane");
     static_assert(!PK || TAB != 0, "packed words hold table indices");
     // group g of WAVES x SPW slices; consecutive products of a handle ALTERNATE the direction (SellPlan::products): g0 = last
@@ -514,7 +526,7 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
                 pw[u] = TAB == 2 ? packed_word(sval, row + 64 * u, 1) : packed_word_any(sval, row + 64 * u, pbytes);
         }
     };
-    if constexpr(!WIDE)
+    if constexpr(!REC)
         words_by_slice();
     int  mode[SPW];
     bool lists = !UCOL; // the group reads its columns from the lists in col
@@ -522,7 +534,8 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
     for(int u = 0; u < SPW; u++)
     {
         mode[u] = (int)(d[u].w >> 16) & 0xff;
-        lists   = lists || !(mode[u] == SELL_DESC_MODE_LANE_SHIFT || mode[u] == SELL_DESC_MODE_ONE);
+        if constexpr(!REC)
+            lists = lists || !(mode[u] == SELL_DESC_MODE_LANE_SHIFT || mode[u] == SELL_DESC_MODE_ONE);
     }
     [[maybe_unused]] R rr[SPW][WMAX];
     if constexpr(!PK)
@@ -548,10 +561,11 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
 #pragma unroll
             for(int q = 0; q < WMAX; q++)
                 s_pin_arg(uc[u][q]);
-        if constexpr(WIDE)
+        if constexpr(REC)
         {
             // all four words of every record too: the run test reads only w, and the compiler would otherwise fetch x / y / z
-            // (offsets, needed by the lists in col alone) behind the test -- a fourth round trip on that path
+            // (offsets, needed by the lists in col alone; a flagged slice's word and lanes) behind the test -- a fourth round
+            // trip on that path
 #pragma unroll
             for(int u = 0; u < SPW; u++)
                 s_pin_arg(d[u].x), s_pin_arg(d[u].y), s_pin_arg(d[u].z), s_pin_arg(d[u].w);
@@ -559,6 +573,21 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
         if constexpr(TAB == 2)
             s_pin_arg(t0), s_pin_arg(t1);
         __builtin_amdgcn_sched_barrier(0);
+    }
+    [[maybe_unused]] unsigned ew[SPW]; // the record's w with the mode of a flagged slice read as "shifted"
+    [[maybe_unused]] bool     alluw = REC, anyex = false; // every slice has its word in the record / some slice has exception lanes
+    if constexpr(REC)
+    {
+        // (behind the batch: scalar work on the records in front of it would split it in two round trips)
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+        {
+            const bool ex = (d[u].w & SELL_DESC_EXCEPT) != 0u;
+            ew[u]         = ex ? ((d[u].w & 0xff00ffffu) | (unsigned)SELL_DESC_MODE_LANE_SHIFT << 16) : d[u].w;
+            alluw         = alluw && (d[u].w & SELL_DESC_UWORD) != 0u;
+            anyex         = anyex || ex;
+            lists         = lists || !(ex || mode[u] == SELL_DESC_MODE_LANE_SHIFT || mode[u] == SELL_DESC_MODE_ONE);
+        }
     }
     // A RUN: the group's SPW slices are all mode 1, of one width, and each list continues the list before it (column + 64 in
     // every used cell): row j of the group's 64 SPW rows reads x[uc[0][q] + j].  Scalar compares on what the batch above brought.
@@ -568,13 +597,13 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
     {
         // (one word of differences, no branch per compare: mode and width are bits 0 .. 7 and 16 .. 23 of w)
         const int w0  = (int)(d[0].w & 0xffu);
-        unsigned  dif = (d[0].w ^ ((unsigned)SELL_DESC_MODE_LANE_SHIFT << 16)) & 0xff0000u;
+        unsigned  dif = (ew[0] ^ ((unsigned)SELL_DESC_MODE_LANE_SHIFT << 16)) & 0xff0000u;
         if constexpr(TAB != 2)
             dif |= (unsigned)(pbytes - 1);
 #pragma unroll
         for(int u = 1; u < SPW; u++)
         {
-            dif |= (d[u].w ^ d[0].w) & 0xff00ffu;
+            dif |= (ew[u] ^ ew[0]) & 0xff00ffu;
 #pragma unroll
             for(int q = 0; q < WMAX; q++)
                 dif |= q < w0 ? (unsigned)(uc[u][q] - uc[0][q] - 64 * u) : 0u;
@@ -632,7 +661,9 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
     {
         if(__builtin_expect(lists, 0)) // wave-uniform
         {
-            if constexpr(WIDE)
+            // (a flagged slice is read here as every reader but this kernel reads it: its rows' own words, its lists through
+            // follow[] -- the word of the record sits at the canonical cell positions, which are not the rows' own)
+            if constexpr(REC)
                 words_by_slice();
             from_lists();
         }
@@ -646,10 +677,37 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
             {
                 using RowVec = SellRows<T, SPW>;
                 using PW = std::conditional_t<SPW == 2, unsigned short, unsigned>;
-                const unsigned word = *reinterpret_cast<const PW *>(reinterpret_cast<const unsigned char *>(sval) + (long long)sb * 64 + SPW * lane);
+                // the lane's SPW rows lie in ONE slice of the group, slice lane / (64 / SPW): its record's word where it has one
+                const int ls   = lane / (64 / SPW);
+                unsigned  rw   = d[0].x & 0xffu;
+                bool      huw  = (d[0].w & SELL_DESC_UWORD) != 0u;
+#pragma unroll
+                for(int u = 1; u < SPW; u++)
+                    rw = ls == u ? (d[u].x & 0xffu) : rw, huw = ls == u ? (d[u].w & SELL_DESC_UWORD) != 0u : huw;
+                unsigned word = 0;
+                if(!__builtin_expect(alluw, 1)) // wave-uniform: with every word in a record none is read
+                    word = *reinterpret_cast<const PW *>(reinterpret_cast<const unsigned char *>(sval) + (long long)sb * 64 + SPW * lane);
 #pragma unroll
                 for(int u = 0; u < SPW; u++)
-                    pw[u] = (word >> (8 * u)) & 0xffu, okm[u] = (1u << (d[0].w & 0xffu)) - 1u;
+                    okm[u] = (1u << (d[0].w & 0xffu)) - 1u;
+                if(__builtin_expect(anyex, 0)) // wave-uniform: row 64 v + (exception lane) of the group is row u of lane owner
+                {
+#pragma unroll
+                    for(int v = 0; v < SPW; v++)
+                    {
+                        const bool     ex = (d[v].w & SELL_DESC_EXCEPT) != 0u;
+                        const unsigned la = (d[v].x >> 8) & 0xffu, lb = d[v].x >> 24;
+                        const unsigned ma = (d[v].x >> 16) & 0xffu, mb = d[v].z & 0xffu;
+                        const int      ga = ex && la != SELL_DESC_NO_LANE ? 64 * v + (int)la : -SPW;
+                        const int      gb = ex && lb != SELL_DESC_NO_LANE ? 64 * v + (int)lb : -SPW;
+#pragma unroll
+                        for(int u = 0; u < SPW; u++)
+                        {
+                            okm[u] = (ga >= 0 && ga % SPW == u && lane == ga / SPW) ? ma : okm[u];
+                            okm[u] = (gb >= 0 && gb % SPW == u && lane == gb / SPW) ? mb : okm[u];
+                        }
+                    }
+                }
                 using GV = const __attribute__((address_space(1))) RowVec;
                 using GC = const __attribute__((address_space(1))) char;
 #pragma unroll
@@ -662,12 +720,21 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
                     for(int u = 0; u < SPW; u++)
                         xx[u][q] = xv[u];
                 }
+#pragma unroll
+                for(int u = 0; u < SPW; u++) // (behind the gathers: the first use of a word that was read)
+                    pw[u] = huw ? rw : (word >> (8 * u)) & 0xffu;
             }
         }
         else
         {
-            if constexpr(WIDE)
-                words_by_slice();
+            if constexpr(REC)
+            {
+#pragma unroll
+                for(int u = 0; u < SPW; u++)
+                    pw[u] = 0;
+                if(!__builtin_expect(alluw, 1)) // wave-uniform: with every word in a record none is read
+                    words_by_slice();
+            }
             // every slice of the group has one list: a gather is a scalar base, x + column, plus the lane's shift (mode 1) in
             // bytes -- no address arithmetic in vector registers.  An unused entry (-1) gathers at x + shift, which is inside x:
             // a mode-1 slice has 64 distinct columns in its first cell, and the empty records behind the last slice are mode 2
@@ -675,7 +742,10 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
 #pragma unroll
             for(int u = 0; u < SPW; u++)
             {
-                const unsigned sh = mode[u] == SELL_DESC_MODE_LANE_SHIFT ? (unsigned)lane * (unsigned)sizeof(T) : 0u;
+                bool shifted = mode[u] == SELL_DESC_MODE_LANE_SHIFT;
+                if constexpr(REC)
+                    shifted = shifted || (d[u].w & SELL_DESC_EXCEPT) != 0u;
+                const unsigned sh = shifted ? (unsigned)lane * (unsigned)sizeof(T) : 0u;
 #pragma unroll
                 for(int q = 0; q < WMAX; q++)
                 {
@@ -695,6 +765,21 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
                         xx[u][q] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(xb) + sh);
                 }
                 okm[u] = (1u << (d[u].w & 0xffu)) - 1u;
+                if constexpr(REC)
+                {
+                    // an exception lane has only the cells of its mask (its other gathers, at B + lane, are inside x and are
+                    // dropped by the select of the chain); without the flag no lane compares equal
+                    const bool     ex = (d[u].w & SELL_DESC_EXCEPT) != 0u;
+                    const unsigned la = ex ? (d[u].x >> 8) & 0xffu : SELL_DESC_NO_LANE, lb = ex ? d[u].x >> 24 : SELL_DESC_NO_LANE;
+                    okm[u]            = (unsigned)lane == la ? (d[u].x >> 16) & 0xffu : okm[u];
+                    okm[u]            = (unsigned)lane == lb ? d[u].z & 0xffu : okm[u];
+                }
+            }
+            if constexpr(REC)
+            {
+#pragma unroll
+                for(int u = 0; u < SPW; u++) // (behind the gathers: the first use of a word that was read)
+                    pw[u] = (d[u].w & SELL_DESC_UWORD) != 0u ? (d[u].x & 0xffu) : pw[u];
             }
         }
     }

@@ -803,4 +803,17 @@ aoclsparse_status aoclsparse_mi355_get_sell_packing(const aoclsparse_matrix A, a
     return aoclsparse_status_success;
 }
 
+aoclsparse_status aoclsparse_mi355_get_sell_records(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *uniform_word_slices,
+                                                    aoclsparse_int *exception_slices)
+{
+    if(!A || !uniform_word_slices || !exception_slices)
+        return aoclsparse_status_invalid_pointer;
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
+    const bool                          on = p.sell.valid && p.sell.ucol.ptr;
+    *uniform_word_slices                   = on ? p.sell.uniform_words : 0;
+    *exception_slices                      = on ? p.sell.exceptions : 0;
+    return aoclsparse_status_success;
+}
+
 } // extern "C"

@@ -261,6 +261,15 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_values(const aoclsparse_m
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_packing(const aoclsparse_matrix A, aoclsparse_operation op,
                                                                aoclsparse_int *index_bits, aoclsparse_int *word_bytes,
                                                                aoclsparse_int *uniform_slices);
+/* What the slice records of op(A)'s SELL-64 copy say beyond offsets, width and mode (copies with uniform lists and one-byte
+ * words only; 0, 0 otherwise).  uniform_word_slices = full slices with one column list whose 64 rows share ONE packed word: the
+ * record holds the word and the short-row kernel does not read the rows' words.  exception_slices = those among them that are
+ * "one list shifted by one per row" in which at most two rows omit cells of it (the first and last slice of a stencil's grid
+ * line): the record names the two rows and the cells they have, and the slice runs as a shifted one.  Both are recounted
+ * whenever the copy is rebuilt (a value change).  Derived operators are not reported. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_records(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                               aoclsparse_int *uniform_word_slices,
+                                                               aoclsparse_int *exception_slices);
 /* The plan behind mm_bell_xcd_chunk / the lattice sweep, computed from host arrays (no device involved; what aoclsparse_optimize runs on the
  * blocked-ELL copy's block columns): bcol = nbr x width block columns, ascending per block row, empty slots (-1) last; nbc = block columns of
  * the matrix.  forced: -2 automatic, -1 the lattice sweep whenever a lattice is found, 0 launch order, c >= 1 chunks of c block rows.
