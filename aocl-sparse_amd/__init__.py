@@ -409,6 +409,8 @@ SIGNATURES = {
     "aoclsparse_mi355_get_sell_values": (c_int, [_P, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_sell_packing": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I)]),
     "aoclsparse_mi355_get_sell_records": (c_int, [_P, c_int, POINTER(_I), POINTER(_I)]),
+    "aoclsparse_mi355_get_sell_period": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_I)]),
+    "aoclsparse_mi355_sell_find_period": (c_int, [_I, _P, _P, _I, POINTER(_I), POINTER(ctypes.c_longlong)]),
     "aoclsparse_mi355_get_trsv_levels": (c_int, [_P, c_int, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_info": (c_int, [_P, c_int, c_int, POINTER(TrsvInfo)]),
     "aoclsparse_mi355_trsv_status": (c_int, [_P]),
@@ -584,6 +586,13 @@ class Matrix:
         assert lib().aoclsparse_mi355_get_sell_records(self.h, op, byref(u), byref(e)) == 0
         return u.value, e.value
 
+    def sell_period(self, op=OP_NONE):
+        """(first slice, end slice, period in slices, column shift per period) of the periodic range of the copy's slice records and
+        uniform lists; all 0 when it has none"""
+        a, b, p, c = _I(-1), _I(-1), _I(-1), _I(-1)
+        assert lib().aoclsparse_mi355_get_sell_period(self.h, op, byref(a), byref(b), byref(p), byref(c)) == 0
+        return a.value, b.value, p.value, c.value
+
     def trsv_info(self, fill, op=OP_NONE):
         info = TrsvInfo()
         assert lib().aoclsparse_mi355_get_trsv_info(self.h, fill, op, byref(info)) == 0
@@ -742,6 +751,22 @@ def scsrmm(op, alpha, A, descr, order, B, n, ldb, beta, C, ldc, kid=None):
     if kid is None:
         return lib().aoclsparse_scsrmm(op, alpha, A.h, descr.h, order, _ptr(B), n, ldb, beta, _ptr(C), ldc)
     return lib().aoclsparse_scsrmm_kid(op, alpha, A.h, descr.h, order, _ptr(B), n, ldb, beta, _ptr(C), ldc, kid)
+
+
+def sell_find_period(records, lists, max_period, work=False):
+    """the periodic range of host arrays (no device): records = (nslices, 4) uint32 {cell_lo, col_lo, hi, wsm}, lists =
+    (nslices, 8) int32 -> (first slice, end slice, period in slices, column shift per period); work=True: -> (that tuple, the pairs
+    of slices the search compared)"""
+    import numpy as np
+
+    records = np.ascontiguousarray(records, dtype=np.uint32)
+    lists = np.ascontiguousarray(lists, dtype=np.int32)
+    assert records.ndim == 2 and records.shape[1] == 4 and lists.shape == (records.shape[0], 8)
+    out = (_I * 4)(-1, -1, -1, -1)
+    n = ctypes.c_longlong(-1)
+    st = lib().aoclsparse_mi355_sell_find_period(records.shape[0], _ptr(records), _ptr(lists), max_period, out, byref(n))
+    assert st == 0, STATUS.get(st, st)
+    return (tuple(out), n.value) if work else tuple(out)
 
 
 def device_info():

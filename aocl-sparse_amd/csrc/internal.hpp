@@ -297,6 +297,29 @@ constexpr int            SELL_CELL_PAD = 64;
 // sell_leaders_kernel writes them (nullptr: column lists not shared, entry of a cell = its cell offset), ccells = column entries in all
 void sell_pack_descriptors(aoclsparse_int nslices, const long long *slice_ptr, const aoclsparse_int *leaders, long long ccells,
                            SellSliceDesc *out);
+// The periodic range of the DEVICE records and uniform lists (sell_period.cpp, which states the rule; host arrays, nslices records
+// and nslices x SELL_SHORT_WMAX columns): out = {first slice, end slice, period in slices, column shift per period}: the records
+// and lists of slice s in [first + period, end) are those of slice s - period with every column moved by the shift.  The smallest
+// period that is a multiple of 4 slices and at most cap, first and end multiples of 4; all zero when no such range holds two
+// periods and half of the slices, or when the search gives up (sell_period.cpp).
+void sell_find_period(const SellSliceDesc *desc, const aoclsparse_int *ucol, aoclsparse_int nslices, aoclsparse_int cap,
+                      aoclsparse_int out[4], long long *comparisons = nullptr);
+// the longest period looked for: 4096 slices = 192 KB of records and lists, which stay in an L2
+constexpr aoclsparse_int SELL_PERIOD_CAP = 4096;
+// What the short-row kernel can do with a range: it divides by the period with ONE multiply -- the high word of (slice - first) x
+// the reciprocal, exact for a power of two and otherwise while slices x period < 2^32 -- and adds the column shift to x in
+// bytes, 32 bits (vsize = bytes per value).  build_sell keeps no range that fails this, so what aoclsparse_mi355_get_sell_period
+// reports is what the kernel is handed.
+inline bool sell_period_usable(aoclsparse_int nslices, long long lo, long long hi, long long per, long long stride, size_t vsize)
+{
+    if(per <= 0 || hi <= lo || lo < 0 || stride < 0)
+        return false;
+    if((unsigned long long)((hi - lo) / per) * (unsigned long long)stride * vsize >= (1ull << 32))
+        return false;
+    return (per & (per - 1)) == 0 || (unsigned long long)nslices * (unsigned long long)per < (1ull << 32);
+}
+// pairs of slices the search compares per slice at most; beyond that it reports no range (*comparisons: how many it made)
+constexpr int SELL_PERIOD_WORK = 8;
 
 // What a SELL-64 launcher reads of a plan (SellPlan::view): sizes and device pointers, nothing owned.
 struct SellView
@@ -317,6 +340,8 @@ struct SellView
     int                   pbits = 0, pbytes = 0;
     // one list of SELL_SHORT_WMAX columns per slice (mode 1 / 2 slices; -1 everywhere else); nullptr when the plan has none
     const aoclsparse_int *ucol = nullptr;
+    // the periodic range of the records and lists (SellPlan::pslo ..; all zero: none)
+    int                   pslo = 0, pshi = 0, pper = 0, pstride = 0;
 };
 
 // SELL-64 twin of a device CSR (matrix.cpp: build_sell; layout in sell_build_kernels.hip, products in sell_kernels.hip): built by
@@ -350,6 +375,10 @@ struct SellPlan
     aoclsparse_int uniform = 0;
     // slices whose device record carries SELL_DESC_UWORD / SELL_DESC_EXCEPT (counted by the kernel that sets them)
     aoclsparse_int uniform_words = 0, exceptions = 0;
+    // the periodic range of the records and lists (sell_find_period on a copy of the device arrays, behind the kernel that writes
+    // the flags): slices [pslo, pshi), period pper slices, column shift pstride per period; all zero: none.  Four integers, no
+    // array: the short-row kernel reads the first period's records for every slice of the range
+    int            pslo = 0, pshi = 0, pper = 0, pstride = 0;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
@@ -365,6 +394,7 @@ struct SellPlan
         v.cells     = ntab ? (pbits ? pidx.ptr : vidx.ptr) : val.ptr;
         v.pbits = ntab ? pbits : 0, v.pbytes = ntab ? pbytes : 0;
         v.ucol = ucol.as<aoclsparse_int>();
+        v.pslo = pslo, v.pshi = pshi, v.pper = pper, v.pstride = pstride;
         v.col = col.as<aoclsparse_int>(), v.rowlen = rowlen.as<aoclsparse_int>();
         v.cptr = shared ? cptr.as<long long>() : nullptr;
         v.lead = shared ? lead.as<unsigned short>() : nullptr;

@@ -704,6 +704,7 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     sp.tried = true;
     sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
     sp.pbits = sp.pbytes = 0, sp.uniform = 0, sp.uniform_words = sp.exceptions = 0;
+    sp.pslo = sp.pshi = sp.pper = sp.pstride = 0;
     sp.vtab.release(), sp.vidx.release(), sp.pidx.release(), sp.desc.release(), sp.ucol.release();
     const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
@@ -891,6 +892,32 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     }
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr / desc (host) are read by the uploads until here
     sp.uniform_words = (aoclsparse_int)rc[0], sp.exceptions = (aoclsparse_int)rc[1];
+    // the periodic range of the records and lists as the device now holds them (flags, words and canonical lists included: they
+    // depend on the values, so every rebuild passes here too).  A stencil's records repeat from grid line to grid line, and the
+    // short-row kernel then reads one period's for the whole range (sell_period.cpp).  A copy that cannot be made keeps no range.
+    if(sp.ucol.ptr && sp.pbytes == 1)
+    {
+        PhaseTimer                  pt("sell: periodic range of the records");
+        std::vector<aoclsparse_int> uh;
+        try
+        {
+            uh.resize((size_t)nslices * SELL_SHORT_WMAX);
+        }
+        catch(const std::bad_alloc &)
+        {
+            uh.clear();
+        }
+        if(!uh.empty())
+        {
+            MI355_HIP_TRY(hipMemcpyAsync(desc.data(), sp.desc.ptr, sizeof(SellSliceDesc) * (size_t)nslices, hipMemcpyDeviceToHost, rt.stream()));
+            MI355_HIP_TRY(hipMemcpyAsync(uh.data(), sp.ucol.ptr, sizeof(aoclsparse_int) * uh.size(), hipMemcpyDeviceToHost, rt.stream()));
+            MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
+            aoclsparse_int pr[4];
+            sell_find_period(desc.data(), uh.data(), nslices, SELL_PERIOD_CAP, pr);
+            if(sell_period_usable(nslices, pr[0], pr[1], pr[2], pr[3], vsize))
+                sp.pslo = (int)pr[0], sp.pshi = (int)pr[1], sp.pper = (int)pr[2], sp.pstride = (int)pr[3];
+        }
+    }
     sp.valid = sp.wanted = true;
     return aoclsparse_status_success;
 }

@@ -478,373 +478,28 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
                                                                    const T *__restrict__ vtab, const aoclsparse_int *__restrict__ ucol,
                                                                    int pbits, int pbytes)
 {
-    using R = typename SellCell<T, TAB != 0>::raw;
-    // the mapping of a run (below): double, several slices per wavefront, uniform lists and packed words.  (Float was built and
-    // measured with it -- 28 -> 7 vector memory instructions per wavefront and the same time, DESIGN.md 5.1 -- and keeps the
-    // mapping by slice; the code below is written for any real type and any SPW > 1.)
-    constexpr bool WIDE = UCOL && PK && SPW > 1 && std::is_same_v<T, double>;
-    // what the records say beyond offsets and mode (plans with uniform lists and one-byte words: internal.hpp, SELL_DESC_UWORD /
-    // SELL_DESC_EXCEPT): a slice's rows share ONE word, held by the record; a mode-0 slice is one list shifted by lane in which
-    // two lanes at most omit cells -- it counts as shifted here, for the column decision and the run test
-    constexpr bool REC = UCOL && PK;
-    static_assert(WAVES * SPW <= SELL_DESC_PAD && 64 * WAVES == SELL_VTAB_MAX, "padding of the slice records / one table entry per lane");
-    static_assert(!PK || TAB != 0, "packed words hold table indices");
-    // group g of WAVES x SPW slices; consecutive products of a handle ALTERNATE the direction (SellPlan::products): g0 = last
-    // group, gstep = -1 on odd ones
-    const int sb   = __builtin_amdgcn_readfirstlane(((g0 + gstep * (int)blockIdx.x) * WAVES + (int)(threadIdx.x >> 6)) * SPW);
-    const int lane = threadIdx.x & 63;
-    s_pin_arg(alpha), s_pin_arg(beta), s_pin_arg(y), s_pin_arg((int)nt), s_pin_arg(x), s_pin_arg(sval), s_pin_arg(scol), s_pin_arg(follow);
-    s_pin_arg(pbits), s_pin_arg(pbytes); // (not ucol / vtab: a pointer handed to an asm statement is no longer read with scalar loads)
-    [[maybe_unused]] T t0, t1;
-    if constexpr(TAB == 2)
-        t0 = vtab[0], t1 = vtab[1];
-    else if constexpr(TAB != 0)
-        t0 = vtab[threadIdx.x];
-    uint4 d[SPW];
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-        d[u] = desc[sb + u];
-    [[maybe_unused]] int uc[SPW][WMAX]; // the slices' uniform lists: scalars
-    if constexpr(UCOL)
-    {
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-#pragma unroll
-            for(int q = 0; q < WMAX; q++)
-                uc[u][q] = ucol[(sb + u) * SELL_SHORT_WMAX + q];
-    }
-    // the rows' packed index words.  Kernels without the run mapping load them HERE, with the records; the others behind the
-    // decision, which says whose rows they are
-    [[maybe_unused]] unsigned pw[SPW];
-    auto words_by_slice = [&]() {
-        if constexpr(PK)
-        {
-            // (TAB 2: <= 8 cells of one bit, always a byte; else the width is a run-time scalar and the load has no branch)
-            const long long row = (long long)sb * 64 + lane;
-#pragma unroll
-            for(int u = 0; u < SPW; u++)
-                pw[u] = TAB == 2 ? packed_word(sval, row + 64 * u, 1) : packed_word_any(sval, row + 64 * u, pbytes);
-        }
-    };
-    if constexpr(!REC)
-        words_by_slice();
-    int  mode[SPW];
-    bool lists = !UCOL; // the group reads its columns from the lists in col
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-    {
-        mode[u] = (int)(d[u].w >> 16) & 0xff;
-        if constexpr(!REC)
-            lists = lists || !(mode[u] == SELL_DESC_MODE_LANE_SHIFT || mode[u] == SELL_DESC_MODE_ONE);
-    }
-    [[maybe_unused]] R rr[SPW][WMAX];
-    if constexpr(!PK)
-    {
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-        {
-            const long long o0 = (long long)d[u].x | (long long)(d[u].z & 0xffffu) << 32;
-            const int       w  = (int)(d[u].w & 0xffu);
-            const auto     *v  = sval + o0 + lane;
-#pragma unroll
-            for(int q = 0; q < WMAX; q++)
-                rr[u][q] = v[max(min(q, w - 1), 0) * 64]; // (wave-uniform index)
-        }
-    }
-    if constexpr(UCOL)
-    {
-        // the lists (and the two table entries) are in their scalar registers HERE: their loads go out with the records, in front of
-        // the branch, not inside the path that uses them (one more scalar round trip there); then the whole batch is issued
-        // before the branch
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-#pragma unroll
-            for(int q = 0; q < WMAX; q++)
-                s_pin_arg(uc[u][q]);
-        if constexpr(REC)
-        {
-            // all four words of every record too: the run test reads only w, and the compiler would otherwise fetch x / y / z
-            // (offsets, needed by the lists in col alone; a flagged slice's word and lanes) behind the test -- a fourth round
-            // trip on that path
-#pragma unroll
-            for(int u = 0; u < SPW; u++)
-                s_pin_arg(d[u].x), s_pin_arg(d[u].y), s_pin_arg(d[u].z), s_pin_arg(d[u].w);
-        }
-        if constexpr(TAB == 2)
-            s_pin_arg(t0), s_pin_arg(t1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    [[maybe_unused]] unsigned ew[SPW]; // the record's w with the mode of a flagged slice read as "shifted"
-    [[maybe_unused]] bool     alluw = REC, anyex = false; // every slice has its word in the record / some slice has exception lanes
-    if constexpr(REC)
-    {
-        // (behind the batch: scalar work on the records in front of it would split it in two round trips)
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-        {
-            const bool ex = (d[u].w & SELL_DESC_EXCEPT) != 0u;
-            ew[u]         = ex ? ((d[u].w & 0xff00ffffu) | (unsigned)SELL_DESC_MODE_LANE_SHIFT << 16) : d[u].w;
-            alluw         = alluw && (d[u].w & SELL_DESC_UWORD) != 0u;
-            anyex         = anyex || ex;
-            lists         = lists || !(ex || mode[u] == SELL_DESC_MODE_LANE_SHIFT || mode[u] == SELL_DESC_MODE_ONE);
-        }
-    }
-    // A RUN: the group's SPW slices are all mode 1, of one width, and each list continues the list before it (column + 64 in
-    // every used cell): row j of the group's 64 SPW rows reads x[uc[0][q] + j].  Scalar compares on what the batch above brought.
-    // Words of more than one byte per row stay on the mapping by slice.
-    [[maybe_unused]] bool run = false;
-    if constexpr(WIDE)
-    {
-        // (one word of differences, no branch per compare: mode and width are bits 0 .. 7 and 16 .. 23 of w)
-        const int w0  = (int)(d[0].w & 0xffu);
-        unsigned  dif = (ew[0] ^ ((unsigned)SELL_DESC_MODE_LANE_SHIFT << 16)) & 0xff0000u;
-        if constexpr(TAB != 2)
-            dif |= (unsigned)(pbytes - 1);
-#pragma unroll
-        for(int u = 1; u < SPW; u++)
-        {
-            dif |= (ew[u] ^ ew[0]) & 0xff00ffu;
-#pragma unroll
-            for(int q = 0; q < WMAX; q++)
-                dif |= q < w0 ? (unsigned)(uc[u][q] - uc[0][q] - 64 * u) : 0u;
-        }
-        run = dif == 0u;
-    }
-    T        xx[SPW][WMAX];
-    unsigned okm[SPW]; // bit q: cell q of this lane's row is a cell of the matrix (inside the slice's width, no padding)
-    // the columns from the lists in col, as a lane finds them through the slice's mode; then the gathers
-    auto from_lists = [&]() {
-        int  f[SPW]; // list of this lane | column shift << 8
-        bool follows = false;
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-        {
-            follows = follows || mode[u] == SELL_DESC_MODE_FOLLOW;
-            f[u]    = mode[u] == SELL_DESC_MODE_LANE_SHIFT ? lane << 8 : (mode[u] == SELL_DESC_MODE_OWN ? lane : 0);
-        }
-        if(follows) // wave-uniform
-        {
-            int ff[SPW];
-#pragma unroll
-            for(int u = 0; u < SPW; u++)
-                ff[u] = follow[min((sb + u) * 64 + lane, (int)m - 1)];
-#pragma unroll
-            for(int u = 0; u < SPW; u++)
-                f[u] = mode[u] == SELL_DESC_MODE_FOLLOW ? ff[u] : f[u];
-        }
-        int cc[SPW][WMAX];
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-        {
-            const long long c0 = (long long)d[u].y | (long long)(d[u].z >> 16) << 32;
-            const int       w = (int)(d[u].w & 0xffu), cs = (int)(d[u].w >> 8) & 0xff;
-            const aoclsparse_int *c = scol + c0 + (f[u] & 0xff);
-#pragma unroll
-            for(int q = 0; q < WMAX; q++)
-                cc[u][q] = c[max(min(q, w - 1), 0) * cs]; // (wave-uniform index)
-        }
-        __builtin_amdgcn_sched_barrier(0); // (every line load is issued before the first wait for one)
-#pragma unroll
-        for(int u = 0; u < SPW; u++)
-        {
-            const int w = (int)(d[u].w & 0xffu);
-            okm[u]      = 0;
-#pragma unroll
-            for(int q = 0; q < WMAX; q++) // (a padding cell, -1, is never used, but its gather must stay inside x: index 0)
-            {
-                xx[u][q] = x[cc[u][q] >= 0 ? cc[u][q] + (f[u] >> 8) : 0];
-                okm[u] |= (q < w && cc[u][q] >= 0) ? 1u << q : 0u;
-            }
-        }
-    };
-    if constexpr(UCOL)
-    {
-        if(__builtin_expect(lists, 0)) // wave-uniform
-        {
-            // (a flagged slice is read here as every reader but this kernel reads it: its rows' own words, its lists through
-            // follow[] -- the word of the record sits at the canonical cell positions, which are not the rows' own)
-            if constexpr(REC)
-                words_by_slice();
-            from_lists();
-        }
-        else if(WIDE && __builtin_expect(run, 1)) // wave-uniform
-        {
-            // lane l owns the SPW CONSECUTIVE rows SPW l .. SPW l + SPW - 1 of the group: xx[u] / pw[u] / r[u] are row SPW l + u.
-            // One gather per cell, SPW elements (16 bytes) per lane at the scalar base x + column (element-aligned only: column
-            // i - 1 is odd); one load of the lane's SPW adjacent word bytes.  An unused entry (-1) gathers at x + the lane's
-            // offset: inside x, a run has 64 SPW distinct columns in its first cell.
-            if constexpr(WIDE)
-            {
-                using RowVec = SellRows<T, SPW>;
-                using PW = std::conditional_t<SPW == 2, unsigned short, unsigned>;
-                // the lane's SPW rows lie in ONE slice of the group, slice lane / (64 / SPW): its record's word where it has one
-                const int ls   = lane / (64 / SPW);
-                unsigned  rw   = d[0].x & 0xffu;
-                bool      huw  = (d[0].w & SELL_DESC_UWORD) != 0u;
-#pragma unroll
-                for(int u = 1; u < SPW; u++)
-                    rw = ls == u ? (d[u].x & 0xffu) : rw, huw = ls == u ? (d[u].w & SELL_DESC_UWORD) != 0u : huw;
-                unsigned word = 0;
-                if(!__builtin_expect(alluw, 1)) // wave-uniform: with every word in a record none is read
-                    word = *reinterpret_cast<const PW *>(reinterpret_cast<const unsigned char *>(sval) + (long long)sb * 64 + SPW * lane);
-#pragma unroll
-                for(int u = 0; u < SPW; u++)
-                    okm[u] = (1u << (d[0].w & 0xffu)) - 1u;
-                if(__builtin_expect(anyex, 0)) // wave-uniform: row 64 v + (exception lane) of the group is row u of lane owner
-                {
-#pragma unroll
-                    for(int v = 0; v < SPW; v++)
-                    {
-                        const bool     ex = (d[v].w & SELL_DESC_EXCEPT) != 0u;
-                        const unsigned la = (d[v].x >> 8) & 0xffu, lb = d[v].x >> 24;
-                        const unsigned ma = (d[v].x >> 16) & 0xffu, mb = d[v].z & 0xffu;
-                        const int      ga = ex && la != SELL_DESC_NO_LANE ? 64 * v + (int)la : -SPW;
-                        const int      gb = ex && lb != SELL_DESC_NO_LANE ? 64 * v + (int)lb : -SPW;
-#pragma unroll
-                        for(int u = 0; u < SPW; u++)
-                        {
-                            okm[u] = (ga >= 0 && ga % SPW == u && lane == ga / SPW) ? ma : okm[u];
-                            okm[u] = (gb >= 0 && gb % SPW == u && lane == gb / SPW) ? mb : okm[u];
-                        }
-                    }
-                }
-                using GV = const __attribute__((address_space(1))) RowVec;
-                using GC = const __attribute__((address_space(1))) char;
-#pragma unroll
-                for(int q = 0; q < WMAX; q++)
-                {
-                    GC *gb = (GC *)(x + max(uc[0][q], 0));
-                    asm volatile("" : "+s"(gb)); // (the base stays a scalar pair: as on the path below)
-                    const RowVec xv = *(GV *)(gb + (unsigned)lane * (unsigned)sizeof(RowVec));
-#pragma unroll
-                    for(int u = 0; u < SPW; u++)
-                        xx[u][q] = xv[u];
-                }
-#pragma unroll
-                for(int u = 0; u < SPW; u++) // (behind the gathers: the first use of a word that was read)
-                    pw[u] = huw ? rw : (word >> (8 * u)) & 0xffu;
-            }
-        }
-        else
-        {
-            if constexpr(REC)
-            {
-#pragma unroll
-                for(int u = 0; u < SPW; u++)
-                    pw[u] = 0;
-                if(!__builtin_expect(alluw, 1)) // wave-uniform: with every word in a record none is read
-                    words_by_slice();
-            }
-            // every slice of the group has one list: a gather is a scalar base, x + column, plus the lane's shift (mode 1) in
-            // bytes -- no address arithmetic in vector registers.  An unused entry (-1) gathers at x + shift, which is inside x:
-            // a mode-1 slice has 64 distinct columns in its first cell, and the empty records behind the last slice are mode 2
-            // (no shift).  A mode 1 / 2 slice is full and its rows repeat one list: every row has exactly w cells, none padded.
-#pragma unroll
-            for(int u = 0; u < SPW; u++)
-            {
-                bool shifted = mode[u] == SELL_DESC_MODE_LANE_SHIFT;
-                if constexpr(REC)
-                    shifted = shifted || (d[u].w & SELL_DESC_EXCEPT) != 0u;
-                const unsigned sh = shifted ? (unsigned)lane * (unsigned)sizeof(T) : 0u;
-#pragma unroll
-                for(int q = 0; q < WMAX; q++)
-                {
-                    const T *xb = x + max(uc[u][q], 0);
-                    if constexpr(std::is_floating_point_v<T>)
-                    {
-                        // (the base stays a scalar pair, in the global address space: the load takes it as it is.  If a compiler
-                        // stops honouring this the base moves to vector registers: slower, the same loads, the same bits --
-                        // profiles/r10/isa_waits_after.txt is the check)
-                        using GT = const __attribute__((address_space(1))) T;
-                        using GC = const __attribute__((address_space(1))) char;
-                        GT *gb   = (GT *)xb;
-                        asm volatile("" : "+s"(gb));
-                        xx[u][q] = *(GT *)((GC *)gb + sh);
-                    }
-                    else
-                        xx[u][q] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(xb) + sh);
-                }
-                okm[u] = (1u << (d[u].w & 0xffu)) - 1u;
-                if constexpr(REC)
-                {
-                    // an exception lane has only the cells of its mask (its other gathers, at B + lane, are inside x and are
-                    // dropped by the select of the chain); without the flag no lane compares equal
-                    const bool     ex = (d[u].w & SELL_DESC_EXCEPT) != 0u;
-                    const unsigned la = ex ? (d[u].x >> 8) & 0xffu : SELL_DESC_NO_LANE, lb = ex ? d[u].x >> 24 : SELL_DESC_NO_LANE;
-                    okm[u]            = (unsigned)lane == la ? (d[u].x >> 16) & 0xffu : okm[u];
-                    okm[u]            = (unsigned)lane == lb ? d[u].z & 0xffu : okm[u];
-                }
-            }
-            if constexpr(REC)
-            {
-#pragma unroll
-                for(int u = 0; u < SPW; u++) // (behind the gathers: the first use of a word that was read)
-                    pw[u] = (d[u].w & SELL_DESC_UWORD) != 0u ? (d[u].x & 0xffu) : pw[u];
-            }
-        }
-    }
-    else
-        from_lists();
-    [[maybe_unused]] __shared__ T ltab[TAB > 2 ? SELL_VTAB_MAX : 1];
-    if constexpr(TAB > 2) // (behind the gathers: the barrier is waited for while they are in flight)
-    {
-        ltab[threadIdx.x] = t0;
-        __syncthreads();
-    }
-    T r[SPW];
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-    {
-        r[u] = T(0);
-#pragma unroll
-        for(int q = 0; q < WMAX; q++)
-        {
-            T vv;
-            if constexpr(TAB == 0)
-                vv = s_cj<CONJ>(rr[u][q]);
-            else if constexpr(TAB == 2 && PK)
-                vv = ((pw[u] >> q) & 1u) ? t1 : t0;
-            else if constexpr(TAB == 2)
-                vv = rr[u][q] ? t1 : t0;
-            else if constexpr(PK)
-                vv = ltab[packed_index(pw[u], q, pbits)];
-            else
-                vv = ltab[rr[u][q]];
-            r[u] = ((okm[u] >> q) & 1u) ? s_fma(vv, xx[u][q], r[u]) : r[u];
-        }
-    }
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-        s_pin(r[u]); // (every load above is issued before the first guarded store)
-    if constexpr(WIDE)
-    {
-        if(__builtin_expect(run, 1)) // the lane's SPW rows are adjacent, inside m (mode 1 slices are full): one store
-        {
-            using RowVec = SellRows<T, SPW>;
-            RowVec *yp = reinterpret_cast<RowVec *>(y + (long long)sb * 64 + SPW * lane);
-            RowVec  yv = {};
-            if(beta != T(0))
-                yv = *yp;
-#pragma unroll
-            for(int u = 0; u < SPW; u++)
-            {
-                const T yu = yv[u];
-                yv[u]      = s_finish(r[u], alpha, beta, &yu);
-            }
-            if(nt)
-                __builtin_nontemporal_store(yv, yp);
-            else
-                *yp = yv;
-            return;
-        }
-    }
-#pragma unroll
-    for(int u = 0; u < SPW; u++)
-    {
-        const int i = (sb + u) * 64 + lane;
-        if(sb + u < nslices && i < m)
-            s_store(y + i, s_finish(r[u], alpha, beta, y + i), nt);
-    }
+    constexpr bool PERIOD = false; // (no periodic range: the names the body reads under PERIOD, never used)
+    [[maybe_unused]] constexpr int      pslo = 0, plen = 0, pper = 0;
+    [[maybe_unused]] constexpr unsigned prcp = 0, pstrideb = 0;
+#include "sell_short_body.inc"
+}
+
+// The kernel of a plan with uniform lists and packed words (real types; UCOL && PK): the same body with the plan's periodic
+// range -- slices [pslo, pslo + plen), period pper slices, prcp = the launcher's reciprocal of pper, pstrideb = the column shift
+// per period in bytes; plen = 0: the plan has none and every wavefront reads its own records.
+template <typename T, int WMAX, int WAVES, int SPW, int TAB>
+__global__ __launch_bounds__(64 * WAVES) void sell_mv_short_period_kernel(aoclsparse_int m, aoclsparse_int nslices, int g0, int gstep,
+                                                                          const uint4 *__restrict__ desc,
+                                                                          const typename SellCell<T, true>::src *__restrict__ sval,
+                                                                          const aoclsparse_int *__restrict__ scol,
+                                                                          const unsigned short *__restrict__ follow, T alpha,
+                                                                          const T *__restrict__ x, T beta, T *__restrict__ y, bool nt,
+                                                                          const T *__restrict__ vtab,
+                                                                          const aoclsparse_int *__restrict__ ucol, int pbits, int pbytes,
+                                                                          int pslo, int plen, int pper, unsigned prcp, unsigned pstrideb)
+{
+    constexpr bool CONJ = false, UCOL = true, PK = true, PERIOD = true;
+#include "sell_short_body.inc"
 }
 
 // slices per wavefront of the short-row kernel: AOCLSPARSE_MI355_SELL_SPW = 1 / 2 / 4 overrides the rule (measurements only;
@@ -869,16 +524,17 @@ bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T 
     constexpr bool       COMPLEX = !std::is_floating_point_v<T>;
     const aoclsparse_int m = v.m, nslices = v.nslices;
     // Slices per wavefront, by measurement (5-point Laplacians, cold products, one box, median of 20, ms; 1 / 2 / 4 slices per
-    // wavefront; profiles/r10/spw_sweep.txt, which also has the VGPRs and the occupancy of each variant; table = packed words and
-    // uniform lists, values = the cells hold values -- measured there WITH uniform lists, which lost and are not built for them):
+    // wavefront).  table = packed words, uniform lists, the periodic range: sell_mv_short_period_kernel, profiles/r17/spw_sweep.txt;
+    // values = the cells hold values: sell_mv_short_kernel, profiles/r10/spw_sweep.txt, which also has the VGPRs and the
+    // occupancy of each variant (measured there WITH uniform lists, which lost and are not built for them):
     //                       4096^2 (262,144 slices)    3000^2 (140,625)          2000^2 (62,500)
-    //   double, table       0.0951 / 0.0816 / 0.0843   0.0498 / 0.0475 / 0.0485  0.0256 / 0.0239 / 0.0256
+    //   double, table       0.0700 / 0.0539 / 0.0642   0.0431 / 0.0437 / 0.0442  0.0220 / 0.0203 / 0.0235
     //   double, values      0.1741 / 0.1774 / 0.1811   0.0905 / 0.0943 / 0.0962  0.0421 / 0.0444 / 0.0470
-    //   float, table        0.0770 / 0.0538 / 0.0461   0.0394 / 0.0305 / 0.0292  0.0209 / 0.0168 / 0.0173
+    //   float, table        0.0540 / 0.0407 / 0.0368   0.0342 / 0.0270 / 0.0253  0.0181 / 0.0154 / 0.0149
     //   float, values       0.1028 / 0.0864 / 0.0887   0.0555 / 0.0533 / 0.0534  0.0275 / 0.0256 / 0.0276
-    // -> from 60,000 slices on: double with a table 2, float with a table 4 (2000^2: 2 and 4 within each other's spread), float
-    // values 2; double values stay at 1 (8-byte cells: the bytes in flight of ONE slice already fill the wave's share).  The same
-    // rule as before the packed words (profiles/r8/spw_sweep.txt).  Not measured below 60,000 slices: 1.  Complex: 1.
+    // -> from 60,000 slices on: double with a table 2 (3000^2: 1, 2 and 4 within 2.5 %, inside the spread), float with a table 4,
+    // float values 2; double values stay at 1 (8-byte cells: the bytes in flight of ONE slice already fill the wave's share).
+    // The same rule since profiles/r8/spw_sweep.txt.  Not measured below 60,000 slices: 1.  Complex: 1.
     int spw = 1;
     if constexpr(!COMPLEX)
     {
@@ -896,12 +552,27 @@ bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T 
     const T        *vtab = static_cast<const T *>(v.vtab);
     if(TAB == 2 && !(v.pbits == 1 && v.pbytes == 1)) // (a plan with slice records and <= 2 table entries always packs)
         return false;
+    // the plan's periodic range (SellView::pslo ..; none, or one the kernel can use: sell_period_usable, checked again here because
+    // a range that failed it would read other slices' records) and the reciprocal of the period: 2^32 / period for a power of
+    // two, else floor(2^32 / period) + 1
+    int      pslo = v.pslo, pshi = v.pshi, pper = v.pper, pstride = v.pstride;
+    unsigned prcp = 0;
+    if(sell_period_usable(nslices, pslo, pshi, pper, pstride, sizeof(T)))
+        prcp = (unsigned)((1ull << 32) / (unsigned)pper) + ((pper & (pper - 1)) == 0 ? 0u : 1u);
+    else
+        pslo = pshi = pper = pstride = 0;
     // the kernel's path: PK when the plan's table indices are packed words (a table of two always is: <= 8 cells of one bit), UCOL
-    // when it also has uniform column lists (build_sell makes them next to packed words only)
+    // when it also has uniform column lists (build_sell makes them next to packed words only); with both, for a real type, the kernel
+    // that takes the periodic range
     auto launch = [&](auto wt, auto st, auto ut, auto pt) {
-        hipLaunchKernelGGL((sell_mv_short_kernel<T, decltype(wt)::value, WAVES, decltype(st)::value, CONJ, TAB, decltype(ut)::value, decltype(pt)::value>),
-                           grid, block, 0, s, m, nslices, g0, gstep, dp, sval, v.col, v.lead, alpha, x, beta, y, nt, vtab, v.ucol, v.pbits,
-                           v.pbytes);
+        if constexpr(decltype(ut)::value && decltype(pt)::value && TAB != 0 && !COMPLEX)
+            hipLaunchKernelGGL((sell_mv_short_period_kernel<T, decltype(wt)::value, WAVES, decltype(st)::value, TAB>), grid, block, 0, s, m,
+                               nslices, g0, gstep, dp, sval, v.col, v.lead, alpha, x, beta, y, nt, vtab, v.ucol, v.pbits, v.pbytes, pslo,
+                               pshi - pslo, pper, prcp, (unsigned)pstride * (unsigned)sizeof(T));
+        else
+            hipLaunchKernelGGL((sell_mv_short_kernel<T, decltype(wt)::value, WAVES, decltype(st)::value, CONJ, TAB, decltype(ut)::value, decltype(pt)::value>),
+                               grid, block, 0, s, m, nslices, g0, gstep, dp, sval, v.col, v.lead, alpha, x, beta, y, nt, vtab, v.ucol,
+                               v.pbits, v.pbytes);
     };
     auto path = [&](auto wt, auto st) {
         if constexpr(TAB == 2)

@@ -816,4 +816,30 @@ aoclsparse_status aoclsparse_mi355_get_sell_records(const aoclsparse_matrix A, a
     return aoclsparse_status_success;
 }
 
+aoclsparse_status aoclsparse_mi355_get_sell_period(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *first_slice,
+                                                   aoclsparse_int *end_slice, aoclsparse_int *period_slices, aoclsparse_int *column_stride)
+{
+    if(!A || !first_slice || !end_slice || !period_slices || !column_stride)
+        return aoclsparse_status_invalid_pointer;
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
+    const bool                          on = p.sell.valid && p.sell.ucol.ptr;
+    *first_slice                           = on ? p.sell.pslo : 0;
+    *end_slice                             = on ? p.sell.pshi : 0;
+    *period_slices                         = on ? p.sell.pper : 0;
+    *column_stride                         = on ? p.sell.pstride : 0;
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_sell_find_period(aoclsparse_int nslices, const void *records, const aoclsparse_int *lists,
+                                                    aoclsparse_int max_period, aoclsparse_int range[4], long long *comparisons)
+{
+    if(!records || !lists || !range)
+        return aoclsparse_status_invalid_pointer;
+    if(nslices < 0 || max_period < 0)
+        return aoclsparse_status_invalid_size;
+    sell_find_period(static_cast<const SellSliceDesc *>(records), lists, nslices, max_period, range, comparisons);
+    return aoclsparse_status_success;
+}
+
 } // extern "C"

@@ -270,6 +270,25 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_packing(const aoclsparse_
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_records(const aoclsparse_matrix A, aoclsparse_operation op,
                                                                aoclsparse_int *uniform_word_slices,
                                                                aoclsparse_int *exception_slices);
+/* The periodic range of the slice records and uniform column lists of op(A)'s SELL-64 copy (copies with uniform lists and
+ * one-byte words only; all 0 otherwise, or when there is none).  The records and lists of slice s in [first_slice + period_slices,
+ * end_slice) are those of slice s - period_slices with every column moved by column_stride -- a stencil's grid lines -- and the
+ * short-row kernel reads the first period's records and lists for every slice of the range.  period_slices is the smallest
+ * multiple of 4 (at most 4096) for which such a range holds two periods and half of the slices; first_slice and end_slice are
+ * multiples of 4; column_stride = 64 * period_slices.  What is reported is what the kernel is handed: a range the kernel's 32-bit
+ * arithmetic could not serve is not kept.  Found again whenever the copy is rebuilt (a value change).  Derived
+ * operators are not reported. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_period(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                              aoclsparse_int *first_slice, aoclsparse_int *end_slice,
+                                                              aoclsparse_int *period_slices, aoclsparse_int *column_stride);
+/* The same search on the caller's host arrays (no device involved): records = nslices slice records of four 32-bit words
+ * {cell_lo, col_lo, hi, wsm} (wsm: bits 0-7 width, 16-23 mode, bit 24 "one word, in cell_lo bits 0-7", bit 25 "exception lanes,
+ * in cell_lo and hi bits 0-7"), lists = nslices x 8 columns (-1: unused), max_period in slices.  range = {first_slice, end_slice,
+ * period_slices, column_stride}.  comparisons (may be null) receives the pairs of slices the search compared: it makes 8 x nslices
+ * at most and reports no range when that does not suffice. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sell_find_period(aoclsparse_int nslices, const void *records,
+                                                               const aoclsparse_int *lists, aoclsparse_int max_period,
+                                                               aoclsparse_int range[4], long long *comparisons);
 /* The plan behind mm_bell_xcd_chunk / the lattice sweep, computed from host arrays (no device involved; what aoclsparse_optimize runs on the
  * blocked-ELL copy's block columns): bcol = nbr x width block columns, ascending per block row, empty slots (-1) last; nbc = block columns of
  * the matrix.  forced: -2 automatic, -1 the lattice sweep whenever a lattice is found, 0 launch order, c >= 1 chunks of c block rows.
