@@ -391,6 +391,16 @@ SIGNATURES = {
     "aoclsparse_mi355_set_option": (c_int, [c_int, _I]),
     "aoclsparse_mi355_mm_state_export": (c_int, [_P, POINTER(MmState), _P]),
     "aoclsparse_mi355_mm_state_adopt": (c_int, [_P, POINTER(MmState), _P]),
+    "aoclsparse_mi355_create_scsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
+    "aoclsparse_mi355_create_dcsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
+    "aoclsparse_mi355_create_ccsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
+    "aoclsparse_mi355_create_zcsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
+    "aoclsparse_mi355_supdate_values_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_dupdate_values_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_cupdate_values_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_zupdate_values_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
+                                                   POINTER(_P)]),
     "aoclsparse_mi355_comm_unique_id": (c_int, [POINTER(CommId)]),
     "aoclsparse_mi355_comm_init": (c_int, [_I, _I, POINTER(CommId)]),
     "aoclsparse_mi355_comm_destroy": (c_int, []),
@@ -507,6 +517,66 @@ class Matrix:
         assert e["status"] == 0, STATUS.get(e["status"], e["status"])
         self.m, self.n, self.nnz, self.base = e["m"], e["n"], e["nnz"], e["base"]
         return self
+
+    # value type letter of the C entry points by numpy dtype name (torch dtypes print as "torch.<name>")
+    _LETTER = {"float32": "s", "float64": "d", "complex64": "c", "complex128": "z"}
+
+    @classmethod
+    def from_device(cls, base, m, n, nnz, row_ptr, col_ind, val, dtype=None):
+        """aoclsparse_mi355_create_?csr_device: a handle from CSR arrays in HBM (torch device tensors or integer addresses; int32
+        indices).  The arrays are copied -- nothing is kept alive here -- and must be complete before the call
+        (torch.cuda.synchronize() after the kernels that fill them).  The value type is val's dtype, or `dtype` (a numpy / torch
+        dtype or its name) when val is an address.  Look at .status, as with Matrix(...)."""
+        name = str(val.dtype if dtype is None else dtype).split(".")[-1]
+        for t in (row_ptr, col_ind):
+            assert not hasattr(t, "dtype") or str(t.dtype).split(".")[-1] == "int32", "aoclsparse_int is 32-bit"
+        self = cls.__new__(cls)
+        self.row_ptr = self.col_ind = self.val = None  # the handle owns its arrays
+        self.letter = cls._LETTER[name]
+        self.double = name == "float64"
+        self.m, self.n, self.nnz, self.base = m, n, nnz, base
+        self.h = c_void_p()
+        fn = getattr(lib(), "aoclsparse_mi355_create_%scsr_device" % self.letter)
+        self.status = fn(byref(self.h), base, m, n, nnz, _ptr(row_ptr), _ptr(col_ind), _ptr(val))
+        return self
+
+    @classmethod
+    def from_torch_csr(cls, t, base=0):
+        """a torch.sparse_csr tensor on the GPU -> handle (zero-based); its int64 indices are cast to int32 on the device"""
+        import torch
+
+        assert t.layout == torch.sparse_csr and t.is_cuda and t.dim() == 2
+        m, n = t.shape
+        rp = t.crow_indices().to(torch.int32).contiguous()
+        ci = t.col_indices().to(torch.int32).contiguous()
+        v = t.values().contiguous()
+        nnz = int(v.numel())
+        if nnz == 0:  # (an empty tensor has no address; the library wants allocations, as the host call wants non-null arrays)
+            ci, v = torch.zeros(1, dtype=torch.int32, device=t.device), torch.zeros(1, dtype=v.dtype, device=t.device)
+        if base:
+            rp, ci = rp + base, ci + base
+        torch.cuda.synchronize()
+        return cls.from_device(base, m, n, nnz, rp, ci, v)
+
+    def _letter(self):
+        return getattr(self, "letter", None) or (self._LETTER[str(self.val.dtype)] if self.val is not None
+                                                 else "d" if self.double else "s")
+
+    def update_values_device(self, val):
+        """aoclsparse_mi355_?update_values_device: nnz new values (a torch device tensor or an address) in the order of the CSR
+        arrays -> status"""
+        n = int(val.numel()) if hasattr(val, "numel") else self.nnz
+        return getattr(lib(), "aoclsparse_mi355_%supdate_values_device" % self._letter())(self.h, n, _ptr(val))
+
+    def export_device(self):
+        """aoclsparse_mi355_export_csr_device -> dict(status, base, m, n, nnz, row_ptr, col_ind, val): the last three are device
+        ADDRESSES (read-only, valid until the handle is modified or destroyed)"""
+        base, m, n, nnz = c_int(), c_int32(), c_int32(), c_int32()
+        rp, ci, v = c_void_p(), c_void_p(), c_void_p()
+        st = lib().aoclsparse_mi355_export_csr_device(self.h, byref(base), byref(m), byref(n), byref(nnz), byref(rp), byref(ci), byref(v))
+        if st != 0:
+            return dict(status=st)
+        return dict(status=0, base=base.value, m=m.value, n=n.value, nnz=nnz.value, row_ptr=rp.value, col_ind=ci.value, val=v.value)
 
     def mm_state_export(self):
         """-> (status, MmState, [MM_STATE_BUFFERS device pointers]) : aoclsparse_mi355_mm_state_export"""

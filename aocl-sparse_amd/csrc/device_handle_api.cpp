@@ -1,0 +1,217 @@
+// device_handle_api.cpp -- matrix handles whose CSR arrays are already in HBM (round 7): create, update the values, export.
+//
+// The reference has no counterpart (a CPU library has one address space).  Until round 7 a matrix entered the library through host
+// arrays only (aoclsparse_create_?csr aliases them, the first product uploads them), so a matrix assembled on the GPU crossed PCIe
+// twice.  The three groups here keep the design of aoclsparse_mi355_mm_state_adopt (comm_api.cpp): the caller's device arrays are
+// COPIED into the handle's device mirror (dev_user), the handle gets an owned host view (`user`) by one copy back, and from then on
+// every entry point of the library works on it unchanged -- some 280 of them read A->user.  No aliasing, no handle without host
+// arrays.  What mat_check decides on the host for aoclsparse_create_?csr (validity, sort class, full diagonal) is decided by
+// matcheck_kernels.hip on the device.
+#include "matcheck.hpp"
+
+using namespace mi355;
+
+namespace
+{
+    template <typename T>
+    aoclsparse_status create_csr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N,
+                                        aoclsparse_int nnz, const aoclsparse_int *row_ptr, const aoclsparse_int *col_idx,
+                                        const T *val, aoclsparse_matrix_data_type vt)
+    {
+        // decided before the device is touched, in the order of create_csr / mat_check (matrix.cpp)
+        if(!mat)
+            return aoclsparse_status_invalid_pointer;
+        *mat = nullptr;
+        if(!row_ptr || !col_idx || !val)
+            return aoclsparse_status_invalid_pointer;
+        if(N < 0 || M < 0 || nnz < 0)
+            return aoclsparse_status_invalid_size;
+        Runtime          &rt = Runtime::get();
+        aoclsparse_status rc = rt.init();
+        if(rc != aoclsparse_status_success)
+            return rc;
+        if(!rt.is_device_pointer(row_ptr) || !rt.is_device_pointer(col_idx) || !rt.is_device_pointer(val))
+            return aoclsparse_status_invalid_pointer;
+        std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (one user of the library's stream at a time, as everywhere)
+        hipStream_t                           s = rt.stream();
+        // any base is checked like mat_check checks it: against ptr[0], and every index after subtracting it
+        LapTimer     lt; // (AOCLSPARSE_MI355_TIMING=1: where a creation's time goes)
+        DeviceBuffer res;
+        if((rc = res.alloc(sizeof(MatCheckResult))) != aoclsparse_status_success)
+            return rc;
+        MatCheckResult *d_res = res.as<MatCheckResult>(), h{};
+        if((rc = launch_matcheck_ptr(s, M, nnz, (int)base, row_ptr, d_res)) != aoclsparse_status_success)
+            return rc;
+        MI355_HIP_TRY(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipStreamSynchronize(s));
+        if(h.ptr_bad)
+            return aoclsparse_status_invalid_value; // col_idx is not looked at: its bounds would come from this row_ptr
+        if((rc = launch_matcheck_rows(s, M, N, (int)base, row_ptr, col_idx, d_res)) != aoclsparse_status_success)
+            return rc;
+        MI355_HIP_TRY(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipStreamSynchronize(s));
+        if(h.first_err)
+            return (aoclsparse_status)(~h.first_err & 0xff);
+        lt.lap("create_device: check kernels");
+
+        aoclsparse_matrix H = nullptr;
+        if((rc = new_csr_result(&H, M, N, nnz, vt, nullptr, base)) != aoclsparse_status_success)
+            return rc;
+        H->sort = h.cls ? h.cls : 1, H->fulldiag = !h.notfull;
+        // the device mirror and the host view, both from the caller's arrays
+        DeviceCsr   &d  = H->dev_user;
+        const size_t pb = sizeof(aoclsparse_int) * ((size_t)M + 1), ib = sizeof(aoclsparse_int) * (size_t)nnz, vb = sizeof(T) * (size_t)nnz;
+        rc = d.ptr.alloc(pb);
+        if(rc == aoclsparse_status_success)
+            rc = d.ind.alloc(ib);
+        if(rc == aoclsparse_status_success)
+            rc = d.val.alloc(vb);
+        auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+            if(rc == aoclsparse_status_success && bytes && hipMemcpyAsync(dst, src, bytes, kind, s) != hipSuccess)
+                rc = aoclsparse_status_internal_error;
+        };
+        copy(d.ptr.ptr, row_ptr, pb, hipMemcpyDeviceToDevice);
+        copy(d.ind.ptr, col_idx, ib, hipMemcpyDeviceToDevice);
+        copy(d.val.ptr, val, vb, hipMemcpyDeviceToDevice);
+        if(PhaseTimer::on() && rc == aoclsparse_status_success) // (the diagnostic separates the two directions)
+            (void)hipStreamSynchronize(s);
+        lt.lap("create_device: handle + device copy");
+        copy(H->user.ptr, row_ptr, pb, hipMemcpyDeviceToHost);
+        if(rc == aoclsparse_status_success && nnz > 0)
+        {
+            host_result_touch(H->user.ind, ib); // (fresh arrays: see host_result_alloc)
+            host_result_touch(H->user.val, vb);
+        }
+        copy(H->user.ind, col_idx, ib, hipMemcpyDeviceToHost);
+        copy(H->user.val, val, vb, hipMemcpyDeviceToHost);
+        if(rc == aoclsparse_status_success && hipStreamSynchronize(s) != hipSuccess) // the caller may overwrite or free its arrays now
+            rc = aoclsparse_status_internal_error;
+        if(rc != aoclsparse_status_success)
+        {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s); // (nothing in flight into the handle's arrays when they go)
+            aoclsparse_destroy(&H);
+            return rc;
+        }
+        lt.lap("create_device: host view");
+        d.m = M, d.n = N, d.nnz = nnz, d.base = base;
+        d.valid = true; // (the row-block plan is built from the host view at the first product, as for every handle)
+        *mat    = H;
+        return aoclsparse_status_success;
+    }
+
+    template <typename T>
+    aoclsparse_status update_values_device(aoclsparse_matrix A, aoclsparse_int len, const T *val, aoclsparse_matrix_data_type vt)
+    {
+        // the statuses of update_values (matrix.cpp), in its order
+        const bool coo = A && A->input_format == aoclsparse_coo_mat, nocsr = A && holds_no_csr(A);
+        if(!A || !val || (coo ? !A->coo_val : (!nocsr && !A->user.ptr)))
+            return aoclsparse_status_invalid_pointer;
+        if(len != A->nnz)
+            return aoclsparse_status_invalid_size;
+        if(A->val_type != vt)
+            return aoclsparse_status_wrong_type;
+        if(nocsr) // TCSR and BSR handles
+            return aoclsparse_status_not_implemented;
+        // ... and the handles whose first representation is not the CSR in `user`: their values follow the order of the caller's
+        // COO / CSC arrays, which live on the host
+        if(coo || A->csc_ptr)
+            return aoclsparse_status_not_implemented;
+        if(!A->user.val)
+            return aoclsparse_status_invalid_pointer;
+        Runtime          &rt = Runtime::get();
+        aoclsparse_status rc = rt.init();
+        if(rc != aoclsparse_status_success)
+            return rc;
+        if(!rt.is_device_pointer(val))
+            return aoclsparse_status_invalid_pointer;
+        std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
+        std::unique_lock<std::shared_mutex>   w(A->guard);
+        hipStream_t                           s     = rt.stream();
+        const size_t                          bytes = sizeof(T) * (size_t)len;
+        DeviceCsr                            &d     = A->dev_user;
+        // the mirror's row pointers and columns are the handle's structure exactly while the mirror is valid (aoclsparse_order_mat
+        // reorders the host arrays and leaves stale buffers behind an invalid mirror): only then do the values alone travel
+        const bool keep = d.valid && d.m == A->m && d.nnz == A->nnz && d.ptr.ptr && d.ind.ptr && d.val.ptr && d.val.bytes >= bytes;
+        if(bytes)
+        {
+            // (in stream order behind every product enqueued on the library's stream: they read the old values)
+            MI355_HIP_TRY(hipMemcpyAsync(A->user.val, val, bytes, hipMemcpyDeviceToHost, s));
+            if(keep && val != d.val.ptr)
+                MI355_HIP_TRY(hipMemcpyAsync(d.val.ptr, val, bytes, hipMemcpyDeviceToDevice, s));
+            MI355_HIP_TRY(hipStreamSynchronize(s));
+        }
+        drop_derived_state(A); // SELL-64 / blocked-ELL copies, TRSV plans, derived operators, replicas: rebuilt lazily
+        d.valid = keep;
+        return aoclsparse_status_success;
+    }
+} // namespace
+
+extern "C" {
+
+aoclsparse_status aoclsparse_mi355_create_scsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                      aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                      const aoclsparse_int *col_idx, const float *val)
+{
+    return create_csr_device(mat, base, M, N, nnz, row_ptr, col_idx, val, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_mi355_create_dcsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                      aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                      const aoclsparse_int *col_idx, const double *val)
+{
+    return create_csr_device(mat, base, M, N, nnz, row_ptr, col_idx, val, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_mi355_create_ccsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                      aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                      const aoclsparse_int *col_idx, const aoclsparse_float_complex *val)
+{
+    return create_csr_device(mat, base, M, N, nnz, row_ptr, col_idx, val, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_mi355_create_zcsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                      aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                      const aoclsparse_int *col_idx, const aoclsparse_double_complex *val)
+{
+    return create_csr_device(mat, base, M, N, nnz, row_ptr, col_idx, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_supdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const float *val)
+{
+    return update_values_device(A, len, val, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_mi355_dupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const double *val)
+{
+    return update_values_device(A, len, val, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_mi355_cupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const aoclsparse_float_complex *val)
+{
+    return update_values_device(A, len, val, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_mi355_zupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const aoclsparse_double_complex *val)
+{
+    return update_values_device(A, len, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
+                                                     aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
+                                                     const aoclsparse_int **col_idx, const void **val)
+{
+    if(!A || !base || !M || !N || !nnz || !row_ptr || !col_idx || !val)
+        return aoclsparse_status_invalid_pointer;
+    if(A->input_format != aoclsparse_csr_mat || !A->user.ptr || !A->user.ind || !A->user.val)
+        return aoclsparse_status_invalid_value; // COO, TCSR and BSR handles hold no CSR
+    Runtime          &rt = Runtime::get();
+    aoclsparse_status rc = rt.init();
+    if(rc != aoclsparse_status_success)
+        return rc;
+    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    std::unique_lock<std::shared_mutex>   w(A->guard);
+    if(!A->dev_user.valid && (rc = upload_csr(A->user, val_size(A->val_type), A->dev_user)) != aoclsparse_status_success)
+        return rc;
+    MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // the caller reads the arrays from streams of its own
+    const DeviceCsr &d = A->dev_user;
+    *base = (aoclsparse_index_base)d.base, *M = d.m, *N = d.n, *nnz = d.nnz;
+    *row_ptr = d.ptr.as<const aoclsparse_int>(), *col_idx = d.ind.as<const aoclsparse_int>(), *val = d.val.ptr;
+    return aoclsparse_status_success;
+}
+
+} // extern "C"

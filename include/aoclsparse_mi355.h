@@ -180,6 +180,68 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_export(aoclsparse_matrix 
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *R, const aoclsparse_mi355_mm_state *state,
                                                              const void *const buffers[AOCLSPARSE_MI355_MM_STATE_BUFFERS]);
 
+/* ---- the matrix is already on the GPU: CSR handles from, to and updated by arrays in HBM (round 7) --------------------------
+ * aoclsparse_create_?csr takes host arrays, which the first product uploads; ?update_values and aoclsparse_export_?csr speak host
+ * arrays too.  For a matrix that was assembled on the device (a sparse_csr tensor, a time-stepping code that refreshes its values)
+ * the three groups below do the same work from and to device arrays.  aoclsparse_int is 32-bit, here as everywhere.
+ *
+ *   create_?csr_device   The arguments of aoclsparse_create_?csr, with row_ptr (M + 1 entries), col_idx and val (nnz entries each)
+ *           in device memory.  The arrays are COPIED: on return the handle owns a device copy (resident: spmv_info.device_resident
+ *           is 1 before any product) and an owned host view made by one copy back, so every aoclsparse_* entry point works on the
+ *           handle as on a host-created one and gives the same bits.  The caller may overwrite or free its arrays afterwards.
+ *           The caller's arrays must be COMPLETE before the call (the work that fills them on other streams has finished: the
+ *           library reads them on its own stream and does not wait for anyone else's); the call synchronises the library's stream
+ *           before it returns.
+ *           Validity, the sort class and the full-diagonal flag are decided on the device and are exactly what
+ *           aoclsparse_create_?csr decides for the same arrays on the host: invalid_value for a row_ptr that does not start at
+ *           base, does not end at base + nnz or decreases (col_idx is then never read); otherwise the status of the first
+ *           offending row -- invalid_index_value for a column outside [base, base + N), invalid_value for a second diagonal
+ *           entry, whichever comes first in that row.
+ *           Decided before the device is touched, in the host call's order: invalid_pointer for a null mat or a null array,
+ *           invalid_size for a negative M, N or nnz.  A base other than 0 / 1 is not refused as such (aoclsparse_create_?csr does
+ *           not either): the arrays are checked against it like against any base.  An array that is not device (or managed)
+ *           memory in the current pointer mode: invalid_pointer.  M == 0 and nnz == 0 are valid, as on the host; the arrays must
+ *           still be non-null device allocations.
+ *   ?update_values_device   aoclsparse_?update_values with a device array of len = nnz values in the order of the handle's CSR
+ *           arrays.  Same statuses in the same order (invalid_pointer, invalid_size, wrong_type, not_implemented for TCSR / BSR
+ *           handles); in addition not_implemented for a COO handle and a handle created from CSC arrays, whose values follow the
+ *           order of host arrays.  The values are copied into the host view (for a host-created handle that is the caller's own
+ *           val array, as with ?update_values) and, when the handle's CSR is resident, device to device into the resident copy,
+ *           which stays resident: the next product uploads nothing.  Everything derived from the values (SELL-64 and blocked-ELL
+ *           copies, TRSV plans, derived operators, replicas) is dropped and rebuilt on first use, as after the host call.
+ *           `val` must be complete before the call; the library's stream is synchronised before return.
+ *   export_csr_device   The device pointers of the handle's resident CSR arrays (uploaded first when they are not resident):
+ *           the arrays the handle was created from / holds as `user` arrays, in their base -- not the clean copy
+ *           aoclsparse_export_?csr prefers after aoclsparse_optimize.  Works on every CSR-format handle: host-created,
+ *           device-created, a result of sp2m / syrk / sypr, an adopted one.  COO, TCSR and BSR handles: invalid_value.  The
+ *           pointers are READ-ONLY and valid until the handle is modified (?update_values*, ?set_value, aoclsparse_order_mat,
+ *           aoclsparse_mi355_invalidate) or destroyed; val points to values of the handle's type.  The library's stream is
+ *           synchronised before return.
+ *
+ * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
+ * COO, TCSR or BSR handles from device arrays. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_scsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                                 aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                                 const aoclsparse_int *col_idx, const float *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_dcsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                                 aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                                 const aoclsparse_int *col_idx, const double *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_ccsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                                 aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                                 const aoclsparse_int *col_idx, const aoclsparse_float_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_zcsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                                 aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
+                                                                 const aoclsparse_int *col_idx, const aoclsparse_double_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_supdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const float *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_dupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const double *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_cupdate_values_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                                    const aoclsparse_float_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zupdate_values_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                                    const aoclsparse_double_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
+                                                                aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
+                                                                const aoclsparse_int **col_idx, const void **val);
+
 /* ---- the same over a communicator the LIBRARY owns: RCCL (librccl.so, loaded with dlopen at the first call) ---------------
  * One communicator per process, on the library's device.  Rank 0 calls comm_unique_id and hands the 128 bytes to the other
  * ranks by any means (MPI, a file, torch.distributed's store); every rank then calls comm_init -- a collective, like all calls
