@@ -421,6 +421,9 @@ SIGNATURES = {
     "aoclsparse_mi355_get_sell_records": (c_int, [_P, c_int, POINTER(_I), POINTER(_I)]),
     "aoclsparse_mi355_get_sell_period": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_I)]),
     "aoclsparse_mi355_sell_find_period": (c_int, [_I, _P, _P, _I, POINTER(_I), POINTER(ctypes.c_longlong)]),
+    "aoclsparse_mi355_get_sell_march": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_I)]),
+    "aoclsparse_mi355_sell_find_march": (c_int, [_I, _P, _P, POINTER(_I), _I, POINTER(_I)]),
+    "aoclsparse_mi355_sell_march_rule": (c_int, [_I, _I, POINTER(_I), _I, _I, _I, _I, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_levels": (c_int, [_P, c_int, c_int, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_info": (c_int, [_P, c_int, c_int, POINTER(TrsvInfo)]),
     "aoclsparse_mi355_trsv_status": (c_int, [_P]),
@@ -663,6 +666,13 @@ class Matrix:
         assert lib().aoclsparse_mi355_get_sell_period(self.h, op, byref(a), byref(b), byref(p), byref(c)) == 0
         return a.value, b.value, p.value, c.value
 
+    def sell_march(self, op=OP_NONE):
+        """(first slice, end slice, periods per wavefront, alias map) of the stacked part of the copy's periodic range, as the
+        launcher will use it; all 0 when the product runs the kernel without stacking"""
+        a, b, g, c = _I(-1), _I(-1), _I(-1), _I(-1)
+        assert lib().aoclsparse_mi355_get_sell_march(self.h, op, byref(a), byref(b), byref(g), byref(c)) == 0
+        return a.value, b.value, g.value, c.value
+
     def trsv_info(self, fill, op=OP_NONE):
         info = TrsvInfo()
         assert lib().aoclsparse_mi355_get_trsv_info(self.h, fill, op, byref(info)) == 0
@@ -837,6 +847,30 @@ def sell_find_period(records, lists, max_period, work=False):
     st = lib().aoclsparse_mi355_sell_find_period(records.shape[0], _ptr(records), _ptr(lists), max_period, out, byref(n))
     assert st == 0, STATUS.get(st, st)
     return (tuple(out), n.value) if work else tuple(out)
+
+
+def sell_find_march(records, lists, rng, word_bytes=1):
+    """the two plan rules of the stacked periods on host arrays (records, lists as for sell_find_period; rng = the range that
+    search reported) -> (1 if the range can be stacked else 0, the alias map of its first period)"""
+    import numpy as np
+
+    records = np.ascontiguousarray(records, dtype=np.uint32)
+    lists = np.ascontiguousarray(lists, dtype=np.int32)
+    assert records.ndim == 2 and records.shape[1] == 4 and lists.shape == (records.shape[0], 8)
+    out = (_I * 2)(-1, -1)
+    st = lib().aoclsparse_mi355_sell_find_march(records.shape[0], _ptr(records), _ptr(lists), (_I * 4)(*rng), word_bytes, out)
+    assert st == 0, STATUS.get(st, st)
+    return tuple(out)
+
+
+def sell_march_rule(nslices, max_width, rng, stack, alias_map, value_bytes=8, slices_per_wavefront=2):
+    """what the launcher does with those two results -> (first slice, end slice, periods per wavefront, alias map), all 0: no
+    stacking"""
+    out = (_I * 4)(-1, -1, -1, -1)
+    st = lib().aoclsparse_mi355_sell_march_rule(nslices, max_width, (_I * 4)(*rng), stack, alias_map, value_bytes,
+                                                slices_per_wavefront, out)
+    assert st == 0, STATUS.get(st, st)
+    return tuple(out)
 
 
 def device_info():

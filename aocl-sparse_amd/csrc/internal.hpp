@@ -321,6 +321,84 @@ inline bool sell_period_usable(aoclsparse_int nslices, long long lo, long long h
 // pairs of slices the search compares per slice at most; beyond that it reports no range (*comparisons: how many it made)
 constexpr int SELL_PERIOD_WORK = 8;
 
+// STACKED PERIODS (sell_kernels.hip: sell_mv_short_march_kernel).  Two further facts about a periodic range, decided on its FIRST
+// period alone (sell_period.cpp: sell_find_march; range = what sell_find_period reported, word_bytes = the plan's pbytes):
+//   out[0] = 1: the range can be stacked -- every group of SELL_MARCH_GROUP consecutive slices of the first period is a run in
+//            the kernel's sense (all shifted, counting SELL_DESC_EXCEPT slices; one width; every list the list before it + 64 in
+//            every used cell), every slice carries SELL_DESC_UWORD and the words are one byte; else 0;
+//   out[1] = the alias map, four bits per cell: nibble q = a(q) + 1, where a(q) is the cell q' with ucol[q'] == ucol[q] + stride
+//            in EVERY slice of the period (both cells used in every slice; an entry of -1 never aliases), 0: none.
+// Cell q of a slice in period k + 1 is then cell a(q) of the same slice in period k: a wavefront that walks G periods of its
+// strip loads it once.
+constexpr int SELL_MARCH_GROUP = 4; // covers 2 and 4 slices per wavefront: range bounds and period are multiples of 4
+void sell_find_march(const SellSliceDesc *desc, const aoclsparse_int *ucol, aoclsparse_int nslices, const aoclsparse_int range[4],
+                     int word_bytes, aoclsparse_int out[2]);
+// slices from which a wavefront of the short-row kernel takes several (sell_kernels.hip: sell_launch_short, which has the table)
+constexpr aoclsparse_int SELL_SHORT_SPW_SLICES = 60000;
+// slices per wavefront of the short-row kernel: AOCLSPARSE_MI355_SELL_SPW = 1 / 2 / 4 overrides the rule (measurements only;
+// read once per process)
+inline int sell_short_spw_override()
+{
+    static const int v = [] {
+        const char *e = std::getenv("AOCLSPARSE_MI355_SELL_SPW");
+        const int   k = e ? std::atoi(e) : 0;
+        return (k == 1 || k == 2 || k == 4) ? k : 0;
+    }();
+    return v;
+}
+// the rule for a real type of vsize bytes (the table it comes from: sell_launch_short); table = the cells hold table indices
+inline int sell_short_spw(aoclsparse_int nslices, size_t vsize, bool table)
+{
+    int spw = 1;
+    if(nslices >= SELL_SHORT_SPW_SLICES)
+        spw = vsize == 4 ? (table ? 4 : 2) : (table ? 2 : 1);
+    return sell_short_spw_override() ? sell_short_spw_override() : spw;
+}
+// The alias maps the march kernel is built for, each at ONE width (= the plan's widest slice); read by the rule below and by the
+// launcher.  Today the 5-point stencil whose period is one grid line (cells -P, -1, 0, +1, +P: a(0) = 2, a(2) = 4).  A plan with
+// any other map is not stacked: where a plan really has no alias -- grid lines that are no multiple of 64 rows, whose period is
+// several lines: 3000^2, 2000^2, 3008 x 3000 -- stacking without shared loads measured within 2 % of the kernel without stacking
+// on either side (profiles/r18/g_sweep.txt).  The 7-offset map (0x6040) was not measured and is not built.
+struct SellMarchMap
+{
+    int      width;
+    unsigned alias;
+};
+constexpr SellMarchMap SELL_MARCH_MAPS[] = {{5, 0x503u}};
+// periods per stacked wavefront (profiles/r18/upper_bound.txt, g_sweep.txt: the table is in sell_launch_short), slices per
+// wavefront and wavefronts per workgroup of that kernel
+constexpr int SELL_MARCH_G = 3, SELL_MARCH_SPW = 2, SELL_MARCH_WAVES = 4;
+// What the launcher does with a plan (the ONE rule: sell_launch_short and aoclsparse_mi355_get_sell_march both call it): slices
+// [lo, hi) run stacked, g periods per wavefront, with the map alias; g = 0: nothing is stacked and the product runs
+// sell_mv_short_period_kernel.  vsize = bytes per value (double only: float was not measured), spw = the slices per wavefront the
+// launcher chose, stack / alias = SellView::mstack / malias.  hi - lo is a whole number of g periods AND of workgroups, so the
+// kernel has no partial workgroup on the stacked side; what is left of the range runs with the slices outside it.
+struct SellMarch
+{
+    int      lo = 0, hi = 0, g = 0;
+    unsigned alias = 0;
+};
+inline SellMarch sell_march_rule(aoclsparse_int nslices, aoclsparse_int max_width, int pslo, int pshi, int pper, int pstride, int stack,
+                                 unsigned alias, size_t vsize, int spw)
+{
+    constexpr int g = SELL_MARCH_G;
+    SellMarch     r;
+    if(!stack || vsize != 8 || spw != SELL_MARCH_SPW || !sell_period_usable(nslices, pslo, pshi, pper, pstride, vsize))
+        return r;
+    bool known = false;
+    for(const SellMarchMap &k : SELL_MARCH_MAPS)
+        known = known || (k.width == (int)max_width && k.alias == alias);
+    if(!known)
+        return r;
+    long long groups = (pshi - pslo) / pper / g; // of g whole periods
+    while(groups > 0 && (groups * (pper / SELL_MARCH_SPW)) % SELL_MARCH_WAVES != 0)
+        groups--;
+    if(groups <= 0)
+        return r;
+    r.lo = pslo, r.hi = pslo + (int)(groups * g * pper), r.g = g, r.alias = alias;
+    return r;
+}
+
 // What a SELL-64 launcher reads of a plan (SellPlan::view): sizes and device pointers, nothing owned.
 struct SellView
 {
@@ -342,6 +420,9 @@ struct SellView
     const aoclsparse_int *ucol = nullptr;
     // the periodic range of the records and lists (SellPlan::pslo ..; all zero: none)
     int                   pslo = 0, pshi = 0, pper = 0, pstride = 0;
+    // whether that range can be stacked, and its alias map (SellPlan::mstack, malias)
+    int                   mstack = 0;
+    unsigned              malias = 0;
 };
 
 // SELL-64 twin of a device CSR (matrix.cpp: build_sell; layout in sell_build_kernels.hip, products in sell_kernels.hip): built by
@@ -379,6 +460,9 @@ struct SellPlan
     // the flags): slices [pslo, pshi), period pper slices, column shift pstride per period; all zero: none.  Four integers, no
     // array: the short-row kernel reads the first period's records for every slice of the range
     int            pslo = 0, pshi = 0, pper = 0, pstride = 0;
+    // the range can be stacked (1 / 0) and the alias map of its first period (sell_find_march, on the same host copies)
+    int            mstack = 0;
+    unsigned       malias = 0;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
@@ -395,6 +479,7 @@ struct SellPlan
         v.pbits = ntab ? pbits : 0, v.pbytes = ntab ? pbytes : 0;
         v.ucol = ucol.as<aoclsparse_int>();
         v.pslo = pslo, v.pshi = pshi, v.pper = pper, v.pstride = pstride;
+        v.mstack = mstack, v.malias = malias;
         v.col = col.as<aoclsparse_int>(), v.rowlen = rowlen.as<aoclsparse_int>();
         v.cptr = shared ? cptr.as<long long>() : nullptr;
         v.lead = shared ? lead.as<unsigned short>() : nullptr;

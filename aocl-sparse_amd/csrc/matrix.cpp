@@ -705,6 +705,7 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
     sp.pbits = sp.pbytes = 0, sp.uniform = 0, sp.uniform_words = sp.exceptions = 0;
     sp.pslo = sp.pshi = sp.pper = sp.pstride = 0;
+    sp.mstack = 0, sp.malias = 0;
     sp.vtab.release(), sp.vidx.release(), sp.pidx.release(), sp.desc.release(), sp.ucol.release();
     const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
@@ -915,7 +916,14 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
             aoclsparse_int pr[4];
             sell_find_period(desc.data(), uh.data(), nslices, SELL_PERIOD_CAP, pr);
             if(sell_period_usable(nslices, pr[0], pr[1], pr[2], pr[3], vsize))
+            {
                 sp.pslo = (int)pr[0], sp.pshi = (int)pr[1], sp.pper = (int)pr[2], sp.pstride = (int)pr[3];
+                // whether the range can be stacked, and its alias map: one pass over the first period (<= SELL_PERIOD_CAP slices)
+                PhaseTimer     mt("sell: stacking and alias map of the period");
+                aoclsparse_int mr[2];
+                sell_find_march(desc.data(), uh.data(), nslices, pr, sp.pbytes, mr);
+                sp.mstack = (int)mr[0], sp.malias = (unsigned)mr[1];
+            }
         }
     }
     sp.valid = sp.wanted = true;

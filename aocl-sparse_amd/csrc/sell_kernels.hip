@@ -478,9 +478,10 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_kernel(aoclsparse_in
                                                                    const T *__restrict__ vtab, const aoclsparse_int *__restrict__ ucol,
                                                                    int pbits, int pbytes)
 {
-    constexpr bool PERIOD = false; // (no periodic range: the names the body reads under PERIOD, never used)
-    [[maybe_unused]] constexpr int      pslo = 0, plen = 0, pper = 0;
+    constexpr bool PERIOD = false, MARCH = false; // (no periodic range: the names the body reads under PERIOD / MARCH, never used)
+    [[maybe_unused]] constexpr int      pslo = 0, plen = 0, pper = 0, mskip = 0;
     [[maybe_unused]] constexpr unsigned prcp = 0, pstrideb = 0;
+    const int bgroup = g0 + gstep * (int)blockIdx.x;
 #include "sell_short_body.inc"
 }
 
@@ -498,23 +499,178 @@ __global__ __launch_bounds__(64 * WAVES) void sell_mv_short_period_kernel(aoclsp
                                                                           const aoclsparse_int *__restrict__ ucol, int pbits, int pbytes,
                                                                           int pslo, int plen, int pper, unsigned prcp, unsigned pstrideb)
 {
-    constexpr bool CONJ = false, UCOL = true, PK = true, PERIOD = true;
+    constexpr bool CONJ = false, UCOL = true, PK = true, PERIOD = true, MARCH = false;
+    [[maybe_unused]] constexpr int mskip = 0;
+    const int bgroup = g0 + gstep * (int)blockIdx.x;
 #include "sell_short_body.inc"
 }
 
-// slices per wavefront of the short-row kernel: AOCLSPARSE_MI355_SELL_SPW = 1 / 2 / 4 overrides the rule (measurements only;
-// read once per process)
-inline int sell_short_spw_override()
+// STACKED PERIODS (double; a plan whose periodic range can be stacked: internal.hpp, sell_march_rule).  In a range of period
+// pper slices and column shift pstride, the wavefront at position s of the period sees in period k + 1 exactly what it saw in
+// period k -- records, lists, words, exception lanes -- and only x and y move on by pstride elements.  So ONE wavefront takes G
+// consecutive periods of its strip of SPW slices, in straight-line code: it reads the first period's records once, issues every
+// gather of its G periods before the first wait, runs G x SPW chains and stores G times.  No loop, no barrier, no LDS,
+// no test: the plan has decided that every group of the period is a run with its words in the records, so this is the body's run
+// path with the decisions taken out.
+// ALIAS (four bits per cell: a(q) + 1, 0 = none; SELL_MARCH_MAPS): cell q of period k + 1 IS cell a(q) of period k -- on the
+// 5-point stencil the centre strip of grid line t is the south strip of line t - 1 and the north strip of line t + 1 -- so from
+// the second period on only the cells without a(q) are gathered: 3 G + 2 gathers on the 5-point stencil where G wavefronts of
+// sell_mv_short_period_kernel issue 5 G.  Every gather issued is one that kernel issues for the same slice (base x + (k + t) pstride
+// + column, 16 bytes per lane), so each stays inside x by its argument; none is added.  Each row's chain is its own cells front to
+// back with the record's masks and the table's values, as in the body: the same bits.
+// ONE launch: workgroups [0, mblocks) of the sweep (g0 / gstep, alternating as in the body) are stacked -- wavefront j takes position
+// j % mhp of the period (mhp = pper / SPW, mrcp the launcher's reciprocal of it) and the periods G (j / mhp) .. + G - 1 -- and the
+// others run the body over the slices outside [pslo, pslo + mskip): before the range, behind it, and the periods left over.
+template <typename T, int WMAX, int WAVES, int SPW, int TAB, int G, unsigned ALIAS>
+__global__ __launch_bounds__(64 * WAVES) void sell_mv_short_march_kernel(aoclsparse_int m, aoclsparse_int nslices, int g0, int gstep,
+                                                                         const uint4 *__restrict__ desc,
+                                                                         const typename SellCell<T, true>::src *__restrict__ sval,
+                                                                         const aoclsparse_int *__restrict__ scol,
+                                                                         const unsigned short *__restrict__ follow, T alpha,
+                                                                         const T *__restrict__ x, T beta, T *__restrict__ y, bool nt,
+                                                                         const T *__restrict__ vtab,
+                                                                         const aoclsparse_int *__restrict__ ucol, int pbits, int pbytes,
+                                                                         int pslo, int plen, int pper, unsigned prcp, unsigned pstrideb,
+                                                                         int mblocks, int mhp, unsigned mrcp, int mskip)
 {
-    static const int v = [] {
-        const char *e = std::getenv("AOCLSPARSE_MI355_SELL_SPW");
-        const int   k = e ? std::atoi(e) : 0;
-        return (k == 1 || k == 2 || k == 4) ? k : 0;
-    }();
-    return v;
+    constexpr bool CONJ = false, UCOL = true, PK = true, PERIOD = true, MARCH = true;
+    // (TAB 2 only: one-byte words of the 5 cells of the one map built leave one bit per cell, a table of two)
+    static_assert(SPW > 1 && std::is_same_v<T, double> && TAB == 2 && G >= 2, "the run mapping of a double plan with a table of two");
+    const int vgroup = g0 + gstep * (int)blockIdx.x;
+    if(vgroup < mblocks) // uniform over the workgroup
+    {
+        using RowVec = SellRows<T, SPW>;
+        using GV     = const __attribute__((address_space(1))) RowVec;
+        using GC     = const __attribute__((address_space(1))) char;
+        const unsigned j    = (unsigned)__builtin_amdgcn_readfirstlane(vgroup * WAVES + (int)(threadIdx.x >> 6));
+        const int      lane = threadIdx.x & 63;
+        s_pin_arg(alpha), s_pin_arg(beta), s_pin_arg(y), s_pin_arg((int)nt), s_pin_arg(x);
+        const T t0 = vtab[0], t1 = vtab[1];
+        // position in the period and first period: one multiply by the reciprocal, no division, no branch
+        const unsigned gi  = __umulhi(j, mrcp);
+        const unsigned pos = j - gi * (unsigned)mhp;
+        const unsigned sp  = (unsigned)pslo + pos * (unsigned)SPW; // the strip's slices in the FIRST period
+        const unsigned k0  = gi * (unsigned)G;
+        const uint4          *dp = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(desc) + sp * (unsigned)sizeof(uint4));
+        const aoclsparse_int *up = reinterpret_cast<const aoclsparse_int *>(reinterpret_cast<const char *>(ucol)
+                                                                            + sp * (unsigned)(SELL_SHORT_WMAX * sizeof(aoclsparse_int)));
+        uint4 d[SPW];
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+            d[u] = dp[u];
+        int uc[WMAX]; // the first slice's list: the run's one base per cell
+#pragma unroll
+        for(int q = 0; q < WMAX; q++)
+            uc[q] = up[q];
+#pragma unroll
+        for(int q = 0; q < WMAX; q++)
+            s_pin_arg(uc[q]);
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+            s_pin_arg(d[u].x), s_pin_arg(d[u].y), s_pin_arg(d[u].z), s_pin_arg(d[u].w); // (whole records: one wide load, no register reused inside the batch)
+        s_pin_arg(t0), s_pin_arg(t1);
+        __builtin_amdgcn_sched_barrier(0);
+        // the gathers of all G periods: every cell of the first, the cells without a(q) of the others
+        T xx[G][SPW][WMAX];
+#pragma unroll
+        for(int t = 0; t < G; t++)
+        {
+            GC *xt = (GC *)x + (k0 + (unsigned)t) * pstrideb; // (below 2^32 by the launcher's check, as in the body)
+#pragma unroll
+            for(int q = 0; q < WMAX; q++)
+            {
+                const int a = (int)((ALIAS >> (4 * q)) & 0xfu) - 1;
+                if(t > 0 && a >= 0)
+                {
+#pragma unroll
+                    for(int u = 0; u < SPW; u++)
+                        xx[t][u][q] = xx[t - 1][u][a];
+                }
+                else
+                {
+                    GC *gb = xt + (long long)max(uc[q], 0) * (long long)sizeof(T);
+                    asm volatile("" : "+s"(gb)); // (the base stays a scalar pair: as in the body)
+                    const RowVec xv = *(GV *)(gb + (unsigned)lane * (unsigned)sizeof(RowVec));
+#pragma unroll
+                    for(int u = 0; u < SPW; u++)
+                        xx[t][u][q] = xv[u];
+                }
+            }
+        }
+        // the lane's SPW rows lie in ONE slice of the group, slice lane / (64 / SPW): its record's word; the masks of the exception
+        // lanes (row 64 v + lane of the group is row u of its owner): the same in every period
+        const int ls = lane / (64 / SPW);
+        unsigned  rw = d[0].x & 0xffu;
+#pragma unroll
+        for(int u = 1; u < SPW; u++)
+            rw = ls == u ? (d[u].x & 0xffu) : rw;
+        unsigned okm[SPW];
+        bool     anyex = false;
+#pragma unroll
+        for(int u = 0; u < SPW; u++)
+            okm[u] = (1u << (d[0].w & 0xffu)) - 1u, anyex = anyex || (d[u].w & SELL_DESC_EXCEPT) != 0u;
+        if(__builtin_expect(anyex, 0)) // wave-uniform
+        {
+#pragma unroll
+            for(int v = 0; v < SPW; v++)
+            {
+                const bool     ex = (d[v].w & SELL_DESC_EXCEPT) != 0u;
+                const unsigned la = (d[v].x >> 8) & 0xffu, lb = d[v].x >> 24;
+                const unsigned ma = (d[v].x >> 16) & 0xffu, mb = d[v].z & 0xffu;
+                const int      ga = ex && la != SELL_DESC_NO_LANE ? 64 * v + (int)la : -SPW;
+                const int      gb = ex && lb != SELL_DESC_NO_LANE ? 64 * v + (int)lb : -SPW;
+#pragma unroll
+                for(int u = 0; u < SPW; u++)
+                {
+                    okm[u] = (ga >= 0 && ga % SPW == u && lane == ga / SPW) ? ma : okm[u];
+                    okm[u] = (gb >= 0 && gb % SPW == u && lane == gb / SPW) ? mb : okm[u];
+                }
+            }
+        }
+        T r[G][SPW];
+#pragma unroll
+        for(int t = 0; t < G; t++)
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+            {
+                r[t][u] = T(0);
+#pragma unroll
+                for(int q = 0; q < WMAX; q++)
+                {
+                    const T vv = ((rw >> q) & 1u) ? t1 : t0;
+                    r[t][u]    = ((okm[u] >> q) & 1u) ? s_fma(vv, xx[t][u][q], r[t][u]) : r[t][u];
+                }
+            }
+#pragma unroll
+        for(int t = 0; t < G; t++)
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+                s_pin(r[t][u]); // (every load above is issued before the first store)
+        // the lane's SPW rows are adjacent, inside m (the slices of a run are full): one store per period
+#pragma unroll
+        for(int t = 0; t < G; t++)
+        {
+            const long long sbt = (long long)sp + (long long)(k0 + (unsigned)t) * (long long)pper;
+            RowVec         *yp  = reinterpret_cast<RowVec *>(y + sbt * 64 + SPW * lane);
+            RowVec          yv  = {};
+            if(beta != T(0))
+                yv = *yp;
+#pragma unroll
+            for(int u = 0; u < SPW; u++)
+            {
+                const T yu = yv[u];
+                yv[u]      = s_finish(r[t][u], alpha, beta, &yu);
+            }
+            if(nt)
+                __builtin_nontemporal_store(yv, yp);
+            else
+                *yp = yv;
+        }
+        return;
+    }
+    const int bgroup = vgroup - mblocks;
+#include "sell_short_body.inc"
 }
-
-constexpr aoclsparse_int SELL_SHORT_SPW_SLICES = 60000;
 
 // TAB as the kernel's; CONJ for complex T only.  false: no kernel for this width (v.max_width > SELL_SHORT_WMAX)
 template <typename T, int TAB, bool CONJ>
@@ -537,12 +693,7 @@ bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T 
     // The same rule since profiles/r8/spw_sweep.txt.  Not measured below 60,000 slices: 1.  Complex: 1.
     int spw = 1;
     if constexpr(!COMPLEX)
-    {
-        if(nslices >= SELL_SHORT_SPW_SLICES)
-            spw = sizeof(T) == 4 ? (TAB != 0 ? 4 : 2) : (TAB != 0 ? 2 : 1);
-        if(sell_short_spw_override())
-            spw = sell_short_spw_override();
-    }
+        spw = sell_short_spw(nslices, sizeof(T), TAB != 0);
     const long long per_wg = (long long)WAVES * spw;
     const int       groups = (int)((nslices + per_wg - 1) / per_wg);
     const dim3      grid((unsigned)groups), block(64 * WAVES);
@@ -561,6 +712,54 @@ bool sell_launch_short(hipStream_t s, const SellView &v, T alpha, const T *x, T 
         prcp = (unsigned)((1ull << 32) / (unsigned)pper) + ((pper & (pper - 1)) == 0 ? 0u : 1u);
     else
         pslo = pshi = pper = pstride = 0;
+    // STACKED PERIODS (sell_mv_short_march_kernel; the rule: internal.hpp, sell_march_rule, which aoclsparse_mi355_get_sell_march
+    // reports): a double plan whose range can be stacked and whose alias map is in SELL_MARCH_MAPS runs SELL_MARCH_G = 3 periods
+    // per wavefront with the shared loads of its map.  By measurement (5-point Laplacians of gx x gy points and the boundary-free
+    // 5-cell stencil with lines of 256, double, cold products, one box, medians of 40 over three alternated rounds, ms;
+    // profiles/r18/upper_bound.txt, g_sweep.txt: not stacked / G = 2 / 3 / 4 with shared loads | G = 2 / 3 / 4 without):
+    //   gx x gy (slices, period)          not stacked   shared 2 / 3 / 4               not shared 2 / 3 / 4
+    //   4096 x 4096 (262,144, 64)         0.0524        0.0447 / 0.0452 / 0.0454      0.0471 / 0.0468 / 0.0465
+    //   free, lines of 256 (262,144, 4)   0.0601        0.0511 / 0.0491 / 0.0482      0.0513 / 0.0492 / 0.0485
+    //   1024 x 16384 (262,144, 16)        0.0750        0.0599 / 0.0548 / 0.0528      0.0603 / 0.0560 / 0.0541
+    //   8192 x 2048 (262,144, 128)        0.0533        0.0459 / 0.0450 / 0.0451      0.0480 / 0.0465 / 0.0460
+    //   16384 x 1024 (262,144, 256)       0.0537        0.0463 / 0.0453 / 0.0452      0.0484 / 0.0467 / 0.0460
+    //   32768 x 512 (262,144, 512)        0.0536        0.0471 / 0.0456 / 0.0454      0.0493 / 0.0477 / 0.0468
+    //   4096 x 2048 (131,072, 64)         0.0313        0.0261 / 0.0256 / 0.0263      0.0270 / 0.0277 / 0.0278
+    //   4096 x 1024 (65,536, 64)          0.0191        0.0165 / 0.0163 / 0.0171      0.0169 / 0.0175 / 0.0181
+    //   3000 x 3000 (140,625, 1500)       0.0439        (no alias: the period is 32 lines)  0.0444 / 0.0436 / 0.0446
+    //   2000 x 2000 (62,500, 500)         0.0204        (no alias: 16 lines)                0.0212 / 0.0202 / 0.0204
+    //   3008 x 3000 (140,952, 188)        0.0429        (no alias: 4 lines)                 0.0438 / 0.0436 / 0.0437
+    // -> with the shared loads every G gains 12 - 30 % wherever the map exists; G = 3 is the best or within 1 % of it on six of the
+    // eight, 1.1 % behind 2 on the headline and 2 - 4 % behind 4 at periods of 4 and 16 slices: one value, 3.  Without shared loads
+    // stacking gains where it was forced on a plan that has the map and nothing (-1 .. +2 %) on the plans that really have none,
+    // so a plan without a map in the table keeps sell_mv_short_period_kernel.  Float (four rows per lane) was not built.
+    if constexpr(!COMPLEX && TAB == 2 && sizeof(T) == 8) // (a larger table leaves no room for 5 cells in a one-byte word)
+    {
+        if(v.ucol && v.pbits && prcp)
+        {
+            const SellMarch mr = sell_march_rule(nslices, v.max_width, pslo, pshi, pper, pstride, v.mstack, v.malias, sizeof(T), spw);
+            if(mr.g)
+            {
+                // stacked wavefronts: (periods / g) x (pper / SPW), a whole number of workgroups by the rule; then the workgroups
+                // of the slices outside [lo, hi).  Stacked first in the ascending sweep, last in the descending one (the other order
+                // was not measured: on the headline 192 of 262,144 slices lie outside).
+                const int       hp      = pper / SELL_MARCH_SPW;
+                const unsigned  mrcp    = (unsigned)((1ull << 32) / (unsigned)hp) + ((hp & (hp - 1)) == 0 ? 0u : 1u);
+                const int       mskip   = mr.hi - mr.lo;
+                const int       mblocks = (int)((long long)(mskip / pper / mr.g) * hp / WAVES);
+                const long long rest    = (long long)nslices - mskip, per_rest = (long long)WAVES * SELL_MARCH_SPW;
+                const int       total   = mblocks + (int)((rest + per_rest - 1) / per_rest);
+                const int       mg0     = rev ? total - 1 : 0;
+                static_assert(WAVES == SELL_MARCH_WAVES && SELL_MARCH_MAPS[0].width == 5 && SELL_MARCH_MAPS[0].alias == 0x503u
+                                  && sizeof(SELL_MARCH_MAPS) == sizeof(SellMarchMap),
+                              "one kernel per entry of SELL_MARCH_MAPS");
+                hipLaunchKernelGGL((sell_mv_short_march_kernel<T, 5, WAVES, SELL_MARCH_SPW, TAB, SELL_MARCH_G, 0x503u>), dim3((unsigned)total), block,
+                                   0, s, m, nslices, mg0, gstep, dp, sval, v.col, v.lead, alpha, x, beta, y, nt, vtab, v.ucol, v.pbits, v.pbytes,
+                                   pslo, pshi - pslo, pper, prcp, (unsigned)pstride * (unsigned)sizeof(T), mblocks, hp, mrcp, mskip);
+                return true;
+            }
+        }
+    }
     // the kernel's path: PK when the plan's table indices are packed words (a table of two always is: <= 8 cells of one bit), UCOL
     // when it also has uniform column lists (build_sell makes them next to packed words only); with both, for a real type, the kernel
     // that takes the periodic range

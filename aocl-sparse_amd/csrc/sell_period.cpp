@@ -157,4 +157,51 @@ void sell_find_period(const SellSliceDesc *desc, const aoclsparse_int *ucol, aoc
         *comparisons = work;
 }
 
+// Whether a periodic range can be stacked, and the alias map of its first period (internal.hpp states both rules; the kernel that
+// relies on them makes no test of its own, so every comparison is on the fields themselves, as above).
+void sell_find_march(const SellSliceDesc *desc, const aoclsparse_int *ucol, aoclsparse_int nslices, const aoclsparse_int range[4],
+                     int word_bytes, aoclsparse_int out[2])
+{
+    out[0] = out[1] = 0;
+    if(!desc || !ucol || !range)
+        return;
+    const long long lo = range[0], hi = range[1], p = range[2], stride = range[3];
+    if(p < SELL_MARCH_GROUP || p % SELL_MARCH_GROUP != 0 || lo < 0 || lo % SELL_MARCH_GROUP != 0 || hi > nslices || hi - lo < p)
+        return;
+    // the record's word as the kernel's run test reads it: the mode of a flagged slice counts as "shifted"
+    auto shifted_word = [&](long long s) {
+        const uint32_t w = desc[s].wsm;
+        return (w & SELL_DESC_EXCEPT) ? ((w & 0xff00ffffu) | (uint32_t)SELL_DESC_MODE_LANE_SHIFT << 16) : w;
+    };
+    bool stack = word_bytes == 1;
+    for(long long g = lo; g < lo + p && stack; g += SELL_MARCH_GROUP)
+    {
+        const uint32_t e0 = shifted_word(g);
+        const int      w0 = std::min<int>((int)(e0 & 0xffu), SELL_SHORT_WMAX);
+        stack             = ((e0 >> 16) & 0xffu) == (uint32_t)SELL_DESC_MODE_LANE_SHIFT && w0 >= 1;
+        for(int u = 0; u < SELL_MARCH_GROUP && stack; u++)
+        {
+            stack = (desc[g + u].wsm & SELL_DESC_UWORD) != 0u && ((shifted_word(g + u) ^ e0) & 0xff00ffu) == 0u;
+            for(int q = 0; q < w0 && stack; q++)
+                stack = (long long)ucol[(g + u) * SELL_SHORT_WMAX + q] == (long long)ucol[g * SELL_SHORT_WMAX + q] + 64 * u;
+        }
+    }
+    out[0] = stack ? 1 : 0;
+    uint32_t map = 0;
+    for(int q = 0; q < SELL_SHORT_WMAX; q++)
+        for(int r = 0; r < SELL_SHORT_WMAX; r++)
+        {
+            bool all = r != q;
+            for(long long s = lo; s < lo + p && all; s++)
+            {
+                const int            w = std::min<int>((int)(desc[s].wsm & 0xffu), SELL_SHORT_WMAX);
+                const aoclsparse_int a = ucol[s * SELL_SHORT_WMAX + q], b = ucol[s * SELL_SHORT_WMAX + r];
+                all                    = q < w && r < w && a >= 0 && b >= 0 && (long long)b == (long long)a + stride;
+            }
+            if(all && !((map >> (4 * q)) & 0xfu)) // (two equal columns in one list: the first)
+                map |= (uint32_t)(r + 1) << (4 * q);
+        }
+    out[1] = (aoclsparse_int)map;
+}
+
 } // namespace mi355

@@ -1,6 +1,7 @@
-// The body of sell_mv_short_kernel and sell_mv_short_period_kernel (sell_kernels.hip, which describes both): included inside
+// The body of sell_mv_short_kernel, sell_mv_short_period_kernel and sell_mv_short_march_kernel (sell_kernels.hip): included inside
 // each kernel, not a function of its own, so that the kernels without a periodic range stay the machine code they were.  Reads the
-// kernel's template parameters and arguments by name; PERIOD: the kernel has the range arguments pslo, plen, pper, prcp, pstrideb.
+// kernel's template parameters and arguments by name, and its group of slices as bgroup; PERIOD: the kernel has the range arguments
+// pslo, plen, pper, prcp, pstrideb.
 // (As a PERIOD-templated __forceinline__ device function the same text gave the 120 short-row kernels without uniform lists the same
 // instructions in other registers -- tools/isa_identity.py -- which is the only reason for the include: worth trying again with a
 // later compiler.)
@@ -17,7 +18,13 @@
     static_assert(!PK || TAB != 0, "packed words hold table indices");
     // group g of WAVES x SPW slices; consecutive products of a handle ALTERNATE the direction (SellPlan::products): g0 = last
     // group, gstep = -1 on odd ones
-    const int sb   = __builtin_amdgcn_readfirstlane(((g0 + gstep * (int)blockIdx.x) * WAVES + (int)(threadIdx.x >> 6)) * SPW);
+    // (bgroup: the including kernel's name for that group.  MARCH -- sell_mv_short_march_kernel, whose other workgroups take the
+    // slices [pslo, pslo + mskip) stacked: the groups here count the slices OUTSIDE that part, which starts and ends at a multiple
+    // of 4 slices, so a wavefront's SPW slices are all before it or all behind it)
+    int sbg = __builtin_amdgcn_readfirstlane((bgroup * WAVES + (int)(threadIdx.x >> 6)) * SPW);
+    if constexpr(MARCH)
+        sbg = sbg >= pslo ? sbg + mskip : sbg;
+    const int sb   = sbg;
     const int lane = threadIdx.x & 63;
     s_pin_arg(alpha), s_pin_arg(beta), s_pin_arg(y), s_pin_arg((int)nt), s_pin_arg(x), s_pin_arg(sval), s_pin_arg(scol), s_pin_arg(follow);
     s_pin_arg(pbits), s_pin_arg(pbytes); // (not ucol / vtab: a pointer handed to an asm statement is no longer read with scalar loads)

@@ -831,6 +831,46 @@ aoclsparse_status aoclsparse_mi355_get_sell_period(const aoclsparse_matrix A, ao
     return aoclsparse_status_success;
 }
 
+aoclsparse_status aoclsparse_mi355_get_sell_march(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *first_slice,
+                                                  aoclsparse_int *end_slice, aoclsparse_int *periods, aoclsparse_int *alias_map)
+{
+    if(!A || !first_slice || !end_slice || !periods || !alias_map)
+        return aoclsparse_status_invalid_pointer;
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
+    SellMarch                           mr;
+    // (what sell_launch_short asks before it calls the rule: a real plan with slice records, uniform lists and packed words)
+    if(p.sell.valid && p.sell.pack == 1 && p.sell.desc.ptr && p.sell.ucol.ptr && p.sell.ntab > 0 && p.sell.ntab <= 2 && p.sell.pbits > 0
+       && !is_complex_type(A->val_type) && p.max_row_nnz <= SELL_SHORT_WMAX)
+        mr = sell_march_rule(p.sell.nslices, p.max_row_nnz, p.sell.pslo, p.sell.pshi, p.sell.pper, p.sell.pstride, p.sell.mstack,
+                             p.sell.malias, val_size(A->val_type), sell_short_spw(p.sell.nslices, val_size(A->val_type), true));
+    *first_slice = mr.lo, *end_slice = mr.hi, *periods = mr.g, *alias_map = (aoclsparse_int)mr.alias;
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_sell_find_march(aoclsparse_int nslices, const void *records, const aoclsparse_int *lists,
+                                                   const aoclsparse_int range[4], aoclsparse_int word_bytes, aoclsparse_int out[2])
+{
+    if(!records || !lists || !range || !out)
+        return aoclsparse_status_invalid_pointer;
+    if(nslices < 0)
+        return aoclsparse_status_invalid_size;
+    sell_find_march(static_cast<const SellSliceDesc *>(records), lists, nslices, range, (int)word_bytes, out);
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_sell_march_rule(aoclsparse_int nslices, aoclsparse_int max_width, const aoclsparse_int range[4],
+                                                   aoclsparse_int stack, aoclsparse_int alias_map, aoclsparse_int value_bytes,
+                                                   aoclsparse_int slices_per_wavefront, aoclsparse_int out[4])
+{
+    if(!range || !out)
+        return aoclsparse_status_invalid_pointer;
+    const SellMarch mr = sell_march_rule(nslices, max_width, (int)range[0], (int)range[1], (int)range[2], (int)range[3], (int)stack,
+                                         (unsigned)alias_map, (size_t)value_bytes, (int)slices_per_wavefront);
+    out[0] = mr.lo, out[1] = mr.hi, out[2] = mr.g, out[3] = (aoclsparse_int)mr.alias;
+    return aoclsparse_status_success;
+}
+
 aoclsparse_status aoclsparse_mi355_sell_find_period(aoclsparse_int nslices, const void *records, const aoclsparse_int *lists,
                                                     aoclsparse_int max_period, aoclsparse_int range[4], long long *comparisons)
 {

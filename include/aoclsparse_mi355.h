@@ -351,6 +351,30 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_period(const aoclsparse_m
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sell_find_period(aoclsparse_int nslices, const void *records,
                                                                const aoclsparse_int *lists, aoclsparse_int max_period,
                                                                aoclsparse_int range[4], long long *comparisons);
+/* STACKED PERIODS of op(A)'s SELL-64 copy: what the short-row launcher will do with the periodic range.  Slices [first_slice,
+ * end_slice) run stacked -- one wavefront takes `periods` consecutive periods of its strip of slices, reads the first period's
+ * records once and issues all gathers before its first wait -- and alias_map says which gathers it shares between periods:
+ * four bits per cell, nibble q = a(q) + 1 where cell q of a slice in period k + 1 is cell a(q) of the same slice in period k
+ * (its column + column_stride), 0 = none (0x503: the 5-point stencil; 0x6040: a 7-offset stencil whose period is one line).
+ * end_slice - first_slice is a whole number of `periods` periods and of workgroups; what is left of the range runs with the
+ * slices outside it, in the same launch.  All 0 whenever the product runs the kernel without stacking: no range, a group of 4
+ * slices of the first period that is not a run of shifted slices with their words in the records, an alias map the kernel is
+ * not built for, a float plan, fewer than 60,000 slices.  Decided again whenever the copy is rebuilt (a value change). */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_march(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                             aoclsparse_int *first_slice, aoclsparse_int *end_slice,
+                                                             aoclsparse_int *periods, aoclsparse_int *alias_map);
+/* The two plan rules behind it on the caller's host arrays (no device involved; records and lists as for
+ * aoclsparse_mi355_sell_find_period, range = what that search reported, word_bytes = bytes per packed row word):
+ * out = {1 if the range can be stacked else 0, the alias map of its first period}. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sell_find_march(aoclsparse_int nslices, const void *records,
+                                                              const aoclsparse_int *lists, const aoclsparse_int range[4],
+                                                              aoclsparse_int word_bytes, aoclsparse_int out[2]);
+/* ... and the launcher's rule on them: max_width = the widest slice, stack / alias_map = the two results above, value_bytes = 4
+ * or 8, slices_per_wavefront = what the launcher chose.  out = {first_slice, end_slice, periods, alias_map}, all 0: no stacking. */
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sell_march_rule(aoclsparse_int nslices, aoclsparse_int max_width,
+                                                              const aoclsparse_int range[4], aoclsparse_int stack,
+                                                              aoclsparse_int alias_map, aoclsparse_int value_bytes,
+                                                              aoclsparse_int slices_per_wavefront, aoclsparse_int out[4]);
 /* The plan behind mm_bell_xcd_chunk / the lattice sweep, computed from host arrays (no device involved; what aoclsparse_optimize runs on the
  * blocked-ELL copy's block columns): bcol = nbr x width block columns, ascending per block row, empty slots (-1) last; nbc = block columns of
  * the matrix.  forced: -2 automatic, -1 the lattice sweep whenever a lattice is found, 0 launch order, c >= 1 chunks of c block rows.
