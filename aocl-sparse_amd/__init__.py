@@ -28,6 +28,8 @@ MEM_MINIMAL, MEM_UNRESTRICTED = 0, 1
 PTR_AUTO, PTR_HOST, PTR_DEVICE = 0, 1, 2
 OPTION_SPMV_KERNEL, OPTION_SELL, OPTION_SPMV_STRICT, OPTION_ALTERNATE_SWEEPS, OPTION_TRSV_CHUNKS = 0, 1, 2, 3, 4  # aoclsparse_mi355_set_option
 OPTION_SELL_VALUES = 5
+COO_KEEP, COO_SUM = 0, 1  # aoclsparse_mi355_coo_duplicates
+COO_SORT_TILE = 4096  # AOCLSPARSE_MI355_COO_SORT_TILE: entries a workgroup of the triplet sort takes per pass
 
 STATUS = {
     0: "success", 1: "not_implemented", 2: "invalid_pointer", 3: "invalid_size", 4: "internal_error",
@@ -395,6 +397,10 @@ SIGNATURES = {
     "aoclsparse_mi355_create_dcsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
     "aoclsparse_mi355_create_ccsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
     "aoclsparse_mi355_create_zcsr_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P]),
+    "aoclsparse_mi355_create_scsr_from_coo_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _I]),
+    "aoclsparse_mi355_create_dcsr_from_coo_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _I]),
+    "aoclsparse_mi355_create_ccsr_from_coo_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _I]),
+    "aoclsparse_mi355_create_zcsr_from_coo_device": (c_int, [POINTER(_P), c_int, _I, _I, _I, _P, _P, _P, _I]),
     "aoclsparse_mi355_supdate_values_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_dupdate_values_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_cupdate_values_device": (c_int, [_P, _I, _P]),
@@ -560,6 +566,50 @@ class Matrix:
             rp, ci = rp + base, ci + base
         torch.cuda.synchronize()
         return cls.from_device(base, m, n, nnz, rp, ci, v)
+
+    @classmethod
+    def from_coo_device(cls, base, m, n, nnz, row, col, val, duplicates=0, dtype=None):
+        """aoclsparse_mi355_create_?csr_from_coo_device: a CSR handle from nnz unordered (row, col, value) triplets in HBM (torch
+        device tensors or integer addresses; int32 indices).  duplicates = COO_KEEP: the stable sort by row of
+        aoclsparse_convert_csr, repeated coordinates stay separate; COO_SUM: sorted by (row, column), repeated coordinates added
+        left to right in triplet order.  The arrays are copied -- nothing is kept alive here -- and must be complete before the
+        call.  .nnz is the handle's (the distinct coordinates after COO_SUM).  Look at .status, as with Matrix(...)."""
+        name = str(val.dtype if dtype is None else dtype).split(".")[-1]
+        for t in (row, col):
+            assert not hasattr(t, "dtype") or str(t.dtype).split(".")[-1] == "int32", "aoclsparse_int is 32-bit"
+        self = cls.__new__(cls)
+        self.row_ptr = self.col_ind = self.val = None  # the handle owns its arrays
+        self.letter = cls._LETTER[name]
+        self.double = name == "float64"
+        self.m, self.n, self.nnz, self.base = m, n, nnz, base
+        self.h = c_void_p()
+        fn = getattr(lib(), "aoclsparse_mi355_create_%scsr_from_coo_device" % self.letter)
+        self.status = fn(byref(self.h), base, m, n, nnz, _ptr(row), _ptr(col), _ptr(val), duplicates)
+        if self.status == 0 and duplicates == COO_SUM:
+            e = self.export_device()
+            assert e["status"] == 0, STATUS.get(e["status"], e["status"])
+            self.nnz = e["nnz"]
+        return self
+
+    @classmethod
+    def from_torch_coo(cls, t, base=0, duplicates=1):
+        """a torch.sparse_coo tensor on the GPU -> CSR handle; its int64 indices are cast to int32 on the device, uncoalesced as
+        they are (duplicates = COO_SUM adds repeated coordinates in the order the tensor holds them)"""
+        import torch
+
+        assert t.layout == torch.sparse_coo and t.is_cuda and t.dim() == 2 and t.sparse_dim() == 2
+        m, n = t.shape
+        idx = t._indices().to(torch.int32)
+        row, col = idx[0].contiguous(), idx[1].contiguous()
+        v = t._values().contiguous()
+        nnz = int(v.numel())
+        if nnz == 0:  # (an empty tensor has no address; the library wants allocations, as the host call wants non-null arrays)
+            row = col = torch.zeros(1, dtype=torch.int32, device=t.device)
+            v = torch.zeros(1, dtype=v.dtype, device=t.device)
+        if base:
+            row, col = row + base, col + base
+        torch.cuda.synchronize()
+        return cls.from_coo_device(base, m, n, nnz, row, col, v, duplicates)
 
     def _letter(self):
         return getattr(self, "letter", None) or (self._LETTER[str(self.val.dtype)] if self.val is not None

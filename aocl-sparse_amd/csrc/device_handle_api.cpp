@@ -7,31 +7,26 @@
 // every entry point of the library works on it unchanged -- some 280 of them read A->user.  No aliasing, no handle without host
 // arrays.  What mat_check decides on the host for aoclsparse_create_?csr (validity, sort class, full diagonal) is decided by
 // matcheck_kernels.hip on the device.
+//
+// Round 19 adds the way in for a matrix that is not CSR yet: unordered (row, col, value) triplets in HBM are sorted into CSR
+// arrays on the device (coo_sort_kernels.hip), and those arrays -- the library's own -- are MOVED into the mirror by the same
+// helper that copies a caller's.
 #include "matcheck.hpp"
 
 using namespace mi355;
 
 namespace
 {
-    template <typename T>
-    aoclsparse_status create_csr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N,
-                                        aoclsparse_int nnz, const aoclsparse_int *row_ptr, const aoclsparse_int *col_idx,
-                                        const T *val, aoclsparse_matrix_data_type vt)
+    // From CSR arrays in HBM to a handle: the check kernels, the device mirror, the host view.  The arrays are the caller's (own ==
+    // nullptr: copied device to device into the mirror) or the library's own, built a moment ago (own[0..2] hold row_ptr, col_idx
+    // and val: MOVED into the mirror -- a copy of 1 GB is for a caller's arrays, not for ours).  *mat is null on entry.
+    aoclsparse_status csr_handle_from_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N,
+                                             aoclsparse_int nnz, const aoclsparse_int *row_ptr, const aoclsparse_int *col_idx,
+                                             const void *val, aoclsparse_matrix_data_type vt, DeviceBuffer *own)
     {
-        // decided before the device is touched, in the order of create_csr / mat_check (matrix.cpp)
-        if(!mat)
-            return aoclsparse_status_invalid_pointer;
-        *mat = nullptr;
-        if(!row_ptr || !col_idx || !val)
-            return aoclsparse_status_invalid_pointer;
-        if(N < 0 || M < 0 || nnz < 0)
-            return aoclsparse_status_invalid_size;
-        Runtime          &rt = Runtime::get();
-        aoclsparse_status rc = rt.init();
-        if(rc != aoclsparse_status_success)
-            return rc;
-        if(!rt.is_device_pointer(row_ptr) || !rt.is_device_pointer(col_idx) || !rt.is_device_pointer(val))
-            return aoclsparse_status_invalid_pointer;
+        Runtime                              &rt = Runtime::get();
+        aoclsparse_status                     rc;
+        const size_t                          vsz = val_size(vt);
         std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (one user of the library's stream at a time, as everywhere)
         hipStream_t                           s = rt.stream();
         // any base is checked like mat_check checks it: against ptr[0], and every index after subtracting it
@@ -58,21 +53,26 @@ namespace
         if((rc = new_csr_result(&H, M, N, nnz, vt, nullptr, base)) != aoclsparse_status_success)
             return rc;
         H->sort = h.cls ? h.cls : 1, H->fulldiag = !h.notfull;
-        // the device mirror and the host view, both from the caller's arrays
+        // the device mirror (a copy of the caller's arrays, or the library's own buffers moved in) and the host view
         DeviceCsr   &d  = H->dev_user;
-        const size_t pb = sizeof(aoclsparse_int) * ((size_t)M + 1), ib = sizeof(aoclsparse_int) * (size_t)nnz, vb = sizeof(T) * (size_t)nnz;
-        rc = d.ptr.alloc(pb);
-        if(rc == aoclsparse_status_success)
-            rc = d.ind.alloc(ib);
-        if(rc == aoclsparse_status_success)
-            rc = d.val.alloc(vb);
+        const size_t pb = sizeof(aoclsparse_int) * ((size_t)M + 1), ib = sizeof(aoclsparse_int) * (size_t)nnz, vb = vsz * (size_t)nnz;
         auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
             if(rc == aoclsparse_status_success && bytes && hipMemcpyAsync(dst, src, bytes, kind, s) != hipSuccess)
                 rc = aoclsparse_status_internal_error;
         };
-        copy(d.ptr.ptr, row_ptr, pb, hipMemcpyDeviceToDevice);
-        copy(d.ind.ptr, col_idx, ib, hipMemcpyDeviceToDevice);
-        copy(d.val.ptr, val, vb, hipMemcpyDeviceToDevice);
+        if(own)
+            d.ptr.adopt(own[0]), d.ind.adopt(own[1]), d.val.adopt(own[2]); // (row_ptr, col_idx and val point into them still)
+        else
+        {
+            rc = d.ptr.alloc(pb);
+            if(rc == aoclsparse_status_success)
+                rc = d.ind.alloc(ib);
+            if(rc == aoclsparse_status_success)
+                rc = d.val.alloc(vb);
+            copy(d.ptr.ptr, row_ptr, pb, hipMemcpyDeviceToDevice);
+            copy(d.ind.ptr, col_idx, ib, hipMemcpyDeviceToDevice);
+            copy(d.val.ptr, val, vb, hipMemcpyDeviceToDevice);
+        }
         if(PhaseTimer::on() && rc == aoclsparse_status_success) // (the diagnostic separates the two directions)
             (void)hipStreamSynchronize(s);
         lt.lap("create_device: handle + device copy");
@@ -98,6 +98,64 @@ namespace
         d.valid = true; // (the row-block plan is built from the host view at the first product, as for every handle)
         *mat    = H;
         return aoclsparse_status_success;
+    }
+
+    template <typename T>
+    aoclsparse_status create_csr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N,
+                                        aoclsparse_int nnz, const aoclsparse_int *row_ptr, const aoclsparse_int *col_idx,
+                                        const T *val, aoclsparse_matrix_data_type vt)
+    {
+        // decided before the device is touched, in the order of create_csr / mat_check (matrix.cpp)
+        if(!mat)
+            return aoclsparse_status_invalid_pointer;
+        *mat = nullptr;
+        if(!row_ptr || !col_idx || !val)
+            return aoclsparse_status_invalid_pointer;
+        if(N < 0 || M < 0 || nnz < 0)
+            return aoclsparse_status_invalid_size;
+        Runtime          &rt = Runtime::get();
+        aoclsparse_status rc = rt.init();
+        if(rc != aoclsparse_status_success)
+            return rc;
+        if(!rt.is_device_pointer(row_ptr) || !rt.is_device_pointer(col_idx) || !rt.is_device_pointer(val))
+            return aoclsparse_status_invalid_pointer;
+        return csr_handle_from_device(mat, base, M, N, nnz, row_ptr, col_idx, val, vt, nullptr);
+    }
+
+    // triplets in HBM -> CSR arrays in HBM (coo_sort_kernels.hip) -> handle
+    template <typename T>
+    aoclsparse_status create_csr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M, aoclsparse_int N,
+                                                 aoclsparse_int nnz, const aoclsparse_int *row_ind, const aoclsparse_int *col_ind,
+                                                 const T *val, aoclsparse_int duplicates, aoclsparse_matrix_data_type vt)
+    {
+        // decided before the device is touched, in the order of create_coo (formats_api.cpp): sizes come before arrays there
+        if(!mat)
+            return aoclsparse_status_invalid_pointer;
+        *mat = nullptr;
+        if(M < 0 || N < 0 || nnz < 0)
+            return aoclsparse_status_invalid_size;
+        if(!row_ind || !col_ind || !val)
+            return aoclsparse_status_invalid_pointer;
+        if(duplicates != aoclsparse_mi355_coo_keep && duplicates != aoclsparse_mi355_coo_sum)
+            return aoclsparse_status_invalid_value;
+        Runtime          &rt = Runtime::get();
+        aoclsparse_status rc = rt.init();
+        if(rc != aoclsparse_status_success)
+            return rc;
+        if(!rt.is_device_pointer(row_ind) || !rt.is_device_pointer(col_ind) || !rt.is_device_pointer(val))
+            return aoclsparse_status_invalid_pointer;
+        std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+        LapTimer                              lt;
+        DeviceBuffer                          own[3];
+        aoclsparse_int                        nnz_csr = 0;
+        const bool                            cplx    = vt == aoclsparse_cmat || vt == aoclsparse_zmat;
+        rc = device_coo_to_csr(rt.stream(), M, N, nnz, (int)base, row_ind, col_ind, val, sizeof(T), cplx,
+                               duplicates == aoclsparse_mi355_coo_sum, own[0], own[1], own[2], &nnz_csr);
+        if(rc != aoclsparse_status_success)
+            return rc;
+        lt.lap("create_from_coo_device: sort");
+        return csr_handle_from_device(mat, base, M, N, nnz_csr, own[0].as<const aoclsparse_int>(), own[1].as<const aoclsparse_int>(),
+                                      own[2].ptr, vt, own);
     }
 
     template <typename T>
@@ -172,6 +230,35 @@ aoclsparse_status aoclsparse_mi355_create_zcsr_device(aoclsparse_matrix *mat, ao
                                                       const aoclsparse_int *col_idx, const aoclsparse_double_complex *val)
 {
     return create_csr_device(mat, base, M, N, nnz, row_ptr, col_idx, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_create_scsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                               aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ind,
+                                                               const aoclsparse_int *col_ind, const float *val,
+                                                               aoclsparse_int duplicates)
+{
+    return create_csr_from_coo_device(mat, base, M, N, nnz, row_ind, col_ind, val, duplicates, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_mi355_create_dcsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                               aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ind,
+                                                               const aoclsparse_int *col_ind, const double *val,
+                                                               aoclsparse_int duplicates)
+{
+    return create_csr_from_coo_device(mat, base, M, N, nnz, row_ind, col_ind, val, duplicates, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_mi355_create_ccsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                               aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ind,
+                                                               const aoclsparse_int *col_ind, const aoclsparse_float_complex *val,
+                                                               aoclsparse_int duplicates)
+{
+    return create_csr_from_coo_device(mat, base, M, N, nnz, row_ind, col_ind, val, duplicates, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_mi355_create_zcsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
+                                                               aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ind,
+                                                               const aoclsparse_int *col_ind, const aoclsparse_double_complex *val,
+                                                               aoclsparse_int duplicates)
+{
+    return create_csr_from_coo_device(mat, base, M, N, nnz, row_ind, col_ind, val, duplicates, aoclsparse_zmat);
 }
 
 aoclsparse_status aoclsparse_mi355_supdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const float *val)

@@ -909,8 +909,9 @@ private:
     std::atomic<bool> inited_{false}; // set (release) after init_status_ / device / events are written
     aoclsparse_status init_status_ = aoclsparse_status_success;
     hipStream_t  stream_ = nullptr;
-    DeviceBuffer stage_[48]; // 0-7: csrmv / mv / trsv / dotmv, 8-15: ELL family and BLKCSR (ell_api.cpp, blk_api.cpp), 16-39 and 46: sp2m, syrk, sypr (SPG_SLOT_*),
-                             // 40-45: the temporaries of the device transpose (transpose_kernels.hip; sp2m transposes operands while its own slots are in use)
+    DeviceBuffer stage_[59]; // 0-7: csrmv / mv / trsv / dotmv, 8-15: ELL family and BLKCSR (ell_api.cpp, blk_api.cpp), 16-39 and 46: sp2m, syrk, sypr (SPG_SLOT_*),
+                             // 40-45: the temporaries of the device transpose (transpose_kernels.hip; sp2m transposes operands while its own slots are in use),
+                             // 48-58: the triplet sort (coo_sort_kernels.hip)
 };
 
 // While one of these is alive on a thread, Runtime::get() on that thread is the given slot: its device is current, its
@@ -1012,6 +1013,13 @@ aoclsparse_status build_transpose(aoclsparse_matrix A);
 aoclsparse_status device_transpose(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
                                    const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, const void *d_val, size_t vsize,
                                    DeviceBuffer &tptr, DeviceBuffer &tind, DeviceBuffer &tval);
+// CSR arrays (in the triplets' base) from nnz unordered triplets in HBM by a stable radix sort (coo_sort_kernels.hip), into buffers
+// it allocates once every index is known to be in range (invalid_index_value otherwise; the buffers are then empty).  sum == false:
+// the reference's coo2csr, *nnz_out = nnz; sum == true: sorted by (row, column), equal coordinates added left to right in triplet
+// order, *nnz_out = the distinct coordinates.  vsize / cplx: bytes of a value, and whether it is a pair of reals.
+aoclsparse_status device_coo_to_csr(hipStream_t s, aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz, int base,
+                                    const aoclsparse_int *row, const aoclsparse_int *col, const void *val, size_t vsize, bool cplx,
+                                    bool sum, DeviceBuffer &ptr, DeviceBuffer &ind, DeviceBuffer &valb, aoclsparse_int *nnz_out);
 
 // ---- device mirrors / plans ---------------------------------------------------------------------
 size_t            val_size(aoclsparse_matrix_data_type t);

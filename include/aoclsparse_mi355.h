@@ -218,8 +218,43 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           aoclsparse_mi355_invalidate) or destroyed; val points to values of the handle's type.  The library's stream is
  *           synchronised before return.
  *
+ *   create_?csr_from_coo_device   (round 19) The arguments of aoclsparse_create_?coo plus `duplicates`, with row_ind, col_ind and val
+ *           (nnz entries each) in device memory, in ANY order: the triplets a finite-element assembly, a graph construction or a
+ *           sparse_coo tensor leaves behind.  The result is an ordinary CSR-format handle of the kind create_?csr_device returns:
+ *           a resident device copy (spmv_info.device_resident is 1 before any product), an owned host view, and every
+ *           aoclsparse_* entry point works on it.  The caller's arrays are copied and may be overwritten or freed on return; they
+ *           must be COMPLETE before the call (the library reads them on its own stream and waits for nobody else's); the call
+ *           synchronises the library's stream before it returns.
+ *           The triplets are sorted on the device by a stable least-significant-digit radix sort of (key, position) pairs
+ *           (coo_sort_kernels.hip) that never looks at the length of a row: one row or column may hold any share of the entries.
+ *           A workgroup takes AOCLSPARSE_MI355_COO_SORT_TILE entries per pass.
+ *           duplicates = aoclsparse_mi355_coo_keep: the CSR is exactly what aoclsparse_create_?coo + aoclsparse_convert_csr
+ *           (op = none) give for the same triplets on the host -- the reference's stable counting sort by row.  The entries of a
+ *           row keep their triplet order, repeated coordinates stay separate entries, values are moved and never touched.  The
+ *           sort class and the full-diagonal flag are what aoclsparse_create_?csr decides on the converted arrays.
+ *           duplicates = aoclsparse_mi355_coo_sum: the entries are ordered by (row, column), stably, and every run of equal
+ *           coordinates becomes ONE entry whose value is the left-to-right chain ((v0 + v1) + v2) + ... in triplet order, in the
+ *           value type (complex values component by component).  A sum that comes out zero stays an explicit entry.  The handle's
+ *           nnz is the number of distinct coordinates; its rows are fully sorted.  No float atomics take part: the result is a
+ *           pure function of the input arrays, and two calls on one input give the same bytes.
+ *           Statuses, in this order.  Before the device is touched, in aoclsparse_create_?coo's order: invalid_pointer for a null
+ *           mat (otherwise *mat is cleared first), invalid_size for a negative M, N or nnz, invalid_pointer for a null array,
+ *           invalid_value for a `duplicates` other than 0 / 1.  Then: invalid_pointer for an array that is not device (or managed)
+ *           memory in the current pointer mode; invalid_index_value for any row outside [base, base + M) or column outside
+ *           [base, base + N) -- decided on the device before any output is allocated, nothing is ever written out of range; in
+ *           `keep` mode whatever create_?csr_device answers for the converted arrays, in practice invalid_value for a second
+ *           diagonal entry in a row.  nnz == 0 and M == 0 are valid; the arrays must still be non-null device allocations.
+ *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
- * COO, TCSR or BSR handles from device arrays. */
+ * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
+ * arrays); refreshing the values of a `sum`-mode handle from new triplets (that needs the map from triplets to runs kept); sorting
+ * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still). */
+#define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
+typedef enum
+{
+    aoclsparse_mi355_coo_keep = 0, /* repeated coordinates stay separate entries, in triplet order */
+    aoclsparse_mi355_coo_sum  = 1 /* repeated coordinates are added, left to right in triplet order */
+} aoclsparse_mi355_coo_duplicates;
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_scsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
                                                                  aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
                                                                  const aoclsparse_int *col_idx, const float *val);
@@ -232,6 +267,24 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_ccsr_device(aoclsparse_matr
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_zcsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
                                                                  aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
                                                                  const aoclsparse_int *col_idx, const aoclsparse_double_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_scsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base,
+                                                                          aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
+                                                                          const aoclsparse_int *row_ind, const aoclsparse_int *col_ind,
+                                                                          const float *val, aoclsparse_int duplicates);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_dcsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base,
+                                                                          aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
+                                                                          const aoclsparse_int *row_ind, const aoclsparse_int *col_ind,
+                                                                          const double *val, aoclsparse_int duplicates);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_ccsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base,
+                                                                          aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
+                                                                          const aoclsparse_int *row_ind, const aoclsparse_int *col_ind,
+                                                                          const aoclsparse_float_complex *val,
+                                                                          aoclsparse_int duplicates);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_zcsr_from_coo_device(aoclsparse_matrix *mat, aoclsparse_index_base base,
+                                                                          aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz,
+                                                                          const aoclsparse_int *row_ind, const aoclsparse_int *col_ind,
+                                                                          const aoclsparse_double_complex *val,
+                                                                          aoclsparse_int duplicates);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_supdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const float *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_dupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const double *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_cupdate_values_device(aoclsparse_matrix A, aoclsparse_int len,
