@@ -188,12 +188,11 @@ aoclsparse_status aoclsparse_dblkcsrmv(aoclsparse_operation trans, const double 
         return aoclsparse_status_invalid_size;
     if(!alpha || !beta) // dereferenced unchecked by the reference (its tests note the crash); refused here
         return aoclsparse_status_invalid_pointer;
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    CallScope cs(CallScope::Always);
+    MI355_TRY(cs.st);
+    Runtime             &rt   = cs.rt;
     const aoclsparse_int last = (m - 1) / nRowsblk * nRowsblk; // the last row block's first sub-row holds its range
     aoclsparse_int       nblk = 0;
-    const void          *valoff = nullptr;
     if(rt.is_device_pointer(blk_row_ptr))
     {
         MI355_HIP_TRY(hipMemcpyAsync(&nblk, blk_row_ptr + last + 1, sizeof(nblk), hipMemcpyDeviceToHost, rt.stream()));
@@ -204,32 +203,19 @@ aoclsparse_status aoclsparse_dblkcsrmv(aoclsparse_operation trans, const double 
     nblk -= descr->base;
     if(nblk < 0)
         return aoclsparse_status_invalid_value;
-    StagedArg am, av, ac, ap, ax, ay;
-    MI355_TRY(am.in(rt, 8, masks, (size_t)nblk * nRowsblk, true));
-    MI355_TRY(av.in(rt, 9, blk_csr_val, sizeof(double) * (size_t)nnz, true));
-    MI355_TRY(ac.in(rt, 10, blk_col_ind, sizeof(aoclsparse_int) * (size_t)nblk, true));
-    MI355_TRY(ap.in(rt, 11, blk_row_ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), true));
-    MI355_TRY(ax.in(rt, 3, x, sizeof(double) * (size_t)n, true));
-    MI355_TRY(ay.in(rt, 4, y, sizeof(double) * (size_t)m, *beta != 0.0));
-    {
-        const size_t nparts = ((size_t)nblk + (1u << BLK_PART_SHIFT) - 1) >> BLK_PART_SHIFT;
-        const size_t vbytes = sizeof(aoclsparse_int) * std::max<size_t>(1, (size_t)nblk);
-        const size_t pbytes = sizeof(aoclsparse_int) * std::max<size_t>(1, nparts);
-        void        *vo = nullptr, *pt = nullptr;
-        MI355_TRY(rt.staging(14, vbytes, &vo));
-        MI355_TRY(rt.staging(15, pbytes, &pt));
-        MI355_TRY(launch_blk_valoff(rt.stream(), nblk, (int)nRowsblk, static_cast<const uint8_t *>(am.dev),
-                                    static_cast<aoclsparse_int *>(vo), static_cast<aoclsparse_int *>(pt)));
-        valoff = vo;
-    }
-    MI355_TRY(launch_blkcsrmv(rt.stream(), descr->base, *alpha, m, (int)nRowsblk, static_cast<const uint8_t *>(am.dev),
-                              static_cast<const double *>(av.dev), static_cast<const aoclsparse_int *>(ac.dev),
-                              static_cast<const aoclsparse_int *>(ap.dev), static_cast<const aoclsparse_int *>(valoff),
-                              static_cast<const double *>(ax.dev), *beta, static_cast<double *>(ay.dev)));
-    MI355_TRY(ay.out(rt));
-    if(ay.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+    const size_t          nparts = ((size_t)nblk + (1u << BLK_PART_SHIFT) - 1) >> BLK_PART_SHIFT;
+    const uint8_t        *dm = cs.in(STAGE_BLK_MASKS, masks, (size_t)nblk * nRowsblk);
+    const double         *dv = cs.in(STAGE_BLK_VAL, blk_csr_val, sizeof(double) * (size_t)nnz);
+    const aoclsparse_int *dc = cs.in(STAGE_BLK_COL, blk_col_ind, sizeof(aoclsparse_int) * (size_t)nblk);
+    const aoclsparse_int *dp = cs.in(STAGE_BLK_PTR, blk_row_ptr, sizeof(aoclsparse_int) * ((size_t)m + 1));
+    const double         *dx = cs.in(STAGE_MV_X, x, sizeof(double) * (size_t)n);
+    double               *dy = cs.inout(STAGE_MV_Y, y, sizeof(double) * (size_t)m, *beta != 0.0);
+    aoclsparse_int       *vo = static_cast<aoclsparse_int *>(cs.scratch(STAGE_BLK_VALOFF, sizeof(aoclsparse_int) * std::max<size_t>(1, (size_t)nblk)));
+    aoclsparse_int       *pt = static_cast<aoclsparse_int *>(cs.scratch(STAGE_BLK_PARTS, sizeof(aoclsparse_int) * std::max<size_t>(1, nparts)));
+    MI355_TRY(cs.st);
+    MI355_TRY(launch_blk_valoff(cs.s, nblk, (int)nRowsblk, dm, vo, pt));
+    MI355_TRY(launch_blkcsrmv(cs.s, descr->base, *alpha, m, (int)nRowsblk, dm, dv, dc, dp, vo, dx, *beta, dy));
+    return cs.finish();
 }
 
 } // extern "C"

@@ -73,23 +73,19 @@ aoclsparse_status cmv_t(aoclsparse_operation op, const cplx<R> *alpha, aoclspars
            || A->bsr_order != aoclsparse_order_column))
         return aoclsparse_status_not_implemented;
 
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    const bool                            tr = op != aoclsparse_operation_none;
+    CallScope cs(CallScope::Always);
+    MI355_TRY(cs.st);
+    const bool tr = op != aoclsparse_operation_none;
+    const bool b0 = beta->re == R(0) && beta->im == R(0); // y is not read then
     if(bsr && !empty) // mv.cpp:331-342 with the handle's own base (:165): one chain per scalar row (bsr_complex_kernels.hip)
-        return bsr_handle_mv<C>(rt, A, *alpha, x, *beta, y);
+        return bsr_handle_mv<C>(cs, A, *alpha, x, *beta, y);
     if(empty)
     {
         const aoclsparse_int dim = tr ? A->n : A->m; // mv.cpp:116-121: an empty matrix still scales y
-        StagedArg            ay;
-        const bool           b0 = beta->re == R(0) && beta->im == R(0);
-        MI355_TRY(ay.in(rt, 4, y, sizeof(C) * (size_t)dim, !b0));
-        MI355_TRY(launch_cscale<R>(rt.stream(), static_cast<C *>(ay.dev), dim, *beta));
-        MI355_TRY(ay.out(rt));
-        if(ay.staged)
-            MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-        return aoclsparse_status_success;
+        C                   *dy  = cs.inout(STAGE_MV_Y, y, sizeof(C) * (size_t)dim, !b0);
+        MI355_TRY(cs.st);
+        MI355_TRY(launch_cscale<R>(cs.s, dy, dim, *beta));
+        return cs.finish();
     }
 
     DeviceCsr            *dcsr = nullptr;
@@ -133,21 +129,16 @@ aoclsparse_status cmv_t(aoclsparse_operation op, const cplx<R> *alpha, aoclspars
         }
     }
     std::shared_lock<std::shared_mutex> r(A->guard);
-    StagedArg                           ax, ay;
-    const bool                          b0 = beta->re == R(0) && beta->im == R(0);
-    MI355_TRY(ax.in(rt, 3, x, sizeof(C) * (size_t)dcsr->n, true));
-    MI355_TRY(ay.in(rt, 4, y, sizeof(C) * (size_t)dcsr->m, !b0));
+    const C                            *dx = cs.in(STAGE_MV_X, x, sizeof(C) * (size_t)dcsr->n);
+    C                                  *dy = cs.inout(STAGE_MV_Y, y, sizeof(C) * (size_t)dcsr->m, !b0);
+    MI355_TRY(cs.st);
     if(plan && plan->sell.valid)
-        MI355_TRY(launch_sellmv<C>(rt.stream(), plan->sell.view(dcsr->m, plan->max_row_nnz), 0, conj, *alpha, static_cast<const C *>(ax.dev),
-                                   *beta, static_cast<C *>(ay.dev), plan->sell.next_direction()));
+        MI355_TRY(launch_sellmv<C>(cs.s, plan->sell.view(dcsr->m, plan->max_row_nnz), 0, conj, *alpha, dx, *beta, dy,
+                                   plan->sell.next_direction()));
     else
-        MI355_TRY(launch_cspmv<R>(rt.stream(), dcsr->base, conj, *alpha, dcsr->m, dcsr->nnz, dcsr->val.as<C>(),
-                                  dcsr->ind.as<aoclsparse_int>(), dcsr->ptr.as<aoclsparse_int>(),
-                                  static_cast<const C *>(ax.dev), *beta, static_cast<C *>(ay.dev)));
-    MI355_TRY(ay.out(rt));
-    if(ay.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+        MI355_TRY(launch_cspmv<R>(cs.s, dcsr->base, conj, *alpha, dcsr->m, dcsr->nnz, dcsr->val.as<C>(),
+                                  dcsr->ind.as<aoclsparse_int>(), dcsr->ptr.as<aoclsparse_int>(), dx, *beta, dy));
+    return cs.finish();
 }
 
 // aoclsparse_{c,z}csrmm: checks as level3/aoclsparse_csrmm.hpp:429-640 (same order as csrmm_api.cpp), operator
@@ -199,24 +190,17 @@ aoclsparse_status ccsrmm_t(aoclsparse_operation op, const cplx<R> alpha, const a
     if(kid > 3)
         return aoclsparse_status_invalid_kid;
 
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    StagedArg                             aB, aC;
-    MI355_TRY(aC.in(rt, 4, C, sizeof(Cx) * (size_t)c_outer * (size_t)ldc, true)); // padding of ldc survives
-    auto finish = [&]() -> aoclsparse_status {
-        MI355_TRY(aC.out(rt));
-        if(aC.staged)
-            MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-        return aoclsparse_status_success;
-    };
+    CallScope cs(CallScope::Always);
+    Cx       *dC = cs.inout(STAGE_CSRMM_C, C, sizeof(Cx) * (size_t)c_outer * (size_t)ldc, true); // the whole block: padding of ldc survives
+    MI355_TRY(cs.st);
     if(a0)
     {
-        MI355_TRY(launch_cscale_dense<R>(rt.stream(), order, static_cast<Cx *>(aC.dev), m_c, n, ldc, beta));
-        return finish();
+        MI355_TRY(launch_cscale_dense<R>(cs.s, order, dC, m_c, n, ldc, beta));
+        return cs.finish();
     }
     (void)b0;
-    MI355_TRY(aB.in(rt, 3, B, sizeof(Cx) * (size_t)b_outer * (size_t)ldb, true));
+    const Cx *dB = cs.in(STAGE_CSRMM_B, B, sizeof(Cx) * (size_t)b_outer * (size_t)ldb);
+    MI355_TRY(cs.st);
     DeviceCsr *d    = nullptr;
     bool       conj = false;
     if(sym || herm)
@@ -235,11 +219,10 @@ aoclsparse_status ccsrmm_t(aoclsparse_operation op, const cplx<R> alpha, const a
     }
     {
         std::shared_lock<std::shared_mutex> r(A->guard);
-        MI355_TRY(launch_ccsrmm<R>(rt.stream(), order, d->base, conj, alpha, d->m, d->val.as<Cx>(),
-                                   d->ind.as<aoclsparse_int>(), d->ptr.as<aoclsparse_int>(),
-                                   static_cast<const Cx *>(aB.dev), n, ldb, beta, static_cast<Cx *>(aC.dev), ldc));
+        MI355_TRY(launch_ccsrmm<R>(cs.s, order, d->base, conj, alpha, d->m, d->val.as<Cx>(),
+                                   d->ind.as<aoclsparse_int>(), d->ptr.as<aoclsparse_int>(), dB, n, ldb, beta, dC, ldc));
     }
-    return finish();
+    return cs.finish();
 }
 
 // aoclsparse_{c,z}dotmv (level2/aoclsparse_dotmv.hpp:31-60): y = alpha op(A) x + beta y, then the CONJUGATED dot
@@ -252,25 +235,15 @@ aoclsparse_status cdotmv_t(aoclsparse_operation op, cplx<R> alpha, aoclsparse_ma
     if(!d || !A)
         return aoclsparse_status_invalid_pointer;
     MI355_TRY(cmv_t<R>(op, &alpha, A, descr, x, &beta, y, vt));
-    Runtime                              &rt = Runtime::get();
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    const aoclsparse_int                  n = std::min(A->m, A->n);
-    StagedArg                             ax, ay;
-    MI355_TRY(ax.in(rt, 3, x, sizeof(C) * (size_t)n, true));
-    MI355_TRY(ay.in(rt, 4, y, sizeof(C) * (size_t)n, true));
-    void      *part = nullptr, *dd = d;
-    const bool ddev = rt.is_device_pointer(d);
-    MI355_TRY(rt.staging(6, sizeof(C) * 1024, &part));
-    if(!ddev)
-        MI355_TRY(rt.staging(7, sizeof(C), &dd));
-    MI355_TRY(launch_cdot<R>(rt.stream(), n, static_cast<const C *>(ax.dev), static_cast<const C *>(ay.dev),
-                             static_cast<C *>(part), static_cast<C *>(dd)));
-    if(!ddev)
-    {
-        MI355_HIP_TRY(hipMemcpyAsync(d, dd, sizeof(C), hipMemcpyDeviceToHost, rt.stream()));
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    }
-    return aoclsparse_status_success;
+    CallScope            cs(CallScope::Always); // (after the product has finished: y is staged once more for the dot)
+    const aoclsparse_int n  = std::min(A->m, A->n);
+    const C             *dx = cs.in(STAGE_MV_X, x, sizeof(C) * (size_t)n);
+    const C             *dy = cs.in(STAGE_MV_Y, y, sizeof(C) * (size_t)n);
+    C                   *part = static_cast<C *>(cs.scratch(STAGE_DOTMV_PART, sizeof(C) * 1024));
+    C                   *dd = cs.out(STAGE_DOTMV_D, d, sizeof(C));
+    MI355_TRY(cs.st);
+    MI355_TRY(launch_cdot<R>(cs.s, n, dx, dy, part, dd));
+    return cs.finish();
 }
 
 } // namespace

@@ -320,22 +320,7 @@ namespace
                            scol, runs, static_cast<const V *>(val), cnt, oind, static_cast<V *>(oval));
     }
 
-    // staging slots of the sort (Runtime::stage_: 48-58)
-    enum
-    {
-        SLOT_KEY_A = 48,
-        SLOT_POS_A,
-        SLOT_KEY_B,
-        SLOT_POS_B,
-        SLOT_HIST,
-        SLOT_OFFS,
-        SLOT_SCAN,
-        SLOT_SMALL,
-        SLOT_CNT,
-        SLOT_FLAG,
-        SLOT_RUNS
-    };
-
+    // (staging slots of the sort: COO_SLOT_* of StageSlot, internal.hpp)
     struct SortState
     {
         int *key[2] = {nullptr, nullptr}, *pos[2] = {nullptr, nullptr};
@@ -445,7 +430,7 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
     const long long tiles = ((long long)nnz + COO_TILE - 1) / COO_TILE;
     const size_t    cells = 256 * (size_t)tiles; // bins x tiles: nnz < 2^31, so < 2^27 + 256
     void           *p     = nullptr;
-    MI355_TRY(rt.staging(SLOT_SMALL, 256, &p));
+    MI355_TRY(rt.staging(COO_SLOT_SMALL, 256, &p));
     unsigned int *const d_bad = static_cast<unsigned int *>(p);
     if(nnz > 0)
     {
@@ -460,9 +445,9 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
     }
     // from here on: when nnz > 0, every row key is in [0, M) and every column key in [0, N)
     MI355_TRY(ptr_b.alloc(sizeof(aoclsparse_int) * ((size_t)M + 1)));
-    MI355_TRY(rt.staging(SLOT_CNT, sizeof(int) * ((size_t)M + 1), &p));
+    MI355_TRY(rt.staging(COO_SLOT_CNT, sizeof(int) * ((size_t)M + 1), &p));
     int *const cnt_p = static_cast<int *>(p);
-    MI355_TRY(rt.staging(SLOT_SCAN, spg_scan_scratch_bytes((aoclsparse_int)std::max<size_t>(cells, (size_t)std::max(M, nnz))), &p));
+    MI355_TRY(rt.staging(COO_SLOT_SCAN, spg_scan_scratch_bytes((aoclsparse_int)std::max<size_t>(cells, (size_t)std::max(M, nnz))), &p));
     long long *const scan_p = static_cast<long long *>(p);
     if(M > 0)
         MI355_HIP_TRY(hipMemsetAsync(cnt_p, 0, sizeof(int) * (size_t)M, s));
@@ -479,14 +464,14 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
         st.tiles = tiles, st.scan = scan_p;
         for(int q = 0; q < 2; q++)
         {
-            MI355_TRY(rt.staging(q ? SLOT_KEY_B : SLOT_KEY_A, n4, &p));
+            MI355_TRY(rt.staging(q ? COO_SLOT_KEY_B : COO_SLOT_KEY_A, n4, &p));
             st.key[q] = static_cast<int *>(p);
-            MI355_TRY(rt.staging(q ? SLOT_POS_B : SLOT_POS_A, n4, &p));
+            MI355_TRY(rt.staging(q ? COO_SLOT_POS_B : COO_SLOT_POS_A, n4, &p));
             st.pos[q] = static_cast<int *>(p);
         }
-        MI355_TRY(rt.staging(SLOT_HIST, sizeof(int) * cells, &p));
+        MI355_TRY(rt.staging(COO_SLOT_HIST, sizeof(int) * cells, &p));
         st.hist = static_cast<int *>(p);
-        MI355_TRY(rt.staging(SLOT_OFFS, sizeof(aoclsparse_int) * (cells + 1), &p));
+        MI355_TRY(rt.staging(COO_SLOT_OFFS, sizeof(aoclsparse_int) * (cells + 1), &p));
         st.offs = static_cast<aoclsparse_int *>(p);
         // the (key, position) pairs to start from: the columns in `sum` mode, the rows otherwise
         marks.record(0, s);
@@ -512,7 +497,7 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
             // the sorted columns and the run heads go where the last pass read from; the scan of the heads has a slot of its own
             aoclsparse_int *const scol = st.key[st.cur ^ 1];
             int *const            flag = st.pos[st.cur ^ 1];
-            MI355_TRY(rt.staging(SLOT_FLAG, sizeof(aoclsparse_int) * ((size_t)nnz + 1), &p));
+            MI355_TRY(rt.staging(COO_SLOT_FLAG, sizeof(aoclsparse_int) * ((size_t)nnz + 1), &p));
             aoclsparse_int *const outpos = static_cast<aoclsparse_int *>(p);
             launch_gather<aoclsparse_int>(s, nnz, pos, col, scol);
             hipLaunchKernelGGL(coo_flag_kernel, dim3(gq), dim3(256), 0, s, nnz, keys, scol, flag);
@@ -525,7 +510,7 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
             const aoclsparse_int nout = (aoclsparse_int)distinct;
             MI355_TRY(ind_b.alloc(sizeof(aoclsparse_int) * (size_t)nout));
             MI355_TRY(val_b.alloc(vsize * (size_t)nout));
-            MI355_TRY(rt.staging(SLOT_RUNS, sizeof(int) * ((size_t)nout + 1), &p));
+            MI355_TRY(rt.staging(COO_SLOT_RUNS, sizeof(int) * ((size_t)nout + 1), &p));
             int *const runs = static_cast<int *>(p);
             hipLaunchKernelGGL(coo_runs_kernel, dim3(gq), dim3(256), 0, s, nnz, nout, flag, outpos, runs);
             MI355_TRY(by_value_type(vsize, cplx, [&](auto v) {

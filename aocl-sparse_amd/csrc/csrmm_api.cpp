@@ -22,40 +22,6 @@ namespace
 
 constexpr int CM_DETOUR_NNZ_PER_ROW = 8; // = the column kernel's register cache (CM_K)
 
-// Host <-> staging copy of a strided dense operand: ONLY the `inner` elements of each of the `outer` lines move; the ld
-// padding -- which for a column shard of a row-major matrix is the other shards' columns -- is neither sent nor, on the way
-// back, written (round 3: the contiguous-span copy of round 2 rewrote it with the values it had read, which is a lost update
-// as soon as another thread -- another device's worker of ?csrmm_multi -- owns those columns, and sent 8 x the bytes a
-// 1/8 shard needs).
-template <typename T>
-aoclsparse_status copy_dense(Runtime &rt, void *dst, const void *src, aoclsparse_int outer, aoclsparse_int inner,
-                             aoclsparse_int ld, hipMemcpyKind kind)
-{
-    if(outer <= 0 || inner <= 0)
-        return aoclsparse_status_success;
-    if(ld == inner || outer == 1)
-        MI355_HIP_TRY(hipMemcpyAsync(dst, src, sizeof(T) * ((size_t)(outer - 1) * (size_t)ld + (size_t)inner), kind, rt.stream()));
-    else
-        MI355_HIP_TRY(hipMemcpy2DAsync(dst, sizeof(T) * (size_t)ld, src, sizeof(T) * (size_t)ld, sizeof(T) * (size_t)inner,
-                                       (size_t)outer, kind, rt.stream()));
-    return aoclsparse_status_success;
-}
-
-template <typename T>
-aoclsparse_status stage_dense(Runtime &rt, int slot, const T *host, aoclsparse_int outer, aoclsparse_int inner,
-                              aoclsparse_int ld, bool copy, void **dev, size_t *bytes)
-{
-    // exact extent of a strided dense matrix: the last row / column carries no ld padding (BLAS convention), and a
-    // column shard of a row-major matrix starts j0 elements into its first row
-    *bytes               = outer > 0 ? sizeof(T) * ((size_t)(outer - 1) * (size_t)ld + (size_t)inner) : 0;
-    aoclsparse_status st = rt.staging(slot, *bytes, dev);
-    if(st != aoclsparse_status_success)
-        return st;
-    if(copy && *bytes)
-        return copy_dense<T>(rt, *dev, host, outer, inner, ld, hipMemcpyHostToDevice);
-    return aoclsparse_status_success;
-}
-
 // Row groups for the row-major kernel: maximal runs (<= CSRMM_GROUP) of consecutive rows whose column arrays are
 // equal entry for entry.  Kept only when they pay: at least 1.5 rows per group on average.
 aoclsparse_status build_mm_groups(const HostCsr &h, SpmvPlan &plan)
@@ -812,49 +778,26 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
     const aoclsparse_int m_c    = tr ? k : m; // rows of C
     const long long      c_outer = colmaj ? n : m_c, b_outer = colmaj ? n : b_rows;
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
-
-    const bool bdev = rt.is_device_pointer(B), cdev = rt.is_device_pointer(C);
-    void      *dB = const_cast<T *>(B), *dC = C;
-    size_t     bbytes = 0, cbytes = 0;
-    if(!cdev)
-    {
-        st = stage_dense<T>(rt, 4, C, (aoclsparse_int)c_outer, colmaj ? m_c : n, ldc, true, &dC, &cbytes);
-        if(st != aoclsparse_status_success)
-            return st;
-    }
-    auto finish = [&]() -> aoclsparse_status {
-        if(!cdev)
-        {
-            const aoclsparse_status cs = copy_dense<T>(rt, C, dC, (aoclsparse_int)c_outer, colmaj ? m_c : n, ldc, hipMemcpyDeviceToHost);
-            if(cs != aoclsparse_status_success)
-                return cs;
-            MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-        }
-        return aoclsparse_status_success;
-    };
+    CallScope cs(CallScope::Conditional);
+    Runtime  &rt = cs.rt;
+    // only the `inner` elements of each line of a host B or C travel (CallScope::dense_in)
+    T *const dC = cs.dense_inout(STAGE_CSRMM_C, C, (aoclsparse_int)c_outer, colmaj ? m_c : n, ldc, true);
+    if(!cs.ok())
+        return cs.st;
+    aoclsparse_status st = aoclsparse_status_success;
 
     if(alpha == T(0))
     {
         // csrmm.hpp:614-618
-        st = launch_scale_dense<T>(rt.stream(), order, static_cast<T *>(dC), m_c, n, ldc, beta);
-        return st == aoclsparse_status_success ? finish() : st;
+        st = launch_scale_dense<T>(rt.stream(), order, dC, m_c, n, ldc, beta);
+        return st == aoclsparse_status_success ? cs.finish() : st;
     }
     if(descr->type == aoclsparse_matrix_type_hermitian)
         return aoclsparse_status_not_implemented; // real types: hermitian csrmm is not offered
 
-    if(!bdev)
-    {
-        st = stage_dense<T>(rt, 3, B, (aoclsparse_int)b_outer, colmaj ? b_rows : n, ldb, true, &dB, &bbytes);
-        if(st != aoclsparse_status_success)
-            return st;
-    }
+    const T *const dB = cs.dense_in(STAGE_CSRMM_B, B, (aoclsparse_int)b_outer, colmaj ? b_rows : n, ldb);
+    if(!cs.ok())
+        return cs.st;
     DeviceCsr *d = nullptr;
     SpmvPlan  *p = nullptr;
     if(descr->type == aoclsparse_matrix_type_symmetric)
@@ -904,21 +847,21 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
             std::shared_lock<std::shared_mutex> r(A->guard);
             aoclsparse_status                   ks = aoclsparse_status_not_implemented;
             // (matrices with row groups: the group kernels have no KT form; the per-row kernels below ignore the groups)
-            if(p->nblocks > 0 && csrmm_tiled_applies<T>(n, ldb, ldc, static_cast<const T *>(dB), static_cast<const T *>(dC)))
+            if(p->nblocks > 0 && csrmm_tiled_applies<T>(n, ldb, ldc, dB, dC))
                 ks = launch_csrmm_tiled<T>(rt.stream(), d->base, alpha, d->val.as<T>(), d->ind.as<aoclsparse_int>(),
                                            d->ptr.as<aoclsparse_int>(), p->rowblocks.as<aoclsparse_int>(), p->nblocks, p->tile,
-                                           p->max_row_nnz, static_cast<const T *>(dB), n, ldb, beta, static_cast<T *>(dC), ldc, lanes);
+                                           p->max_row_nnz, dB, n, ldb, beta, dC, ldc, lanes);
             else
                 ks = launch_csrmm<T>(rt.stream(), order, d->base, alpha, d->m, d->n, d->val.as<T>(), d->ind.as<aoclsparse_int>(),
-                                     d->ptr.as<aoclsparse_int>(), static_cast<const T *>(dB), n, ldb, beta, static_cast<T *>(dC),
+                                     d->ptr.as<aoclsparse_int>(), dB, n, ldb, beta, dC,
                                      ldc, nullptr, 0, 0, false, nullptr, lanes);
             if(ks != aoclsparse_status_not_implemented)
-                return ks == aoclsparse_status_success ? finish() : ks;
+                return ks == aoclsparse_status_success ? cs.finish() : ks;
         }
         std::shared_lock<std::shared_mutex> r(A->guard);
         st = launch_csrmm_kt<T>(rt.stream(), order, lanes, d->base, alpha, d->m, d->val.as<T>(), d->ind.as<aoclsparse_int>(),
-                                d->ptr.as<aoclsparse_int>(), static_cast<const T *>(dB), n, ldb, beta, static_cast<T *>(dC), ldc);
-        return st == aoclsparse_status_success ? finish() : st;
+                                d->ptr.as<aoclsparse_int>(), dB, n, ldb, beta, dC, ldc);
+        return st == aoclsparse_status_success ? cs.finish() : st;
     }
     // Column-major operands with many columns and rows longer than the column kernel's register cache: that kernel
     // would re-read A once per 4 columns (100 ms on the shell-like stand-in).  Detour: B and C are copied to packed
@@ -933,7 +876,7 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
         if(st != aoclsparse_status_success)
             return st;
     }
-    const bool windowed = colmaj && p && p->mm.win && csrmm_window_applies<T>(n, ldb, static_cast<const T *>(dB));
+    const bool windowed = colmaj && p && p->mm.win && csrmm_window_applies<T>(n, ldb, dB);
     // block-dense matrix: the blocked-ELL copy for the MFMA kernels (either layout)
     // (a second copy of the matrix: not under aoclsparse_memory_usage_minimal, which forbids such copies -- analysis.cpp:446)
     if(p && !windowed && !p->bell.tried && A->mem_policy == aoclsparse_memory_usage_unrestricted)
@@ -966,8 +909,8 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
         if(st != aoclsparse_status_success)
             return st;
     }
-    if(detour && !sl.owns_lock())
-        sl.lock(); // the scratch slots are shared; taken before the handle's guard, as everywhere else
+    if(detour)
+        cs.lock(); // the scratch slots are shared; taken before the handle's guard, as everywhere else
     {
         std::shared_lock<std::shared_mutex> r(A->guard);
         const bool                          grouped = p && p->mm.valid;
@@ -976,33 +919,33 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
         if(detour)
         {
             void *bt = nullptr, *ct = nullptr;
-            st = rt.staging(5, sizeof(T) * (size_t)b_rows * (size_t)n, &bt);
+            st = rt.staging(STAGE_CSRMM_BT, sizeof(T) * (size_t)b_rows * (size_t)n, &bt);
             // handles with row groups: only B changes layout; the row-group kernel writes (and, beta != 0, reads) the caller's
             // column-major C in place -- two of the detour's three copy passes gone (shell-like, 256 columns: 6.6 -> see DESIGN)
             const bool direct = st == aoclsparse_status_success && grouped
                                 && csrmm_groups_ccol_applies<T>(n, n, static_cast<const T *>(bt));
             if(direct)
             {
-                st = launch_relayout<T>(rt.stream(), true, static_cast<const T *>(dB), static_cast<T *>(bt), b_rows, n, ldb);
+                st = launch_relayout<T>(rt.stream(), true, dB, static_cast<T *>(bt), b_rows, n, ldb);
                 if(st == aoclsparse_status_success)
                     st = launch_csrmm_groups_ccol<T>(rt.stream(), d->base, alpha, d->val.as<T>(), d->ind.as<aoclsparse_int>(),
                                                      d->ptr.as<aoclsparse_int>(), static_cast<const T *>(bt), n, n, beta,
-                                                     static_cast<T *>(dC), ldc, grp, ngrp, p->mm.max_rows, d->m, p->mm.band);
-                return st == aoclsparse_status_success ? finish() : st;
+                                                     dC, ldc, grp, ngrp, p->mm.max_rows, d->m, p->mm.band);
+                return st == aoclsparse_status_success ? cs.finish() : st;
             }
             if(st == aoclsparse_status_success)
-                st = rt.staging(6, sizeof(T) * (size_t)m_c * (size_t)n, &ct);
+                st = rt.staging(STAGE_CSRMM_CT, sizeof(T) * (size_t)m_c * (size_t)n, &ct);
             if(st == aoclsparse_status_success)
-                st = launch_relayout<T>(rt.stream(), true, static_cast<const T *>(dB), static_cast<T *>(bt), b_rows, n, ldb);
+                st = launch_relayout<T>(rt.stream(), true, dB, static_cast<T *>(bt), b_rows, n, ldb);
             if(st == aoclsparse_status_success)
-                st = launch_relayout<T>(rt.stream(), true, static_cast<const T *>(dC), static_cast<T *>(ct), m_c, n, ldc);
+                st = launch_relayout<T>(rt.stream(), true, dC, static_cast<T *>(ct), m_c, n, ldc);
             if(st == aoclsparse_status_success)
                 st = launch_csrmm<T>(rt.stream(), aoclsparse_order_row, d->base, alpha, d->m, d->n, d->val.as<T>(),
                                      d->ind.as<aoclsparse_int>(), d->ptr.as<aoclsparse_int>(), static_cast<const T *>(bt),
                                      n, n, beta, static_cast<T *>(ct), n, grp, ngrp, grouped ? p->mm.max_rows : 0, false, nullptr, 0,
                                      grouped ? p->mm.band : 0);
             if(st == aoclsparse_status_success)
-                st = launch_relayout<T>(rt.stream(), false, static_cast<const T *>(ct), static_cast<T *>(dC), m_c, n, ldc);
+                st = launch_relayout<T>(rt.stream(), false, static_cast<const T *>(ct), dC, m_c, n, ldc);
         }
         else if(!colmaj && p && p->bell.valid && std::is_same<T, double>::value)
         {
@@ -1013,7 +956,7 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
                                        beta, static_cast<double *>(dC), ldc);
         }
         else if(!colmaj && !grouped && p && p->valid && p->nblocks > 0
-                && csrmm_tiled_applies<T>(n, ldb, ldc, static_cast<const T *>(dB), static_cast<const T *>(dC)))
+                && csrmm_tiled_applies<T>(n, ldb, ldc, dB, dC))
         {
             // narrow row-major operands (a multi-GPU column slab): row blocks of the SpMV plan -- or, on a banded matrix, the blocks that
             // follow its lines -- A staged in LDS
@@ -1022,8 +965,8 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
             st = launch_csrmm_tiled<T>(rt.stream(), d->base, alpha, d->val.as<T>(), d->ind.as<aoclsparse_int>(),
                                        d->ptr.as<aoclsparse_int>(),
                                        lines ? p->mm.slab_blocks.as<aoclsparse_int>() : p->rowblocks.as<aoclsparse_int>(),
-                                       lines ? p->mm.slab_nblocks : p->nblocks, p->tile, p->max_row_nnz, static_cast<const T *>(dB), n, ldb,
-                                       beta, static_cast<T *>(dC), ldc, 0, lines);
+                                       lines ? p->mm.slab_nblocks : p->nblocks, p->tile, p->max_row_nnz, dB, n, ldb,
+                                       beta, dC, ldc, 0, lines);
         }
         else if(on_mfma_col)
         {
@@ -1037,23 +980,23 @@ aoclsparse_status csrmm_t(aoclsparse_operation op, const T alpha, const aoclspar
             // column-major operands, banded matrix: each B column's stretch staged in LDS, rows' entries in registers
             st = launch_csrmm_window<T>(rt.stream(), d->base, alpha, d->m, d->val.as<T>(), d->ind.as<aoclsparse_int>(),
                                         d->ptr.as<aoclsparse_int>(), p->mm.windows.as<aoclsparse_int>(), p->mm.win_rows,
-                                        p->max_row_nnz, static_cast<const T *>(dB), n, ldb, beta, static_cast<T *>(dC), ldc);
+                                        p->max_row_nnz, dB, n, ldb, beta, dC, ldc);
         else if(colmaj && p && p->mm.pairs && (long long)ldb * (long long)sizeof(T) < (1LL << 32)
                 && reinterpret_cast<uintptr_t>(dB) % sizeof(T) == 0)
             // column-major operands, rows paired with a one-column shift: 16-byte loads / stores
             st = launch_csrmm_colpair<T>(rt.stream(), d->base, alpha, p->mm.npairs, p->mm.pair_first.as<aoclsparse_int>(),
                                          p->mm.nsingles, p->mm.single_rows.as<aoclsparse_int>(), d->val.as<T>(),
                                          d->ind.as<aoclsparse_int>(), d->ptr.as<aoclsparse_int>(), p->max_row_nnz,
-                                         static_cast<const T *>(dB), n, ldb, beta, static_cast<T *>(dC), ldc);
+                                         dB, n, ldb, beta, dC, ldc);
         else
             st = launch_csrmm<T>(rt.stream(), order, d->base, alpha, d->m, d->n, d->val.as<T>(),
-                                 d->ind.as<aoclsparse_int>(), d->ptr.as<aoclsparse_int>(), static_cast<const T *>(dB),
-                                 n, ldb, beta, static_cast<T *>(dC), ldc, colmaj ? nullptr : grp, colmaj ? 0 : ngrp,
+                                 d->ind.as<aoclsparse_int>(), d->ptr.as<aoclsparse_int>(), dB,
+                                 n, ldb, beta, dC, ldc, colmaj ? nullptr : grp, colmaj ? 0 : ngrp,
                                  grouped ? p->mm.max_rows : 0, !colmaj && p && p->mm.row_runs,
                                  !colmaj && p && p->mm.row_runs && p->mm.band > 0 ? p->mm.run_order.as<aoclsparse_int>() : nullptr, 0,
                                  !colmaj && p && (p->mm.row_runs || grouped) ? p->mm.band : 0);
     }
-    return st == aoclsparse_status_success ? finish() : st;
+    return st == aoclsparse_status_success ? cs.finish() : st;
 }
 
 } // namespace

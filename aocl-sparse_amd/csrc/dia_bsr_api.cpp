@@ -164,36 +164,6 @@ aoclsparse_status csr2bsr_t(aoclsparse_int m, aoclsparse_int n, const aoclsparse
     return aoclsparse_status_success;
 }
 
-// device view of a host array for one call (slot of the runtime's scratch), or the pointer itself
-template <typename U>
-aoclsparse_status view_in(Runtime &rt, int slot, const U *p, size_t count, const U **out, bool copy = true)
-{
-    if(rt.is_device_pointer(p))
-    {
-        *out = p;
-        return aoclsparse_status_success;
-    }
-    void             *d = nullptr;
-    aoclsparse_status st = rt.staging(slot, sizeof(U) * std::max<size_t>(count, 1), &d);
-    if(st != aoclsparse_status_success)
-        return st;
-    if(count && copy)
-        MI355_HIP_TRY(hipMemcpyAsync(d, p, sizeof(U) * count, hipMemcpyHostToDevice, rt.stream()));
-    *out = static_cast<const U *>(d);
-    return aoclsparse_status_success;
-}
-
-template <typename T>
-aoclsparse_status finish_y(Runtime &rt, T *y, T *dy, size_t count)
-{
-    if(dy != y)
-    {
-        MI355_HIP_TRY(hipMemcpyAsync(y, dy, sizeof(T) * count, hipMemcpyDeviceToHost, rt.stream()));
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    }
-    return aoclsparse_status_success;
-}
-
 template <typename T>
 aoclsparse_status diamv_t(aoclsparse_operation trans, const T *alpha, aoclsparse_int m, aoclsparse_int n,
                           const T *dia_val, const aoclsparse_int *dia_offset, aoclsparse_int ndiag,
@@ -211,27 +181,15 @@ aoclsparse_status diamv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
         return aoclsparse_status_success;
     if(kid > 3)
         return aoclsparse_status_invalid_kid;
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
-    const T              *dv = nullptr, *dx = nullptr, *dy0 = nullptr;
-    const aoclsparse_int *doff = nullptr;
-    st = view_in(rt, 8, dia_val, (size_t)m * (size_t)ndiag, &dv);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 9, dia_offset, (size_t)ndiag, &doff);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 10, x, (size_t)n, &dx);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 11, const_cast<const T *>(y), (size_t)m, &dy0, *beta != T(0)); // y is not read when beta == 0
-    if(st != aoclsparse_status_success)
-        return st;
-    T *dy = const_cast<T *>(dy0);
-    st    = launch_diamv<T>(rt.stream(), *alpha, m, n, dv, doff, ndiag, dx, *beta, dy);
-    return st == aoclsparse_status_success ? finish_y(rt, y, dy, (size_t)m) : st;
+    CallScope             cs(CallScope::Conditional);
+    const T              *dv   = cs.in(STAGE_DIA_VAL, dia_val, sizeof(T) * (size_t)m * (size_t)ndiag);
+    const aoclsparse_int *doff = cs.in(STAGE_DIA_OFFSET, dia_offset, sizeof(aoclsparse_int) * (size_t)ndiag);
+    const T              *dx   = cs.in(STAGE_FMT_X, x, sizeof(T) * (size_t)n);
+    T                    *dy   = cs.inout(STAGE_FMT_Y, y, sizeof(T) * (size_t)m, *beta != T(0)); // y is not read when beta == 0
+    if(!cs.ok())
+        return cs.st;
+    const aoclsparse_status st = launch_diamv<T>(cs.s, *alpha, m, n, dv, doff, ndiag, dx, *beta, dy);
+    return st == aoclsparse_status_success ? cs.finish() : st;
 }
 
 template <typename T>
@@ -253,16 +211,11 @@ aoclsparse_status bsrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
         return aoclsparse_status_success;
     if(!val || !row_ptr || !col || !x || !y)
         return aoclsparse_status_invalid_pointer;
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
-    const T              *dv = nullptr, *dx = nullptr, *dy0 = nullptr;
-    const aoclsparse_int *dc = nullptr, *dp = nullptr;
-    size_t                nblk = 0;
+    CallScope cs(CallScope::Conditional);
+    if(!cs.ok())
+        return cs.st;
+    Runtime &rt   = cs.rt;
+    size_t   nblk = 0;
     if(!rt.is_device_pointer(row_ptr))
     {
         if(row_ptr[mb] < descr->base)
@@ -271,20 +224,15 @@ aoclsparse_status bsrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
     }
     else if(!rt.is_device_pointer(val) || !rt.is_device_pointer(col))
         return aoclsparse_status_invalid_value; // the block count lives in row_ptr: keep the three arrays together
-    st = view_in(rt, 8, val, nblk * (size_t)dim * (size_t)dim, &dv);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 9, col, nblk, &dc);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 12, row_ptr, (size_t)mb + 1, &dp);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 10, x, (size_t)nb * (size_t)dim, &dx);
-    if(st == aoclsparse_status_success)
-        st = view_in(rt, 11, const_cast<const T *>(y), (size_t)mb * (size_t)dim, &dy0, *beta != T(0));
-    if(st != aoclsparse_status_success)
-        return st;
-    T *dy = const_cast<T *>(dy0);
-    st    = launch_bsrmv<T>(rt.stream(), *alpha, mb, dim, descr->base, dv, dc, dp, dx, *beta, dy);
-    return st == aoclsparse_status_success ? finish_y(rt, y, dy, (size_t)mb * (size_t)dim) : st;
+    const T              *dv = cs.in(STAGE_BSR_VAL, val, sizeof(T) * nblk * (size_t)dim * (size_t)dim);
+    const aoclsparse_int *dc = cs.in(STAGE_BSR_COL, col, sizeof(aoclsparse_int) * nblk);
+    const aoclsparse_int *dp = cs.in(STAGE_BSR_PTR, row_ptr, sizeof(aoclsparse_int) * ((size_t)mb + 1));
+    const T              *dx = cs.in(STAGE_FMT_X, x, sizeof(T) * (size_t)nb * (size_t)dim);
+    T                    *dy = cs.inout(STAGE_FMT_Y, y, sizeof(T) * (size_t)mb * (size_t)dim, *beta != T(0));
+    if(!cs.ok())
+        return cs.st;
+    const aoclsparse_status st = launch_bsrmv<T>(cs.s, *alpha, mb, dim, descr->base, dv, dc, dp, dx, *beta, dy);
+    return st == aoclsparse_status_success ? cs.finish() : st;
 }
 
 } // namespace
@@ -320,7 +268,7 @@ inline aoclsparse_status launch_bsr_any(hipStream_t s, cplx<R> alpha, aoclsparse
 } // namespace
 
 template <typename T>
-aoclsparse_status bsr_handle_mv(Runtime &rt, aoclsparse_matrix A, T alpha, const T *x, T beta, T *y)
+aoclsparse_status bsr_handle_mv(CallScope &cs, aoclsparse_matrix A, T alpha, const T *x, T beta, T *y)
 {
     // the mirror stays valid from here to the launch: the shared lock is held across it, and an upload (exclusive) is followed by a
     // fresh look under the shared lock, since aoclsparse_mi355_invalidate may have come between
@@ -334,25 +282,18 @@ aoclsparse_status bsr_handle_mv(Runtime &rt, aoclsparse_matrix A, T alpha, const
         r.lock();
     }
     const DeviceCsr  &d = A->dev_bsr;
-    StagedArg         ax, ay;
-    aoclsparse_status st = ax.in(rt, 3, x, sizeof(T) * (size_t)A->n, true);
-    if(st == aoclsparse_status_success)
-        st = ay.in(rt, 4, y, sizeof(T) * (size_t)A->m, !is_zero(beta)); // y is not read when beta == 0
-    if(st == aoclsparse_status_success)
-        st = launch_bsr_any(rt.stream(), alpha, d.m, A->bsr_dim, d.base, d.val.as<T>(), d.ind.as<aoclsparse_int>(),
-                            d.ptr.as<aoclsparse_int>(), static_cast<const T *>(ax.dev), beta, static_cast<T *>(ay.dev));
-    if(st == aoclsparse_status_success)
-        st = ay.out(rt);
-    if(st != aoclsparse_status_success)
-        return st;
-    if(ay.staged) // host-pointer semantics: result visible on return
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+    const T          *dx = cs.in(STAGE_MV_X, x, sizeof(T) * (size_t)A->n);
+    T                *dy = cs.inout(STAGE_MV_Y, y, sizeof(T) * (size_t)A->m, !is_zero(beta)); // y is not read when beta == 0
+    if(!cs.ok())
+        return cs.st;
+    const aoclsparse_status st = launch_bsr_any(cs.s, alpha, d.m, A->bsr_dim, d.base, d.val.as<T>(), d.ind.as<aoclsparse_int>(),
+                                                d.ptr.as<aoclsparse_int>(), dx, beta, dy);
+    return st == aoclsparse_status_success ? cs.finish() : st; // host-pointer semantics: result visible on return
 }
-template aoclsparse_status bsr_handle_mv<float>(Runtime &, aoclsparse_matrix, float, const float *, float, float *);
-template aoclsparse_status bsr_handle_mv<double>(Runtime &, aoclsparse_matrix, double, const double *, double, double *);
-template aoclsparse_status bsr_handle_mv<cfloat>(Runtime &, aoclsparse_matrix, cfloat, const cfloat *, cfloat, cfloat *);
-template aoclsparse_status bsr_handle_mv<cdouble>(Runtime &, aoclsparse_matrix, cdouble, const cdouble *, cdouble, cdouble *);
+template aoclsparse_status bsr_handle_mv<float>(CallScope &, aoclsparse_matrix, float, const float *, float, float *);
+template aoclsparse_status bsr_handle_mv<double>(CallScope &, aoclsparse_matrix, double, const double *, double, double *);
+template aoclsparse_status bsr_handle_mv<cfloat>(CallScope &, aoclsparse_matrix, cfloat, const cfloat *, cfloat, cfloat *);
+template aoclsparse_status bsr_handle_mv<cdouble>(CallScope &, aoclsparse_matrix, cdouble, const cdouble *, cdouble, cdouble *);
 } // namespace mi355
 
 extern "C" {

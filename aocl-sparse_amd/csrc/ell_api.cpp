@@ -62,27 +62,18 @@ aoclsparse_status ellmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
         return aoclsparse_status_success;
     if(!alpha || !beta) // the reference dereferences them unchecked; refuse instead of crashing
         return aoclsparse_status_invalid_pointer;
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    const size_t                          cells = (size_t)m * (size_t)ell_width;
-    StagedArg                             av, ac, ax, ay;
-    MI355_TRY(av.in(rt, 8, ell_val, sizeof(T) * cells, true));
-    MI355_TRY(ac.in(rt, 9, ell_col_ind, sizeof(aoclsparse_int) * cells, true));
-    MI355_TRY(ax.in(rt, 3, x, sizeof(T) * (size_t)n, true));
-    MI355_TRY(ay.in(rt, 4, y, sizeof(T) * (size_t)m, *beta != T(0)));
+    CallScope             cs(CallScope::Always);
+    const size_t          cells = (size_t)m * (size_t)ell_width;
+    const T              *dv = cs.in(STAGE_ELL_VAL, ell_val, sizeof(T) * cells);
+    const aoclsparse_int *dc = cs.in(STAGE_ELL_COL, ell_col_ind, sizeof(aoclsparse_int) * cells);
+    const T              *dx = cs.in(STAGE_MV_X, x, sizeof(T) * (size_t)n);
+    T                    *dy = cs.inout(STAGE_MV_Y, y, sizeof(T) * (size_t)m, *beta != T(0));
+    MI355_TRY(cs.st);
     if(TRANSPOSED_LAYOUT)
-        MI355_TRY(launch_elltmv<T>(rt.stream(), descr->base, *alpha, m, static_cast<const T *>(av.dev),
-                                   static_cast<const aoclsparse_int *>(ac.dev), ell_width,
-                                   static_cast<const T *>(ax.dev), *beta, static_cast<T *>(ay.dev)));
+        MI355_TRY(launch_elltmv<T>(cs.s, descr->base, *alpha, m, dv, dc, ell_width, dx, *beta, dy));
     else
-        MI355_TRY(launch_ellmv<T>(rt.stream(), descr->base, *alpha, m, static_cast<const T *>(av.dev),
-                                  static_cast<const aoclsparse_int *>(ac.dev), ell_width,
-                                  static_cast<const T *>(ax.dev), *beta, static_cast<T *>(ay.dev)));
-    MI355_TRY(ay.out(rt));
-    if(ay.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+        MI355_TRY(launch_ellmv<T>(cs.s, descr->base, *alpha, m, dv, dc, ell_width, dx, *beta, dy));
+    return cs.finish();
 }
 
 aoclsparse_status ellthybmv_d(const double *alpha, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz,
@@ -100,46 +91,34 @@ aoclsparse_status ellthybmv_d(const double *alpha, aoclsparse_int m, aoclsparse_
         return aoclsparse_status_success;
     if((ell_width > 0 && (!ell_val || !ell_col_ind)) || (ell_m < m && (!csr_val || !csr_row_ind || !csr_col_ind || !csr_row_idx_map)))
         return aoclsparse_status_invalid_pointer;
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    const aoclsparse_int                  nlong = m - ell_m;
-    const size_t                          cells = (size_t)m * (size_t)ell_width;
-    StagedArg                             av, ac, ax, ay, cv, cr, cc, mp;
-    MI355_TRY(av.in(rt, 8, ell_val, sizeof(double) * cells, true));
-    MI355_TRY(ac.in(rt, 9, ell_col_ind, sizeof(aoclsparse_int) * cells, true));
-    MI355_TRY(ax.in(rt, 3, x, sizeof(double) * (size_t)n, true));
-    MI355_TRY(ay.in(rt, 4, y, sizeof(double) * (size_t)m, *beta != 0.0));
-    void *ytmp = nullptr;
+    CallScope             cs(CallScope::Always);
+    const aoclsparse_int  nlong = m - ell_m;
+    const size_t          cells = (size_t)m * (size_t)ell_width;
+    const double         *dv = cs.in(STAGE_ELL_VAL, ell_val, sizeof(double) * cells);
+    const aoclsparse_int *dc = cs.in(STAGE_ELL_COL, ell_col_ind, sizeof(aoclsparse_int) * cells);
+    const double         *dx = cs.in(STAGE_MV_X, x, sizeof(double) * (size_t)n);
+    double               *dy = cs.inout(STAGE_MV_Y, y, sizeof(double) * (size_t)m, *beta != 0.0);
+    const double         *cv = nullptr;
+    const aoclsparse_int *cc = nullptr, *cr = nullptr, *mp = nullptr;
+    double               *ytmp = nullptr;
     if(nlong > 0)
     {
-        MI355_TRY(cv.in(rt, 10, csr_val, sizeof(double) * (size_t)nnz, true));
-        MI355_TRY(cc.in(rt, 11, csr_col_ind, sizeof(aoclsparse_int) * (size_t)nnz, true));
-        MI355_TRY(cr.in(rt, 12, csr_row_ind, sizeof(aoclsparse_int) * ((size_t)m + 1), true));
-        MI355_TRY(mp.in(rt, 13, csr_row_idx_map, sizeof(aoclsparse_int) * (size_t)nlong, true));
-        MI355_TRY(rt.staging(14, sizeof(double) * (size_t)nlong, &ytmp));
-        if(*beta != 0.0) // the long rows' y survives the ELL pass in a side buffer (:585-601, :652-660)
-            MI355_TRY(launch_gather_rows<double>(rt.stream(), nlong, static_cast<const aoclsparse_int *>(mp.dev),
-                                                 static_cast<const double *>(ay.dev), static_cast<double *>(ytmp)));
+        cv   = cs.in(STAGE_HYB_CSR_VAL, csr_val, sizeof(double) * (size_t)nnz);
+        cc   = cs.in(STAGE_HYB_CSR_COL, csr_col_ind, sizeof(aoclsparse_int) * (size_t)nnz);
+        cr   = cs.in(STAGE_HYB_CSR_PTR, csr_row_ind, sizeof(aoclsparse_int) * ((size_t)m + 1));
+        mp   = cs.in(STAGE_HYB_ROWMAP, csr_row_idx_map, sizeof(aoclsparse_int) * (size_t)nlong);
+        ytmp = static_cast<double *>(cs.scratch(STAGE_HYB_YTMP, sizeof(double) * (size_t)nlong));
     }
+    MI355_TRY(cs.st);
+    if(nlong > 0 && *beta != 0.0) // the long rows' y survives the ELL pass in a side buffer (:585-601, :652-660)
+        MI355_TRY(launch_gather_rows<double>(cs.s, nlong, mp, dy, ytmp));
     if(ell_width > 0)
-        MI355_TRY(launch_elltmv<double>(rt.stream(), descr->base, *alpha, m, static_cast<const double *>(av.dev),
-                                        static_cast<const aoclsparse_int *>(ac.dev), ell_width,
-                                        static_cast<const double *>(ax.dev), *beta, static_cast<double *>(ay.dev)));
+        MI355_TRY(launch_elltmv<double>(cs.s, descr->base, *alpha, m, dv, dc, ell_width, dx, *beta, dy));
     else if(ell_m == m) // width 0 and no long rows: the ELL pass alone defines y
-        MI355_TRY(launch_scale<double>(rt.stream(), static_cast<double *>(ay.dev), m, *beta));
+        MI355_TRY(launch_scale<double>(cs.s, dy, m, *beta));
     if(nlong > 0)
-        MI355_TRY(launch_csr_rows<double>(rt.stream(), descr->base, *alpha, nlong,
-                                          static_cast<const aoclsparse_int *>(mp.dev),
-                                          static_cast<const double *>(cv.dev),
-                                          static_cast<const aoclsparse_int *>(cc.dev),
-                                          static_cast<const aoclsparse_int *>(cr.dev),
-                                          static_cast<const double *>(ax.dev), *beta,
-                                          static_cast<const double *>(ytmp), static_cast<double *>(ay.dev)));
-    MI355_TRY(ay.out(rt));
-    if(ay.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+        MI355_TRY(launch_csr_rows<double>(cs.s, descr->base, *alpha, nlong, mp, cv, cc, cr, dx, *beta, ytmp, dy));
+    return cs.finish();
 }
 
 // ---- conversions (host) --------------------------------------------------------------------------------

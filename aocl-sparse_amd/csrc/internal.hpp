@@ -852,6 +852,123 @@ inline aoclsparse_status workspace_stream_guard(_aoclsparse_matrix *A, hipStream
 namespace mi355
 {
 
+// ---- staging buffers by name -------------------------------------------------------------------
+// Who owns which of the runtime's staging buffers (Runtime::staging).  A number that several families use has ONE primary name;
+// the others are aliases declared right under it, each with the reason why the two are never live together on one thread.  The
+// entry points of the aliases are leaves: each stages, launches and finishes inside one CallScope and calls no other entry point
+// while its views are live, unless its line says otherwise.  (Composite routines -- symgs, the ILU smoother, the iterative
+// solvers -- run the executors inside a DeviceScope, where nothing is staged.)  No nesting was found in which one number is live
+// twice on a thread.
+enum StageSlot : int
+{
+    // -- 0-2: the three CSR arrays of a raw-array call
+    STAGE_CSR_VAL = 0, // ?csrmv: val
+    STAGE_TRSV_B  = STAGE_CSR_VAL, // ?trsv / ?trsm b: a solve runs on a handle and calls no raw-array product
+    STAGE_L1_X    = STAGE_CSR_VAL, // level 1 x: leaf
+    STAGE_C2D_PTR = STAGE_CSR_VAL, // csr2dense row_ptr: leaf
+    STAGE_CSR_COL, // ?csrmv: col_ind
+    STAGE_L1_IND  = STAGE_CSR_COL, // level 1 indx: leaf
+    STAGE_C2D_COL = STAGE_CSR_COL, // csr2dense col_ind: leaf
+    STAGE_CSR_PTR, // ?csrmv: row_ptr
+    STAGE_TRSV_X  = STAGE_CSR_PTR, // ?trsv / ?trsm x: as STAGE_TRSV_B
+    STAGE_L1_Y    = STAGE_CSR_PTR, // level 1 y: leaf
+    STAGE_C2D_VAL = STAGE_CSR_PTR, // csr2dense val: leaf
+    // -- 3-4: the dense operands of a product
+    STAGE_MV_X, // x of ?mv, ?csrmv, ?dotmv, ell / ellt / ellthyb / blkcsr mv and the BSR handle product
+    STAGE_CSRMM_B = STAGE_MV_X, // ?csrmm B: csrmm calls no mv
+    STAGE_L1_DOT  = STAGE_MV_X, // ?doti partial sums and result: leaf.  (Not a nesting, but noted: in device-pointer mode ?doti takes
+                                // no stage lock, so two THREADS calling it at once share this buffer; as before this enum.)
+    STAGE_MV_Y, // y of the same products; ?dotmv stages y here again AFTER its ?mv has finished (copied back and synchronised)
+    STAGE_CSRMM_C = STAGE_MV_Y, // ?csrmm C: csrmm calls no mv
+    STAGE_DENSE_C = STAGE_MV_Y, // C of ?syrkd / ?syprd / ?sp2md / ?spmmd, A of csr2dense: their kernels are their own, no mv inside
+    // -- 5-7
+    STAGE_CSRMM_BT, // the csrmm detour's row-major copy of B (taken under the stage lock whatever the pointer mode)
+    STAGE_SYPRD_B = STAGE_CSRMM_BT, // ?syprd B: syprd runs launch_syprd only, never csrmm
+    STAGE_CSRMM_CT, // the csrmm detour's row-major copy of C
+    STAGE_SYPRD_SCRATCH = STAGE_CSRMM_CT, // ?syprd's m_c x n_in intermediate: as STAGE_SYPRD_B
+    STAGE_DOTMV_PART    = STAGE_CSRMM_CT, // ?dotmv partial sums: taken after its ?mv has finished; mv never takes the detour
+    STAGE_DOTMV_D, // ?dotmv: the result scalar of a host d
+    // -- 8-15: the raw-array formats (ELL family, BLKCSR, DIA, BSR): all leaves
+    STAGE_ELL_VAL,
+    STAGE_BLK_MASKS = STAGE_ELL_VAL,
+    STAGE_DIA_VAL   = STAGE_ELL_VAL,
+    STAGE_BSR_VAL   = STAGE_ELL_VAL,
+    STAGE_ELL_COL,
+    STAGE_BLK_VAL    = STAGE_ELL_COL,
+    STAGE_DIA_OFFSET = STAGE_ELL_COL,
+    STAGE_BSR_COL    = STAGE_ELL_COL,
+    STAGE_HYB_CSR_VAL, // ellthybmv: the CSR part of the long rows (val, col, row, row map)
+    STAGE_BLK_COL = STAGE_HYB_CSR_VAL,
+    STAGE_FMT_X   = STAGE_HYB_CSR_VAL, // x of diamv / bsrmv (the ELL family and BLKCSR stage x and y in STAGE_MV_X / _Y)
+    STAGE_HYB_CSR_COL,
+    STAGE_BLK_PTR = STAGE_HYB_CSR_COL,
+    STAGE_FMT_Y   = STAGE_HYB_CSR_COL, // y of diamv / bsrmv
+    STAGE_HYB_CSR_PTR,
+    STAGE_BSR_PTR = STAGE_HYB_CSR_PTR,
+    STAGE_HYB_ROWMAP,
+    STAGE_HYB_YTMP, // ellthybmv: the long rows' y across the ELL pass
+    STAGE_BLK_VALOFF = STAGE_HYB_YTMP,
+    STAGE_BLK_PARTS,
+    // -- 16-39: one first-touch product D = X * Y (sp2m, syrk, sypr; SpgProduct in sp2m_api.cpp).  The caller holds the stage
+    // lock from analyse() to the last pass.
+    SPG_SLOT_XP, // operands that no handle keeps resident: X (ptr, ind, val), then Y
+    SPG_SLOT_XI,
+    SPG_SLOT_XV,
+    SPG_SLOT_YP,
+    SPG_SLOT_YI,
+    SPG_SLOT_YV,
+    SPG_SLOT_CNT, // the list size of every row: the counts themselves
+    SPG_SLOT_ORDER_COUNT,
+    SPG_SLOT_ORDER_FILL,
+    SPG_SLOT_HEAVY_COUNT,
+    SPG_SLOT_HEAVY_FILL,
+    SPG_SLOT_G_KEY,
+    SPG_SLOT_G_POS,
+    SPG_SLOT_G_LIST,
+    SPG_SLOT_G_ACC,
+    SPG_SLOT_CAP,
+    SPG_SLOT_SMALL,
+    SPG_SLOT_SCAN,
+    SPG_SLOT_HEAVY_KEYS,
+    SPG_SLOT_TP, // sypr: the intermediate product T = sym(B) * A (ptr, ind, val), which never leaves HBM
+    SPG_SLOT_TI,
+    SPG_SLOT_TV,
+    SPG_SLOT_CP, // syrk / sypr: the result before it goes to the handle's host arrays (ptr, ind; val: SPG_SLOT_CV)
+    SPG_SLOT_CI,
+    // -- 40-45: the temporaries of the device transpose (transpose_kernels.hip).  Names of their own because they ARE live inside
+    // another family: sp2m / syrk / sypr transpose operands while the SPG slots are in use.
+    STAGE_TR_CNT,
+    STAGE_TR_SMALL,
+    STAGE_TR_CURSOR,
+    STAGE_TR_TPOS,
+    STAGE_TR_SCAN,
+    STAGE_TR_ORDER,
+    SPG_SLOT_CV, // 46: the values of the syrk / sypr result
+    STAGE_UNUSED_47,
+    // -- 48-58: the triplet sort (coo_sort_kernels.hip); a handle is created from triplets outside every product
+    COO_SLOT_KEY_A,
+    COO_SLOT_POS_A,
+    COO_SLOT_KEY_B,
+    COO_SLOT_POS_B,
+    COO_SLOT_HIST,
+    COO_SLOT_OFFS,
+    COO_SLOT_SCAN,
+    COO_SLOT_SMALL,
+    COO_SLOT_CNT,
+    COO_SLOT_FLAG,
+    COO_SLOT_RUNS,
+    STAGE_SLOT_COUNT
+};
+// every site keeps the buffer it has always used (what aoclsparse_mi355_release_staging reports depends on it)
+static_assert(STAGE_MV_Y == 4 && STAGE_DOTMV_D == 7 && STAGE_BLK_PARTS == 15 && SPG_SLOT_XP == 16 && STAGE_TR_CNT == 40
+                  && SPG_SLOT_CV == 46 && COO_SLOT_KEY_A == 48 && STAGE_SLOT_COUNT == 59,
+              "StageSlot: a slot moved");
+// the k-th slot after a named one (the ptr / ind / val triples of an operand; the A / B pair of the sort)
+constexpr StageSlot operator+(StageSlot s, int k)
+{
+    return static_cast<StageSlot>(static_cast<int>(s) + k);
+}
+
 // ---- runtime (one process per GPU; uses the current HIP device) ----------------------------
 class Runtime
 {
@@ -882,7 +999,7 @@ public:
     int  device = -1, cus = 0;
     char name[256] = {0};
     // scratch staging buffers for host-pointer calls (grown on demand, reused)
-    aoclsparse_status staging(int slot, size_t bytes, void **out);
+    aoclsparse_status staging(StageSlot slot, size_t bytes, void **out);
     size_t            release_staging(); // frees every slot (after the stream has drained); bytes freed
     // Host <-> device copies of PAGEABLE caller memory on the library's stream (plain stream-ordered copies: the runtime's own
     // staging runs at 56 GB/s on these boxes; h2d returns once enqueued, d2h likewise -- callers synchronise the stream)
@@ -909,9 +1026,7 @@ private:
     std::atomic<bool> inited_{false}; // set (release) after init_status_ / device / events are written
     aoclsparse_status init_status_ = aoclsparse_status_success;
     hipStream_t  stream_ = nullptr;
-    DeviceBuffer stage_[59]; // 0-7: csrmv / mv / trsv / dotmv, 8-15: ELL family and BLKCSR (ell_api.cpp, blk_api.cpp), 16-39 and 46: sp2m, syrk, sypr (SPG_SLOT_*),
-                             // 40-45: the temporaries of the device transpose (transpose_kernels.hip; sp2m transposes operands while its own slots are in use),
-                             // 48-58: the triplet sort (coo_sort_kernels.hip)
+    DeviceBuffer stage_[STAGE_SLOT_COUNT]; // one per StageSlot, which says who owns it
 };
 
 // While one of these is alive on a thread, Runtime::get() on that thread is the given slot: its device is current, its
@@ -938,36 +1053,12 @@ struct DeviceScope
     DeviceScope &operator=(const DeviceScope &) = delete;
 };
 
-// A host or device array made addressable by the GPU for one call of a raw-array entry point.
-struct StagedArg
+} // namespace mi355
+
+#include "staging.hpp" // CallScope: the host-pointer arguments of one call
+
+namespace mi355
 {
-    void  *dev = nullptr, *host = nullptr;
-    size_t bytes  = 0;
-    bool   staged = false;
-    aoclsparse_status in(Runtime &rt, int slot, const void *p, size_t nbytes, bool copy)
-    {
-        bytes = nbytes;
-        if(rt.is_device_pointer(p))
-        {
-            dev = const_cast<void *>(p);
-            return aoclsparse_status_success;
-        }
-        staged = true;
-        host   = const_cast<void *>(p);
-        aoclsparse_status st = rt.staging(slot, nbytes ? nbytes : 1, &dev);
-        if(st != aoclsparse_status_success)
-            return st;
-        if(copy && nbytes)
-            return rt.h2d(dev, p, nbytes); // pipelined through pinned memory when large
-        return aoclsparse_status_success;
-    }
-    aoclsparse_status out(Runtime &rt)
-    {
-        if(staged && bytes)
-            return rt.d2h(host, dev, bytes);
-        return aoclsparse_status_success;
-    }
-};
 
 // ---- host analysis (matrix.cpp) --------------------------------------------------------------
 aoclsparse_status mat_check(aoclsparse_int maj, aoclsparse_int mind, aoclsparse_int nnz,
@@ -1099,7 +1190,7 @@ aoclsparse_status ensure_bsr_mirror(aoclsparse_matrix A);
 // y = alpha A x + beta y on a BSR handle with column-major blocks (dia_bsr_api.cpp): T = float / double / cfloat / cdouble, x and y
 // host or device memory, the matrix read from the handle's mirror.  The caller has initialised the runtime and holds its stage lock
 template <typename T>
-aoclsparse_status bsr_handle_mv(Runtime &rt, aoclsparse_matrix A, T alpha, const T *x, T beta, T *y);
+aoclsparse_status bsr_handle_mv(CallScope &cs, aoclsparse_matrix A, T alpha, const T *x, T beta, T *y);
 template <typename T>
 aoclsparse_status launch_mergepath(hipStream_t s, int base, T alpha, aoclsparse_int ntiles, const aoclsparse_int *starts,
                                    const aoclsparse_int *first, const T *val, const aoclsparse_int *col,
@@ -1368,38 +1459,8 @@ aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclspa
 
 // ---- one first-touch product D = X * Y on the device (sp2m_api.cpp; kernels: spgemm_kernels.hip) ----------------------------------
 // What aoclsparse_sp2m, aoclsparse_syrk and aoclsparse_sypr share: the upper bound of every row's list, the bins, the count pass
-// with its prefix sum and the fill pass.  X and Y are CSR arrays in HBM (any base), D is 0-based.  Staging slots 16-39 and 46 of the
+// with its prefix sum and the fill pass.  X and Y are CSR arrays in HBM (any base), D is 0-based.  The SPG_SLOT_* staging slots (StageSlot) of the
 // runtime belong to these three entry points; the caller holds the runtime's stage lock from analyse() to the last pass.
-enum
-{
-    SPG_SLOT_XP = 16, // operands that no handle keeps resident: X (ptr, ind, val), then Y
-    SPG_SLOT_XI,
-    SPG_SLOT_XV,
-    SPG_SLOT_YP,
-    SPG_SLOT_YI,
-    SPG_SLOT_YV,
-    SPG_SLOT_CNT, // the list size of every row: the counts themselves
-    SPG_SLOT_ORDER_COUNT,
-    SPG_SLOT_ORDER_FILL,
-    SPG_SLOT_HEAVY_COUNT,
-    SPG_SLOT_HEAVY_FILL,
-    SPG_SLOT_G_KEY,
-    SPG_SLOT_G_POS,
-    SPG_SLOT_G_LIST,
-    SPG_SLOT_G_ACC,
-    SPG_SLOT_CAP,
-    SPG_SLOT_SMALL,
-    SPG_SLOT_SCAN,
-    SPG_SLOT_HEAVY_KEYS,
-    SPG_SLOT_TP, // sypr: the intermediate product T = sym(B) * A (ptr, ind, val), which never leaves HBM
-    SPG_SLOT_TI,
-    SPG_SLOT_TV,
-    SPG_SLOT_CP, // syrk / sypr: the result before it goes to the handle's host arrays (ptr, ind; val: SPG_SLOT_CV)
-    SPG_SLOT_CI,
-    SPG_SLOT_END,
-    SPG_SLOT_CV = 46
-};
-static_assert(SPG_SLOT_END <= 40, "Runtime::stage_: slots 40-45 belong to the device transpose");
 struct SpgDevOp
 {
     const aoclsparse_int *ptr = nullptr, *ind = nullptr;

@@ -20,63 +20,6 @@ using namespace mi355;
 namespace
 {
 
-// one call's staging state: slot k of the runtime's scratch holds array k when it came from the host
-struct Stage
-{
-    Runtime                               &rt;
-    std::unique_lock<std::recursive_mutex> sl;
-    hipStream_t                            s = nullptr;
-    aoclsparse_status                      st;
-    struct Back
-    {
-        void  *host;
-        void  *dev;
-        size_t bytes;
-    } back[3];
-    int nback = 0;
-
-    Stage()
-        : rt(Runtime::get())
-        , sl(rt.stage_lock, std::defer_lock)
-    {
-        st = rt.init();
-        if(st == aoclsparse_status_success)
-        {
-            if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-                sl.lock();
-            s = rt.stream();
-        }
-    }
-    // device view of `p` (bytes long); host arrays are copied in when `in`, copied back at finish() when `out`
-    void *view(int slot, const void *p, size_t bytes, bool in, bool out)
-    {
-        if(st != aoclsparse_status_success)
-            return nullptr;
-        if(rt.is_device_pointer(p))
-            return const_cast<void *>(p);
-        void *d = nullptr;
-        st      = rt.staging(slot, bytes ? bytes : 1, &d);
-        if(st != aoclsparse_status_success)
-            return nullptr;
-        if(in && bytes && hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-            st = aoclsparse_status_internal_error;
-        if(out)
-            back[nback++] = {const_cast<void *>(p), d, bytes};
-        return d;
-    }
-    aoclsparse_status finish()
-    {
-        if(st != aoclsparse_status_success)
-            return st;
-        for(int i = 0; i < nback; i++)
-            if(back[i].bytes && hipMemcpyAsync(back[i].host, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
-                return aoclsparse_status_internal_error;
-        if(nback && hipStreamSynchronize(s) != hipSuccess)
-            return aoclsparse_status_internal_error;
-        return aoclsparse_status_success;
-    }
-};
-
 // number of elements of y the entries reach; -1: a negative index; host indices only (device: 0 = "not needed")
 long long extent_of(Runtime &rt, const aoclsparse_int *indx, aoclsparse_int nnz)
 {
@@ -103,7 +46,7 @@ aoclsparse_status axpyi_t(aoclsparse_int nnz, T a, const T *x, const aoclsparse_
         return aoclsparse_status_invalid_size;
     if(kid > 3)
         return aoclsparse_status_invalid_kid;
-    Stage g;
+    CallScope g(CallScope::Conditional);
     if(g.st != aoclsparse_status_success)
         return g.st;
     const long long ext = extent_of(g.rt, indx, nnz);
@@ -111,9 +54,9 @@ aoclsparse_status axpyi_t(aoclsparse_int nnz, T a, const T *x, const aoclsparse_
         return aoclsparse_status_invalid_index_value;
     if(ext == 0 && !g.rt.is_device_pointer(y))
         return aoclsparse_status_invalid_value; // host y with device indices: its extent is unknown
-    const T              *dx = static_cast<const T *>(g.view(0, x, sizeof(T) * (size_t)nnz, true, false));
-    const aoclsparse_int *di = static_cast<const aoclsparse_int *>(g.view(1, indx, sizeof(aoclsparse_int) * (size_t)nnz, true, false));
-    T                    *dy = static_cast<T *>(g.view(2, y, sizeof(T) * (size_t)ext, true, true));
+    const T              *dx = g.in(STAGE_L1_X, x, sizeof(T) * (size_t)nnz);
+    const aoclsparse_int *di = g.in(STAGE_L1_IND, indx, sizeof(aoclsparse_int) * (size_t)nnz);
+    T                    *dy = g.inout(STAGE_L1_Y, y, sizeof(T) * (size_t)ext, true);
     if(g.st == aoclsparse_status_success)
         g.st = launch_axpyi<T>(g.s, nnz, a, dx, di, dy);
     return g.finish();
@@ -134,7 +77,7 @@ aoclsparse_status dot_t(aoclsparse_int nnz, const T *x, const aoclsparse_int *in
         return aoclsparse_status_invalid_pointer;
     if(kid > 3)
         return aoclsparse_status_invalid_kid;
-    Stage g;
+    CallScope g(CallScope::Conditional);
     if(g.st != aoclsparse_status_success)
         return g.st;
     const long long ext = extent_of(g.rt, indx, nnz);
@@ -142,15 +85,12 @@ aoclsparse_status dot_t(aoclsparse_int nnz, const T *x, const aoclsparse_int *in
         return aoclsparse_status_invalid_index_value;
     if(ext == 0 && !g.rt.is_device_pointer(y))
         return aoclsparse_status_invalid_value;
-    const T              *dx = static_cast<const T *>(g.view(0, x, sizeof(T) * (size_t)nnz, true, false));
-    const aoclsparse_int *di = static_cast<const aoclsparse_int *>(g.view(1, indx, sizeof(aoclsparse_int) * (size_t)nnz, true, false));
-    const T              *dy = static_cast<const T *>(g.view(2, y, sizeof(T) * (size_t)ext, true, false));
-    void                 *scratch = nullptr;
-    if(g.st == aoclsparse_status_success)
-        g.st = g.rt.staging(3, sizeof(T) * (size_t)(L1_DOT_PARTIALS + 1), &scratch);
+    const T              *dx = g.in(STAGE_L1_X, x, sizeof(T) * (size_t)nnz);
+    const aoclsparse_int *di = g.in(STAGE_L1_IND, indx, sizeof(aoclsparse_int) * (size_t)nnz);
+    const T              *dy = g.in(STAGE_L1_Y, y, sizeof(T) * (size_t)ext);
+    T *part = static_cast<T *>(g.scratch(STAGE_L1_DOT, sizeof(T) * (size_t)(L1_DOT_PARTIALS + 1))), *out = part + L1_DOT_PARTIALS;
     if(g.st != aoclsparse_status_success)
         return g.st;
-    T *part = static_cast<T *>(scratch), *out = part + L1_DOT_PARTIALS;
     g.st    = launch_doti<T>(g.s, nnz, dx, di, dy, conj, part, out);
     if(g.st != aoclsparse_status_success)
         return g.st;
@@ -195,7 +135,7 @@ aoclsparse_status move_t(int mode, aoclsparse_int nnz, T *y, T *x, const aoclspa
     }
     if(kid > 3)
         return aoclsparse_status_invalid_kid;
-    Stage g;
+    CallScope g(CallScope::Conditional);
     if(g.st != aoclsparse_status_success)
         return g.st;
     long long ext = strided ? (long long)stride * (nnz - 1) + 1 : extent_of(g.rt, indx, nnz);
@@ -203,12 +143,10 @@ aoclsparse_status move_t(int mode, aoclsparse_int nnz, T *y, T *x, const aoclspa
         return aoclsparse_status_invalid_index_value;
     if(ext == 0 && !g.rt.is_device_pointer(y))
         return aoclsparse_status_invalid_value;
-    const bool            y_in = true; // scatter keeps the untouched elements, gather reads
-    T                    *dx = static_cast<T *>(g.view(0, x, sizeof(T) * (size_t)nnz, mode == 2, mode != 2));
-    const aoclsparse_int *di = strided ? nullptr
-                                       : static_cast<const aoclsparse_int *>(
-                                           g.view(1, indx, sizeof(aoclsparse_int) * (size_t)nnz, true, false));
-    T                    *dy = static_cast<T *>(g.view(2, y, sizeof(T) * (size_t)ext, y_in, mode != 0));
+    // x: read by scatter, written by the gathers;  y: always read (scatter keeps the untouched elements), written unless gthr
+    T                    *dx = g.inout(STAGE_L1_X, x, sizeof(T) * (size_t)nnz, mode == 2, mode != 2);
+    const aoclsparse_int *di = strided ? nullptr : g.in(STAGE_L1_IND, indx, sizeof(aoclsparse_int) * (size_t)nnz);
+    T                    *dy = g.inout(STAGE_L1_Y, y, sizeof(T) * (size_t)ext, true, mode != 0);
     if(g.st == aoclsparse_status_success)
         g.st = launch_gather_scatter<T>(g.s, nnz, dx, di, (long long)stride, dy, mode);
     return g.finish();
@@ -225,7 +163,7 @@ aoclsparse_status roti_t(aoclsparse_int nnz, T *x, const aoclsparse_int *indx, T
         return aoclsparse_status_invalid_size;
     if(kid > 3)
         return aoclsparse_status_invalid_kid;
-    Stage g;
+    CallScope g(CallScope::Conditional);
     if(g.st != aoclsparse_status_success)
         return g.st;
     const long long ext = extent_of(g.rt, indx, nnz);
@@ -233,9 +171,9 @@ aoclsparse_status roti_t(aoclsparse_int nnz, T *x, const aoclsparse_int *indx, T
         return aoclsparse_status_invalid_index_value;
     if(ext == 0 && !g.rt.is_device_pointer(y))
         return aoclsparse_status_invalid_value;
-    T                    *dx = static_cast<T *>(g.view(0, x, sizeof(T) * (size_t)nnz, true, true));
-    const aoclsparse_int *di = static_cast<const aoclsparse_int *>(g.view(1, indx, sizeof(aoclsparse_int) * (size_t)nnz, true, false));
-    T                    *dy = static_cast<T *>(g.view(2, y, sizeof(T) * (size_t)ext, true, true));
+    T                    *dx = g.inout(STAGE_L1_X, x, sizeof(T) * (size_t)nnz, true);
+    const aoclsparse_int *di = g.in(STAGE_L1_IND, indx, sizeof(aoclsparse_int) * (size_t)nnz);
+    T                    *dy = g.inout(STAGE_L1_Y, y, sizeof(T) * (size_t)ext, true);
     if(g.st == aoclsparse_status_success)
         g.st = launch_roti<T>(g.s, nnz, dx, di, dy, c, s);
     return g.finish();

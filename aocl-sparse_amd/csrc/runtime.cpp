@@ -381,7 +381,7 @@ bool Runtime::is_device_pointer(const void *p)
            || attr.type == hipMemoryTypeUnified;
 }
 
-aoclsparse_status Runtime::staging(int slot, size_t bytes, void **out)
+aoclsparse_status Runtime::staging(StageSlot slot, size_t bytes, void **out)
 {
     aoclsparse_status st = stage_[slot].alloc(bytes);
     *out                 = stage_[slot].ptr;

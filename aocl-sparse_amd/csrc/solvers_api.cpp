@@ -105,38 +105,6 @@ inline aoclsparse_status create_csr(aoclsparse_matrix *M, aoclsparse_index_base 
     return aoclsparse_create_ccsr(M, b, m, n, nnz, p, c, reinterpret_cast<aoclsparse_float_complex *>(v));
 }
 
-// A caller's vector made device-resident for the duration of one composite call.
-template <typename T>
-struct Vec
-{
-    T    *dev  = nullptr;
-    T    *host = nullptr;
-    bool  staged = false;
-    aoclsparse_status in(Runtime &rt, DeviceBuffer &buf, const T *p, aoclsparse_int n, bool copy)
-    {
-        if(rt.is_device_pointer(p))
-        {
-            dev = const_cast<T *>(p);
-            return aoclsparse_status_success;
-        }
-        staged = true;
-        host   = const_cast<T *>(p);
-        aoclsparse_status st = buf.alloc(sizeof(T) * (size_t)n);
-        if(st != aoclsparse_status_success)
-            return st;
-        dev = buf.as<T>();
-        if(copy)
-            MI355_HIP_TRY(hipMemcpyAsync(dev, p, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, rt.stream()));
-        return aoclsparse_status_success;
-    }
-    aoclsparse_status out(Runtime &rt, aoclsparse_int n)
-    {
-        if(staged)
-            MI355_HIP_TRY(hipMemcpyAsync(host, dev, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, rt.stream()));
-        return aoclsparse_status_success;
-    }
-};
-
 #define MI355_TRY(expr)                          \
     do                                           \
     {                                            \
@@ -194,24 +162,24 @@ aoclsparse_status sorv_t(aoclsparse_sor_type sor_type, const aoclsparse_mat_desc
     if(!sorv_full_diag<T>(A->user))
         return aoclsparse_status_invalid_value;
 
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // the handle's workspaces are shared
+    CallScope cs(CallScope::Always); // the handle's workspaces are shared: a caller's host vectors are staged in them
+    MI355_TRY(cs.st);
     const aoclsparse_int m = A->m;
+    const size_t         vbytes = sizeof(T) * (size_t)m;
     // level sets of the strict lower triangle (the solve's analysis) and the user's CSR in HBM
     MI355_TRY(ensure_trsv(A, false, false));
     DeviceCsr *d = nullptr;
     SpmvPlan  *p = nullptr;
     MI355_TRY(ensure_spmv(A, false, d, p));
-    Vec<T> vb, vx;
-    MI355_TRY(workspace_stream_guard(A, rt.stream()));
-    MI355_TRY(vb.in(rt, A->work[2], b, m, true));
-    MI355_TRY(vx.in(rt, A->work[3], x, m, true));
-    MI355_TRY(A->work[0].alloc(sizeof(T) * (size_t)m));
-    hipStream_t s = rt.stream();
+    hipStream_t s = cs.s;
+    MI355_TRY(workspace_stream_guard(A, s));
+    const T *db = cs.in(A->work[2], b, vbytes);
+    T       *dx = cs.inout(A->work[3], x, vbytes, true);
+    MI355_TRY(cs.st);
+    MI355_TRY(A->work[0].alloc(vbytes));
     // x = alpha * x (exact zeros for alpha == 0, sorv.hpp:212-222), snapshot, then level by level
-    MI355_TRY(launch_dense_scale<T>(s, vx.dev, m, 1, m, alpha, alpha == T(0)));
-    MI355_HIP_TRY(hipMemcpyAsync(A->work[0].ptr, vx.dev, sizeof(T) * (size_t)m, hipMemcpyDeviceToDevice, s));
+    MI355_TRY(launch_dense_scale<T>(s, dx, m, 1, m, alpha, alpha == T(0)));
+    MI355_HIP_TRY(hipMemcpyAsync(A->work[0].ptr, dx, vbytes, hipMemcpyDeviceToDevice, s));
     {
         std::shared_lock<std::shared_mutex> r(A->guard);
         const TrsvPlan                     &tp = A->trsv_plan[trsv_plan_index(false, false, false)];
@@ -219,12 +187,9 @@ aoclsparse_status sorv_t(aoclsparse_sor_type sor_type, const aoclsparse_mat_desc
         for(aoclsparse_int l = 0; l < tp.nlevels; l++)
             MI355_TRY(launch_sorv_level<T>(s, rows + tp.level_ptr[l], tp.level_ptr[l + 1] - tp.level_ptr[l], d->base,
                                            d->ptr.as<aoclsparse_int>(), d->ind.as<aoclsparse_int>(), d->val.as<T>(), omega,
-                                           vx.dev, A->work[0].as<T>(), vb.dev));
+                                           dx, A->work[0].as<T>(), db));
     }
-    MI355_TRY(vx.out(rt, m));
-    if(vx.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(s));
-    return aoclsparse_status_success;
+    return cs.finish();
 }
 
 // ---- symmetric Gauss-Seidel ------------------------------------------------------------------------
@@ -273,25 +238,25 @@ aoclsparse_status symgs_t(aoclsparse_operation trans, aoclsparse_matrix A, const
         return aoclsparse_status_invalid_value;
     (void)kid; // symgs.hpp:354-381: every kid runs the reference composition
 
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // the handle's workspaces are shared
-    const aoclsparse_int m = A->m;
-    Vec<T>               vb, vx, vy;
+    CallScope cs(CallScope::Always); // the handle's workspaces are shared: a caller's host vectors are staged in them
+    MI355_TRY(cs.st);
+    Runtime             &rt = cs.rt;
+    const aoclsparse_int m  = A->m;
+    const size_t         vbytes = sizeof(T) * (size_t)m;
     MI355_TRY(workspace_stream_guard(A, rt.stream()));
-    MI355_TRY(vb.in(rt, A->work[2], b, m, true));
-    MI355_TRY(vx.in(rt, A->work[3], x, m, true)); // x carries the initial guess
-    if(fuse_mv)
-        MI355_TRY(vy.in(rt, A->work[4], y, m, false));
+    const T *db = cs.in(A->work[2], b, vbytes);
+    T       *dx = cs.inout(A->work[3], x, vbytes, true); // x carries the initial guess
+    T       *dy = fuse_mv ? cs.out(A->work[4], y, vbytes) : nullptr;
+    MI355_TRY(cs.st);
     const T one = T(1), zero = T(0);
     {
         DeviceScope scope;
         if(descr->type == aoclsparse_matrix_type_triangular)
         {
             // symgs.hpp:128-149: a single solve with the given triangle (+ the product)
-            MI355_TRY(exec_trsv(trans, one, A, descr, vb.dev, vx.dev, -1));
+            MI355_TRY(exec_trsv(trans, one, A, descr, db, dx, -1));
             if(fuse_mv)
-                MI355_TRY(exec_mv(trans, &one, A, descr, vx.dev, &zero, vy.dev));
+                MI355_TRY(exec_mv(trans, &one, A, descr, dx, &zero, dy));
         }
         else
         {
@@ -330,24 +295,19 @@ aoclsparse_status symgs_t(aoclsparse_operation trans, aoclsparse_matrix A, const
                 return &d;
             };
             // 1: (L + D) x1 = b - alpha U x0
-            MI355_TRY(exec_mv(u_trans, &alpha, A, with(u_fill, aoclsparse_diag_type_zero), vx.dev, &zero, q));
-            MI355_TRY(exec_diff(rt.stream(), m, vb.dev, q, r));
+            MI355_TRY(exec_mv(u_trans, &alpha, A, with(u_fill, aoclsparse_diag_type_zero), dx, &zero, q));
+            MI355_TRY(exec_diff(rt.stream(), m, db, q, r));
             MI355_TRY(exec_trsv(l_trans, one, A, with(l_fill, aoclsparse_diag_type_non_unit), r, q, -1));
             // 2: (U + D) x = b - L x1
             MI355_TRY(exec_mv(l_trans, &one, A, with(l_fill, aoclsparse_diag_type_zero), q, &zero, r));
-            MI355_TRY(exec_diff(rt.stream(), m, vb.dev, r, q));
-            MI355_TRY(exec_trsv(u_trans, one, A, with(u_fill, aoclsparse_diag_type_non_unit), q, vx.dev, -1));
+            MI355_TRY(exec_diff(rt.stream(), m, db, r, q));
+            MI355_TRY(exec_trsv(u_trans, one, A, with(u_fill, aoclsparse_diag_type_non_unit), q, dx, -1));
             // 3: y = op(A) x
             if(fuse_mv)
-                MI355_TRY(exec_mv(trans, &one, A, descr, vx.dev, &zero, vy.dev));
+                MI355_TRY(exec_mv(trans, &one, A, descr, dx, &zero, dy));
         }
     }
-    MI355_TRY(vx.out(rt, m));
-    if(fuse_mv)
-        MI355_TRY(vy.out(rt, m));
-    if(vx.staged || vy.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+    return cs.finish(); // x, then y
 }
 
 // ---- ILU(0) ------------------------------------------------------------------------------------------
@@ -481,9 +441,8 @@ aoclsparse_status ilu_smoother_t(aoclsparse_operation op, aoclsparse_matrix A, c
         MI355_TRY(ilu_prepare(A));
     }
 
-    Runtime &rt = Runtime::get();
-    MI355_TRY(rt.init());
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    CallScope cs(CallScope::Always);
+    MI355_TRY(cs.st);
     *precond_csr_val = nullptr;
     if(!A->ilu_factorized)
     {
@@ -499,26 +458,23 @@ aoclsparse_status ilu_smoother_t(aoclsparse_operation op, aoclsparse_matrix A, c
     }
     *precond_csr_val = static_cast<T *>(A->ilu_val);
 
-    const aoclsparse_int m = A->m;
-    Vec<T>               vb, vx;
-    MI355_TRY(workspace_stream_guard(A, rt.stream()));
-    MI355_TRY(vb.in(rt, A->work[2], b, m, true));
-    MI355_TRY(vx.in(rt, A->work[3], x, m, false));
-    MI355_TRY(A->work[0].alloc(sizeof(T) * (size_t)m));
+    const size_t vbytes = sizeof(T) * (size_t)A->m;
+    MI355_TRY(workspace_stream_guard(A, cs.s));
+    const T *db = cs.in(A->work[2], b, vbytes);
+    T       *dx = cs.out(A->work[3], x, vbytes);
+    MI355_TRY(cs.st);
+    MI355_TRY(A->work[0].alloc(vbytes));
     {
         // ilu0.hpp:113-156: L y = b with the unit lower factor, then U x = y
         DeviceScope           scope;
         _aoclsparse_mat_descr d = *descr;
         d.type                  = aoclsparse_matrix_type_triangular;
         d.fill_mode = aoclsparse_fill_mode_lower, d.diag_type = aoclsparse_diag_type_unit;
-        MI355_TRY(exec_trsv(aoclsparse_operation_none, T(1), A->ilu_factor, &d, vb.dev, A->work[0].as<T>(), -1));
+        MI355_TRY(exec_trsv(aoclsparse_operation_none, T(1), A->ilu_factor, &d, db, A->work[0].as<T>(), -1));
         d.fill_mode = aoclsparse_fill_mode_upper, d.diag_type = aoclsparse_diag_type_non_unit;
-        MI355_TRY(exec_trsv(aoclsparse_operation_none, T(1), A->ilu_factor, &d, A->work[0].as<T>(), vx.dev, -1));
+        MI355_TRY(exec_trsv(aoclsparse_operation_none, T(1), A->ilu_factor, &d, A->work[0].as<T>(), dx, -1));
     }
-    MI355_TRY(vx.out(rt, m));
-    if(vx.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+    return cs.finish();
 }
 
 } // namespace

@@ -346,11 +346,11 @@ aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr de
         return aoclsparse_status_success;
     }
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    CallScope cs(CallScope::Always); // the SPG_SLOT_* slots are shared
+    if(!cs.ok())
+        return cs.st;
+    Runtime          &rt = cs.rt;
+    aoclsparse_status st = aoclsparse_status_success;
     try
     {
         // operands in computation orientation (csr2m.cpp:743-830)
@@ -444,7 +444,7 @@ aoclsparse_status sp2m_t(aoclsparse_operation opA, const aoclsparse_mat_descr de
             return aoclsparse_status_success;
         };
         const aoclsparse_matrix HX = opflag == 3 ? B : A, HY = opflag == 3 ? A : B;
-        auto send = [&](const Operand<T> *o, const aoclsparse_matrix H, DevOp &dv, int slot) {
+        auto send = [&](const Operand<T> *o, const aoclsparse_matrix H, DevOp &dv, StageSlot slot) {
             aoclsparse_status rc = resident(o, H, dv);
             if(rc != aoclsparse_status_not_implemented)
                 return rc;

@@ -77,27 +77,15 @@ aoclsparse_status sp2md_t(aoclsparse_operation opA, const aoclsparse_mat_descr d
     if(outer == 0 || inner == 0)
         return aoclsparse_status_success;
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
-    const bool   cdev = rt.is_device_pointer(C);
-    void        *dC = C;
-    const size_t cbytes = sizeof(T) * (size_t)outer * (size_t)ldc;
-    if(!cdev)
-    {
-        // the whole outer x ldc block travels both ways, so padding beyond `inner` keeps the caller's bytes
-        st = rt.staging(4, cbytes, &dC);
-        if(st != aoclsparse_status_success)
-            return st;
-        MI355_HIP_TRY(hipMemcpyAsync(dC, C, cbytes, hipMemcpyHostToDevice, rt.stream()));
-    }
+    CallScope cs(CallScope::Conditional);
+    // the whole outer x ldc block travels both ways, so padding beyond `inner` keeps the caller's bytes
+    T *const dC = cs.inout(STAGE_DENSE_C, C, sizeof(T) * (size_t)outer * (size_t)ldc, true);
+    if(!cs.ok())
+        return cs.st;
+    aoclsparse_status st = aoclsparse_status_success;
     if(!eq(beta, 1.0))
     {
-        st = launch_dense_scale<T>(rt.stream(), static_cast<T *>(dC), inner, outer, ldc, beta, eq(beta, 0.0));
+        st = launch_dense_scale<T>(cs.s, dC, inner, outer, ldc, beta, eq(beta, 0.0));
         if(st != aoclsparse_status_success)
             return st;
     }
@@ -116,19 +104,14 @@ aoclsparse_status sp2md_t(aoclsparse_operation opA, const aoclsparse_mat_descr d
         ra.lock();
         if(B != A)
             rb.lock();
-        st = launch_sp2md<T>(rt.stream(), da->m, da->base, da->ptr.as<aoclsparse_int>(), da->ind.as<aoclsparse_int>(),
+        st = launch_sp2md<T>(cs.s, da->m, da->base, da->ptr.as<aoclsparse_int>(), da->ind.as<aoclsparse_int>(),
                              da->val.as<T>(), conj_a, db->base, db->ptr.as<aoclsparse_int>(),
-                             db->ind.as<aoclsparse_int>(), db->val.as<T>(), conj_b, alpha, static_cast<T *>(dC),
+                             db->ind.as<aoclsparse_int>(), db->val.as<T>(), conj_b, alpha, dC,
                              rowmaj ? (long long)ldc : 1LL, rowmaj ? 1LL : (long long)ldc);
         if(st != aoclsparse_status_success)
             return st;
     }
-    if(!cdev)
-    {
-        MI355_HIP_TRY(hipMemcpyAsync(C, dC, cbytes, hipMemcpyDeviceToHost, rt.stream()));
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    }
-    return aoclsparse_status_success;
+    return cs.finish();
 }
 
 template <typename T>
@@ -184,54 +167,25 @@ aoclsparse_status csr2dense_t(aoclsparse_int m, aoclsparse_int n, const aoclspar
     if((long long)outer * (long long)ld > 2147483647LL)
         return aoclsparse_status_invalid_size;
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
-    hipStream_t s = rt.stream();
-    // CSR arrays: device pointers are used in place, host arrays are staged (slots 0-2)
-    const bool            sdev = rt.is_device_pointer(row_ptr);
-    const aoclsparse_int *dptr = row_ptr, *dind = col_ind;
-    const T              *dval = val;
-    if(!sdev)
-    {
-        const aoclsparse_int nnz = row_ptr[m] - descr->base;
-        if(nnz < 0)
-            return aoclsparse_status_invalid_value;
-        void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
-        st = rt.staging(0, sizeof(aoclsparse_int) * ((size_t)m + 1), &p0);
-        if(st == aoclsparse_status_success)
-            st = rt.staging(1, sizeof(aoclsparse_int) * (size_t)std::max(nnz, 1), &p1);
-        if(st == aoclsparse_status_success)
-            st = rt.staging(2, sizeof(T) * (size_t)std::max(nnz, 1), &p2);
-        if(st != aoclsparse_status_success)
-            return st;
-        MI355_HIP_TRY(hipMemcpyAsync(p0, row_ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), hipMemcpyHostToDevice, s));
-        if(nnz > 0)
-        {
-            MI355_HIP_TRY(hipMemcpyAsync(p1, col_ind, sizeof(aoclsparse_int) * (size_t)nnz, hipMemcpyHostToDevice, s));
-            MI355_HIP_TRY(hipMemcpyAsync(p2, val, sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice, s));
-        }
-        dptr = static_cast<const aoclsparse_int *>(p0), dind = static_cast<const aoclsparse_int *>(p1);
-        dval = static_cast<const T *>(p2);
-    }
-    const bool   adev = rt.is_device_pointer(A);
-    void        *dA = A;
-    const size_t abytes = sizeof(T) * (size_t)outer * (size_t)ld;
-    if(!adev)
-    {
-        st = rt.staging(4, abytes, &dA);
-        if(st != aoclsparse_status_success)
-            return st;
-        if(ld != inner) // padding keeps the caller's bytes
-            MI355_HIP_TRY(hipMemcpyAsync(dA, A, abytes, hipMemcpyHostToDevice, s));
-    }
+    CallScope scope(CallScope::Conditional);
+    if(!scope.ok())
+        return scope.st;
+    hipStream_t s = scope.s;
+    // CSR arrays: device pointers are used in place, host arrays are staged; where row_ptr lives decides for all three
+    const bool     sdev = scope.rt.is_device_pointer(row_ptr);
+    aoclsparse_int nnz  = 0;
+    if(!sdev && (nnz = row_ptr[m] - descr->base) < 0)
+        return aoclsparse_status_invalid_value;
+    const void *dptr = scope.view(STAGE_C2D_PTR, row_ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), sdev, true, false);
+    const void *dind = scope.view(STAGE_C2D_COL, col_ind, sizeof(aoclsparse_int) * (size_t)nnz, sdev, true, false);
+    const void *dval = scope.view(STAGE_C2D_VAL, val, sizeof(T) * (size_t)nnz, sdev, true, false);
+    // the whole outer x ld block comes back; it goes in only when there is padding, which keeps the caller's bytes
+    T *const dA = scope.inout(STAGE_DENSE_C, A, sizeof(T) * (size_t)outer * (size_t)ld, ld != inner);
+    if(!scope.ok())
+        return scope.st;
     T zero{};
     std::memset(&zero, 0, sizeof(T));
-    st = launch_dense_scale<T>(s, static_cast<T *>(dA), inner, outer, ld, zero, true);
+    aoclsparse_status st = launch_dense_scale<T>(s, dA, inner, outer, ld, zero, true);
     if(st != aoclsparse_status_success)
         return st;
     // The reference's column-major symmetric branch addresses the diagonal and both mirrors through
@@ -241,19 +195,13 @@ aoclsparse_status csr2dense_t(aoclsparse_int m, aoclsparse_int n, const aoclspar
                      : ty == aoclsparse_matrix_type_hermitian ? 2
                                                               : 3;
     const long long rs = colmaj ? 1LL : (long long)ld, cs = colmaj ? (long long)ld : 1LL;
-    st = launch_csr2dense<T>(s, m, descr->base, dptr, dind, dval, static_cast<T *>(dA), rs, cs, mode,
+    st = launch_csr2dense<T>(s, m, descr->base, static_cast<const aoclsparse_int *>(dptr), static_cast<const aoclsparse_int *>(dind),
+                             static_cast<const T *>(dval), dA, rs, cs, mode,
                              descr->fill_mode == aoclsparse_fill_mode_upper ? 1 : 0,
                              descr->diag_type == aoclsparse_diag_type_unit   ? 1
                              : descr->diag_type == aoclsparse_diag_type_zero ? 2
                                                                              : 0);
-    if(st != aoclsparse_status_success)
-        return st;
-    if(!adev)
-    {
-        MI355_HIP_TRY(hipMemcpyAsync(A, dA, abytes, hipMemcpyDeviceToHost, s));
-        MI355_HIP_TRY(hipStreamSynchronize(s));
-    }
-    return aoclsparse_status_success;
+    return st == aoclsparse_status_success ? scope.finish() : st;
 }
 
 template <typename T>

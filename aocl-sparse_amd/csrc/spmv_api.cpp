@@ -14,38 +14,6 @@ using namespace mi355;
 namespace
 {
 
-// A host or device array made addressable by the GPU for one call.
-struct Arg
-{
-    void       *dev   = nullptr;
-    void       *host  = nullptr;
-    size_t      bytes = 0;
-    bool        staged = false;
-    aoclsparse_status in(Runtime &rt, int slot, const void *p, size_t nbytes, bool is_dev, bool copy)
-    {
-        bytes = nbytes;
-        if(is_dev)
-        {
-            dev = const_cast<void *>(p);
-            return aoclsparse_status_success;
-        }
-        staged = true;
-        host   = const_cast<void *>(p);
-        aoclsparse_status st = rt.staging(slot, nbytes, &dev);
-        if(st != aoclsparse_status_success)
-            return st;
-        if(copy && nbytes)
-            return rt.h2d(dev, p, nbytes); // pipelined through pinned memory when large
-        return aoclsparse_status_success;
-    }
-    aoclsparse_status out(Runtime &rt)
-    {
-        if(staged && bytes)
-            return rt.d2h(host, dev, bytes);
-        return aoclsparse_status_success;
-    }
-};
-
 inline bool valid_op(aoclsparse_operation op)
 {
     return op == aoclsparse_operation_none || op == aoclsparse_operation_transpose
@@ -92,7 +60,7 @@ aoclsparse_status resolve_order(aoclsparse_int kid, aoclsparse_int m, aoclsparse
 }
 
 template <typename T>
-aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const DeviceCsr &d,
+aoclsparse_status run_on_device_csr(CallScope &cs, aoclsparse_int kid, const DeviceCsr &d,
                                     const SpmvPlan &plan, T alpha, const T *x, T beta, T *y,
                                     aoclsparse_int nx, aoclsparse_int ny, unsigned int *stale = nullptr)
 {
@@ -106,17 +74,14 @@ aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const Devic
         strict = true;
     if(st != aoclsparse_status_success)
         return st;
-    const bool xdev = rt.is_device_pointer(x), ydev = rt.is_device_pointer(y);
-    Arg        ax, ay;
-    st = ax.in(rt, 3, x, sizeof(T) * (size_t)nx, xdev, true);
-    if(st != aoclsparse_status_success)
-        return st;
-    st = ay.in(rt, 4, y, sizeof(T) * (size_t)ny, ydev, beta != T(0));
-    if(st != aoclsparse_status_success)
-        return st;
+    Runtime &rt = cs.rt;
+    const T *dx = cs.in(STAGE_MV_X, x, sizeof(T) * (size_t)nx);
+    T       *dy = cs.inout(STAGE_MV_Y, y, sizeof(T) * (size_t)ny, beta != T(0)); // y is not read when beta == 0
+    if(!cs.ok())
+        return cs.st;
     if(plan.sell.valid) // format chosen by optimize for an mv hint: every order is exact there
-        st = launch_sellmv<T>(rt.stream(), plan.sell.view(d.m, plan.max_row_nnz), order, false, alpha, static_cast<const T *>(ax.dev), beta,
-                              static_cast<T *>(ay.dev), plan.sell.next_direction());
+        st = launch_sellmv<T>(rt.stream(), plan.sell.view(d.m, plan.max_row_nnz), order, false, alpha, dx, beta, dy,
+                              plan.sell.next_direction());
     else if(plan.merge.valid && order == 0 && !strict) // balanced tiles for irregular rows (scalar order, no pinned kid)
     {
         // one launch; the pieces of cut rows meet in the piece set of this stream (internal.hpp, MergePlan).  Finding the set
@@ -164,7 +129,7 @@ aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const Devic
         }
         st = launch_mergepath<T>(rt.stream(), d.base, alpha, mp.ntiles, mp.starts.as<aoclsparse_int>(), mp.first.as<aoclsparse_int>(),
                                  d.val.as<T>(), d.ind.as<aoclsparse_int>(), d.ptr.as<aoclsparse_int>(),
-                                 static_cast<const T *>(ax.dev), beta, static_cast<T *>(ay.dev), gs->granules.ptr);
+                                 dx, beta, dy, gs->granules.ptr);
     }
     else
     {
@@ -176,44 +141,29 @@ aoclsparse_status run_on_device_csr(Runtime &rt, aoclsparse_int kid, const Devic
                                  : 0;
         st = launch_csrmv<T>(rt.stream(), order, strict, plan.tile | (rev ? 2 : 0), d.base, alpha, d.m, d.val.as<T>(),
                              d.ind.as<aoclsparse_int>(), d.ptr.as<aoclsparse_int>(),
-                             plan.rowblocks.as<aoclsparse_int>(), plan.nblocks, static_cast<const T *>(ax.dev),
-                             beta, static_cast<T *>(ay.dev),
+                             plan.rowblocks.as<aoclsparse_int>(), plan.nblocks, dx, beta, dy,
                              (plan.heavy_first && (plan.tile & 1) == 0) ? plan.rowblocks4.as<aoclsparse_int>() : nullptr,
                              plan.max_row_nnz, stale);
     }
-    if(st != aoclsparse_status_success)
-        return st;
-    st = ay.out(rt);
-    if(st != aoclsparse_status_success)
-        return st;
-    if(ay.staged) // host-pointer semantics: result visible on return
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+    return st == aoclsparse_status_success ? cs.finish() : st; // host-pointer semantics: result visible on return
 }
 
 template <typename T>
-aoclsparse_status scale_y(Runtime &rt, T *y, aoclsparse_int n, T beta)
+aoclsparse_status scale_y(CallScope &cs, T *y, aoclsparse_int n, T beta)
 {
     if(n <= 0)
         return aoclsparse_status_success;
-    const bool ydev = rt.is_device_pointer(y);
-    Arg        ay;
-    aoclsparse_status st = ay.in(rt, 4, y, sizeof(T) * (size_t)n, ydev, beta != T(0));
-    if(st != aoclsparse_status_success)
-        return st;
-    st = launch_scale<T>(rt.stream(), static_cast<T *>(ay.dev), n, beta);
-    if(st != aoclsparse_status_success)
-        return st;
-    st = ay.out(rt);
-    if(st == aoclsparse_status_success && ay.staged)
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return st;
+    T *dy = cs.inout(STAGE_MV_Y, y, sizeof(T) * (size_t)n, beta != T(0));
+    if(!cs.ok())
+        return cs.st;
+    const aoclsparse_status st = launch_scale<T>(cs.s, dy, n, beta);
+    return st == aoclsparse_status_success ? cs.finish() : st;
 }
 
 // ---- handle path ---------------------------------------------------------------------------------
 // y = alpha (L + U - D) x + beta y on a TCSR handle (tcsr_kernels.hip): both triangles in HBM as the device mirrors of their own
 // handles, one launch on the runtime's stream
-aoclsparse_status tcsr_general_mv(Runtime &rt, aoclsparse_matrix A, double alpha, const double *x, double beta, double *y)
+aoclsparse_status tcsr_general_mv(CallScope &cs, aoclsparse_matrix A, double alpha, const double *x, double beta, double *y)
 {
     // both mirrors stay valid from here to the launch: the shared locks are held across it, and an upload (exclusive) is followed by
     // a fresh look under the shared locks, since aoclsparse_mi355_invalidate may have come between
@@ -235,24 +185,14 @@ aoclsparse_status tcsr_general_mv(Runtime &rt, aoclsparse_matrix A, double alpha
         rl.lock(), ru.lock();
     }
     const DeviceCsr *d[2] = {&tl->dev_user, &tu->dev_user};
-    Arg                                 ax, ay;
-    aoclsparse_status                   st = ax.in(rt, 3, x, sizeof(double) * (size_t)A->n, rt.is_device_pointer(x), true);
-    if(st != aoclsparse_status_success)
-        return st;
-    st = ay.in(rt, 4, y, sizeof(double) * (size_t)A->m, rt.is_device_pointer(y), beta != 0.0);
-    if(st != aoclsparse_status_success)
-        return st;
-    st = launch_tcsrmv(rt.stream(), A->base, alpha, A->m, d[0]->val.as<double>(), d[0]->ind.as<aoclsparse_int>(),
+    const double    *dx = cs.in(STAGE_MV_X, x, sizeof(double) * (size_t)A->n);
+    double          *dy = cs.inout(STAGE_MV_Y, y, sizeof(double) * (size_t)A->m, beta != 0.0);
+    if(!cs.ok())
+        return cs.st;
+    const aoclsparse_status st = launch_tcsrmv(cs.s, A->base, alpha, A->m, d[0]->val.as<double>(), d[0]->ind.as<aoclsparse_int>(),
                        d[0]->ptr.as<aoclsparse_int>(), d[1]->val.as<double>(), d[1]->ind.as<aoclsparse_int>(),
-                       d[1]->ptr.as<aoclsparse_int>(), static_cast<const double *>(ax.dev), beta, static_cast<double *>(ay.dev));
-    if(st != aoclsparse_status_success)
-        return st;
-    st = ay.out(rt);
-    if(st != aoclsparse_status_success)
-        return st;
-    if(ay.staged) // host-pointer semantics: result visible on return
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return aoclsparse_status_success;
+                       d[1]->ptr.as<aoclsparse_int>(), dx, beta, dy);
+    return st == aoclsparse_status_success ? cs.finish() : st; // host-pointer semantics: result visible on return
 }
 
 template <typename T>
@@ -302,21 +242,18 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
            || A->bsr_order != aoclsparse_order_column))
         return aoclsparse_status_not_implemented;
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
+    CallScope cs(CallScope::Conditional);
+    if(!cs.ok())
+        return cs.st;
+    aoclsparse_status st = aoclsparse_status_success;
 
     if(empty)
-        return scale_y<T>(rt, y, op == aoclsparse_operation_none ? A->m : A->n, *beta);
+        return scale_y<T>(cs, y, op == aoclsparse_operation_none ? A->m : A->n, *beta);
     if(bsr) // mv.cpp:331-342 with the handle's own base (:165); launch_bsrmv keeps the reference's chain per scalar row
-        return bsr_handle_mv<T>(rt, A, *alpha, x, *beta, y);
+        return bsr_handle_mv<T>(cs, A, *alpha, x, *beta, y);
     if constexpr(std::is_same<T, double>::value)
         if(tcsr)
-            return tcsr_general_mv(rt, A, *alpha, x, *beta, y);
+            return tcsr_general_mv(cs, A, *alpha, x, *beta, y);
 
     const doid     id  = get_doid(descr, op);
     aoclsparse_int kid = -1; // magic_box.hpp:34-53: first hint with matching action + doid
@@ -360,7 +297,7 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
         }
     }
     std::shared_lock<std::shared_mutex> r(A->guard);
-    return run_on_device_csr<T>(rt, kid, *dcsr, *plan, *alpha, x, *beta, y, dcsr->n, dcsr->m);
+    return run_on_device_csr<T>(cs, kid, *dcsr, *plan, *alpha, x, *beta, y, dcsr->n, dcsr->m);
 }
 
 // ---- raw-array path --------------------------------------------------------------------------------
@@ -408,13 +345,11 @@ aoclsparse_status csrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
         return aoclsparse_status_invalid_size;
     if(!val || !row || !col || !x || !y)
         return aoclsparse_status_invalid_pointer;
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
+    CallScope cs(CallScope::Conditional);
+    if(!cs.ok())
+        return cs.st;
+    Runtime          &rt = cs.rt;
+    aoclsparse_status st = aoclsparse_status_success;
     const bool tr = trans != aoclsparse_operation_none;
     const bool mdev = rt.is_device_pointer(row);
 
@@ -481,7 +416,7 @@ aoclsparse_status csrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
             st              = ensure_spmv(&tmp, false, dcsr, plan);
             if(st != aoclsparse_status_success)
                 return st;
-            st = run_on_device_csr<T>(rt, -1, *dcsr, *plan, *alpha, x, *beta, y, m, m);
+            st = run_on_device_csr<T>(cs, -1, *dcsr, *plan, *alpha, x, *beta, y, m, m);
             if(st == aoclsparse_status_success)
                 MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
             return st;
@@ -523,13 +458,13 @@ aoclsparse_status csrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
         tmp.user.ind = const_cast<aoclsparse_int *>(pcol);
         tmp.user.val = const_cast<T *>(pval);
         if(m == 0 || n == 0 || nnz == 0)
-            return scale_y<T>(rt, y, n, *beta);
+            return scale_y<T>(cs, y, n, *beta);
         DeviceCsr *dcsr = nullptr;
         SpmvPlan  *plan = nullptr;
         st              = ensure_spmv(&tmp, true, dcsr, plan);
         if(st != aoclsparse_status_success)
             return st;
-        st = run_on_device_csr<T>(rt, -1, *dcsr, *plan, *alpha, x, *beta, y, m, n);
+        st = run_on_device_csr<T>(cs, -1, *dcsr, *plan, *alpha, x, *beta, y, m, n);
         if(st == aoclsparse_status_success) // tmp's device buffers die with it: drain first
             MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
         return st;
@@ -539,14 +474,11 @@ aoclsparse_status csrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
         return aoclsparse_status_success;
 
     // non-transposed: make the three CSR arrays device-addressable
-    Arg aval, acol, arow;
-    st = arow.in(rt, 2, row, sizeof(aoclsparse_int) * ((size_t)m + 1), mdev, true);
-    if(st == aoclsparse_status_success)
-        st = acol.in(rt, 1, col, sizeof(aoclsparse_int) * (size_t)nnz, rt.is_device_pointer(col), true);
-    if(st == aoclsparse_status_success)
-        st = aval.in(rt, 0, val, sizeof(T) * (size_t)nnz, rt.is_device_pointer(val), true);
-    if(st != aoclsparse_status_success)
-        return st;
+    void       *drow = cs.view(STAGE_CSR_PTR, row, sizeof(aoclsparse_int) * ((size_t)m + 1), mdev, true, false);
+    const void *dcol = cs.in(STAGE_CSR_COL, col, sizeof(aoclsparse_int) * (size_t)nnz);
+    const void *dval = cs.in(STAGE_CSR_VAL, val, sizeof(T) * (size_t)nnz);
+    if(!cs.ok())
+        return cs.st;
 
     SpmvPlan                  local;
     SpmvPlan                 *plan = &local;
@@ -613,9 +545,9 @@ aoclsparse_status csrmv_t(aoclsparse_operation trans, const T *alpha, aoclsparse
 
     DeviceCsr view; // non-owning view for the shared launcher
     view.m = m, view.n = n, view.nnz = nnz, view.base = descr->base;
-    view.ptr.ptr = arow.dev, view.ind.ptr = acol.dev, view.val.ptr = aval.dev;
+    view.ptr.ptr = drow, view.ind.ptr = const_cast<void *>(dcol), view.val.ptr = const_cast<void *>(dval);
     // (a cached plan is validated inside the kernel; a plan built in this call from this row_ptr needs no validation)
-    st = run_on_device_csr<T>(rt, -1, view, *plan, *alpha, x, *beta, y, n, m, mdev && fresh_plan == false ? rt.plan_stale_dev : nullptr);
+    st = run_on_device_csr<T>(cs, -1, view, *plan, *alpha, x, *beta, y, n, m, mdev && fresh_plan == false ? rt.plan_stale_dev : nullptr);
     view.ptr.ptr = view.ind.ptr = view.val.ptr = nullptr; // not ours to free
     if(st == aoclsparse_status_success && plan == &local)
         MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // local plan buffer is freed on return
@@ -629,35 +561,20 @@ aoclsparse_status dotmv_t(aoclsparse_operation op, T alpha, aoclsparse_matrix A,
 {
     if(!d || !A)
         return aoclsparse_status_invalid_pointer;
-    Runtime &rt = Runtime::get();
-    // keep y on the device between the two steps when the caller's y is a host array
     aoclsparse_status st = mv_t<T>(op, &alpha, A, descr, x, &beta, y, vt);
     if(st != aoclsparse_status_success)
         return st;
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    const aoclsparse_int                  n = std::min(A->m, A->n);
-    const bool xdev = rt.is_device_pointer(x), ydev = rt.is_device_pointer(y), ddev = rt.is_device_pointer(d);
-    Arg        ax, ay;
-    st = ax.in(rt, 3, x, sizeof(T) * (size_t)n, xdev, true);
-    if(st == aoclsparse_status_success)
-        st = ay.in(rt, 4, y, sizeof(T) * (size_t)n, ydev, true);
-    void *part = nullptr, *dd = d;
-    if(st == aoclsparse_status_success)
-        st = rt.staging(6, sizeof(T) * 1024, &part);
-    if(st == aoclsparse_status_success && !ddev)
-        st = rt.staging(7, sizeof(T), &dd);
-    if(st != aoclsparse_status_success)
-        return st;
-    st = launch_dot<T>(rt.stream(), n, static_cast<const T *>(ax.dev), static_cast<const T *>(ay.dev),
-                       static_cast<T *>(part), static_cast<T *>(dd));
-    if(st != aoclsparse_status_success)
-        return st;
-    if(!ddev)
-    {
-        MI355_HIP_TRY(hipMemcpyAsync(d, dd, sizeof(T), hipMemcpyDeviceToHost, rt.stream()));
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    }
-    return aoclsparse_status_success;
+    // (the product has finished: a host y is in the caller's memory again and is staged once more for the dot)
+    CallScope            cs(CallScope::Always);
+    const aoclsparse_int n  = std::min(A->m, A->n);
+    const T             *dx = cs.in(STAGE_MV_X, x, sizeof(T) * (size_t)n);
+    const T             *dy = cs.in(STAGE_MV_Y, y, sizeof(T) * (size_t)n);
+    T                   *part = static_cast<T *>(cs.scratch(STAGE_DOTMV_PART, sizeof(T) * 1024));
+    T                   *dd = cs.out(STAGE_DOTMV_D, d, sizeof(T));
+    if(!cs.ok())
+        return cs.st;
+    st = launch_dot<T>(cs.s, n, dx, dy, part, dd);
+    return st == aoclsparse_status_success ? cs.finish() : st;
 }
 
 } // namespace

@@ -85,36 +85,6 @@ bool repeats_columns(aoclsparse_matrix A)
     return r != 0;
 }
 
-// C (and B) of one call in memory the GPU can address
-template <typename T>
-struct DenseArg
-{
-    T     *host = nullptr, *dev = nullptr;
-    size_t bytes = 0;
-    bool   staged = false;
-    aoclsparse_status in(Runtime &rt, int slot, const T *p, size_t nbytes)
-    {
-        host = const_cast<T *>(p), dev = host, bytes = nbytes;
-        if(rt.is_device_pointer(p))
-            return aoclsparse_status_success;
-        void             *d  = nullptr;
-        aoclsparse_status st = rt.staging(slot, nbytes, &d);
-        if(st != aoclsparse_status_success)
-            return st;
-        dev = static_cast<T *>(d), staged = true;
-        MI355_HIP_TRY(hipMemcpyAsync(dev, host, nbytes, hipMemcpyHostToDevice, rt.stream()));
-        return aoclsparse_status_success;
-    }
-    aoclsparse_status out(Runtime &rt)
-    {
-        if(!staged)
-            return aoclsparse_status_success;
-        MI355_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, rt.stream()));
-        MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-        return aoclsparse_status_success;
-    }
-};
-
 template <typename T>
 aoclsparse_status syrkd_t(aoclsparse_operation op, const aoclsparse_matrix A, T alpha, T beta, T *C, aoclsparse_order layout,
                           aoclsparse_int ldc, aoclsparse_matrix_data_type vt)
@@ -147,22 +117,16 @@ aoclsparse_status syrkd_t(aoclsparse_operation op, const aoclsparse_matrix A, T 
     if(m_c == 0)
         return aoclsparse_status_success;
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::unique_lock<std::recursive_mutex> sl(rt.stage_lock, std::defer_lock);
-    if(rt.pointer_mode != aoclsparse_mi355_pointer_device)
-        sl.lock();
-    const bool  rowmaj = layout == aoclsparse_order_row;
-    DenseArg<T> c;
-    st = c.in(rt, 4, C, sizeof(T) * (size_t)m_c * (size_t)ldc);
-    if(st != aoclsparse_status_success)
-        return st;
+    CallScope  cs(CallScope::Conditional);
+    const bool rowmaj = layout == aoclsparse_order_row;
+    T *const   dC     = cs.inout(STAGE_DENSE_C, C, sizeof(T) * (size_t)m_c * (size_t)ldc, true); // the whole m_c x ldc block
+    if(!cs.ok())
+        return cs.st;
+    aoclsparse_status st = aoclsparse_status_success;
     // :265-313: the upper triangle is scaled before the quick return (beta == 1 leaves every value as it is)
     if(!eq(beta, 1.0))
     {
-        st = launch_sy_scale_upper<T>(rt.stream(), c.dev, m_c, ldc, rowmaj, beta, eq(beta, 0.0));
+        st = launch_sy_scale_upper<T>(cs.s, dC, m_c, ldc, rowmaj, beta, eq(beta, 0.0));
         if(st != aoclsparse_status_success)
             return st;
     }
@@ -184,14 +148,14 @@ aoclsparse_status syrkd_t(aoclsparse_operation op, const aoclsparse_matrix A, T 
         if(none && A->sort != SORT_FULL)
             flags |= SY_ORDERED;
         std::shared_lock<std::shared_mutex> ra(A->guard);
-        st = launch_syrkd<T>(rt.stream(), m_c, x->base, x->ptr.as<aoclsparse_int>(), x->ind.as<aoclsparse_int>(),
+        st = launch_syrkd<T>(cs.s, m_c, x->base, x->ptr.as<aoclsparse_int>(), x->ind.as<aoclsparse_int>(),
                              x->val.as<T>(), is_cplx_v<T> && !none, w->base, w->ptr.as<aoclsparse_int>(),
-                             w->ind.as<aoclsparse_int>(), w->val.as<T>(), is_cplx_v<T> && none, alpha, c.dev,
+                             w->ind.as<aoclsparse_int>(), w->val.as<T>(), is_cplx_v<T> && none, alpha, dC,
                              rowmaj ? (long long)ldc : 1LL, rowmaj ? 1LL : (long long)ldc, flags);
         if(st != aoclsparse_status_success)
             return st;
     }
-    return c.out(rt);
+    return cs.finish();
 }
 
 template <typename T>
@@ -232,32 +196,25 @@ aoclsparse_status syprd_t(aoclsparse_operation op, const aoclsparse_matrix A, co
     if(m_c == 0)
         return aoclsparse_status_success;
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    // (always: the scratch is a staging slot)
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    const bool                            rowmaj = orderC == aoclsparse_order_row;
-    DenseArg<T>                           c;
-    st = c.in(rt, 4, C, sizeof(T) * (size_t)m_c * (size_t)ldc);
-    if(st != aoclsparse_status_success)
-        return st;
+    CallScope  cs(CallScope::Always); // (always: the scratch is a staging slot)
+    const bool rowmaj = orderC == aoclsparse_order_row;
+    T *const   dC     = cs.inout(STAGE_DENSE_C, C, sizeof(T) * (size_t)m_c * (size_t)ldc, true);
+    if(!cs.ok())
+        return cs.st;
+    aoclsparse_status st = aoclsparse_status_success;
     if(eq(alpha, 0.0) || A->nnz == 0 || n_in == 0)
     {
         // :93-96 / :204-207: only the upper triangle is scaled (no entry: every chain is empty)
-        st = launch_sy_scale_upper<T>(rt.stream(), c.dev, m_c, ldc, rowmaj, beta, eq(beta, 0.0));
+        st = launch_sy_scale_upper<T>(cs.s, dC, m_c, ldc, rowmaj, beta, eq(beta, 0.0));
         if(st != aoclsparse_status_success)
             return st;
-        return c.out(rt);
+        return cs.finish();
     }
-    DenseArg<T> b;
-    st = b.in(rt, 5, B, sizeof(T) * (size_t)n_in * (size_t)ldb);
-    if(st != aoclsparse_status_success)
-        return st;
-    void *scratch = nullptr;
-    st            = rt.staging(6, sizeof(T) * (size_t)m_c * (size_t)n_in, &scratch);
-    if(st != aoclsparse_status_success)
+    const T *dB = cs.in(STAGE_SYPRD_B, B, sizeof(T) * (size_t)n_in * (size_t)ldb);
+    if(!cs.ok())
+        return cs.st;
+    T *scratch = static_cast<T *>(cs.scratch(STAGE_SYPRD_SCRATCH, sizeof(T) * (size_t)m_c * (size_t)n_in));
+    if(!cs.ok())
         return aoclsparse_status_memory_error; // :101-109
     // :415-575: op = none runs on the CSR, op = T / H on its stable transpose; CONJLEFT (complex, op = H) conjugates the
     // left factor, otherwise the right one is conjugated
@@ -269,14 +226,14 @@ aoclsparse_status syprd_t(aoclsparse_operation op, const aoclsparse_matrix A, co
     const bool conjleft = is_cplx_v<T> && op == aoclsparse_operation_conjugate_transpose;
     {
         std::shared_lock<std::shared_mutex> ra(A->guard);
-        st = launch_syprd<T>(rt.stream(), m_c, n_in, dm->base, dm->ptr.as<aoclsparse_int>(), dm->ind.as<aoclsparse_int>(),
-                             dm->val.as<T>(), conjleft, is_cplx_v<T> && !conjleft, alpha, b.dev, ldb, rowmaj,
-                             static_cast<T *>(scratch), beta, eq(beta, 0.0) ? 0 : eq(beta, 1.0) ? 1 : 2, c.dev,
+        st = launch_syprd<T>(cs.s, m_c, n_in, dm->base, dm->ptr.as<aoclsparse_int>(), dm->ind.as<aoclsparse_int>(),
+                             dm->val.as<T>(), conjleft, is_cplx_v<T> && !conjleft, alpha, dB, ldb, rowmaj,
+                             scratch, beta, eq(beta, 0.0) ? 0 : eq(beta, 1.0) ? 1 : 2, dC,
                              rowmaj ? (long long)ldc : 1LL, rowmaj ? 1LL : (long long)ldc);
     }
     if(st != aoclsparse_status_success)
         return st;
-    return c.out(rt);
+    return cs.finish();
 }
 
 inline cfloat  cv(aoclsparse_float_complex v) { return cfloat(v.real, v.imag); }

@@ -239,7 +239,7 @@ void searchable(const HostOp<T> &a, HostOp<T> &s)
 
 // host CSR -> three staging slots starting at `slot`
 template <typename T>
-aoclsparse_status send(Runtime &rt, const HostOp<T> &o, int slot, SpgDevOp &dv)
+aoclsparse_status send(Runtime &rt, const HostOp<T> &o, StageSlot slot, SpgDevOp &dv)
 {
     void             *pp = nullptr, *pi = nullptr, *pv = nullptr;
     const size_t      nz = (size_t)std::max<aoclsparse_int>(o.nnz, 1);
@@ -261,7 +261,7 @@ aoclsparse_status send(Runtime &rt, const HostOp<T> &o, int slot, SpgDevOp &dv)
 // the stored CSR of a handle on the device: the handle's own resident copy when the stored arrays are its user arrays
 // (made here when no product has made it yet, as sp2m does), staging slots otherwise (the CSC arrays)
 template <typename T>
-aoclsparse_status send_stored(Runtime &rt, const aoclsparse_matrix A, const HostOp<T> &s, int slot, SpgDevOp &dv)
+aoclsparse_status send_stored(Runtime &rt, const aoclsparse_matrix A, const HostOp<T> &s, StageSlot slot, SpgDevOp &dv)
 {
     if(s.ptr != A->user.ptr)
         return send(rt, s, slot, dv);
@@ -397,11 +397,11 @@ aoclsparse_status syrk_t(aoclsparse_operation op, const aoclsparse_matrix A, aoc
     if(A->m == 0 || A->n == 0 || A->nnz == 0) // :206-214
         return new_csr_result(C, m_c, m_c, 0, vt, nullptr, base);
 
-    Runtime          &rt = Runtime::get();
-    aoclsparse_status st = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    CallScope cs(CallScope::Always); // the SPG_SLOT_* slots are shared
+    if(!cs.ok())
+        return cs.st;
+    Runtime          &rt = cs.rt;
+    aoclsparse_status st = aoclsparse_status_success;
     try
     {
         hipStream_t s = rt.stream();
@@ -556,12 +556,11 @@ aoclsparse_status sypr_t(aoclsparse_operation op, const aoclsparse_matrix A, con
     if(!B->opt || !B->opt->idiag)
         return aoclsparse_status_internal_error; // :791
 
-    Runtime &rt = Runtime::get();
-    st          = rt.init();
-    if(st != aoclsparse_status_success)
-        return st;
-    const bool                            count = request != aoclsparse_stage_finalize;
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
+    CallScope cs(CallScope::Always); // the SPG_SLOT_* slots are shared
+    if(!cs.ok())
+        return cs.st;
+    Runtime   &rt    = cs.rt;
+    const bool count = request != aoclsparse_stage_finalize;
     try
     {
         hipStream_t s = rt.stream();

@@ -184,8 +184,8 @@ static aoclsparse_status device_transpose_run(hipStream_t s, aoclsparse_int m, a
                 (void)hipGetLastError();
         }
     } drain{s};
-    MI355_TRY(rt.staging(40, sizeof(int) * (size_t)n, &p_cnt));
-    MI355_TRY(rt.staging(41, 256, &p_small));
+    MI355_TRY(rt.staging(STAGE_TR_CNT, sizeof(int) * (size_t)n, &p_cnt));
+    MI355_TRY(rt.staging(STAGE_TR_SMALL, 256, &p_small));
     MI355_HIP_TRY(hipMemsetAsync(p_cnt, 0, sizeof(int) * (size_t)n, s));
     MI355_HIP_TRY(hipMemsetAsync(p_small, 0, 256, s));
     int *const          cnt_p   = static_cast<int *>(p_cnt);
@@ -206,9 +206,9 @@ static aoclsparse_status device_transpose_run(hipStream_t s, aoclsparse_int m, a
     MI355_TRY(tptr_b.alloc(sizeof(aoclsparse_int) * ((size_t)n + 1)));
     MI355_TRY(tind_b.alloc(sizeof(aoclsparse_int) * (size_t)nnz));
     MI355_TRY(tval_b.alloc(vsize * (size_t)nnz));
-    MI355_TRY(rt.staging(42, sizeof(int) * (size_t)n, &p_cursor));
-    MI355_TRY(rt.staging(43, sizeof(int) * (size_t)nnz, &p_tpos));
-    MI355_TRY(rt.staging(44, spg_scan_scratch_bytes(n), &p_scan));
+    MI355_TRY(rt.staging(STAGE_TR_CURSOR, sizeof(int) * (size_t)n, &p_cursor));
+    MI355_TRY(rt.staging(STAGE_TR_TPOS, sizeof(int) * (size_t)nnz, &p_tpos));
+    MI355_TRY(rt.staging(STAGE_TR_SCAN, spg_scan_scratch_bytes(n), &p_scan));
     MI355_HIP_TRY(hipMemsetAsync(p_cursor, 0, sizeof(int) * (size_t)n, s));
     int *const cursor_p = static_cast<int *>(p_cursor), *const tpos_p = static_cast<int *>(p_tpos);
     aoclsparse_int *tptr = tptr_b.as<aoclsparse_int>(), *tind = tind_b.as<aoclsparse_int>();
@@ -225,7 +225,7 @@ static aoclsparse_status device_transpose_run(hipStream_t s, aoclsparse_int m, a
         bounds[0] = 0;
         for(int b = 0; b < SPGEMM_BINS; b++)
             bounds[b + 1] = bounds[b] + (aoclsparse_int)hist[b];
-        MI355_TRY(rt.staging(45, sizeof(aoclsparse_int) * (size_t)n, &p_order));
+        MI355_TRY(rt.staging(STAGE_TR_ORDER, sizeof(aoclsparse_int) * (size_t)n, &p_order));
         aoclsparse_int *const order_p = static_cast<aoclsparse_int *>(p_order);
         MI355_TRY(launch_spg_order(s, n, cnt_p, false, bounds, d_cursor, order_p));
         hipLaunchKernelGGL(tr_sort_wave_kernel, dim3((unsigned)nmid), dim3(64), 0, s, nmid, order_p + bounds[1], tptr, tpos_p, tind);

@@ -67,9 +67,10 @@ aoclsparse_status solve_core(aoclsparse_operation trans, T alpha, aoclsparse_mat
         }
     }
     // solves on one handle share its workspaces: serialise their enqueue (kernels are stream-ordered)
-    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
-    std::shared_lock<std::shared_mutex>   r(A->guard);
-    const TrsvChoice                      choice = resolve(); // what runs, now that the plan is complete
+    CallScope cs(CallScope::Always);
+    MI355_TRY(cs.st);
+    std::shared_lock<std::shared_mutex> r(A->guard);
+    const TrsvChoice                    choice = resolve(); // what runs, now that the plan is complete
     // the handle's own timeout word (pinned, device-mapped): allocated once per handle
     if(!is_cplx && !A->trsv_timeout_dev)
     {
@@ -109,27 +110,12 @@ aoclsparse_status solve_core(aoclsparse_operation trans, T alpha, aoclsparse_mat
     if(st != aoclsparse_status_success)
         return st;
 
-    const bool bdev = rt.is_device_pointer(b), xdev = rt.is_device_pointer(x);
-    const T   *db   = b;
-    T         *dx   = x;
-    void      *tmp  = nullptr;
-    if(!bdev)
-    {
-        st = rt.staging(0, sizeof(T) * span_b, &tmp);
-        if(st != aoclsparse_status_success)
-            return st;
-        MI355_HIP_TRY(hipMemcpyAsync(tmp, b, sizeof(T) * span_b, hipMemcpyHostToDevice, rt.stream()));
-        db = static_cast<const T *>(tmp);
-    }
-    if(!xdev)
-    {
-        st = rt.staging(2, sizeof(T) * span_x, &tmp);
-        if(st != aoclsparse_status_success)
-            return st;
-        if(x_partial) // strided / padded x: the untouched slots must survive the round trip
-            MI355_HIP_TRY(hipMemcpyAsync(tmp, x, sizeof(T) * span_x, hipMemcpyHostToDevice, rt.stream()));
-        dx = static_cast<T *>(tmp);
-    }
+    // the scope serves the views only: when to copy x back and synchronise also depends on the timeout word, below
+    // (strided / padded x goes in: the untouched slots must survive the round trip)
+    const T *db = cs.in(STAGE_TRSV_B, b, sizeof(T) * span_b);
+    T       *dx = cs.inout(STAGE_TRSV_X, x, sizeof(T) * span_x, x_partial, /*copy_back=*/false);
+    MI355_TRY(cs.st);
+    const bool xdev = dx == x;
     if constexpr(is_cplx)
         st = launch_ctrsv(rt.stream(), unit, conj, alpha, m, plan, A->dev_diag.as<T>(), db, dx, A->trsv_xp.as<T>(), nrhs,
                           b_off, incb, x_off, incx);
