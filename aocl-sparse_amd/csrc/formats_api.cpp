@@ -11,7 +11,7 @@
 // differs from the reference in ONE respect: the reference keeps the CSC arrays as "the CSR of A^T" and flips
 // the operation at dispatch time; here the CSR of A is built once at creation (counting sort, owned by the
 // handle) so that every executor of the path runs unchanged, and export_?csc hands back the caller's arrays.
-#include "internal.hpp"
+#include "spg_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -92,20 +92,7 @@ aoclsparse_status csr2csc(aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz
             (void)hipGetLastError();
         }
     }
-    std::fill(optr, optr + n + 1, 0);
-    for(aoclsparse_int i = 0; i < nnz; i++)
-        ++optr[ind[i] - base_in + 1];
-    for(aoclsparse_int i = 0; i < n; i++)
-        optr[i + 1] += optr[i];
-    for(aoclsparse_int i = 0; i < m; i++)
-        for(aoclsparse_int j = ptr[i] - base_in; j < ptr[i + 1] - base_in; j++)
-        {
-            const aoclsparse_int c = ind[j] - base_in, o = optr[c]++;
-            oind[o] = i + base_out, oval[o] = val[j];
-        }
-    for(aoclsparse_int i = n; i > 0; i--)
-        optr[i] = optr[i - 1] + base_out;
-    optr[0] = base_out;
+    host_transpose(m, n, nnz, base_in, base_out, ptr, ind, val, optr, oind, oval);
     return aoclsparse_status_success;
 }
 

@@ -733,6 +733,7 @@ struct HostCsr
 // (tools/history/pagefault_probe.cpp on the GPU box).  2 MB-aligned + MADV_HUGEPAGE from 4 MB up, plain malloc below; released with free().
 void *host_result_alloc(size_t bytes);
 void  host_result_touch(void *p, size_t bytes); // first touch by several threads (no-op for small arrays)
+constexpr size_t HOST_RESULT_BIG = (size_t)4 << 20; // ... that is, for fewer bytes than this; huge pages from here up
 
 // A general CSR derived from the clean CSR so that the general kernels can serve a symmetric or
 // triangular descriptor: key = (type, fill, diag, transposed).
@@ -909,7 +910,7 @@ enum StageSlot : int
     STAGE_HYB_YTMP, // ellthybmv: the long rows' y across the ELL pass
     STAGE_BLK_VALOFF = STAGE_HYB_YTMP,
     STAGE_BLK_PARTS,
-    // -- 16-39: one first-touch product D = X * Y (sp2m, syrk, sypr; SpgProduct in sp2m_api.cpp).  The caller holds the stage
+    // -- 16-39: one first-touch product D = X * Y (sp2m, syrk, sypr; SpgProduct in spg_product.cpp).  The caller holds the stage
     // lock from analyse() to the last pass.
     SPG_SLOT_XP, // operands that no handle keeps resident: X (ptr, ind, val), then Y
     SPG_SLOT_XI,
@@ -1452,12 +1453,12 @@ template <typename T>
 aoclsparse_status launch_syprd(hipStream_t s, aoclsparse_int mc, aoclsparse_int nin, int base, const aoclsparse_int *ptr,
                                const aoclsparse_int *ind, const T *val, bool conj_1, bool conj_2, T alpha, const T *B,
                                long long ldb, bool rowmajor, T *scratch, T beta, int beta_mode, T *C, long long rs, long long cs);
-// a new handle that owns host CSR arrays (sp2m_api.cpp); row_ptr copied when given, else filled with `base`
+// a new handle that owns host CSR arrays (spg_product.cpp); row_ptr copied when given, else filled with `base`
 aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz,
                                  aoclsparse_matrix_data_type vt, const aoclsparse_int *row_ptr,
                                  aoclsparse_index_base base = aoclsparse_index_base_zero);
 
-// ---- one first-touch product D = X * Y on the device (sp2m_api.cpp; kernels: spgemm_kernels.hip) ----------------------------------
+// ---- one first-touch product D = X * Y on the device (spg_product.cpp; kernels: spgemm_kernels.hip; host side: spg_host.hpp) ------
 // What aoclsparse_sp2m, aoclsparse_syrk and aoclsparse_sypr share: the upper bound of every row's list, the bins, the count pass
 // with its prefix sum and the fill pass.  X and Y are CSR arrays in HBM (any base), D is 0-based.  The SPG_SLOT_* staging slots (StageSlot) of the
 // runtime belong to these three entry points; the caller holds the runtime's stage lock from analyse() to the last pass.

@@ -2,7 +2,7 @@
 //
 // Behaviour follows the reference (cited per function, paths relative to
 // /root/reference/library/src); the data layout behind the opaque handles is our own.
-#include "internal.hpp"
+#include "spg_host.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -375,28 +375,6 @@ aoclsparse_status csr_optimize(aoclsparse_matrix A)
     return aoclsparse_status_success;
 }
 
-// ---- transpose of the user CSR, conversion/aoclsparse_convert.hpp:552-655 (counting sort) ---------
-template <typename T>
-static void transpose_into(const HostCsr &u, aoclsparse_int nnz, HostCsr &t)
-{
-    const aoclsparse_int m = u.m, n = u.n, b = u.base;
-    const T             *uv = static_cast<const T *>(u.val);
-    T                   *tv = static_cast<T *>(t.val);
-    std::fill(t.ptr, t.ptr + n + 1, 0);
-    for(aoclsparse_int p = 0; p < nnz; p++)
-        t.ptr[u.ind[p] - b + 1]++;
-    for(aoclsparse_int j = 0; j < n; j++)
-        t.ptr[j + 1] += t.ptr[j];
-    std::vector<aoclsparse_int> next(t.ptr, t.ptr + n);
-    for(aoclsparse_int i = 0; i < m; i++)
-        for(aoclsparse_int p = u.ptr[i] - b; p < u.ptr[i + 1] - b; p++)
-        {
-            const aoclsparse_int q = next[u.ind[p] - b]++;
-            t.ind[q]               = i;
-            tv[q]                  = uv[p];
-        }
-}
-
 // from this many entries on the handles' transposes are sorted on the device
 constexpr aoclsparse_int DEVICE_TRANSPOSE_MIN_NNZ = 1 << 20;
 
@@ -462,7 +440,10 @@ aoclsparse_status build_transpose(aoclsparse_matrix A)
         }
         if(!on_device)
             dispatch_value_type(A->val_type, [&](auto tag) {
-                transpose_into<decltype(tag)>(A->user, A->nnz, *t);
+                using T          = decltype(tag); // (the counting sort of spg_host.hpp, 0-based out, over the entries the rows span)
+                const HostCsr &u = A->user;
+                host_transpose<T>(u.m, u.n, u.ptr[u.m] - u.base, u.base, 0, u.ptr, u.ind, static_cast<const T *>(u.val), t->ptr, t->ind,
+                                  static_cast<T *>(t->val));
                 return 0;
             });
         A->trans = std::move(t);

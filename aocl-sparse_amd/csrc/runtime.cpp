@@ -105,7 +105,7 @@ HostCsr::~HostCsr()
     delete[] iurow;
 }
 
-constexpr size_t HOST_RESULT_BIG = (size_t)4 << 20, HOST_RESULT_PAGE = (size_t)2 << 20;
+constexpr size_t HOST_RESULT_PAGE = (size_t)2 << 20; // (HOST_RESULT_BIG: internal.hpp)
 
 void *host_result_alloc(size_t bytes)
 {

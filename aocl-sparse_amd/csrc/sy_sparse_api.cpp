@@ -22,7 +22,7 @@
 // Rows that repeat a column: the reference's walk pushes such a row back onto the list it is walking and loses the rest
 // of the row, and its dense row keeps the last repeat only.  Neither is reproduced: every stored entry is its own
 // element and the complete product is returned (walk_order, searchable).  Such inputs are outside the parity contract.
-#include "internal.hpp"
+#include "spg_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -55,57 +55,15 @@ T conj_of(T v)
         return v;
 }
 
-// a host CSR: a view (of a handle's arrays) or owned
-template <typename T>
-struct HostOp
-{
-    aoclsparse_int              m = 0, n = 0, nnz = 0, base = 0;
-    const aoclsparse_int       *ptr = nullptr, *ind = nullptr;
-    const T                    *val = nullptr;
-    std::vector<aoclsparse_int> optr, oind;
-    std::vector<T>              oval;
-    void own()
-    {
-        ptr = optr.data(), ind = oind.data(), val = oval.data();
-    }
-};
-
 // the CSR the reference holds for the handle (auxiliary.cpp:1057-1066): the caller's arrays; for a handle made from CSC
 // they describe A^T (n x m)
 template <typename T>
-void stored_of(const aoclsparse_matrix A, HostOp<T> &s)
+void stored_of(const aoclsparse_matrix A, HostCsrOp<T> &s)
 {
     const bool csc = A->csc_ptr != nullptr;
     s.m = csc ? A->n : A->m, s.n = csc ? A->m : A->n, s.nnz = A->nnz, s.base = A->base;
     s.ptr = csc ? A->csc_ptr : A->user.ptr, s.ind = csc ? A->csc_ind : A->user.ind;
     s.val = static_cast<const T *>(csc ? A->csc_val : A->user.val);
-}
-
-// aoclsparse_csr2csc_template with equal bases (conversion/aoclsparse_convert.hpp:552-655): stable counting sort
-template <typename T>
-void transpose_of(const HostOp<T> &a, HostOp<T> &t)
-{
-    const aoclsparse_int b = a.base;
-    t.m = a.n, t.n = a.m, t.nnz = a.nnz, t.base = b;
-    t.optr.assign((size_t)t.m + 1, 0);
-    t.oind.resize((size_t)std::max(a.nnz, 1));
-    t.oval.resize((size_t)std::max(a.nnz, 1));
-    for(aoclsparse_int i = 0; i < a.m; i++)
-        for(aoclsparse_int p = a.ptr[i] - b; p < a.ptr[i + 1] - b; p++)
-            t.optr[a.ind[p] - b + 1]++;
-    for(aoclsparse_int j = 0; j < t.m; j++)
-        t.optr[j + 1] += t.optr[j];
-    std::vector<aoclsparse_int> next(t.optr.begin(), t.optr.end() - 1);
-    for(aoclsparse_int i = 0; i < a.m; i++)
-        for(aoclsparse_int p = a.ptr[i] - b; p < a.ptr[i + 1] - b; p++)
-        {
-            const aoclsparse_int q = next[a.ind[p] - b]++;
-            t.oind[q]              = i + b;
-            t.oval[q]              = a.val[p];
-        }
-    for(aoclsparse_int j = 0; j <= t.m; j++)
-        t.optr[j] += b;
-    t.own();
 }
 
 // oftrans (sypr.hpp:120-243) run to its end.  Of every row r of an m x k CSR with sorted rows the entries at the 0-based
@@ -152,7 +110,7 @@ void walk_order(aoclsparse_int m, aoclsparse_int k, First first, Last last, cons
 
 // "L^T in walk order": the left operand of sp2m_online_atb (sypr.hpp:470-496) as a 0-based k x m CSR
 template <typename T>
-void walked_transpose(const HostOp<T> &l, HostOp<T> &w)
+void walked_transpose(const HostCsrOp<T> &l, HostCsrOp<T> &w)
 {
     const aoclsparse_int        b = l.base;
     std::vector<aoclsparse_int> pos;
@@ -170,7 +128,7 @@ void walked_transpose(const HostOp<T> &l, HostOp<T> &w)
 // the left operand of sp2m_online_symab (sypr.hpp:301-378) as a 0-based m x m CSR: row i = the stored triangle's part of
 // row i of B, diagonal included, then the other half from the walk over the strict triangle, conjugated
 template <typename T>
-void symmetrised(const HostCsr &o, bool lower, HostOp<T> &sb)
+void symmetrised(const HostCsr &o, bool lower, HostCsrOp<T> &sb)
 {
     const aoclsparse_int m = o.m, b = o.base;
     const T             *v = static_cast<const T *>(o.val);
@@ -203,7 +161,7 @@ void symmetrised(const HostCsr &o, bool lower, HostOp<T> &sb)
 // the last repeat only, which is the product of nothing.  Without repeats -- the inputs of the parity contract -- the
 // two are the same.
 template <typename T>
-void searchable(const HostOp<T> &a, HostOp<T> &s)
+void searchable(const HostCsrOp<T> &a, HostCsrOp<T> &s)
 {
     const aoclsparse_int b = a.base;
     s.m = a.m, s.n = a.n, s.base = 0;
@@ -237,77 +195,30 @@ void searchable(const HostOp<T> &a, HostOp<T> &s)
     s.own();
 }
 
-// host CSR -> three staging slots starting at `slot`
-template <typename T>
-aoclsparse_status send(Runtime &rt, const HostOp<T> &o, StageSlot slot, SpgDevOp &dv)
-{
-    void             *pp = nullptr, *pi = nullptr, *pv = nullptr;
-    const size_t      nz = (size_t)std::max<aoclsparse_int>(o.nnz, 1);
-    aoclsparse_status rc = rt.staging(slot, sizeof(aoclsparse_int) * ((size_t)o.m + 1), &pp);
-    if(rc == aoclsparse_status_success)
-        rc = rt.staging(slot + 1, sizeof(aoclsparse_int) * nz, &pi);
-    if(rc == aoclsparse_status_success)
-        rc = rt.staging(slot + 2, sizeof(T) * nz, &pv);
-    if(rc == aoclsparse_status_success)
-        rc = rt.h2d(pp, o.ptr, sizeof(aoclsparse_int) * ((size_t)o.m + 1));
-    if(rc == aoclsparse_status_success)
-        rc = rt.h2d(pi, o.ind, sizeof(aoclsparse_int) * (size_t)o.nnz);
-    if(rc == aoclsparse_status_success)
-        rc = rt.h2d(pv, o.val, sizeof(T) * (size_t)o.nnz);
-    dv = SpgDevOp{static_cast<const aoclsparse_int *>(pp), static_cast<const aoclsparse_int *>(pi), pv, (int)o.base};
-    return rc;
-}
-
-// the stored CSR of a handle on the device: the handle's own resident copy when the stored arrays are its user arrays
-// (made here when no product has made it yet, as sp2m does), staging slots otherwise (the CSC arrays)
-template <typename T>
-aoclsparse_status send_stored(Runtime &rt, const aoclsparse_matrix A, const HostOp<T> &s, StageSlot slot, SpgDevOp &dv)
-{
-    if(s.ptr != A->user.ptr)
-        return send(rt, s, slot, dv);
-    std::unique_lock<std::shared_mutex> w(A->guard);
-    DeviceCsr                          &dc = A->dev_user;
-    if(!dc.valid)
-    {
-        const aoclsparse_status rc = upload_csr(A->user, sizeof(T), dc);
-        if(rc != aoclsparse_status_success)
-            return rc;
-    }
-    dv = SpgDevOp{dc.ptr.as<aoclsparse_int>(), dc.ind.as<aoclsparse_int>(), dc.val.ptr, (int)s.base};
-    return aoclsparse_status_success;
-}
-
-// The count pass, the fill pass or both of `prod` (an m_c x m_c upper triangle), into a handle in index base `base`.
-// count: creates *C with its row pointer and allocated ind / val.  fill without count: fills the *C it is given, whose
-// row pointer is checked against this product on the device before anything of *C is written.
+// The count pass, the fill pass or both of `prod` (an m_c x m_c upper triangle), into a handle in index base `base`, through
+// SPG_SLOT_CP / CI / CV.  count: creates *C with its row pointer and allocated ind / val.  fill without count: fills the *C it is
+// given, whose row pointer is checked against this product on the device before anything of *C is written.
 template <typename T>
 aoclsparse_status product_to_handle(SpgProduct<T> &prod, bool count, bool fill, aoclsparse_matrix *C,
                                     aoclsparse_matrix_data_type vt, aoclsparse_index_base base)
 {
     Runtime             &rt = prod.rt;
-    hipStream_t          s  = rt.stream();
     const aoclsparse_int m  = prod.m;
-    void                *pp = nullptr;
+    void                *pp = nullptr, *pi = nullptr, *pv = nullptr;
     aoclsparse_status    st = rt.staging(SPG_SLOT_CP, sizeof(aoclsparse_int) * ((size_t)m + 1), &pp);
     if(st != aoclsparse_status_success)
         return st;
     aoclsparse_int *d_ptr = static_cast<aoclsparse_int *>(pp);
     if(count)
     {
-        long long *d_total = nullptr, total = 0;
+        long long                  *d_total = nullptr;
+        aoclsparse_int              total   = 0;
+        std::vector<aoclsparse_int> cptr;
         st = prod.count(d_ptr, &d_total);
-        if(st != aoclsparse_status_success)
-            return st;
-        std::vector<aoclsparse_int> cptr((size_t)m + 1);
-        MI355_HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(long long), hipMemcpyDeviceToHost, s));
-        MI355_HIP_TRY(hipMemcpyAsync(cptr.data(), d_ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), hipMemcpyDeviceToHost, s));
-        MI355_HIP_TRY(hipStreamSynchronize(s));
-        if(total > 2147483647LL - base) // sypr.hpp:391-396, :512-517
-            return aoclsparse_status_invalid_size;
-        if(base)
-            for(aoclsparse_int &p : cptr)
-                p += base; // sypr.hpp:518-525
-        st = new_csr_result(C, m, m, (aoclsparse_int)total, vt, cptr.data(), base);
+        if(st == aoclsparse_status_success)
+            st = spg_count_to_host(rt, d_total, d_ptr, m, base, &cptr, total); // sypr.hpp:391-396, :512-525
+        if(st == aoclsparse_status_success)
+            st = new_csr_result(C, m, m, total, vt, cptr.data(), base);
         if(st != aoclsparse_status_success)
             return st;
     }
@@ -315,49 +226,74 @@ aoclsparse_status product_to_handle(SpgProduct<T> &prod, bool count, bool fill, 
         return aoclsparse_status_success;
     _aoclsparse_matrix  *c     = *C;
     const aoclsparse_int nnz_c = c->user.ptr[m] - base;
-    if(!count)
-    {
-        std::vector<aoclsparse_int> cptr(c->user.ptr, c->user.ptr + m + 1);
-        for(aoclsparse_int &p : cptr)
-            p -= base;
-        st = rt.h2d(d_ptr, cptr.data(), sizeof(aoclsparse_int) * ((size_t)m + 1));
-        if(st == aoclsparse_status_success)
-            MI355_HIP_TRY(hipStreamSynchronize(s)); // (cptr leaves scope)
-        if(st == aoclsparse_status_success)
-            st = prod.counts_from(d_ptr);
-        if(st != aoclsparse_status_success)
-            return st;
-    }
-    void        *pi = nullptr, *pv = nullptr;
+    const size_t         nz    = (size_t)std::max<aoclsparse_int>(nnz_c, 1);
+    st                         = rt.staging(SPG_SLOT_CI, sizeof(aoclsparse_int) * nz, &pi);
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_CV, sizeof(T) * nz, &pv);
+    if(st == aoclsparse_status_success) // (finalize: whatever the handle derived from an earlier fill mirrors the old values)
+        st = spg_fill_to_host<T>(prod, !count, d_ptr, static_cast<aoclsparse_int *>(pi), static_cast<T *>(pv), c->user, [c, count] {
+            if(!count)
+                (void)aoclsparse_mi355_invalidate(c);
+        });
+    if(st == aoclsparse_status_success && base)
+        for(aoclsparse_int p = 0; p < nnz_c; p++)
+            c->user.ind[p] += base;
+    return st;
+}
+
+// syrk's dense-row path (syrk.hpp:46-113) for a short, wide CSR S = A: count, scan, fill with aat_dense_row_kernel
+template <typename T>
+aoclsparse_status syrk_dense_rows(Runtime &rt, const aoclsparse_matrix A, const HostCsrOp<T> &S, aoclsparse_matrix *C,
+                                  aoclsparse_matrix_data_type vt)
+{
+    hipStream_t                 s = rt.stream();
+    const aoclsparse_int        m = S.m;
+    const aoclsparse_index_base base = A->base;
+    HostCsrOp<T>                Q;
+    searchable(S, Q);
+    SpgDevOp          da, dq;
+    aoclsparse_status st = spg_to_device(rt, A, S, SPG_SLOT_YP, true, da);
+    if(st == aoclsparse_status_success)
+        st = spg_send(rt, Q, SPG_SLOT_XP, true, dq);
+    void *p_cnt = nullptr, *p_scan = nullptr, *pp = nullptr, *pi = nullptr, *pv = nullptr;
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_CNT, sizeof(int) * (size_t)m, &p_cnt);
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_SCAN, spg_scan_scratch_bytes(m), &p_scan);
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_CP, sizeof(aoclsparse_int) * ((size_t)m + 1), &pp);
+    if(st != aoclsparse_status_success)
+        return st;
+    std::shared_lock<std::shared_mutex> ra(A->guard);
+    aoclsparse_int                     *d_ptr = static_cast<aoclsparse_int *>(pp);
+    const T *av = static_cast<const T *>(da.val), *qv = static_cast<const T *>(dq.val);
+    st = launch_aat_dense_row<T>(s, false, m, da.base, da.ptr, da.ind, av, dq.ptr, dq.ind, qv, nullptr, static_cast<int *>(p_cnt), base,
+                                 nullptr, nullptr);
+    long long                  *d_total = nullptr;
+    aoclsparse_int              nnz_c   = 0; // (at most m (m + 1) / 2 < 2^23)
+    std::vector<aoclsparse_int> cptr;
+    if(st == aoclsparse_status_success)
+        st = launch_spg_scan(s, m, static_cast<const int *>(p_cnt), d_ptr, static_cast<long long *>(p_scan), &d_total);
+    if(st == aoclsparse_status_success)
+        st = spg_count_to_host(rt, d_total, d_ptr, m, base, &cptr, nnz_c); // :89, :108
+    if(st == aoclsparse_status_success)
+        st = new_csr_result(C, m, m, nnz_c, vt, cptr.data(), base);
+    if(st != aoclsparse_status_success)
+        return st;
     const size_t nz = (size_t)std::max<aoclsparse_int>(nnz_c, 1);
     st              = rt.staging(SPG_SLOT_CI, sizeof(aoclsparse_int) * nz, &pi);
     if(st == aoclsparse_status_success)
         st = rt.staging(SPG_SLOT_CV, sizeof(T) * nz, &pv);
     if(st == aoclsparse_status_success)
-        st = prod.fill(d_ptr, static_cast<aoclsparse_int *>(pi), static_cast<T *>(pv));
-    if(st != aoclsparse_status_success)
-        return st;
-    unsigned int bad = 0;
-    MI355_HIP_TRY(hipMemcpyAsync(&bad, prod.bad_word(), sizeof(bad), hipMemcpyDeviceToHost, s));
-    if(!count)
-    {
-        // the row pointer is whatever the caller's handle holds: the verdict is read before *C is touched
-        MI355_HIP_TRY(hipStreamSynchronize(s));
-        if(bad)
-            return aoclsparse_status_invalid_value;
-        (void)aoclsparse_mi355_invalidate(c); // whatever the handle derived from an earlier fill mirrors the old values
-    }
-    host_result_touch(c->user.ind, sizeof(aoclsparse_int) * (size_t)nnz_c);
-    host_result_touch(c->user.val, sizeof(T) * (size_t)nnz_c);
-    MI355_HIP_TRY(hipMemcpyAsync(c->user.ind, pi, sizeof(aoclsparse_int) * (size_t)nnz_c, hipMemcpyDeviceToHost, s));
-    MI355_HIP_TRY(hipMemcpyAsync(c->user.val, pv, sizeof(T) * (size_t)nnz_c, hipMemcpyDeviceToHost, s));
-    MI355_HIP_TRY(hipStreamSynchronize(s));
-    if(bad)
-        return aoclsparse_status_invalid_value;
-    if(base)
-        for(aoclsparse_int p = 0; p < nnz_c; p++)
-            c->user.ind[p] += base;
-    return aoclsparse_status_success;
+        st = launch_aat_dense_row<T>(s, true, m, da.base, da.ptr, da.ind, av, dq.ptr, dq.ind, qv, d_ptr, nullptr, base,
+                                     static_cast<aoclsparse_int *>(pi), static_cast<T *>(pv));
+    if(st == aoclsparse_status_success)
+        st = rt.d2h((*C)->user.ind, pi, sizeof(aoclsparse_int) * (size_t)nnz_c);
+    if(st == aoclsparse_status_success)
+        st = rt.d2h((*C)->user.val, pv, sizeof(T) * (size_t)nnz_c);
+    if(st == aoclsparse_status_success)
+        st = map_hip_error(hipStreamSynchronize(s));
+    return st;
 }
 
 void drop(aoclsparse_matrix *C)
@@ -387,7 +323,7 @@ aoclsparse_status syrk_t(aoclsparse_operation op, const aoclsparse_matrix A, aoc
         return aoclsparse_status_not_implemented;
     // :150-173: the stored CSR is A (CSR handle) or A^T (CSC handle: the operation flips, the conjugation moves)
     const bool csc = A->csc_ptr != nullptr;
-    HostOp<T>  S;
+    HostCsrOp<T>  S;
     stored_of<T>(A, S);
     const bool eff_none = csc ? op != aoclsparse_operation_none : op == aoclsparse_operation_none;
     if(!eff_none && (csc ? A->csc_sort : A->sort) != SORT_FULL) // :175
@@ -404,77 +340,28 @@ aoclsparse_status syrk_t(aoclsparse_operation op, const aoclsparse_matrix A, aoc
     aoclsparse_status st = aoclsparse_status_success;
     try
     {
-        hipStream_t s = rt.stream();
         if(eff_none && !csc && m < 3000 && m < n && (long long)A->nnz <= 10LL * m) // :221
         {
-            // ---- dense-row path (:46-113): count, scan, fill ----
-            HostOp<T> Q;
-            searchable(S, Q);
-            SpgDevOp da, dq;
-            st = send_stored(rt, A, S, SPG_SLOT_YP, da);
-            if(st == aoclsparse_status_success)
-                st = send(rt, Q, SPG_SLOT_XP, dq);
-            void *p_cnt = nullptr, *p_scan = nullptr, *pp = nullptr, *pi = nullptr, *pv = nullptr;
-            if(st == aoclsparse_status_success)
-                st = rt.staging(SPG_SLOT_CNT, sizeof(int) * (size_t)m, &p_cnt);
-            if(st == aoclsparse_status_success)
-                st = rt.staging(SPG_SLOT_SCAN, spg_scan_scratch_bytes(m), &p_scan);
-            if(st == aoclsparse_status_success)
-                st = rt.staging(SPG_SLOT_CP, sizeof(aoclsparse_int) * ((size_t)m + 1), &pp);
-            if(st != aoclsparse_status_success)
-                return st;
-            std::shared_lock<std::shared_mutex> ra(A->guard);
-            aoclsparse_int                     *d_ptr = static_cast<aoclsparse_int *>(pp);
-            st = launch_aat_dense_row<T>(s, false, m, da.base, da.ptr, da.ind, static_cast<const T *>(da.val), dq.ptr, dq.ind,
-                                         static_cast<const T *>(dq.val), nullptr, static_cast<int *>(p_cnt), base, nullptr, nullptr);
-            long long *d_total = nullptr, total = 0;
-            if(st == aoclsparse_status_success)
-                st = launch_spg_scan(s, m, static_cast<const int *>(p_cnt), d_ptr, static_cast<long long *>(p_scan), &d_total);
-            if(st != aoclsparse_status_success)
-                return st;
-            std::vector<aoclsparse_int> cptr((size_t)m + 1);
-            MI355_HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(long long), hipMemcpyDeviceToHost, s));
-            MI355_HIP_TRY(hipMemcpyAsync(cptr.data(), d_ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), hipMemcpyDeviceToHost, s));
-            MI355_HIP_TRY(hipStreamSynchronize(s));
-            const aoclsparse_int nnz_c = (aoclsparse_int)total; // (at most m (m + 1) / 2 < 2^23)
-            for(aoclsparse_int &p : cptr)
-                p += base; // :89, :108
-            st = new_csr_result(C, m, m, nnz_c, vt, cptr.data(), base);
-            if(st != aoclsparse_status_success)
-                return st;
-            const size_t nz = (size_t)std::max<aoclsparse_int>(nnz_c, 1);
-            st              = rt.staging(SPG_SLOT_CI, sizeof(aoclsparse_int) * nz, &pi);
-            if(st == aoclsparse_status_success)
-                st = rt.staging(SPG_SLOT_CV, sizeof(T) * nz, &pv);
-            if(st == aoclsparse_status_success)
-                st = launch_aat_dense_row<T>(s, true, m, da.base, da.ptr, da.ind, static_cast<const T *>(da.val), dq.ptr, dq.ind,
-                                             static_cast<const T *>(dq.val), d_ptr, nullptr, base, static_cast<aoclsparse_int *>(pi),
-                                             static_cast<T *>(pv));
-            if(st == aoclsparse_status_success)
-                st = rt.d2h((*C)->user.ind, pi, sizeof(aoclsparse_int) * (size_t)nnz_c);
-            if(st == aoclsparse_status_success)
-                st = rt.d2h((*C)->user.val, pv, sizeof(T) * (size_t)nnz_c);
-            if(st == aoclsparse_status_success)
-                st = map_hip_error(hipStreamSynchronize(s));
+            st = syrk_dense_rows(rt, A, S, C, vt);
             if(st != aoclsparse_status_success)
                 drop(C); // :333-337
             return st;
         }
         // ---- online A^T * B path (sypr.hpp:400-527, BUILD_ONLY_U): L = the stored CSR (:286-331) or its csr2csc transpose
         // (:228-283); the left operand is L^T in walk order, the right one L itself
-        HostOp<T> Lt, W;
+        HostCsrOp<T> Lt, W;
         if(eff_none)
             transpose_of(S, Lt);
-        const HostOp<T> &L = eff_none ? Lt : S;
+        const HostCsrOp<T> &L = eff_none ? Lt : S;
         walked_transpose(L, W);
         SpgProduct<T> prod(rt);
         prod.m = m_c, prod.n = m_c, prod.upper = true;
         // which factor is conjugated: :263-265 with CONJ_A = true (:267); :288-289
         prod.conj_x = is_cplx_v<T> && (eff_none ? csc : !csc);
         prod.conj_y = is_cplx_v<T> && (eff_none ? !csc : csc);
-        st = send(rt, W, SPG_SLOT_XP, prod.x);
+        st = spg_send(rt, W, SPG_SLOT_XP, true, prod.x);
         if(st == aoclsparse_status_success)
-            st = eff_none ? send(rt, L, SPG_SLOT_YP, prod.y) : send_stored(rt, A, L, SPG_SLOT_YP, prod.y);
+            st = spg_to_device(rt, A, L, SPG_SLOT_YP, true, prod.y); // (resident when L is the handle's own CSR)
         if(st != aoclsparse_status_success)
             return st;
         std::shared_lock<std::shared_mutex> ra(A->guard);
@@ -490,6 +377,70 @@ aoclsparse_status syrk_t(aoclsparse_operation op, const aoclsparse_matrix A, aoc
         drop(C);
         return aoclsparse_status_memory_error;
     }
+}
+
+// ---- the two products of sypr, after every check: stage 1 T = sym(B) * L, stage 2 C = the upper triangle of L^H * T ----
+template <typename T>
+aoclsparse_status sypr_stages(Runtime &rt, const aoclsparse_matrix A, const aoclsparse_matrix B, bool lower, bool csc, bool eff_none,
+                              bool conj_flip, bool count, bool fill, aoclsparse_matrix *C, aoclsparse_matrix_data_type vt)
+{
+    const aoclsparse_int m = B->m;
+    aoclsparse_status    st;
+    // L: the stored CSR (:737-743) or its csr2csc transpose (:750-786); both stages read it, m x n
+    HostCsrOp<T> S, Lt, SB, W;
+    stored_of<T>(A, S);
+    if(eff_none)
+        transpose_of(S, Lt);
+    const HostCsrOp<T> &L = eff_none ? Lt : S;
+    const aoclsparse_int n = L.n; // C is n x n
+    {
+        std::shared_lock<std::shared_mutex> rb(B->guard);
+        symmetrised<T>(*B->opt, lower, SB); // :800
+    }
+    // ---- stage 1, T = sym(B) * L (:822-921), every request: count, scan, fill; T stays in HBM ----
+    SpgProduct<T> one(rt);
+    one.m = m, one.n = n;
+    // :780-785 (CSR, op = none: the transpose is conjugated before both stages), :824 (CONJ_B = conj_flip)
+    one.conj_y = is_cplx_v<T> && (eff_none ? !csc : conj_flip);
+    st = spg_send(rt, SB, SPG_SLOT_XP, true, one.x);
+    if(st == aoclsparse_status_success)
+        st = spg_to_device(rt, A, L, SPG_SLOT_YP, true, one.y); // (resident when L is the handle's own CSR)
+    if(st != aoclsparse_status_success)
+        return st;
+    std::shared_lock<std::shared_mutex> ra(A->guard);
+    void                               *tp = nullptr, *ti = nullptr, *tv = nullptr;
+    long long                          *d_total = nullptr;
+    aoclsparse_int                      nnz_t   = 0;
+    st = one.analyse();
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_TP, sizeof(aoclsparse_int) * ((size_t)m + 1), &tp);
+    if(st == aoclsparse_status_success)
+        st = one.count(static_cast<aoclsparse_int *>(tp), &d_total);
+    if(st == aoclsparse_status_success) // :391-396 (the total alone: T's row pointer stays in HBM)
+        st = spg_count_to_host(rt, d_total, nullptr, m, aoclsparse_index_base_zero, nullptr, nnz_t);
+    if(st != aoclsparse_status_success)
+        return st;
+    const size_t tz = (size_t)std::max<aoclsparse_int>(nnz_t, 1);
+    st              = rt.staging(SPG_SLOT_TI, sizeof(aoclsparse_int) * tz, &ti);
+    if(st == aoclsparse_status_success)
+        st = rt.staging(SPG_SLOT_TV, sizeof(T) * tz, &tv);
+    if(st == aoclsparse_status_success)
+        st = one.fill(static_cast<const aoclsparse_int *>(tp), static_cast<aoclsparse_int *>(ti), static_cast<T *>(tv));
+    if(st != aoclsparse_status_success)
+        return st;
+    // ---- stage 2, C = the upper triangle of L^H * T (:923-1058): the left operand is L^T in walk order ----
+    walked_transpose(L, W);
+    SpgProduct<T> two(rt);
+    two.m = n, two.n = n, two.upper = true;
+    // :945-985: CONJ_A = !conj_flip, on values that :780-785 may have conjugated already
+    two.conj_x = is_cplx_v<T> && (eff_none ? csc : !conj_flip);
+    two.y      = SpgDevOp{static_cast<const aoclsparse_int *>(tp), static_cast<const aoclsparse_int *>(ti), tv, 0};
+    st         = spg_send(rt, W, SPG_SLOT_XP, true, two.x); // (stream order: stage 1 has read these slots by then)
+    if(st == aoclsparse_status_success)
+        st = two.analyse();
+    if(st == aoclsparse_status_success)
+        st = product_to_handle(two, count, fill, C, vt, aoclsparse_index_base_zero);
+    return st;
 }
 
 // ---- sypr ---------------------------------------------------------------------------------------------------------------
@@ -559,67 +510,11 @@ aoclsparse_status sypr_t(aoclsparse_operation op, const aoclsparse_matrix A, con
     CallScope cs(CallScope::Always); // the SPG_SLOT_* slots are shared
     if(!cs.ok())
         return cs.st;
-    Runtime   &rt    = cs.rt;
     const bool count = request != aoclsparse_stage_finalize;
     try
     {
-        hipStream_t s = rt.stream();
-        // L: the stored CSR (:737-743) or its csr2csc transpose (:750-786); both stages read it, m x n
-        HostOp<T> S, Lt, SB, W;
-        stored_of<T>(A, S);
-        if(eff_none)
-            transpose_of(S, Lt);
-        const HostOp<T> &L = eff_none ? Lt : S;
-        {
-            std::shared_lock<std::shared_mutex> rb(B->guard);
-            symmetrised<T>(*B->opt, descrB->fill_mode == aoclsparse_fill_mode_lower, SB); // :800
-        }
-        // ---- stage 1, T = sym(B) * L (:822-921), every request: count, scan, fill; T stays in HBM ----
-        SpgProduct<T> one(rt);
-        one.m = m, one.n = n;
-        // :780-785 (CSR, op = none: the transpose is conjugated before both stages), :824 (CONJ_B = conj_flip)
-        one.conj_y = is_cplx_v<T> && (eff_none ? !csc : conj_flip);
-        SpgDevOp dl;
-        st = send(rt, SB, SPG_SLOT_XP, one.x);
-        if(st == aoclsparse_status_success)
-            st = eff_none ? send(rt, L, SPG_SLOT_YP, dl) : send_stored(rt, A, L, SPG_SLOT_YP, dl);
-        if(st != aoclsparse_status_success)
-            return st;
-        one.y = dl;
-        std::shared_lock<std::shared_mutex> ra(A->guard);
-        void                               *tp = nullptr, *ti = nullptr, *tv = nullptr;
-        long long                          *d_total = nullptr, nnz_t = 0;
-        st = one.analyse();
-        if(st == aoclsparse_status_success)
-            st = rt.staging(SPG_SLOT_TP, sizeof(aoclsparse_int) * ((size_t)m + 1), &tp);
-        if(st == aoclsparse_status_success)
-            st = one.count(static_cast<aoclsparse_int *>(tp), &d_total);
-        if(st != aoclsparse_status_success)
-            return st;
-        MI355_HIP_TRY(hipMemcpyAsync(&nnz_t, d_total, sizeof(long long), hipMemcpyDeviceToHost, s));
-        MI355_HIP_TRY(hipStreamSynchronize(s));
-        if(nnz_t > 2147483647LL) // :391-396
-            return aoclsparse_status_invalid_size;
-        const size_t tz = (size_t)std::max<long long>(nnz_t, 1);
-        st              = rt.staging(SPG_SLOT_TI, sizeof(aoclsparse_int) * tz, &ti);
-        if(st == aoclsparse_status_success)
-            st = rt.staging(SPG_SLOT_TV, sizeof(T) * tz, &tv);
-        if(st == aoclsparse_status_success)
-            st = one.fill(static_cast<const aoclsparse_int *>(tp), static_cast<aoclsparse_int *>(ti), static_cast<T *>(tv));
-        if(st != aoclsparse_status_success)
-            return st;
-        // ---- stage 2, C = the upper triangle of L^H * T (:923-1058): the left operand is L^T in walk order ----
-        walked_transpose(L, W);
-        SpgProduct<T> two(rt);
-        two.m = n, two.n = n, two.upper = true;
-        // :945-985: CONJ_A = !conj_flip, on values that :780-785 may have conjugated already
-        two.conj_x = is_cplx_v<T> && (eff_none ? csc : !conj_flip);
-        two.y      = SpgDevOp{static_cast<const aoclsparse_int *>(tp), static_cast<const aoclsparse_int *>(ti), tv, 0};
-        st         = send(rt, W, SPG_SLOT_XP, two.x); // (stream order: stage 1 has read these slots by then)
-        if(st == aoclsparse_status_success)
-            st = two.analyse();
-        if(st == aoclsparse_status_success)
-            st = product_to_handle(two, count, request != aoclsparse_stage_nnz_count, C, vt, aoclsparse_index_base_zero);
+        st = sypr_stages<T>(cs.rt, A, B, descrB->fill_mode == aoclsparse_fill_mode_lower, csc, eff_none, conj_flip, count,
+                            request != aoclsparse_stage_nnz_count, C, vt);
         if(st != aoclsparse_status_success && count)
             drop(C); // :986-990, :1052-1057
         return st;

@@ -5,7 +5,7 @@ checks that the operands have the properties they were built for, tests/test_gpu
 
 The kernel's constants are restated here on purpose -- the tests have to aim at them:
   CAPS     list capacity of the bins (SPG_CAP); the fill pass has the first three, its rows above 2,048 go to the global slab;
-  a table has twice its capacity in slots; the heavy rows' table is the next power of two >= 2 * list size (sp2m_api.cpp);
+  a table has twice its capacity in slots; the heavy rows' table is the next power of two >= 2 * list size (spg_product.cpp: bin_rows);
   GROUPS   entries of a B row (and of A's row) taken at a time: 16 in bin 0, 64 elsewhere;
   hslot    (uint32(c) * 2654435761 mod 2^32) >> (32 - logh)."""
 import numpy as np
