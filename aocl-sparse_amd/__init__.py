@@ -29,6 +29,7 @@ PTR_AUTO, PTR_HOST, PTR_DEVICE = 0, 1, 2
 OPTION_SPMV_KERNEL, OPTION_SELL, OPTION_SPMV_STRICT, OPTION_ALTERNATE_SWEEPS, OPTION_TRSV_CHUNKS = 0, 1, 2, 3, 4  # aoclsparse_mi355_set_option
 OPTION_SELL_VALUES = 5
 COO_KEEP, COO_SUM = 0, 1  # aoclsparse_mi355_coo_duplicates
+COO_KEEP_MAP = 16  # aoclsparse_mi355_coo_keep_map: flag ORed to either, the handle keeps the sort's map for refresh_from_coo_device
 COO_SORT_TILE = 4096  # AOCLSPARSE_MI355_COO_SORT_TILE: entries a workgroup of the triplet sort takes per pass
 
 STATUS = {
@@ -60,6 +61,12 @@ class SpmvInfo(ctypes.Structure):
 class TrsvInfo(ctypes.Structure):
     _fields_ = [(k, c_int32) for k in ("levels", "blocks", "block_levels", "chunks", "steps", "lds_slots", "model_chunk_us",
                                       "model_block_us", "schedule", "slices", "slice_fan_in_permille")]
+
+
+class CooMapInfo(ctypes.Structure):
+    """aoclsparse_mi355_coo_map_info: the caller sets struct_size, the library writes no more than that"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("kept", c_int32), ("mode", c_int32), ("triplets", c_int32),
+                ("entries", c_int32), ("map_bytes", ctypes.c_longlong)]
 
 
 MM_STATE_BUFFERS = 14
@@ -405,6 +412,11 @@ SIGNATURES = {
     "aoclsparse_mi355_dupdate_values_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_cupdate_values_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_zupdate_values_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_srefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_drefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_crefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_zrefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_get_coo_map_info": (c_int, [_P, _P]),
     "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
                                                    POINTER(_P)]),
     "aoclsparse_mi355_comm_unique_id": (c_int, [POINTER(CommId)]),
@@ -568,12 +580,15 @@ class Matrix:
         return cls.from_device(base, m, n, nnz, rp, ci, v)
 
     @classmethod
-    def from_coo_device(cls, base, m, n, nnz, row, col, val, duplicates=0, dtype=None):
+    def from_coo_device(cls, base, m, n, nnz, row, col, val, duplicates=0, dtype=None, refreshable=False):
         """aoclsparse_mi355_create_?csr_from_coo_device: a CSR handle from nnz unordered (row, col, value) triplets in HBM (torch
         device tensors or integer addresses; int32 indices).  duplicates = COO_KEEP: the stable sort by row of
         aoclsparse_convert_csr, repeated coordinates stay separate; COO_SUM: sorted by (row, column), repeated coordinates added
         left to right in triplet order.  The arrays are copied -- nothing is kept alive here -- and must be complete before the
-        call.  .nnz is the handle's (the distinct coordinates after COO_SUM).  Look at .status, as with Matrix(...)."""
+        call.  .nnz is the handle's (the distinct coordinates after COO_SUM).  refreshable=True ORs COO_KEEP_MAP in: the handle keeps
+        the sort's map, and refresh_from_coo_device brings new values of the same triplets.  Look at .status, as with Matrix(...)."""
+        if refreshable:
+            duplicates |= COO_KEEP_MAP
         name = str(val.dtype if dtype is None else dtype).split(".")[-1]
         for t in (row, col):
             assert not hasattr(t, "dtype") or str(t.dtype).split(".")[-1] == "int32", "aoclsparse_int is 32-bit"
@@ -585,14 +600,15 @@ class Matrix:
         self.h = c_void_p()
         fn = getattr(lib(), "aoclsparse_mi355_create_%scsr_from_coo_device" % self.letter)
         self.status = fn(byref(self.h), base, m, n, nnz, _ptr(row), _ptr(col), _ptr(val), duplicates)
-        if self.status == 0 and duplicates == COO_SUM:
+        self.triplets = nnz
+        if self.status == 0 and duplicates & ~COO_KEEP_MAP == COO_SUM:
             e = self.export_device()
             assert e["status"] == 0, STATUS.get(e["status"], e["status"])
             self.nnz = e["nnz"]
         return self
 
     @classmethod
-    def from_torch_coo(cls, t, base=0, duplicates=1):
+    def from_torch_coo(cls, t, base=0, duplicates=1, refreshable=False):
         """a torch.sparse_coo tensor on the GPU -> CSR handle; its int64 indices are cast to int32 on the device, uncoalesced as
         they are (duplicates = COO_SUM adds repeated coordinates in the order the tensor holds them)"""
         import torch
@@ -609,7 +625,7 @@ class Matrix:
         if base:
             row, col = row + base, col + base
         torch.cuda.synchronize()
-        return cls.from_coo_device(base, m, n, nnz, row, col, v, duplicates)
+        return cls.from_coo_device(base, m, n, nnz, row, col, v, duplicates, refreshable=refreshable)
 
     def _letter(self):
         return getattr(self, "letter", None) or (self._LETTER[str(self.val.dtype)] if self.val is not None
@@ -620,6 +636,19 @@ class Matrix:
         arrays -> status"""
         n = int(val.numel()) if hasattr(val, "numel") else self.nnz
         return getattr(lib(), "aoclsparse_mi355_%supdate_values_device" % self._letter())(self.h, n, _ptr(val))
+
+    def refresh_from_coo_device(self, val):
+        """aoclsparse_mi355_?refresh_values_from_coo_device: new values (a torch device tensor or an address) of the triplets a
+        refreshable handle was created from, in their order -> status"""
+        n = int(val.numel()) if hasattr(val, "numel") else getattr(self, "triplets", self.nnz)
+        return getattr(lib(), "aoclsparse_mi355_%srefresh_values_from_coo_device" % self._letter())(self.h, n, _ptr(val))
+
+    def coo_map_info(self):
+        """aoclsparse_mi355_get_coo_map_info -> CooMapInfo (kept, mode, triplets, entries, map_bytes)"""
+        info = CooMapInfo(struct_size=ctypes.sizeof(CooMapInfo))
+        st = lib().aoclsparse_mi355_get_coo_map_info(self.h, byref(info))
+        assert st == 0, STATUS.get(st, st)
+        return info
 
     def export_device(self):
         """aoclsparse_mi355_export_csr_device -> dict(status, base, m, n, nnz, row_ptr, col_ind, val): the last three are device

@@ -25,6 +25,11 @@
 // per output entry walks its run in order: v0 + v1, + v2, ... (a run of more than 64 entries is walked by the lane's wavefront,
 // which fetches 64 values at a time and adds them in the same order).  No float atomics anywhere; the integer atomics that count
 // rows commute exactly.
+//
+// Round 22: on request the sort's map -- the final positions, in `sum` mode the run starts -- leaves the staging slots in buffers
+// that hang on the handle, and device_coo_refresh_values makes the values again from new triplet values with one kernel that reads
+// no key and no column: a gather with COO_REFRESH_ILP loads in flight per lane (`keep`), or the creation's own chain
+// (coo_run_chain) per run (`sum`).
 #include "internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -251,22 +256,17 @@ namespace
 
     constexpr int COO_RUN_WAVE = 64; // runs longer than this are walked by the lane's whole wavefront
 
-    // A lane per output entry: it writes the run's column, counts it for its row and adds the run's values from left to right.
-    // A run of more than COO_RUN_WAVE entries is walked by the wavefront instead: the lanes fetch 64 values at a time, and the
-    // same chain v0 + v1, + v2, ... is then added from the fetched values in lane order (as one lane's loop a run of a million
-    // repeats would be a million dependent loads).
+    // The sum of the run [s, e) of sorted entries, for the lane that owns it (act: it owns one): its values from left to right,
+    // v0 + v1, + v2, ...  A run of more than COO_RUN_WAVE entries is walked by the wavefront instead: the lanes fetch 64 values
+    // at a time, and the same chain is then added from the fetched values in lane order (as one lane's loop a run of a million
+    // repeats would be a million dependent loads).  Every lane of the wavefront comes here together.  THE chain: the creation
+    // (coo_sum_kernel) and the value refresh (coo_refresh_sum_kernel) both call it, so the two give the same bits.
     template <typename V>
-    __global__ __launch_bounds__(256) void coo_sum_kernel(aoclsparse_int nnz, aoclsparse_int nout, const int *__restrict__ key,
-                                                          const int *__restrict__ pos, const aoclsparse_int *__restrict__ scol,
-                                                          const int *__restrict__ runs, const V *__restrict__ val, int *cnt,
-                                                          aoclsparse_int *__restrict__ oind, V *__restrict__ oval)
+    __device__ __forceinline__ V coo_run_chain(bool act, int s, int e, int lane, const int *__restrict__ pos,
+                                               const V *__restrict__ val)
     {
-        const long long o    = (long long)blockIdx.x * 256 + threadIdx.x;
-        const int       lane = threadIdx.x & 63;
-        const int       s = o < nout ? runs[o] : 0, e = o < nout ? runs[o + 1] : 0;
-        const bool      act = o < nout && 0 <= s && s < e && e <= nnz; // (every run is like that: the guard costs nothing)
-        const bool      lng = act && e - s > COO_RUN_WAVE;
-        V               acc{};
+        const bool lng = act && e - s > COO_RUN_WAVE;
+        V          acc{};
         if(act && !lng)
         {
             acc = val[pos[s]];
@@ -290,11 +290,72 @@ namespace
             if(lane == l)
                 acc = a;
         }
+        return acc;
+    }
+
+    // A lane per output entry: it writes the run's column, counts it for its row and adds the run's values (coo_run_chain).
+    template <typename V>
+    __global__ __launch_bounds__(256) void coo_sum_kernel(aoclsparse_int nnz, aoclsparse_int nout, const int *__restrict__ key,
+                                                          const int *__restrict__ pos, const aoclsparse_int *__restrict__ scol,
+                                                          const int *__restrict__ runs, const V *__restrict__ val, int *cnt,
+                                                          aoclsparse_int *__restrict__ oind, V *__restrict__ oval)
+    {
+        const long long o    = (long long)blockIdx.x * 256 + threadIdx.x;
+        const int       lane = threadIdx.x & 63;
+        const int       s = o < nout ? runs[o] : 0, e = o < nout ? runs[o + 1] : 0;
+        const bool      act = o < nout && 0 <= s && s < e && e <= nnz; // (every run is like that: the guard costs nothing)
+        const V         acc = coo_run_chain(act, s, e, lane, pos, val);
         if(act)
         {
             oind[o] = scol[s], oval[o] = acc;
             atomicAdd(&cnt[key[s]], 1);
         }
+    }
+
+    // ---- the values again, from new triplet values and the map a creation kept (device_coo_refresh_values) ----
+    // `keep` mode, out[q] = val[pos[q]]: a lane takes COO_REFRESH_ILP entries a workgroup's width apart (pos and out coalesced),
+    // loads all their positions, then all their values, then stores -- COO_REFRESH_ILP independent gathers in flight per lane where
+    // coo_gather_kernel has one position load, one dependent value load and a store in a row.
+    constexpr int COO_REFRESH_ILP = 8;
+
+    template <typename V>
+    __global__ __launch_bounds__(256) void coo_refresh_gather_kernel(aoclsparse_int nnz, const int *__restrict__ pos,
+                                                                     const V *__restrict__ val, V *__restrict__ out)
+    {
+        const long long q0 = (long long)blockIdx.x * (256 * COO_REFRESH_ILP) + threadIdx.x;
+        int             p[COO_REFRESH_ILP];
+        V               v[COO_REFRESH_ILP];
+#pragma unroll
+        for(int r = 0; r < COO_REFRESH_ILP; r++)
+        {
+            const long long q = q0 + r * 256;
+            p[r]              = q < nnz ? pos[q] : -1;
+        }
+#pragma unroll
+        for(int r = 0; r < COO_REFRESH_ILP; r++)
+            v[r] = (unsigned)p[r] < (unsigned)nnz ? val[p[r]] : V{}; // (every kept position is a triplet's: the guard costs nothing)
+#pragma unroll
+        for(int r = 0; r < COO_REFRESH_ILP; r++)
+        {
+            const long long q = q0 + r * 256;
+            if(q < nnz)
+                out[q] = v[r];
+        }
+    }
+
+    // `sum` mode: coo_sum_kernel's lane per output entry without its columns and row counts -- runs, pos and val in, oval out
+    template <typename V>
+    __global__ __launch_bounds__(256) void coo_refresh_sum_kernel(aoclsparse_int nnz, aoclsparse_int nout, const int *__restrict__ pos,
+                                                                  const int *__restrict__ runs, const V *__restrict__ val,
+                                                                  V *__restrict__ oval)
+    {
+        const long long o    = (long long)blockIdx.x * 256 + threadIdx.x;
+        const int       lane = threadIdx.x & 63;
+        const int       s = o < nout ? runs[o] : 0, e = o < nout ? runs[o + 1] : 0;
+        const bool      act = o < nout && 0 <= s && s < e && e <= nnz;
+        const V         acc = coo_run_chain(act, s, e, lane, pos, val);
+        if(act)
+            oval[o] = acc;
     }
 
     int bits_of(aoclsparse_int v) // bits needed to write 0 .. v
@@ -407,7 +468,7 @@ namespace
 static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz, int base,
                                                const aoclsparse_int *row, const aoclsparse_int *col, const void *val, size_t vsize,
                                                bool cplx, bool sum, DeviceBuffer &ptr_b, DeviceBuffer &ind_b, DeviceBuffer &val_b,
-                                               aoclsparse_int *nnz_out)
+                                               aoclsparse_int *nnz_out, DeviceBuffer *map)
 {
     if(M < 0 || N < 0 || nnz < 0 || (vsize != 4 && vsize != 8 && vsize != 16))
         return aoclsparse_status_not_implemented;
@@ -457,6 +518,15 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
     {
         MI355_TRY(ind_b.alloc(0)); // (non-null allocations, as the handle's mirror has them)
         MI355_TRY(val_b.alloc(0));
+        if(map)
+        {
+            MI355_TRY(map[0].alloc(0));
+            if(sum) // runs[0] = 0: no run, and where none starts
+            {
+                MI355_TRY(map[1].alloc(sizeof(int)));
+                MI355_HIP_TRY(hipMemsetAsync(map[1].ptr, 0, sizeof(int), s));
+            }
+        }
     }
     else
     {
@@ -484,6 +554,11 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
         MI355_TRY(radix_passes(s, nnz, st, bits_of(M - 1)));
         marks.record(1, s);
         const int *const keys = st.key[st.cur], *const pos = st.pos[st.cur];
+        if(map) // the positions outlive the call in a buffer of the handle's: the slot is the next caller's to grow or free
+        {
+            MI355_TRY(map[0].alloc(n4));
+            MI355_HIP_TRY(hipMemcpyAsync(map[0].ptr, pos, n4, hipMemcpyDeviceToDevice, s));
+        }
         if(!sum)
         {
             MI355_TRY(ind_b.alloc(n4));
@@ -510,8 +585,11 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
             const aoclsparse_int nout = (aoclsparse_int)distinct;
             MI355_TRY(ind_b.alloc(sizeof(aoclsparse_int) * (size_t)nout));
             MI355_TRY(val_b.alloc(vsize * (size_t)nout));
-            MI355_TRY(rt.staging(COO_SLOT_RUNS, sizeof(int) * ((size_t)nout + 1), &p));
-            int *const runs = static_cast<int *>(p);
+            if(map) // the run starts are built where they stay
+                MI355_TRY(map[1].alloc(sizeof(int) * ((size_t)nout + 1)));
+            else
+                MI355_TRY(rt.staging(COO_SLOT_RUNS, sizeof(int) * ((size_t)nout + 1), &p));
+            int *const runs = map ? map[1].as<int>() : static_cast<int *>(p);
             hipLaunchKernelGGL(coo_runs_kernel, dim3(gq), dim3(256), 0, s, nnz, nout, flag, outpos, runs);
             MI355_TRY(by_value_type(vsize, cplx, [&](auto v) {
                 launch_sum<decltype(v)>(s, nnz, nout, keys, pos, scol, runs, val, cnt_p, ind_b.as<aoclsparse_int>(), val_b.ptr);
@@ -533,12 +611,45 @@ static aoclsparse_status device_coo_to_csr_run(hipStream_t s, aoclsparse_int M, 
 
 aoclsparse_status device_coo_to_csr(hipStream_t s, aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz, int base,
                                     const aoclsparse_int *row, const aoclsparse_int *col, const void *val, size_t vsize, bool cplx,
-                                    bool sum, DeviceBuffer &ptr, DeviceBuffer &ind, DeviceBuffer &valb, aoclsparse_int *nnz_out)
+                                    bool sum, DeviceBuffer &ptr, DeviceBuffer &ind, DeviceBuffer &valb, aoclsparse_int *nnz_out,
+                                    DeviceBuffer *map)
 {
-    const aoclsparse_status st = device_coo_to_csr_run(s, M, N, nnz, base, row, col, val, vsize, cplx, sum, ptr, ind, valb, nnz_out);
+    const aoclsparse_status st = device_coo_to_csr_run(s, M, N, nnz, base, row, col, val, vsize, cplx, sum, ptr, ind, valb, nnz_out, map);
     if(st != aoclsparse_status_success)
+    {
         ptr.release(), ind.release(), valb.release();
+        if(map)
+            map[0].release(), map[1].release();
+    }
     return st;
+}
+
+aoclsparse_status device_coo_refresh_values(hipStream_t s, aoclsparse_int triplets, aoclsparse_int entries, bool sum, const int *pos,
+                                            const int *runs, const void *val, size_t vsize, bool cplx, void *out)
+{
+    if(triplets < 0 || entries < 0 || entries > triplets || (!sum && entries != triplets) || !pos || (sum && !runs) || !val || !out)
+        return aoclsparse_status_internal_error;
+    if(entries == 0)
+        return aoclsparse_status_success;
+    SortMarks marks; // (AOCLSPARSE_MI355_TIMING=1: the kernel's own time; the stream is waited for only then)
+    marks.record(0, s);
+    MI355_TRY(by_value_type(vsize, cplx, [&](auto v) {
+        using V = decltype(v);
+        if(sum)
+            hipLaunchKernelGGL((coo_refresh_sum_kernel<V>), dim3((unsigned)(((long long)entries + 255) / 256)), dim3(256), 0, s,
+                               triplets, entries, pos, runs, static_cast<const V *>(val), static_cast<V *>(out));
+        else
+            hipLaunchKernelGGL((coo_refresh_gather_kernel<V>),
+                               dim3((unsigned)(((long long)entries + 256 * COO_REFRESH_ILP - 1) / (256 * COO_REFRESH_ILP))), dim3(256), 0,
+                               s, entries, pos, static_cast<const V *>(val), static_cast<V *>(out));
+    }));
+    marks.record(1, s);
+    MI355_HIP_TRY(hipGetLastError());
+    float ms = 0.f;
+    if(marks.got[0] && marks.got[1] && hipEventSynchronize(marks.ev[1]) == hipSuccess
+       && hipEventElapsedTime(&ms, marks.ev[0], marks.ev[1]) == hipSuccess)
+        std::fprintf(stderr, "[mi355 timing]     coo refresh kernel (%s): %8.3f ms\n", sum ? "sum" : "keep", ms);
+    return aoclsparse_status_success;
 }
 
 } // namespace mi355

@@ -11,7 +11,13 @@
 // Round 19 adds the way in for a matrix that is not CSR yet: unordered (row, col, value) triplets in HBM are sorted into CSR
 // arrays on the device (coo_sort_kernels.hip), and those arrays -- the library's own -- are MOVED into the mirror by the same
 // helper that copies a caller's.
+//
+// Round 22: a creation from triplets may keep the sort's map on the handle (aoclsparse_mi355_coo_keep_map), and
+// ?refresh_values_from_coo_device then brings the values of the same triplets again without sorting: what ?update_values_device
+// does with values in CSR order, behind one kernel that puts them into that order (or adds them into it).
 #include "matcheck.hpp"
+
+#include <cstring>
 
 using namespace mi355;
 
@@ -136,8 +142,10 @@ namespace
             return aoclsparse_status_invalid_size;
         if(!row_ind || !col_ind || !val)
             return aoclsparse_status_invalid_pointer;
-        if(duplicates != aoclsparse_mi355_coo_keep && duplicates != aoclsparse_mi355_coo_sum)
+        const aoclsparse_int mode = duplicates & ~(aoclsparse_int)aoclsparse_mi355_coo_keep_map; // 0, 1, 16 and 17 are valid
+        if(mode != aoclsparse_mi355_coo_keep && mode != aoclsparse_mi355_coo_sum)
             return aoclsparse_status_invalid_value;
+        const bool keep_map = (duplicates & aoclsparse_mi355_coo_keep_map) != 0;
         Runtime          &rt = Runtime::get();
         aoclsparse_status rc = rt.init();
         if(rc != aoclsparse_status_success)
@@ -146,16 +154,78 @@ namespace
             return aoclsparse_status_invalid_pointer;
         std::lock_guard<std::recursive_mutex> sl(rt.stage_lock);
         LapTimer                              lt;
-        DeviceBuffer                          own[3];
+        DeviceBuffer                          own[3], map[2];
         aoclsparse_int                        nnz_csr = 0;
         const bool                            cplx    = vt == aoclsparse_cmat || vt == aoclsparse_zmat;
         rc = device_coo_to_csr(rt.stream(), M, N, nnz, (int)base, row_ind, col_ind, val, sizeof(T), cplx,
-                               duplicates == aoclsparse_mi355_coo_sum, own[0], own[1], own[2], &nnz_csr);
+                               mode == aoclsparse_mi355_coo_sum, own[0], own[1], own[2], &nnz_csr, keep_map ? map : nullptr);
         if(rc != aoclsparse_status_success)
             return rc;
         lt.lap("create_from_coo_device: sort");
-        return csr_handle_from_device(mat, base, M, N, nnz_csr, own[0].as<const aoclsparse_int>(), own[1].as<const aoclsparse_int>(),
-                                      own[2].ptr, vt, own);
+        rc = csr_handle_from_device(mat, base, M, N, nnz_csr, own[0].as<const aoclsparse_int>(), own[1].as<const aoclsparse_int>(),
+                                    own[2].ptr, vt, own);
+        if(rc == aoclsparse_status_success && keep_map) // the sort's map hangs on the handle from here on
+        {
+            aoclsparse_matrix H = *mat;
+            H->coo_pos.adopt(map[0]), H->coo_runs.adopt(map[1]);
+            H->coo_map_kept = true, H->coo_map_mode = mode, H->coo_map_triplets = nnz;
+        }
+        return rc;
+    }
+
+    // the values of a handle that kept its sort's map, again, from the triplets' new values (coo_sort_kernels.hip)
+    template <typename T>
+    aoclsparse_status refresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len, const T *val, aoclsparse_matrix_data_type vt)
+    {
+        // decided before the device is touched, in this order
+        if(!A || !val)
+            return aoclsparse_status_invalid_pointer;
+        if(!A->coo_map_kept)
+            return aoclsparse_status_invalid_value;
+        if(len != A->coo_map_triplets)
+            return aoclsparse_status_invalid_size;
+        if(A->val_type != vt)
+            return aoclsparse_status_wrong_type;
+        Runtime          &rt = Runtime::get();
+        aoclsparse_status rc = rt.init();
+        if(rc != aoclsparse_status_success)
+            return rc;
+        if(!rt.is_device_pointer(val))
+            return aoclsparse_status_invalid_pointer;
+        std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
+        std::unique_lock<std::shared_mutex>   w(A->guard);
+        // (looked at again under the guard: aoclsparse_order_mat on another thread releases the map)
+        if(!A->coo_map_kept || !A->user.val || !A->coo_pos.ptr)
+            return aoclsparse_status_invalid_value;
+        if(len != A->coo_map_triplets)
+            return aoclsparse_status_invalid_size;
+        const bool sum = A->coo_map_mode == aoclsparse_mi355_coo_sum;
+        if(sum ? !A->coo_runs.ptr || A->coo_runs.bytes < sizeof(int) * ((size_t)A->nnz + 1) : A->nnz != len)
+            return aoclsparse_status_internal_error;
+        hipStream_t  s     = rt.stream();
+        const size_t bytes = sizeof(T) * (size_t)A->nnz;
+        DeviceCsr   &d     = A->dev_user;
+        // as update_values_device: the values go into the resident copy while the mirror is the handle's structure, and it stays
+        // resident; behind an invalid mirror (?set_value, ?update_values, aoclsparse_mi355_invalidate) they go through a buffer of
+        // this call's, and the next product uploads the host view as it would have anyway
+        const bool   keep = d.valid && d.m == A->m && d.nnz == A->nnz && d.ptr.ptr && d.ind.ptr && d.val.ptr && d.val.bytes >= bytes;
+        DeviceBuffer tmp;
+        if(!keep && (rc = tmp.alloc(bytes)) != aoclsparse_status_success)
+            return rc;
+        void *const out = keep ? d.val.ptr : tmp.ptr;
+        const bool  cplx = vt == aoclsparse_cmat || vt == aoclsparse_zmat;
+        // (in stream order behind every product enqueued on the library's stream: they read the old values)
+        rc = device_coo_refresh_values(s, len, A->nnz, sum, A->coo_pos.as<const int>(), A->coo_runs.as<const int>(), val, sizeof(T), cplx,
+                                       out);
+        if(rc == aoclsparse_status_success && bytes && hipMemcpyAsync(A->user.val, out, bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = aoclsparse_status_internal_error;
+        if(hipStreamSynchronize(s) != hipSuccess && rc == aoclsparse_status_success) // (`tmp` goes only behind the work that reads it)
+            rc = aoclsparse_status_internal_error;
+        drop_derived_state(A); // SELL-64 / blocked-ELL copies, TRSV plans, derived operators, replicas: rebuilt lazily
+        d.valid = keep && rc == aoclsparse_status_success;
+        if(rc != aoclsparse_status_success)
+            (void)hipGetLastError();
+        return rc;
     }
 
     template <typename T>
@@ -276,6 +346,45 @@ aoclsparse_status aoclsparse_mi355_cupdate_values_device(aoclsparse_matrix A, ao
 aoclsparse_status aoclsparse_mi355_zupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const aoclsparse_double_complex *val)
 {
     return update_values_device(A, len, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_srefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len, const float *val)
+{
+    return refresh_values_from_coo_device(A, len, val, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_mi355_drefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len, const double *val)
+{
+    return refresh_values_from_coo_device(A, len, val, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_mi355_crefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                                   const aoclsparse_float_complex *val)
+{
+    return refresh_values_from_coo_device(A, len, val, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_mi355_zrefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                                   const aoclsparse_double_complex *val)
+{
+    return refresh_values_from_coo_device(A, len, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_get_coo_map_info(aoclsparse_matrix A, aoclsparse_mi355_coo_map_info *info)
+{
+    if(!A || !info)
+        return aoclsparse_status_invalid_pointer;
+    if(info->struct_size < sizeof(info->struct_size))
+        return aoclsparse_status_invalid_size;
+    aoclsparse_mi355_coo_map_info r{};
+    {
+        std::shared_lock<std::shared_mutex> g(A->guard);
+        if(A->coo_map_kept)
+        {
+            r.kept = 1, r.mode = A->coo_map_mode, r.triplets = A->coo_map_triplets, r.entries = A->nnz;
+            r.map_bytes = (long long)(A->coo_pos.bytes + A->coo_runs.bytes);
+        }
+    }
+    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
+    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
 }
 
 aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,

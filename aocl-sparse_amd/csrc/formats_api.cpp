@@ -775,6 +775,7 @@ aoclsparse_status aoclsparse_order_mat(aoclsparse_matrix mat)
     if(mat_check(mat->m, mat->n, mat->nnz, mat->user.ptr, mat->user.ind, mat->user.val, 0, mat->base, sort, fd)
        == aoclsparse_status_success)
         mat->sort = sort, mat->fulldiag = fd;
+    mat->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
     drop_derived_state(mat); // every copy made of the unsorted arrays (clean CSR, device mirrors, plans)
     return aoclsparse_status_success;
 }

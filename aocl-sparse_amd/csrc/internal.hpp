@@ -803,6 +803,18 @@ struct _aoclsparse_matrix
     int             csc_sort = 0; // sort class of those CSC arrays (`sort` is the class of the CSR in `user`)
     aoclsparse_int *coo_row = nullptr, *coo_col = nullptr;
     void           *coo_val = nullptr;
+    // the map of the triplet sort, kept on request (aoclsparse_mi355_coo_keep_map; device_handle_api.cpp): coo_pos[q] = the triplet
+    // that sorted entry q came from (coo_map_triplets ints), in `sum` mode coo_runs[o] = where the run of CSR entry o starts among
+    // the sorted entries (nnz + 1 ints).  They index the handle's value array as it was created: aoclsparse_order_mat releases them;
+    // value changes leave them alone.  Not a copy of the values, so drop_derived_state does not come here.
+    mi355::DeviceBuffer coo_pos, coo_runs;
+    bool                coo_map_kept = false;
+    aoclsparse_int      coo_map_mode = 0, coo_map_triplets = 0;
+    void                drop_coo_map()
+    {
+        coo_pos.release(), coo_runs.release();
+        coo_map_kept = false, coo_map_mode = coo_map_triplets = 0;
+    }
     // TCSR (input_format == aoclsparse_tcsr_mat, no CSR in `user`): [0] = L, [1] = U, each a CSR handle of its own that aliases the
     // caller's three arrays of that triangle (L: the diagonal ends every row, U: it starts every row).  Every copy of the values --
     // device mirrors, TRSV plans, symmetric / triangular expansions -- hangs on these two (drop_derived_state walks them)
@@ -1109,9 +1121,17 @@ aoclsparse_status device_transpose(hipStream_t s, aoclsparse_int m, aoclsparse_i
 // it allocates once every index is known to be in range (invalid_index_value otherwise; the buffers are then empty).  sum == false:
 // the reference's coo2csr, *nnz_out = nnz; sum == true: sorted by (row, column), equal coordinates added left to right in triplet
 // order, *nnz_out = the distinct coordinates.  vsize / cplx: bytes of a value, and whether it is a pair of reals.
+// map != nullptr: the sort's map leaves the staging slots too, in buffers allocated here -- map[0] = the final positions (nnz ints),
+// in `sum` mode map[1] = the run starts (*nnz_out + 1 ints); both empty again on failure.
 aoclsparse_status device_coo_to_csr(hipStream_t s, aoclsparse_int M, aoclsparse_int N, aoclsparse_int nnz, int base,
                                     const aoclsparse_int *row, const aoclsparse_int *col, const void *val, size_t vsize, bool cplx,
-                                    bool sum, DeviceBuffer &ptr, DeviceBuffer &ind, DeviceBuffer &valb, aoclsparse_int *nnz_out);
+                                    bool sum, DeviceBuffer &ptr, DeviceBuffer &ind, DeviceBuffer &valb, aoclsparse_int *nnz_out,
+                                    DeviceBuffer *map = nullptr);
+// The values of a CSR built by device_coo_to_csr, again, from `triplets` new values in the triplets' order and the map kept then:
+// out[q] = val[pos[q]] (sum == false, entries == triplets), or per entry the left-to-right chain over its run (sum == true).
+// Enqueued on s, not waited for; reads pos, runs and val, writes `entries` values.
+aoclsparse_status device_coo_refresh_values(hipStream_t s, aoclsparse_int triplets, aoclsparse_int entries, bool sum, const int *pos,
+                                            const int *runs, const void *val, size_t vsize, bool cplx, void *out);
 
 // ---- device mirrors / plans ---------------------------------------------------------------------
 size_t            val_size(aoclsparse_matrix_data_type t);

@@ -244,17 +244,61 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           [base, base + N) -- decided on the device before any output is allocated, nothing is ever written out of range; in
  *           `keep` mode whatever create_?csr_device answers for the converted arrays, in practice invalid_value for a second
  *           diagonal entry in a row.  nnz == 0 and M == 0 are valid; the arrays must still be non-null device allocations.
+ *           duplicates | aoclsparse_mi355_coo_keep_map (16; the valid values of `duplicates` are 0, 1, 16 and 17, every other one
+ *           is invalid_value at the place named above): the CSR is byte for byte what the call without the flag gives, and the
+ *           handle also keeps the sort's map in device memory -- for every sorted entry the triplet it came from (one int per
+ *           triplet), in `sum` mode also where every run of equal coordinates starts (distinct + 1 ints).  aoclsparse_destroy frees
+ *           it.  Without the flag nothing is kept.
+ *   ?refresh_values_from_coo_device   (round 22) New values for a handle created with aoclsparse_mi355_coo_keep_map, from the SAME
+ *           triplets with other values: what a time step or a Newton iteration of the assembly that made them produces.  `val`
+ *           holds len values in device memory in the order of the triplets the handle was created from; the handle's values
+ *           become exactly -- bit for bit -- what create_?csr_from_coo_device on (the same rows, the same columns, val, the same
+ *           mode) would hold.  `keep`: entry q gets the value of the triplet it came from.  `sum`: per run the left-to-right chain
+ *           ((v0 + v1) + v2) + ... in triplet order, in the value type, complex values component by component, by the very device
+ *           function the creation adds with; a run that sums to zero stays an entry; no float atomics.  Nothing is sorted again:
+ *           one kernel reads the map and val and writes the values.
+ *           The values go where ?update_values_device puts them: into the resident copy when the handle's CSR is resident, which
+ *           stays resident (the next product uploads nothing), and into the host view; everything derived from the values is
+ *           dropped and rebuilt on first use.  The work is ordered behind the products on the library's stream, which is
+ *           synchronised before return.  `val` must be complete before the call and must not overlap the handle's own arrays
+ *           (those export_csr_device returns): that is not detected.
+ *           Statuses, in this order, all decided before the device is touched: invalid_pointer for a null A or val;
+ *           invalid_value for a handle that holds no map (created without the flag, created any other way, or whose map was
+ *           dropped); invalid_size for len other than the triplet count of the creation (in `sum` mode that is not the handle's
+ *           nnz); wrong_type for another value type.  Then invalid_pointer for a val that is not device (or managed) memory in the
+ *           current pointer mode.  len == 0 on a handle created from 0 triplets is valid; val must still be a non-null device
+ *           allocation.
+ *           The map survives ?set_value, ?update_values, ?update_values_device, aoclsparse_optimize and
+ *           aoclsparse_mi355_invalidate (none changes the structure, and the next refresh overwrites every value).
+ *           aoclsparse_order_mat drops it: it reorders the arrays the map points into.  aoclsparse_copy, mm_state_export / adopt
+ *           and the replicas of the multi-device calls do not carry it: their handles hold no map.
+ *   get_coo_map_info   Whether a handle holds a map, and how large.  The caller sets info->struct_size to sizeof(*info); the
+ *           library writes no more than that many bytes (a caller compiled against a shorter struct stays intact) and leaves
+ *           struct_size as it is.  kept = 1 with the creation's mode (0 / 1), its triplet count, the handle's entries and the
+ *           bytes of device memory the map occupies; kept = 0 and zeros for every handle without one, which is no error.
+ *           invalid_pointer for a null A or info, invalid_size for a struct_size that does not hold struct_size itself.
  *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
  * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
- * arrays); refreshing the values of a `sum`-mode handle from new triplets (that needs the map from triplets to runs kept); sorting
+ * arrays); a refresh that changes the set of coordinates; carrying the triplet map through aoclsparse_copy, exported state or
+ * replicas; a host-pointer twin of ?refresh_values_from_coo_device; sorting
  * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still). */
 #define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
 typedef enum
 {
     aoclsparse_mi355_coo_keep = 0, /* repeated coordinates stay separate entries, in triplet order */
-    aoclsparse_mi355_coo_sum  = 1 /* repeated coordinates are added, left to right in triplet order */
+    aoclsparse_mi355_coo_sum  = 1, /* repeated coordinates are added, left to right in triplet order */
+    aoclsparse_mi355_coo_keep_map = 16 /* flag, ORed to either: the handle keeps the sort's map for ?refresh_values_from_coo_device */
 } aoclsparse_mi355_coo_duplicates;
+typedef struct
+{
+    size_t         struct_size; /* in: sizeof(aoclsparse_mi355_coo_map_info) as the caller knows it */
+    aoclsparse_int kept; /* 1: the handle holds a map; 0: none, and everything below is 0 */
+    aoclsparse_int mode; /* aoclsparse_mi355_coo_keep or aoclsparse_mi355_coo_sum */
+    aoclsparse_int triplets; /* the len ?refresh_values_from_coo_device expects */
+    aoclsparse_int entries; /* the handle's nnz */
+    long long      map_bytes; /* device memory allocated for the map */
+} aoclsparse_mi355_coo_map_info;
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_create_scsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
                                                                  aoclsparse_int N, aoclsparse_int nnz, const aoclsparse_int *row_ptr,
                                                                  const aoclsparse_int *col_idx, const float *val);
@@ -291,6 +335,13 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_cupdate_values_device(aoclsparse_m
                                                                     const aoclsparse_float_complex *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zupdate_values_device(aoclsparse_matrix A, aoclsparse_int len,
                                                                     const aoclsparse_double_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_srefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len, const float *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_drefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len, const double *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_crefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                                              const aoclsparse_float_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                                              const aoclsparse_double_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_coo_map_info(aoclsparse_matrix A, aoclsparse_mi355_coo_map_info *info);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
                                                                 aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
                                                                 const aoclsparse_int **col_idx, const void **val);
