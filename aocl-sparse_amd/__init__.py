@@ -31,6 +31,8 @@ OPTION_SELL_VALUES = 5
 COO_KEEP, COO_SUM = 0, 1  # aoclsparse_mi355_coo_duplicates
 COO_KEEP_MAP = 16  # aoclsparse_mi355_coo_keep_map: flag ORed to either, the handle keeps the sort's map for refresh_from_coo_device
 COO_SORT_TILE = 4096  # AOCLSPARSE_MI355_COO_SORT_TILE: entries a workgroup of the triplet sort takes per pass
+ORDER_SHORT_MAX = 32  # AOCLSPARSE_MI355_ORDER_SHORT_MAX: order_device sorts rows of up to this many entries with one lane each
+ORDER_LDS_MAX = 2048  # AOCLSPARSE_MI355_ORDER_LDS_MAX: ... of up to this many in LDS; longer rows go through the radix sort
 
 STATUS = {
     0: "success", 1: "not_implemented", 2: "invalid_pointer", 3: "invalid_size", 4: "internal_error",
@@ -417,6 +419,7 @@ SIGNATURES = {
     "aoclsparse_mi355_crefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_zrefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_get_coo_map_info": (c_int, [_P, _P]),
+    "aoclsparse_mi355_order_mat_device": (c_int, [_P]),
     "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
                                                    POINTER(_P)]),
     "aoclsparse_mi355_comm_unique_id": (c_int, [POINTER(CommId)]),
@@ -649,6 +652,11 @@ class Matrix:
         st = lib().aoclsparse_mi355_get_coo_map_info(self.h, byref(info))
         assert st == 0, STATUS.get(st, st)
         return info
+
+    def order_device(self):
+        """aoclsparse_mi355_order_mat_device: every row into ascending column order (stable), sorted in HBM; the handle is
+        resident afterwards and its host view (for a host-created handle: the caller's arrays) holds the sorted arrays -> status"""
+        return lib().aoclsparse_mi355_order_mat_device(self.h)
 
     def export_device(self):
         """aoclsparse_mi355_export_csr_device -> dict(status, base, m, n, nnz, row_ptr, col_ind, val): the last three are device

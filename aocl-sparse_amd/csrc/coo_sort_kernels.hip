@@ -624,6 +624,43 @@ aoclsparse_status device_coo_to_csr(hipStream_t s, aoclsparse_int M, aoclsparse_
     return st;
 }
 
+// The radix passes alone, for a caller with pairs of its own (order_kernels.hip: the entries of a CSR's long rows): the sequence of
+// `sum` mode above -- the minor keys first, then the major keys read through the positions sorted so far -- in the same slots.
+aoclsparse_status device_sort_pairs(hipStream_t s, aoclsparse_int count, const aoclsparse_int *major, aoclsparse_int major_range,
+                                    const aoclsparse_int *minor, aoclsparse_int minor_range, const int **perm)
+{
+    if(count <= 0 || major_range <= 0 || minor_range <= 0 || !major || !minor || !perm)
+        return aoclsparse_status_internal_error;
+    Runtime                              &rt = Runtime::get();
+    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (the caller's already; it drains the stream before it lets go)
+    const size_t   n4 = sizeof(int) * (size_t)count;
+    const unsigned gq = (unsigned)(((long long)count + 255) / 256);
+    SortState      st;
+    void          *p = nullptr;
+    st.tiles           = ((long long)count + COO_TILE - 1) / COO_TILE;
+    const size_t cells = 256 * (size_t)st.tiles;
+    for(int q = 0; q < 2; q++)
+    {
+        MI355_TRY(rt.staging(q ? COO_SLOT_KEY_B : COO_SLOT_KEY_A, n4, &p));
+        st.key[q] = static_cast<int *>(p);
+        MI355_TRY(rt.staging(q ? COO_SLOT_POS_B : COO_SLOT_POS_A, n4, &p));
+        st.pos[q] = static_cast<int *>(p);
+    }
+    MI355_TRY(rt.staging(COO_SLOT_HIST, sizeof(int) * cells, &p));
+    st.hist = static_cast<int *>(p);
+    MI355_TRY(rt.staging(COO_SLOT_OFFS, sizeof(aoclsparse_int) * (cells + 1), &p));
+    st.offs = static_cast<aoclsparse_int *>(p);
+    MI355_TRY(rt.staging(COO_SLOT_SCAN, spg_scan_scratch_bytes((aoclsparse_int)cells), &p));
+    st.scan = static_cast<long long *>(p);
+    hipLaunchKernelGGL(coo_init_kernel, dim3(gq), dim3(256), 0, s, count, 0, minor, st.key[0], st.pos[0]);
+    MI355_TRY(radix_passes(s, count, st, bits_of(minor_range - 1)));
+    hipLaunchKernelGGL(coo_rekey_kernel, dim3(gq), dim3(256), 0, s, count, 0, major, st.pos[st.cur], st.key[st.cur]);
+    MI355_TRY(radix_passes(s, count, st, bits_of(major_range - 1)));
+    MI355_HIP_TRY(hipGetLastError());
+    *perm = st.pos[st.cur];
+    return aoclsparse_status_success;
+}
+
 aoclsparse_status device_coo_refresh_values(hipStream_t s, aoclsparse_int triplets, aoclsparse_int entries, bool sum, const int *pos,
                                             const int *runs, const void *val, size_t vsize, bool cplx, void *out)
 {

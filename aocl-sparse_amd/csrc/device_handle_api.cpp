@@ -15,6 +15,9 @@
 // Round 22: a creation from triplets may keep the sort's map on the handle (aoclsparse_mi355_coo_keep_map), and
 // ?refresh_values_from_coo_device then brings the values of the same triplets again without sorting: what ?update_values_device
 // does with values in CSR order, behind one kernel that puts them into that order (or adds them into it).
+//
+// Round 23: aoclsparse_mi355_order_mat_device is aoclsparse_order_mat with the sort done on the mirror (order_kernels.hip) and the
+// handle resident afterwards.
 #include "matcheck.hpp"
 
 #include <cstring>
@@ -385,6 +388,89 @@ aoclsparse_status aoclsparse_mi355_get_coo_map_info(aoclsparse_matrix A, aoclspa
     r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
     std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
     return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A)
+{
+    // the statuses of aoclsparse_order_mat (formats_api.cpp), in its order, all before the device is touched
+    if(!A)
+        return aoclsparse_status_invalid_pointer;
+    if(A->m < 0 || A->n < 0 || A->nnz < 0)
+        return aoclsparse_status_invalid_value;
+    if(A->input_format != aoclsparse_csr_mat)
+        return aoclsparse_status_not_implemented;
+    if(A->m == 0 || A->n == 0 || A->nnz == 0)
+        return aoclsparse_status_success;
+    if(!A->user.ptr || !A->user.ind || !A->user.val)
+        return aoclsparse_status_invalid_pointer;
+    if(A->csc_ptr) // the host call sorts the caller's CSC arrays there: they live on the host
+        return aoclsparse_status_not_implemented;
+    Runtime          &rt = Runtime::get();
+    aoclsparse_status rc = rt.init();
+    if(rc != aoclsparse_status_success)
+        return rc;
+    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
+    std::unique_lock<std::shared_mutex>   w(A->guard);
+    hipStream_t                           s   = rt.stream();
+    const size_t                          vsz = val_size(A->val_type);
+    DeviceCsr                            &d   = A->dev_user;
+    DeviceBuffer                          res;
+    if((rc = res.alloc(sizeof(MatCheckResult))) != aoclsparse_status_success)
+        return rc;
+    // a mirror that is not resident (a host-created handle before its first product) or not valid (?set_value, aoclsparse_order_mat,
+    // aoclsparse_mi355_invalidate) comes from the host view first, as for export_csr_device.  Up to here the handle is unchanged.
+    if(!d.valid && (rc = upload_csr(A->user, vsz, d)) != aoclsparse_status_success)
+        return rc;
+    if(d.m != A->m || d.nnz != A->nnz || !d.ptr.ptr || !d.ind.ptr || !d.val.ptr)
+        return aoclsparse_status_internal_error;
+    // The mirror is sorted IN PLACE, in stream order behind every product enqueued on the library's stream; the host view is
+    // committed by one copy back once all device work has succeeded.  A failure before that leaves the host view as it was, the
+    // mirror invalid (the next product uploads the host view again) and everything derived dropped.
+    MatCheckResult *d_res = res.as<MatCheckResult>(), h{};
+    long long       moved = 0;
+    LapTimer        lt;
+    auto            hip = [&](hipError_t e) {
+        if(e != hipSuccess && rc == aoclsparse_status_success)
+            rc = aoclsparse_status_internal_error;
+    };
+    rc = device_order_rows(s, d.m, d.n, d.nnz, (int)d.base, d.ptr.as<const aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.ptr, vsz,
+                           &moved);
+    lt.lap("order_mat_device: sort");
+    // sort class and full diagonal again, over the sorted arrays: mat_check's answer (the row pointer was checked at creation)
+    if(rc == aoclsparse_status_success)
+        hip(hipMemsetAsync(d_res, 0, sizeof(MatCheckResult), s));
+    if(rc == aoclsparse_status_success)
+        rc = launch_matcheck_rows(s, d.m, d.n, (int)d.base, d.ptr.as<const aoclsparse_int>(), d.ind.as<const aoclsparse_int>(), d_res);
+    if(rc == aoclsparse_status_success)
+        hip(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, s));
+    if(rc == aoclsparse_status_success)
+        hip(hipStreamSynchronize(s));
+    lt.lap("order_mat_device: check kernel");
+    if(rc != aoclsparse_status_success)
+    {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(s);
+        drop_derived_state(A); // (d.valid = false with it)
+        return rc;
+    }
+    if(moved > 0) // the one copy back; rows that were ascending were not touched, so nothing moved means nothing to bring
+    {
+        hip(hipMemcpyAsync(A->user.ind, d.ind.ptr, sizeof(aoclsparse_int) * (size_t)d.nnz, hipMemcpyDeviceToHost, s));
+        hip(hipMemcpyAsync(A->user.val, d.val.ptr, vsz * (size_t)d.nnz, hipMemcpyDeviceToHost, s));
+        hip(hipStreamSynchronize(s));
+        lt.lap("order_mat_device: host view");
+    }
+    // A copy back that fails may have written part of the host view.  The class and the diagonal flag then stay what they were
+    // for the unsorted arrays (nothing may take the host view for sorted), and the mirror -- which IS sorted, every row of it --
+    // stays the handle's resident CSR, so no product uploads that view.
+    if(rc == aoclsparse_status_success && !h.first_err) // (as the host call: a row mat_check refuses leaves the two as they were)
+        A->sort = h.cls ? h.cls : 1, A->fulldiag = !h.notfull;
+    A->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
+    drop_derived_state(A); // every copy made of the unsorted arrays (clean CSR, SELL-64 / blocked-ELL, kept transpose, plans, replicas)
+    d.valid = true; // the mirror IS the handle's CSR now: resident before any product
+    if(rc != aoclsparse_status_success)
+        (void)hipGetLastError();
+    return rc;
 }
 
 aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,

@@ -976,6 +976,18 @@ enum StageSlot : int
 static_assert(STAGE_MV_Y == 4 && STAGE_DOTMV_D == 7 && STAGE_BLK_PARTS == 15 && SPG_SLOT_XP == 16 && STAGE_TR_CNT == 40
                   && SPG_SLOT_CV == 46 && COO_SLOT_KEY_A == 48 && STAGE_SLOT_COUNT == 59,
               "StageSlot: a slot moved");
+// The row sort of aoclsparse_mi355_order_mat_device (order_kernels.hip) under names of its own.  A handle is ordered outside every
+// product, under the stage lock from its first slot to the drain, so slots of the product family serve; the long rows go through the
+// COO_SLOT_* of the triplet sort, which is not running either.
+constexpr StageSlot ORD_SLOT_KEY   = SPG_SLOT_XP; // per row: its length when it has to be sorted, 0 otherwise
+constexpr StageSlot ORD_SLOT_ORDER = SPG_SLOT_XI; // the rows by bin
+constexpr StageSlot ORD_SLOT_SMALL = SPG_SLOT_XV; // histogram, cursors, flags
+constexpr StageSlot ORD_SLOT_SCAN  = SPG_SLOT_YP;
+constexpr StageSlot ORD_SLOT_LEN   = SPG_SLOT_YI; // the lengths of the long rows, in list order
+constexpr StageSlot ORD_SLOT_OFF   = SPG_SLOT_YV; // ... and their prefix sum: where a long row starts among the compacted entries
+constexpr StageSlot ORD_SLOT_MAJOR = SPG_SLOT_CNT; // per compacted entry: its long row's place in the list; behind the sort its sorted column
+constexpr StageSlot ORD_SLOT_MINOR = SPG_SLOT_ORDER_COUNT; // per compacted entry: its column
+constexpr StageSlot ORD_SLOT_VAL   = SPG_SLOT_ORDER_FILL; // the sorted values of the long rows before they go back
 // the k-th slot after a named one (the ptr / ind / val triples of an operand; the A / B pair of the sort)
 constexpr StageSlot operator+(StageSlot s, int k)
 {
@@ -1132,6 +1144,18 @@ aoclsparse_status device_coo_to_csr(hipStream_t s, aoclsparse_int M, aoclsparse_
 // Enqueued on s, not waited for; reads pos, runs and val, writes `entries` values.
 aoclsparse_status device_coo_refresh_values(hipStream_t s, aoclsparse_int triplets, aoclsparse_int entries, bool sum, const int *pos,
                                             const int *runs, const void *val, size_t vsize, bool cplx, void *out);
+// The triplet sort's radix passes on their own: `count` (major, minor) pairs in HBM, 0 <= major[i] < major_range and
+// 0 <= minor[i] < minor_range, in; *perm out: count ints in a staging slot, perm[q] = the pair that comes q-th in the stable order by
+// (major, minor).  The caller holds the stage lock and drains the stream before it lets go (COO_SLOT_KEY_A .. COO_SLOT_SCAN are
+// taken); enqueued on s, not waited for.
+aoclsparse_status device_sort_pairs(hipStream_t s, aoclsparse_int count, const aoclsparse_int *major, aoclsparse_int major_range,
+                                    const aoclsparse_int *minor, aoclsparse_int minor_range, const int **perm);
+// Every row of a device CSR into ascending column order, stably, IN PLACE (order_kernels.hip): rows that are ascending already are
+// not touched.  ptr is read only.  Takes the stage lock, returns with the stream drained.  On failure the arrays may be half sorted:
+// the caller gives them up.  moved (optional): the rows that were sorted.
+aoclsparse_status device_order_rows(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
+                                    const aoclsparse_int *d_ptr, aoclsparse_int *d_ind, void *d_val, size_t vsize,
+                                    long long *moved = nullptr);
 
 // ---- device mirrors / plans ---------------------------------------------------------------------
 size_t            val_size(aoclsparse_matrix_data_type t);

@@ -215,8 +215,8 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           aoclsparse_export_?csr prefers after aoclsparse_optimize.  Works on every CSR-format handle: host-created,
  *           device-created, a result of sp2m / syrk / sypr, an adopted one.  COO, TCSR and BSR handles: invalid_value.  The
  *           pointers are READ-ONLY and valid until the handle is modified (?update_values*, ?set_value, aoclsparse_order_mat,
- *           aoclsparse_mi355_invalidate) or destroyed; val points to values of the handle's type.  The library's stream is
- *           synchronised before return.
+ *           aoclsparse_mi355_order_mat_device, aoclsparse_mi355_invalidate) or destroyed; val points to values of the handle's
+ *           type.  The library's stream is synchronised before return.
  *
  *   create_?csr_from_coo_device   (round 19) The arguments of aoclsparse_create_?coo plus `duplicates`, with row_ind, col_ind and val
  *           (nnz entries each) in device memory, in ANY order: the triplets a finite-element assembly, a graph construction or a
@@ -278,12 +278,53 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           bytes of device memory the map occupies; kept = 0 and zeros for every handle without one, which is no error.
  *           invalid_pointer for a null A or info, invalid_size for a struct_size that does not hold struct_size itself.
  *
+ *   order_mat_device   (round 23) aoclsparse_order_mat on the device: every row of the handle's CSR into ascending column order,
+ *           entries with equal columns keeping their relative order (the host call's std::stable_sort).  One entry point for all four
+ *           value types: values are moved as items of 4, 8 or 16 bytes and never computed with.  The handle ends up exactly as
+ *           aoclsparse_order_mat leaves it, bit for bit -- row_ptr, base, nnz and every value's bits untouched; sort class and
+ *           full-diagonal flag decided again over the sorted arrays (on the device, mat_check's answer); a kept triplet map
+ *           dropped; everything derived from the arrays (clean copy, SELL-64 and blocked-ELL copies, kept transpose, TRSV plans,
+ *           derived operators, replicas) dropped and rebuilt on first use -- with two differences: the work is done in HBM, and the
+ *           handle is RESIDENT afterwards (spmv_info.device_resident is 1 on return, the next product uploads nothing).  The
+ *           sorted columns and values also go into the host view by one copy back; for a host-created handle those are the
+ *           caller's own col_idx and val arrays, sorted in place as by the host call.  A mirror that is not resident or not valid
+ *           is uploaded from the host view first, so the call works on every CSR-format handle: host-created, device-created,
+ *           triplet-created, a result of sp2m / syrk / sypr, an adopted one.
+ *           The sort is segmented (a row is a segment) with key (column, position in the row); rows that are ascending already
+ *           are found by one pass over col_idx and not touched -- on a fully sorted handle that pass is all the sort costs, and
+ *           nothing is copied back.  Rows of up to AOCLSPARSE_MI355_ORDER_SHORT_MAX entries are sorted by one lane each, rows of
+ *           up to AOCLSPARSE_MI355_ORDER_LDS_MAX entries by a workgroup in LDS (bitonic network over 64-bit keys), the entries of
+ *           longer rows go, compacted, through the radix passes of the triplet sort: a row may hold any share of the entries.  No
+ *           float atomics: the result is a pure function of the input.
+ *           Statuses, in aoclsparse_order_mat's order, all decided before the device is touched: invalid_pointer for a null A;
+ *           invalid_value for a negative m, n or nnz; not_implemented for a handle whose format is not CSR (COO, TCSR, BSR);
+ *           success at once, nothing touched, for m == 0, n == 0 or nnz == 0; invalid_pointer for a handle without CSR arrays;
+ *           and in addition not_implemented for a handle created from CSC arrays (the host call sorts the caller's host CSC
+ *           arrays there).
+ *           The work is ordered behind the products on the library's stream, which is synchronised before return.  Pointers
+ *           that export_csr_device returned earlier become invalid (the arrays behind them are rewritten in place).
+ *           Failure (allocation, HIP): the mirror is sorted in place and the host view is committed only by the copy back, after
+ *           all device work has succeeded.  Before the mirror is touched the handle is unchanged; after that, a failure leaves
+ *           the host view as it was, the mirror invalid (the next product uploads the host view again) and derived state dropped.
+ *           A failure of the copy back itself is reported as internal_error: the two host arrays may then hold rows of both
+ *           orders, so the sort class and the full-diagonal flag stay those of the unsorted arrays, and the mirror, which is
+ *           sorted in every row, stays the handle's resident CSR (no product uploads that host view).  Destroy such a handle.
+ *           Peak extra device memory: 8 bytes per row (the row's key and its place in the bins), and for the entries of rows
+ *           longer than AOCLSPARSE_MI355_ORDER_LDS_MAX only: 24 + sizeof(value) bytes per entry (two 4-byte keys, the sort's two
+ *           (key, position) pairs, the sorted value) plus 2 KiB per 4,096 of them for the digit counts.  Nothing per entry
+ *           otherwise.  The temporaries are staging slots: aoclsparse_mi355_release_staging frees them.
+ *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
  * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
  * arrays); a refresh that changes the set of coordinates; carrying the triplet map through aoclsparse_copy, exported state or
  * replicas; a host-pointer twin of ?refresh_values_from_coo_device; sorting
- * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still). */
+ * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still);
+ * aoclsparse_order_mat itself taking the device route; adding repeated columns while ordering; ordering CSC-created, TCSR or BSR
+ * handles on the device; building aoclsparse_optimize's clean (sorted, full-diagonal) copy on the device; a host view that is
+ * filled on first use instead of by order_mat_device's copy back. */
 #define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
+#define AOCLSPARSE_MI355_ORDER_SHORT_MAX 32 /* order_mat_device: rows of up to this many entries are sorted by one lane */
+#define AOCLSPARSE_MI355_ORDER_LDS_MAX 2048 /* ... of up to this many by a workgroup in LDS; longer ones by the radix sort */
 typedef enum
 {
     aoclsparse_mi355_coo_keep = 0, /* repeated coordinates stay separate entries, in triplet order */
@@ -342,6 +383,7 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_crefresh_values_from_coo_device(ao
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len,
                                                                               const aoclsparse_double_complex *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_coo_map_info(aoclsparse_matrix A, aoclsparse_mi355_coo_map_info *info);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
                                                                 aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
                                                                 const aoclsparse_int **col_idx, const void **val);
