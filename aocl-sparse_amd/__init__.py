@@ -33,6 +33,7 @@ COO_KEEP_MAP = 16  # aoclsparse_mi355_coo_keep_map: flag ORed to either, the han
 COO_SORT_TILE = 4096  # AOCLSPARSE_MI355_COO_SORT_TILE: entries a workgroup of the triplet sort takes per pass
 ORDER_SHORT_MAX = 32  # AOCLSPARSE_MI355_ORDER_SHORT_MAX: order_device sorts rows of up to this many entries with one lane each
 ORDER_LDS_MAX = 2048  # AOCLSPARSE_MI355_ORDER_LDS_MAX: ... of up to this many in LDS; longer rows go through the radix sort
+CLEAN_ROW_WAVE = 64  # AOCLSPARSE_MI355_CLEAN_ROW_WAVE: clean_device searches rows of up to this many entries with one lane each
 
 STATUS = {
     0: "success", 1: "not_implemented", 2: "invalid_pointer", 3: "invalid_size", 4: "internal_error",
@@ -420,6 +421,7 @@ SIGNATURES = {
     "aoclsparse_mi355_zrefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_get_coo_map_info": (c_int, [_P, _P]),
     "aoclsparse_mi355_order_mat_device": (c_int, [_P]),
+    "aoclsparse_mi355_clean_csr_device": (c_int, [_P]),
     "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
                                                    POINTER(_P)]),
     "aoclsparse_mi355_comm_unique_id": (c_int, [POINTER(CommId)]),
@@ -657,6 +659,11 @@ class Matrix:
         """aoclsparse_mi355_order_mat_device: every row into ascending column order (stable), sorted in HBM; the handle is
         resident afterwards and its host view (for a host-created handle: the caller's arrays) holds the sorted arrays -> status"""
         return lib().aoclsparse_mi355_order_mat_device(self.h)
+
+    def clean_device(self):
+        """aoclsparse_mi355_clean_csr_device: the clean CSR (rows in group order, full diagonal, idiag / iurow) that
+        aoclsparse_optimize and the solves otherwise build on the host, built in HBM; export() and export_diag() show it -> status"""
+        return lib().aoclsparse_mi355_clean_csr_device(self.h)
 
     def export_device(self):
         """aoclsparse_mi355_export_csr_device -> dict(status, base, m, n, nnz, row_ptr, col_ind, val): the last three are device

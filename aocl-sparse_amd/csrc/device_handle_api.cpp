@@ -18,9 +18,13 @@
 //
 // Round 23: aoclsparse_mi355_order_mat_device is aoclsparse_order_mat with the sort done on the mirror (order_kernels.hip) and the
 // handle resident afterwards.
+//
+// Round 24: aoclsparse_mi355_clean_csr_device is csr_optimize (matrix.cpp) with the work done on the mirror
+// (clean_csr_kernels.hip): the clean CSR, idiag / iurow and the diagonal's values, committed after one copy back.
 #include "matcheck.hpp"
 
 #include <cstring>
+#include <limits>
 
 using namespace mi355;
 
@@ -471,6 +475,199 @@ aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A)
     if(rc != aoclsparse_status_success)
         (void)hipGetLastError();
     return rc;
+}
+
+aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A)
+{
+    // the statuses of csr_optimize (matrix.cpp), in its order, all before the device is touched
+    if(!A)
+        return aoclsparse_status_invalid_pointer;
+    {
+        std::shared_lock<std::shared_mutex> r(A->guard);
+        if(A->opt)
+            return aoclsparse_status_success;
+    }
+    if(holds_no_csr(A)) // TCSR and BSR handles
+        return aoclsparse_status_not_implemented;
+    if(!A->user.ptr || !A->user.ind || !A->user.val) // COO handles
+        return aoclsparse_status_invalid_pointer;
+    Runtime          &rt = Runtime::get();
+    aoclsparse_status rc = rt.init();
+    if(rc != aoclsparse_status_success)
+        return rc;
+    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
+    std::unique_lock<std::shared_mutex>   w(A->guard);
+    if(A->opt) // (another thread's csr_optimize got here first)
+        return aoclsparse_status_success;
+    hipStream_t  s   = rt.stream();
+    const size_t vsz = val_size(A->val_type);
+    DeviceCsr   &d   = A->dev_user;
+    // Everything below is built in buffers of this call's and committed at the very end; until then the handle is as it was, except
+    // that a mirror that was not resident or not valid has come from the host view (as for export_csr_device).  Whatever way out is
+    // taken, the stream first finishes what was enqueued on the staging slots and on those buffers (declared first: released last).
+    DeviceBuffer                      res, sind, sval, cptr, cind, cval, didiag, diurow, ddiag;
+    std::unique_ptr<HostCsr>          c;
+    std::unique_ptr<aoclsparse_int[]> idiag, iurow;
+    struct DrainOnExit
+    {
+        hipStream_t s;
+        ~DrainOnExit()
+        {
+            (void)hipStreamSynchronize(s);
+            (void)hipGetLastError(); // (a failed launch or copy is reported by this call's status, not by the next call's)
+        }
+    } drain{s};
+    if(!d.valid && (rc = upload_csr(A->user, vsz, d)) != aoclsparse_status_success)
+        return rc;
+    const aoclsparse_int m = A->user.m, n = A->user.n, nnz = A->nnz; // (what csr_optimize reads)
+    if(d.m != m || d.nnz != nnz || !d.ptr.ptr || !d.ind.ptr || !d.val.ptr)
+        return aoclsparse_status_internal_error;
+    const int             base  = (int)d.base;
+    const aoclsparse_int *d_ptr = d.ptr.as<const aoclsparse_int>();
+    LapTimer              lt;
+    // mat_check's answer over the mirror, once: the row pointer first (the kernels below trust it), then validity, sort class and
+    // full diagonal.  Class <= 2 is check_sort_diag's `sorted`.
+    if((rc = res.alloc(sizeof(MatCheckResult))) != aoclsparse_status_success)
+        return rc;
+    MatCheckResult *d_res = res.as<MatCheckResult>(), h{};
+    if((rc = launch_matcheck_ptr(s, m, nnz, base, d_ptr, d_res)) != aoclsparse_status_success)
+        return rc;
+    MI355_HIP_TRY(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if(h.ptr_bad)
+        return aoclsparse_status_invalid_value;
+    if((rc = launch_matcheck_rows(s, m, n, base, d_ptr, d.ind.as<const aoclsparse_int>(), d_res)) != aoclsparse_status_success)
+        return rc;
+    MI355_HIP_TRY(hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if(h.first_err)
+        return (aoclsparse_status)(~h.first_err & 0xff);
+    const bool sorted = h.cls <= 2, fulldiag = !h.notfull;
+    lt.lap("clean_csr_device: mirror + check");
+
+    // case 3: the rows into ascending order first, on a copy of the mirror's columns and values
+    const void  *src_val = d.val.ptr;
+    auto        *src_ind = d.ind.as<const aoclsparse_int>();
+    if(!sorted)
+    {
+        if((rc = sind.clone_from(d.ind, s)) != aoclsparse_status_success || (rc = sval.clone_from(d.val, s)) != aoclsparse_status_success)
+            return rc;
+        if((rc = device_order_rows(s, m, n, nnz, base, d_ptr, sind.as<aoclsparse_int>(), sval.ptr, vsz)) != aoclsparse_status_success)
+            return rc;
+        src_ind = sind.as<const aoclsparse_int>(), src_val = sval.ptr;
+        lt.lap("clean_csr_device: sort");
+    }
+    // mark, and for a copy the clean row pointer with its 64-bit total
+    const bool   copy = !sorted || !fulldiag;
+    const size_t rb   = sizeof(int) * (size_t)std::max<aoclsparse_int>(m, 1);
+    void        *p    = nullptr;
+    if((rc = rt.staging(CLN_SLOT_AT, rb, &p)) != aoclsparse_status_success)
+        return rc;
+    int *const at_p = static_cast<int *>(p);
+    if((rc = rt.staging(CLN_SLOT_MISS, rb, &p)) != aoclsparse_status_success)
+        return rc;
+    int *const miss_p = static_cast<int *>(p);
+    if((rc = rt.staging(CLN_SLOT_CNT, rb, &p)) != aoclsparse_status_success)
+        return rc;
+    int *const cnt_p = static_cast<int *>(p);
+    if((rc = launch_clean_mark(s, m, n, nnz, base, d_ptr, src_ind, at_p, miss_p, cnt_p)) != aoclsparse_status_success)
+        return rc;
+    aoclsparse_int total = nnz;
+    if(copy)
+    {
+        if((rc = cptr.alloc(sizeof(aoclsparse_int) * ((size_t)m + 1))) != aoclsparse_status_success
+           || (rc = rt.staging(CLN_SLOT_SCAN, spg_scan_scratch_bytes(m), &p)) != aoclsparse_status_success)
+            return rc;
+        long long *total_dev = nullptr, total_ll = 0;
+        if((rc = launch_spg_scan(s, m, cnt_p, cptr.as<aoclsparse_int>(), static_cast<long long *>(p), &total_dev))
+           != aoclsparse_status_success)
+            return rc;
+        MI355_HIP_TRY(hipMemcpyAsync(&total_ll, total_dev, sizeof(total_ll), hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipStreamSynchronize(s));
+        if(total_ll > (long long)std::numeric_limits<aoclsparse_int>::max())
+            return aoclsparse_status_invalid_size; // nnz + the inserted entries do not fit the index type
+        if(total_ll < (long long)nnz || total_ll > (long long)nnz + std::min(m, n))
+            return aoclsparse_status_internal_error;
+        total = (aoclsparse_int)total_ll;
+        lt.lap("clean_csr_device: mark + scan");
+    }
+    // the host arrays the result goes into: big ones as build_transpose allocates them
+    idiag.reset(new(std::nothrow) aoclsparse_int[m > 0 ? m : 1]);
+    iurow.reset(new(std::nothrow) aoclsparse_int[m > 0 ? m : 1]);
+    if(!idiag || !iurow)
+        return aoclsparse_status_memory_error;
+    const size_t ib = sizeof(aoclsparse_int) * (size_t)total, vb = vsz * (size_t)total;
+    if(copy)
+    {
+        c.reset(new(std::nothrow) HostCsr);
+        if(!c)
+            return aoclsparse_status_memory_error;
+        c->m = m, c->n = n, c->nnz = total, c->base = aoclsparse_index_base_zero;
+        c->owned = c->result_arrays = true;
+        c->ptr = new(std::nothrow) aoclsparse_int[(size_t)m + 1];
+        c->ind = static_cast<aoclsparse_int *>(host_result_alloc(ib));
+        c->val = host_result_alloc(vb);
+        if(!c->ptr || !c->ind || !c->val)
+            return aoclsparse_status_memory_error;
+        host_result_touch(c->ind, ib);
+        host_result_touch(c->val, vb);
+        lt.lap("clean_csr_device: host arrays");
+    }
+    // expand and finish
+    if((rc = didiag.alloc(rb)) != aoclsparse_status_success || (rc = diurow.alloc(rb)) != aoclsparse_status_success
+       || (rc = ddiag.alloc(vsz * (size_t)std::max<aoclsparse_int>(m, 1))) != aoclsparse_status_success)
+        return rc;
+    if(copy)
+    {
+        if((rc = cind.alloc(ib)) != aoclsparse_status_success || (rc = cval.alloc(vb)) != aoclsparse_status_success)
+            return rc;
+        if((rc = launch_clean_expand(s, m, nnz, total, base, d_ptr, src_ind, src_val, vsz, cptr.as<const aoclsparse_int>(), at_p, miss_p,
+                                     cind.as<aoclsparse_int>(), cval.ptr))
+           != aoclsparse_status_success)
+            return rc;
+    }
+    if((rc = launch_clean_finish(s, m, n, nnz, base, d_ptr, src_val, vsz, copy ? cptr.as<const aoclsparse_int>() : nullptr, at_p, miss_p,
+                                 didiag.as<aoclsparse_int>(), diurow.as<aoclsparse_int>(), ddiag.ptr))
+       != aoclsparse_status_success)
+        return rc;
+    if(PhaseTimer::on()) // (the diagnostic separates the kernels from the copy back)
+        MI355_HIP_TRY(hipStreamSynchronize(s));
+    lt.lap("clean_csr_device: expand + finish");
+    // the one copy back; the diagonal's values stay in HBM
+    if(m > 0)
+    {
+        MI355_HIP_TRY(hipMemcpyAsync(idiag.get(), didiag.ptr, sizeof(aoclsparse_int) * (size_t)m, hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipMemcpyAsync(iurow.get(), diurow.ptr, sizeof(aoclsparse_int) * (size_t)m, hipMemcpyDeviceToHost, s));
+    }
+    if(copy)
+    {
+        MI355_HIP_TRY(hipMemcpyAsync(c->ptr, cptr.ptr, sizeof(aoclsparse_int) * ((size_t)m + 1), hipMemcpyDeviceToHost, s));
+        if(total > 0)
+        {
+            MI355_HIP_TRY(hipMemcpyAsync(c->ind, cind.ptr, ib, hipMemcpyDeviceToHost, s));
+            MI355_HIP_TRY(hipMemcpyAsync(c->val, cval.ptr, vb, hipMemcpyDeviceToHost, s));
+        }
+    }
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    lt.lap("clean_csr_device: copy back");
+    // commit: what csr_optimize sets, and the diagonal ensure_trsv would otherwise gather on the host and upload
+    A->sort = h.cls ? h.cls : 1, A->fulldiag = fulldiag;
+    HostCsr &o = copy ? *c : A->user;
+    delete[] o.idiag;
+    delete[] o.iurow;
+    o.idiag = idiag.release(), o.iurow = iurow.release();
+    o.is_optimized = true;
+    if(copy)
+    {
+        A->opt_copy = std::move(c);
+        A->opt      = A->opt_copy.get();
+    }
+    else
+        A->opt = &A->user;
+    A->opt_csr_full_diag = fulldiag;
+    A->optimized         = true;
+    A->dev_diag.adopt(ddiag);
+    return aoclsparse_status_success;
 }
 
 aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,

@@ -988,6 +988,13 @@ constexpr StageSlot ORD_SLOT_OFF   = SPG_SLOT_YV; // ... and their prefix sum: w
 constexpr StageSlot ORD_SLOT_MAJOR = SPG_SLOT_CNT; // per compacted entry: its long row's place in the list; behind the sort its sorted column
 constexpr StageSlot ORD_SLOT_MINOR = SPG_SLOT_ORDER_COUNT; // per compacted entry: its column
 constexpr StageSlot ORD_SLOT_VAL   = SPG_SLOT_ORDER_FILL; // the sorted values of the long rows before they go back
+// The per-row temporaries of aoclsparse_mi355_clean_csr_device (clean_csr_kernels.hip) under names of their own.  device_order_rows
+// runs INSIDE that call (on a copy of an unsorted handle's columns and values), so these are product slots that ORD_SLOT_* and the
+// triplet sort's COO_SLOT_* do not name; a clean copy is built outside every product, under the stage lock to the drain.
+constexpr StageSlot CLN_SLOT_AT   = SPG_SLOT_HEAVY_COUNT; // per row: the offset of its first entry at or right of the diagonal
+constexpr StageSlot CLN_SLOT_MISS = SPG_SLOT_HEAVY_FILL; // per row: 1 when a diagonal entry is inserted
+constexpr StageSlot CLN_SLOT_CNT  = SPG_SLOT_G_KEY; // per row: the clean row length
+constexpr StageSlot CLN_SLOT_SCAN = SPG_SLOT_G_POS;
 // the k-th slot after a named one (the ptr / ind / val triples of an operand; the A / B pair of the sort)
 constexpr StageSlot operator+(StageSlot s, int k)
 {
@@ -1156,6 +1163,19 @@ aoclsparse_status device_sort_pairs(hipStream_t s, aoclsparse_int count, const a
 aoclsparse_status device_order_rows(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
                                     const aoclsparse_int *d_ptr, aoclsparse_int *d_ind, void *d_val, size_t vsize,
                                     long long *moved = nullptr);
+
+// The clean copy of a device CSR (clean_csr_kernels.hip; any base in, 0-based out).  All three are enqueued on s, not waited for.
+// mark: per row at / miss / cnt (m ints each) -- the offset of the first entry with column >= i, whether a diagonal entry is to be
+// inserted, the clean row length.  expand: the `total` entries of the clean copy to cind / cval, cptr = the exclusive scan of cnt.
+// finish: idiag / iurow (positions in cptr; cptr == nullptr: in d_ptr itself, keeping its base) and diag, m items of vsize bytes.
+aoclsparse_status launch_clean_mark(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
+                                    const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, int *at, int *miss, int *cnt);
+aoclsparse_status launch_clean_expand(hipStream_t s, aoclsparse_int m, aoclsparse_int nnz, aoclsparse_int total, int base,
+                                      const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, const void *d_val, size_t vsize,
+                                      const aoclsparse_int *cptr, const int *at, const int *miss, aoclsparse_int *cind, void *cval);
+aoclsparse_status launch_clean_finish(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
+                                      const aoclsparse_int *d_ptr, const void *d_val, size_t vsize, const aoclsparse_int *cptr,
+                                      const int *at, const int *miss, aoclsparse_int *idiag, aoclsparse_int *iurow, void *diag);
 
 // ---- device mirrors / plans ---------------------------------------------------------------------
 size_t            val_size(aoclsparse_matrix_data_type t);

@@ -314,17 +314,56 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           (key, position) pairs, the sorted value) plus 2 KiB per 4,096 of them for the digit counts.  Nothing per entry
  *           otherwise.  The temporaries are staging slots: aoclsparse_mi355_release_staging frees them.
  *
+ *   clean_csr_device   (round 24) The clean CSR aoclsparse_optimize, every ?trsv / ?trsm, symgs, the ILU smoother and the iterative
+ *           solvers build on first use (csr_optimize), built in HBM.  Afterwards the handle holds exactly what csr_optimize would
+ *           have given it, bit for bit -- the clean arrays with idiag / iurow, the full-diagonal flag of the ORIGINAL arrays (the
+ *           non-unit solves refuse on it), `optimized` -- so every later caller finds the clean CSR present and does nothing;
+ *           aoclsparse_export_?csr and aoclsparse_mi355_export_diag show it.  No plan option chooses this route: it is taken through
+ *           this call only.  One entry point for all four value types: values are moved as items of 4, 8 or 16 bytes and never
+ *           computed with.  The three cases are csr_optimize's, decided by the check kernels over the handle's mirror:
+ *           (1) rows in L | D | U group order (sort class 1 or 2) and a full diagonal: no copy, the clean CSR is the handle's own
+ *           arrays; only idiag / iurow are computed, in the matrix's base (idiag[i] = the first position of row i whose column is
+ *           >= i, or the row end; iurow[i] = idiag[i] + 1 when that entry is the diagonal), and come back as 2 x 4 bytes per row;
+ *           export_diag reports is_internal = 0.  (2) group order, a diagonal entry missing: a 0-based copy with every row's entries
+ *           in their GIVEN order (a class-2 row is not sorted, as on the host) and, in every row i < min(m, n) without a diagonal
+ *           entry, an explicit zero -- the all-zero bit pattern -- in front of the row's first entry whose column is >= i, at the
+ *           row's end when there is none.  (3) any other order: every row first into ascending column order, stably
+ *           (order_mat_device's sort, run on a device copy of the columns and values, never on the mirror), then as (2).  In (2)
+ *           and (3) idiag / iurow are those of the copy, 0-based, and is_internal = 1.  m == 0 and nnz == 0 behave as on the host:
+ *           a matrix of empty rows with n > 0 gets its diagonal of zeros.
+ *           The mirror is uploaded from the host view first when it is not resident or not valid, stays valid and untouched, and
+ *           the handle is resident on return; the caller's host arrays are not written; a kept triplet map, SELL-64 copies, the
+ *           transpose and the plans stay.  The diagonal's values (what the TRSV launchers read: m items, zero where a row has no
+ *           diagonal entry or got an inserted one) are written on the device in the same pass and stay there.
+ *           Rows of up to AOCLSPARSE_MI355_CLEAN_ROW_WAVE entries are searched by one lane each, longer ones by their wavefront;
+ *           the copy is balanced over entries, not rows: one row may hold every entry.  No atomics, no workgroup waits for another.
+ *           Statuses, in csr_optimize's order, all decided before the device is touched: invalid_pointer for a null A; success at
+ *           once, nothing touched, when the handle has its clean CSR already; not_implemented for TCSR and BSR handles;
+ *           invalid_pointer for a handle without CSR arrays (COO).  After those a failure of the runtime's initialisation is
+ *           returned as it is (a machine without a GPU), then what mat_check answers for arrays it refuses.  invalid_size when
+ *           nnz + the inserted entries exceed 2^31 - 1 (the host route overflows there); the handle is unchanged.
+ *           Failure (allocation, HIP): everything is built in fresh buffers and committed only after the one copy back has
+ *           synchronised successfully; on any failure the handle is as it was before the call, except that its mirror may have
+ *           gone from "not uploaded" to "uploaded".  The library's stream is synchronised before return.
+ *           Peak extra device memory: 20 bytes + sizeof(value) per row (three 4-byte temporaries in staging slots, idiag, iurow,
+ *           the diagonal's value, of which only the last stays) plus 8 bytes per 1,024 rows for the scan; in cases (2) and (3)
+ *           4 bytes per row + (4 + sizeof(value)) per entry of the copy, released after the copy back (nothing consumes a resident
+ *           clean copy yet); in case (3) also (4 + sizeof(value)) per entry for the sorted copy, and what order_mat_device needs.
+ *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
  * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
  * arrays); a refresh that changes the set of coordinates; carrying the triplet map through aoclsparse_copy, exported state or
  * replicas; a host-pointer twin of ?refresh_values_from_coo_device; sorting
  * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still);
  * aoclsparse_order_mat itself taking the device route; adding repeated columns while ordering; ordering CSC-created, TCSR or BSR
- * handles on the device; building aoclsparse_optimize's clean (sorted, full-diagonal) copy on the device; a host view that is
- * filled on first use instead of by order_mat_device's copy back. */
+ * handles on the device; csr_optimize / aoclsparse_optimize choosing the device route for the clean copy by themselves; keeping the
+ * clean copy resident and building TRSV plans, derived operators or ILU factors from it on the device; a values-only refresh of an
+ * existing clean copy after a value update; clean copies of the transpose; a host view that is filled on first use instead of by
+ * order_mat_device's copy back. */
 #define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
 #define AOCLSPARSE_MI355_ORDER_SHORT_MAX 32 /* order_mat_device: rows of up to this many entries are sorted by one lane */
 #define AOCLSPARSE_MI355_ORDER_LDS_MAX 2048 /* ... of up to this many by a workgroup in LDS; longer ones by the radix sort */
+#define AOCLSPARSE_MI355_CLEAN_ROW_WAVE 64 /* clean_csr_device: rows of up to this many entries are searched by one lane */
 typedef enum
 {
     aoclsparse_mi355_coo_keep = 0, /* repeated coordinates stay separate entries, in triplet order */
@@ -384,6 +423,7 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrefresh_values_from_coo_device(ao
                                                                               const aoclsparse_double_complex *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_coo_map_info(aoclsparse_matrix A, aoclsparse_mi355_coo_map_info *info);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
                                                                 aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
                                                                 const aoclsparse_int **col_idx, const void **val);
