@@ -72,6 +72,13 @@ class CooMapInfo(ctypes.Structure):
                 ("entries", c_int32), ("map_bytes", ctypes.c_longlong)]
 
 
+class ValueMapInfo(ctypes.Structure):
+    """aoclsparse_mi355_value_map_info: the caller sets struct_size, the library writes no more than that"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("enabled", c_int32), ("clean_map", c_int32), ("plans_mapped", c_int32),
+                ("last_kept_plans", c_int32), ("plan_builds", ctypes.c_longlong), ("clean_builds", ctypes.c_longlong),
+                ("revalues", ctypes.c_longlong), ("map_bytes", ctypes.c_longlong)]
+
+
 MM_STATE_BUFFERS = 14
 
 
@@ -420,6 +427,12 @@ SIGNATURES = {
     "aoclsparse_mi355_crefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_zrefresh_values_from_coo_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_get_coo_map_info": (c_int, [_P, _P]),
+    "aoclsparse_mi355_keep_value_maps": (c_int, [_P, _I]),
+    "aoclsparse_mi355_srevalue_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_drevalue_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_crevalue_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_zrevalue_device": (c_int, [_P, _I, _P]),
+    "aoclsparse_mi355_get_value_map_info": (c_int, [_P, _P]),
     "aoclsparse_mi355_order_mat_device": (c_int, [_P]),
     "aoclsparse_mi355_clean_csr_device": (c_int, [_P]),
     "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
@@ -652,6 +665,25 @@ class Matrix:
         """aoclsparse_mi355_get_coo_map_info -> CooMapInfo (kept, mode, triplets, entries, map_bytes)"""
         info = CooMapInfo(struct_size=ctypes.sizeof(CooMapInfo))
         st = lib().aoclsparse_mi355_get_coo_map_info(self.h, byref(info))
+        assert st == 0, STATUS.get(st, st)
+        return info
+
+    def keep_value_maps(self, on=True):
+        """aoclsparse_mi355_keep_value_maps: from now on the clean copy clean_device() makes and the TRSV plans record where their
+        values come from, so that revalue_device can carry them over; on=False releases the maps -> status"""
+        return lib().aoclsparse_mi355_keep_value_maps(self.h, 1 if on else 0)
+
+    def revalue_device(self, val):
+        """aoclsparse_mi355_?revalue_device: update_values_device that keeps the clean CSR, the diagonal and the TRSV plans that hold
+        value maps, bringing them the new values in HBM -> status"""
+        n = int(val.numel()) if hasattr(val, "numel") else self.nnz
+        return getattr(lib(), "aoclsparse_mi355_%srevalue_device" % self._letter())(self.h, n, _ptr(val))
+
+    def value_map_info(self):
+        """aoclsparse_mi355_get_value_map_info -> ValueMapInfo (enabled, clean_map, plans_mapped, last_kept_plans, plan_builds,
+        clean_builds, revalues, map_bytes)"""
+        info = ValueMapInfo(struct_size=ctypes.sizeof(ValueMapInfo))
+        st = lib().aoclsparse_mi355_get_value_map_info(self.h, byref(info))
         assert st == 0, STATUS.get(st, st)
         return info
 

@@ -17,7 +17,8 @@
 //   (2) launch_spg_scan    (spgemm_kernels.hip) cnt -> the clean row pointer, with a 64-bit total.
 //   (3) cln_expand_kernel  balanced over ENTRIES of the clean copy, 1,024 per workgroup whatever rows they belong to: a workgroup
 //                          finds the rows of its first and last entry by binary search in the clean row pointer, every thread the
-//                          row of its entry between the two; the entry is the inserted (i, 0) or comes from its source position.
+//                          row of its entry between the two; the entry is the inserted (i, 0) or comes from its source position
+//                          (written out as well where the caller keeps value maps: csrc, -1 for an inserted entry).
 //   (4) cln_finish_kernel  per row: idiag = clean_ptr + at, iurow = idiag + (the clean row holds a diagonal entry: i < min(m, n)),
 //                          diag[i] = the diagonal's value, the zero item where it was inserted or i >= min(m, n).  For arrays that
 //                          are clean already the "clean row pointer" is the matrix's own, and the two keep its base.
@@ -129,7 +130,7 @@ namespace
                                                              const aoclsparse_int *__restrict__ ind, const V *__restrict__ val,
                                                              const aoclsparse_int *__restrict__ cptr, const int *__restrict__ at,
                                                              const int *__restrict__ miss, aoclsparse_int *__restrict__ cind,
-                                                             V *__restrict__ cval)
+                                                             V *__restrict__ cval, int *__restrict__ csrc)
     {
         __shared__ int  rows[2];
         const long long q0 = (long long)blockIdx.x * CLN_EXPAND; // (< total: the grid is ceil(total / CLN_EXPAND))
@@ -148,6 +149,8 @@ namespace
             {
                 cind[q] = i;
                 cval[q] = V{};
+                if(csrc) // (the value map of a handle that keeps them: an inserted entry has no source)
+                    csrc[q] = -1;
             }
             else
             {
@@ -155,6 +158,8 @@ namespace
                 const int src = min(max(ptr[i] - base + k - (ms && k > a), 0), nnz - 1);
                 cind[q]       = ind[src] - base;
                 cval[q]       = val[src];
+                if(csrc)
+                    csrc[q] = src;
             }
         }
     }
@@ -213,7 +218,8 @@ aoclsparse_status launch_clean_mark(hipStream_t s, aoclsparse_int m, aoclsparse_
 
 aoclsparse_status launch_clean_expand(hipStream_t s, aoclsparse_int m, aoclsparse_int nnz, aoclsparse_int total, int base,
                                       const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, const void *d_val, size_t vsize,
-                                      const aoclsparse_int *cptr, const int *at, const int *miss, aoclsparse_int *cind, void *cval)
+                                      const aoclsparse_int *cptr, const int *at, const int *miss, aoclsparse_int *cind, void *cval,
+                                      int *csrc)
 {
     if(m <= 0 || total <= 0)
         return aoclsparse_status_success;
@@ -221,7 +227,7 @@ aoclsparse_status launch_clean_expand(hipStream_t s, aoclsparse_int m, aoclspars
     aoclsparse_status st   = by_item_size(vsize, [&](auto v) {
         using V = decltype(v);
         hipLaunchKernelGGL((cln_expand_kernel<V>), dim3(grid), dim3(256), 0, s, total, m, nnz, base, d_ptr, d_ind,
-                           static_cast<const V *>(d_val), cptr, at, miss, cind, static_cast<V *>(cval));
+                           static_cast<const V *>(d_val), cptr, at, miss, cind, static_cast<V *>(cval), csrc);
     });
     if(st != aoclsparse_status_success)
         return st;

@@ -235,10 +235,10 @@ namespace
         return rc;
     }
 
-    template <typename T>
-    aoclsparse_status update_values_device(aoclsparse_matrix A, aoclsparse_int len, const T *val, aoclsparse_matrix_data_type vt)
+    // what ?update_values_device and ?revalue_device decide before the device is touched: the statuses of update_values
+    // (matrix.cpp), in its order, then the runtime and the kind of pointer
+    aoclsparse_status check_update_values_device(aoclsparse_matrix A, aoclsparse_int len, const void *val, aoclsparse_matrix_data_type vt)
     {
-        // the statuses of update_values (matrix.cpp), in its order
         const bool coo = A && A->input_format == aoclsparse_coo_mat, nocsr = A && holds_no_csr(A);
         if(!A || !val || (coo ? !A->coo_val : (!nocsr && !A->user.ptr)))
             return aoclsparse_status_invalid_pointer;
@@ -260,6 +260,16 @@ namespace
             return rc;
         if(!rt.is_device_pointer(val))
             return aoclsparse_status_invalid_pointer;
+        return aoclsparse_status_success;
+    }
+
+    template <typename T>
+    aoclsparse_status update_values_device(aoclsparse_matrix A, aoclsparse_int len, const T *val, aoclsparse_matrix_data_type vt)
+    {
+        aoclsparse_status rc = check_update_values_device(A, len, val, vt);
+        if(rc != aoclsparse_status_success)
+            return rc;
+        Runtime                              &rt = Runtime::get();
         std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
         std::unique_lock<std::shared_mutex>   w(A->guard);
         hipStream_t                           s     = rt.stream();
@@ -278,6 +288,137 @@ namespace
         }
         drop_derived_state(A); // SELL-64 / blocked-ELL copies, TRSV plans, derived operators, replicas: rebuilt lazily
         d.valid = keep;
+        return aoclsparse_status_success;
+    }
+
+    // ?update_values_device that keeps what holds a value map (round 25): the clean CSR, the diagonal and the TRSV plans get the
+    // new values through their maps (revalue_kernels.hip) instead of being dropped and analysed again.  What has no map goes as
+    // it goes there.
+    template <typename T>
+    aoclsparse_status revalue_device(aoclsparse_matrix A, aoclsparse_int len, const T *val, aoclsparse_matrix_data_type vt)
+    {
+        aoclsparse_status rc = check_update_values_device(A, len, val, vt);
+        if(rc != aoclsparse_status_success)
+            return rc;
+        Runtime                              &rt = Runtime::get();
+        std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
+        std::unique_lock<std::shared_mutex>   w(A->guard);
+        hipStream_t                           s     = rt.stream();
+        const size_t                          vsz   = sizeof(T);
+        const size_t                          bytes = vsz * (size_t)len;
+        DeviceCsr                            &d     = A->dev_user;
+        const bool keep = d.valid && d.m == A->m && d.nnz == A->nnz && d.ptr.ptr && d.ind.ptr && d.val.ptr && d.val.bytes >= bytes;
+        LapTimer   lt; // (AOCLSPARSE_MI355_TIMING=1: where a revalue's time goes; the laps then wait for the stream)
+        auto       hip = [&](hipError_t e) {
+            if(e != hipSuccess && rc == aoclsparse_status_success)
+                rc = aoclsparse_status_internal_error;
+        };
+        auto lap = [&](const char *what) {
+            if(PhaseTimer::on() && rc == aoclsparse_status_success)
+                hip(hipStreamSynchronize(s));
+            lt.lap(what);
+        };
+        // what can follow: the clean CSR when it is the handle's own arrays or a copy that holds its map ...
+        HostCsr *const       o          = A->opt;
+        const bool           clean_copy = o && o != &A->user;
+        const aoclsparse_int total      = o ? o->nnz : 0; // entries of the clean CSR
+        const bool           clean_ok   = o && (!clean_copy || (o == A->opt_copy.get() && o->val && A->clean_src.ptr
+                                                      && A->clean_src.bytes >= sizeof(int) * (size_t)total));
+        // ... the diagonal when it has its map, and with it the plans whose layouts all have theirs
+        const size_t mrows   = (size_t)std::max<aoclsparse_int>(A->m, 1);
+        const bool   diag_ok = clean_ok && A->dev_diag.ptr && A->diag_src.ptr && A->diag_src.bytes >= sizeof(int) * mrows
+                             && A->dev_diag.bytes >= vsz * (size_t)A->m;
+        unsigned keep_plans = 0;
+        int      kept       = 0;
+        if(diag_ok)
+            for(int i = 0; i < 6; i++)
+            {
+                const TrsvPlan &p  = A->trsv_plan[i];
+                const size_t    ne = (size_t)std::max<aoclsparse_int>(p.nnz_tri, 0);
+                if(p.value_mapped() && (!p.rows_valid || (p.psrc.bytes >= sizeof(int) * ne && p.pval.bytes >= vsz * ne))
+                   && (!p.blk.valid || (p.blk.psrc.bytes >= sizeof(int) * ne && p.blk.pval.bytes >= vsz * ne)))
+                    keep_plans |= 1u << i, kept++;
+            }
+        DeviceBuffer cval; // the clean copy's new values, for the gathers below and the copy back
+        if(clean_ok && clean_copy && total > 0 && (rc = cval.alloc(vsz * (size_t)total)) != aoclsparse_status_success)
+            return rc; // (nothing written yet: the handle is as it was)
+        // -- from here on the handle is written.  In stream order behind every product and solve enqueued on the library's stream.
+        if(bytes)
+        {
+            hip(hipMemcpyAsync(A->user.val, val, bytes, hipMemcpyDeviceToHost, s));
+            if(keep && val != d.val.ptr)
+                hip(hipMemcpyAsync(d.val.ptr, val, bytes, hipMemcpyDeviceToDevice, s));
+        }
+        lap("revalue_device: values to host view + mirror");
+        // the diagnostic also times the gather kernels by device events: [0, 1] around the clean gather, [2, 3] around the
+        // diagonal's and the plans' (no host synchronisation in between either way)
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        if(PhaseTimer::on())
+            for(hipEvent_t &e : ev)
+                if(hipEventCreate(&e) != hipSuccess)
+                    e = nullptr;
+        auto mark = [&](int i) {
+            if(ev[i] && rc == aoclsparse_status_success)
+                hip(hipEventRecord(ev[i], s));
+        };
+        const void *clean_vals = val; // the clean CSR's value array in HBM: the new values themselves, or the gathered copy
+        long long   clean_n    = len;
+        if(clean_ok && clean_copy)
+        {
+            mark(0);
+            if(rc == aoclsparse_status_success)
+                rc = launch_revalue_gather(s, total, len, A->clean_src.as<const int>(), val, cval.ptr, vsz, false);
+            mark(1);
+            if(rc == aoclsparse_status_success && total > 0)
+                hip(hipMemcpyAsync(o->val, cval.ptr, vsz * (size_t)total, hipMemcpyDeviceToHost, s));
+            clean_vals = cval.ptr, clean_n = total;
+            lap("revalue_device: clean gather + copy back");
+        }
+        mark(2);
+        if(diag_ok && rc == aoclsparse_status_success)
+            rc = launch_revalue_gather(s, A->m, clean_n, A->diag_src.as<const int>(), clean_vals, A->dev_diag.ptr, vsz, false);
+        for(int i = 0; i < 6 && rc == aoclsparse_status_success; i++)
+        {
+            if(!(keep_plans >> i & 1u))
+                continue;
+            TrsvPlan &p = A->trsv_plan[i];
+            if(p.rows_valid)
+                rc = launch_revalue_gather(s, p.nnz_tri, clean_n, p.psrc.as<const int>(), clean_vals, p.pval.ptr, vsz, p.conj);
+            if(p.blk.valid && rc == aoclsparse_status_success)
+                rc = launch_revalue_gather(s, p.nnz_tri, clean_n, p.blk.psrc.as<const int>(), clean_vals, p.blk.pval.ptr, vsz, p.conj);
+        }
+        mark(3);
+        // the one wait: the copies back have landed, `cval` and the caller's array are no longer read
+        if(hipStreamSynchronize(s) != hipSuccess && rc == aoclsparse_status_success)
+            rc = aoclsparse_status_internal_error;
+        lt.lap("revalue_device: diagonal + plan gathers");
+        for(int i = 0; i < 4; i += 2)
+        {
+            float ms = 0.0f;
+            if(rc == aoclsparse_status_success && ev[i] && ev[i + 1] && (i == 2 || (clean_ok && clean_copy))
+               && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+                std::fprintf(stderr, "[mi355 timing]     %-30s %8.3f ms\n",
+                             i ? "revalue_device: plan gather events" : "revalue_device: clean gather events", ms);
+        }
+        for(hipEvent_t e : ev)
+            if(e)
+                (void)hipEventDestroy(e);
+        if(rc != aoclsparse_status_success)
+        {
+            // what ?update_values_device leaves: everything dropped, no plan with some old and some new values; the maps go too.
+            // The mirror may hold either values: the next product uploads the host view.
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s);
+            drop_derived_state(A);
+            A->drop_value_maps();
+            d.valid = false;
+            return rc;
+        }
+        drop_derived_state_keeping(A, clean_ok, keep_plans); // SELL-64 / blocked-ELL copies, transposes, derived operators, replicas
+        if(!diag_ok) // (a diagonal without its map: ensure_trsv gathers it again; no plan was kept)
+            A->dev_diag.release(), A->diag_src.release();
+        d.valid = keep;
+        A->revalues++, A->last_kept_plans = kept;
         return aoclsparse_status_success;
     }
 } // namespace
@@ -353,6 +494,65 @@ aoclsparse_status aoclsparse_mi355_cupdate_values_device(aoclsparse_matrix A, ao
 aoclsparse_status aoclsparse_mi355_zupdate_values_device(aoclsparse_matrix A, aoclsparse_int len, const aoclsparse_double_complex *val)
 {
     return update_values_device(A, len, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_srevalue_device(aoclsparse_matrix A, aoclsparse_int len, const float *val)
+{
+    return revalue_device(A, len, val, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_mi355_drevalue_device(aoclsparse_matrix A, aoclsparse_int len, const double *val)
+{
+    return revalue_device(A, len, val, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_mi355_crevalue_device(aoclsparse_matrix A, aoclsparse_int len, const aoclsparse_float_complex *val)
+{
+    return revalue_device(A, len, val, aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_mi355_zrevalue_device(aoclsparse_matrix A, aoclsparse_int len, const aoclsparse_double_complex *val)
+{
+    return revalue_device(A, len, val, aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_keep_value_maps(aoclsparse_matrix A, aoclsparse_int on)
+{
+    if(!A)
+        return aoclsparse_status_invalid_pointer;
+    if(holds_no_csr(A)) // TCSR and BSR handles
+        return aoclsparse_status_not_implemented;
+    // stage_lock, then the handle's guard, as the siblings: on == 0 frees device buffers, and whoever enqueues work that reads the
+    // maps (?revalue_device) holds the stage lock until the stream has finished with them
+    std::lock_guard<std::recursive_mutex> sl(Runtime::get().stage_lock);
+    std::unique_lock<std::shared_mutex>   w(A->guard);
+    A->keep_maps = on != 0;
+    if(!on) // (what was built stays as it is: the next ?revalue_device finds it without maps and drops it)
+        A->drop_value_maps();
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_get_value_map_info(aoclsparse_matrix A, aoclsparse_mi355_value_map_info *info)
+{
+    if(!A || !info)
+        return aoclsparse_status_invalid_pointer;
+    if(info->struct_size < sizeof(info->struct_size))
+        return aoclsparse_status_invalid_size;
+    aoclsparse_mi355_value_map_info r{};
+    {
+        std::shared_lock<std::shared_mutex> g(A->guard);
+        r.enabled   = A->keep_maps;
+        r.clean_map = A->opt && (A->opt == &A->user || A->clean_src.ptr);
+        size_t bytes = A->clean_src.bytes + A->diag_src.bytes;
+        for(const TrsvPlan &p : A->trsv_plan)
+        {
+            r.plans_mapped += p.value_mapped();
+            bytes += p.psrc.bytes + p.blk.psrc.bytes;
+        }
+        r.plan_builds = A->plan_builds, r.clean_builds = A->clean_builds, r.revalues = A->revalues;
+        r.last_kept_plans = A->last_kept_plans;
+        r.map_bytes       = (long long)bytes;
+    }
+    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
+    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
 }
 
 aoclsparse_status aoclsparse_mi355_srefresh_values_from_coo_device(aoclsparse_matrix A, aoclsparse_int len, const float *val)
@@ -506,6 +706,7 @@ aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A)
     // that a mirror that was not resident or not valid has come from the host view (as for export_csr_device).  Whatever way out is
     // taken, the stream first finishes what was enqueued on the staging slots and on those buffers (declared first: released last).
     DeviceBuffer                      res, sind, sval, cptr, cind, cval, didiag, diurow, ddiag;
+    DeviceBuffer                      pind, perm, csrc, dsrc; // the value maps of a handle that keeps them (and their scratch)
     std::unique_ptr<HostCsr>          c;
     std::unique_ptr<aoclsparse_int[]> idiag, iurow;
     struct DrainOnExit
@@ -556,6 +757,20 @@ aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A)
             return rc;
         src_ind = sind.as<const aoclsparse_int>(), src_val = sval.ptr;
         lt.lap("clean_csr_device: sort");
+        if(A->keep_maps)
+        {
+            // The sort's permutation: the same sort over a second copy of the columns, moving the entries' positions as its 4-byte
+            // items.  The sort never computes with an item and is a function of the columns alone, so perm[q] = where sorted entry q
+            // stands in the user's arrays.  The arrays sorted above are the ones the call without maps sorts.
+            if((rc = pind.clone_from(d.ind, s)) != aoclsparse_status_success
+               || (rc = perm.alloc(sizeof(int) * (size_t)std::max<aoclsparse_int>(nnz, 1))) != aoclsparse_status_success
+               || (rc = launch_revalue_iota(s, nnz, perm.as<int>())) != aoclsparse_status_success)
+                return rc;
+            if((rc = device_order_rows(s, m, n, nnz, base, d_ptr, pind.as<aoclsparse_int>(), perm.ptr, sizeof(int)))
+               != aoclsparse_status_success)
+                return rc;
+            lt.lap("clean_csr_device: sort of the positions");
+        }
     }
     // mark, and for a copy the clean row pointer with its 64-bit total
     const bool   copy = !sorted || !fulldiag;
@@ -621,15 +836,29 @@ aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A)
     {
         if((rc = cind.alloc(ib)) != aoclsparse_status_success || (rc = cval.alloc(vb)) != aoclsparse_status_success)
             return rc;
+        if(A->keep_maps && (rc = csrc.alloc(sizeof(int) * (size_t)std::max<aoclsparse_int>(total, 1))) != aoclsparse_status_success)
+            return rc;
         if((rc = launch_clean_expand(s, m, nnz, total, base, d_ptr, src_ind, src_val, vsz, cptr.as<const aoclsparse_int>(), at_p, miss_p,
-                                     cind.as<aoclsparse_int>(), cval.ptr))
+                                     cind.as<aoclsparse_int>(), cval.ptr, csrc.as<int>()))
            != aoclsparse_status_success)
+            return rc;
+        // (positions in the sorted arrays so far: through the sort's permutation they are positions in the user's)
+        if(csrc.ptr && !sorted
+           && (rc = launch_revalue_compose(s, total, nnz, perm.as<const int>(), csrc.as<int>())) != aoclsparse_status_success)
             return rc;
     }
     if((rc = launch_clean_finish(s, m, n, nnz, base, d_ptr, src_val, vsz, copy ? cptr.as<const aoclsparse_int>() : nullptr, at_p, miss_p,
                                  didiag.as<aoclsparse_int>(), diurow.as<aoclsparse_int>(), ddiag.ptr))
        != aoclsparse_status_success)
         return rc;
+    if(A->keep_maps) // the diagonal's map, from what the finish kernel has just written
+    {
+        if((rc = dsrc.alloc(rb)) != aoclsparse_status_success
+           || (rc = launch_revalue_diag_map(s, m, n, copy ? 0 : base, total, didiag.as<const aoclsparse_int>(),
+                                            diurow.as<const aoclsparse_int>(), dsrc.as<int>()))
+                  != aoclsparse_status_success)
+            return rc;
+    }
     if(PhaseTimer::on()) // (the diagnostic separates the kernels from the copy back)
         MI355_HIP_TRY(hipStreamSynchronize(s));
     lt.lap("clean_csr_device: expand + finish");
@@ -667,6 +896,8 @@ aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A)
     A->opt_csr_full_diag = fulldiag;
     A->optimized         = true;
     A->dev_diag.adopt(ddiag);
+    A->clean_src.adopt(csrc), A->diag_src.adopt(dsrc); // (empty without the flag; no clean_src when the clean CSR is the handle's own)
+    A->clean_builds++;
     return aoclsparse_status_success;
 }
 

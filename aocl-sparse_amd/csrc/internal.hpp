@@ -685,6 +685,7 @@ struct TrsvBlockPlan
     aoclsparse_int nblocks = 0, nslices = 0, nlevels = 0;
     int            max_rows = 1, max_ext = 0; // largest block / largest external list of a multi-row block
     DeviceBuffer   rowmap, pptr, pind, pval; // as TrsvPlan, in block-level order
+    DeviceBuffer   psrc; // value map (aoclsparse_mi355_keep_value_maps): per entry of pval its position in the clean value array
     DeviceBuffer   bfirst; // nblocks+1: first position of every block
     // nslices+1: first BLOCK of every slice (<= 64 blocks of one block level); then nslices: the slice's block level;
     // then nlevels+1: first slice of every level (the kernel's gate counts finished slices per level)
@@ -710,6 +711,17 @@ struct TrsvPlan
     // automatic schedule never touches it, so it is built only when something asks for it (a forced row-level schedule, the
     // hybrid schedule, complex types, sorv): levels / nlevels / nnz_tri are always valid once `valid` is.
     bool rows_valid = false;
+    // value maps, recorded only while the handle's keep_value_maps flag is set: psrc / blk.psrc = per entry of pval / blk.pval its
+    // 0-based position in the clean CSR's value array; conj = the values are the conjugates (op = H).  They hold no values, but they
+    // index a layout: whatever invalidates the plan releases them.
+    DeviceBuffer psrc;
+    bool         conj = false;
+    void         drop_value_maps() { psrc.release(), blk.psrc.release(); }
+    // every layout this plan holds has its map: aoclsparse_mi355_?revalue_device can carry the plan over
+    bool value_mapped() const
+    {
+        return valid && (rows_valid || blk.valid) && (!rows_valid || psrc.ptr) && (!blk.valid || blk.psrc.ptr);
+    }
 };
 
 // host CSR view; owned==true when the library allocated the arrays (clean copy / transpose)
@@ -772,6 +784,22 @@ struct _aoclsparse_matrix
     mi355::SpmvPlan  plan_user, plan_trans;
     mi355::TrsvPlan  trsv_plan[6]; // index: trsv_plan_index (trsv_schedule.hpp)
     mi355::DeviceBuffer dev_diag; // diagonal values of the clean CSR (length min(m,n))
+    // Value maps (round 25, device_handle_api.cpp).  keep_maps: what is built from now on records where its values come from, so
+    // that aoclsparse_mi355_?revalue_device can bring new values to it instead of dropping it.  clean_src: per entry of the clean
+    // COPY (opt_copy) its 0-based position in the user's value array, -1 for an inserted zero -- only aoclsparse_mi355_clean_csr_device
+    // records it, and it goes with the copy.  diag_src: per row the clean position dev_diag's item comes from, or -1; goes with
+    // dev_diag.  The TRSV layouts' maps hang on their plans.  None of them is a copy of the values.
+    bool                keep_maps = false;
+    mi355::DeviceBuffer clean_src, diag_src;
+    // observers (aoclsparse_mi355_get_value_map_info): builds that did work since the handle was created, successful revalues
+    long long plan_builds = 0, clean_builds = 0, revalues = 0;
+    int       last_kept_plans = 0;
+    void      drop_value_maps()
+    {
+        clean_src.release(), diag_src.release();
+        for(auto &p : trsv_plan)
+            p.drop_value_maps();
+    }
     mi355::DeviceBuffer trsv_scratch; // ticket (one per right-hand side) + timeout words of the sync-free solve
     mi355::DeviceBuffer trsv_xp; // solution(s) in level order, m x nrhs (stream-ordered reuse)
     // the stream of the last call that used the handle's workspaces (the two above, `work` below): they are reused in stream
@@ -1106,6 +1134,9 @@ aoclsparse_status csr_indices(aoclsparse_int m, aoclsparse_index_base base,
 aoclsparse_status csr_optimize(aoclsparse_matrix A);
 // forget every copy derived from the user's arrays (clean CSR, transposes, device mirrors, SELL, TRSV plans)
 void drop_derived_state(aoclsparse_matrix A);
+// the same, except that the clean CSR with dev_diag (keep_clean) and the TRSV plans whose bit is set in keep_plans (bit i =
+// trsv_plan[i]) stay: aoclsparse_mi355_?revalue_device has brought the new values to them
+void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans);
 // value mutation on handles created from CSC / COO arrays (formats_api.cpp): the caller's arrays are the first
 // representation there; csc_refresh_csr rebuilds the handle's CSR values from the CSC arrays
 aoclsparse_status coo_set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int col_idx, const void *val);
@@ -1172,10 +1203,22 @@ aoclsparse_status launch_clean_mark(hipStream_t s, aoclsparse_int m, aoclsparse_
                                     const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, int *at, int *miss, int *cnt);
 aoclsparse_status launch_clean_expand(hipStream_t s, aoclsparse_int m, aoclsparse_int nnz, aoclsparse_int total, int base,
                                       const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, const void *d_val, size_t vsize,
-                                      const aoclsparse_int *cptr, const int *at, const int *miss, aoclsparse_int *cind, void *cval);
+                                      const aoclsparse_int *cptr, const int *at, const int *miss, aoclsparse_int *cind, void *cval,
+                                      int *csrc = nullptr);
 aoclsparse_status launch_clean_finish(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
                                       const aoclsparse_int *d_ptr, const void *d_val, size_t vsize, const aoclsparse_int *cptr,
                                       const int *at, const int *miss, aoclsparse_int *idiag, aoclsparse_int *iurow, void *diag);
+
+// Values through a value map (revalue_kernels.hip; all enqueued on s, not waited for).  gather: out[k] = in[map[k]] for k < count,
+// the all-zero item where map[k] < 0, conjugated when conj (items of 8 or 16 bytes only); nsrc = items of `in`.  iota: out[k] = k.
+// compose: map[k] = perm[map[k]] where map[k] >= 0, in place.  diag_map: per row the 0-based clean position of its diagonal entry
+// (idiag - base where iurow == idiag + 1 and the row is < min(m, n)), else -1.
+aoclsparse_status launch_revalue_gather(hipStream_t s, long long count, long long nsrc, const int *map, const void *in, void *out,
+                                        size_t vsize, bool conj);
+aoclsparse_status launch_revalue_iota(hipStream_t s, aoclsparse_int count, int *out);
+aoclsparse_status launch_revalue_compose(hipStream_t s, aoclsparse_int count, aoclsparse_int nperm, const int *perm, int *map);
+aoclsparse_status launch_revalue_diag_map(hipStream_t s, aoclsparse_int m, aoclsparse_int n, int base, aoclsparse_int total,
+                                          const aoclsparse_int *idiag, const aoclsparse_int *iurow, int *out);
 
 // ---- device mirrors / plans ---------------------------------------------------------------------
 size_t            val_size(aoclsparse_matrix_data_type t);

@@ -367,6 +367,7 @@ aoclsparse_status csr_optimize(aoclsparse_matrix A)
         }
         A->opt_csr_full_diag = fulldiag;
         A->optimized         = true;
+        A->clean_builds++; // (an observer: aoclsparse_mi355_get_value_map_info)
     }
     catch(const std::bad_alloc &)
     {
@@ -1390,17 +1391,25 @@ aoclsparse_status alias_csr(aoclsparse_matrix *mat, aoclsparse_index_base base, 
 // and aoclsparse_mi355_invalidate all come here).  A copy added to the handle that holds values is dropped here, nowhere else.
 void drop_derived_state(aoclsparse_matrix A)
 {
+    drop_derived_state_keeping(A, false, 0u);
+}
+
+// (keep_clean / keep_plans: aoclsparse_mi355_?revalue_device alone passes anything but false / 0 -- it has rewritten the values of
+// what it asks to keep)
+void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans)
+{
     for(aoclsparse_matrix t : A->tcsr_tri) // TCSR: everything that holds values hangs on the two triangle handles
         if(t)
         {
             std::unique_lock<std::shared_mutex> w(t->guard);
             drop_derived_state(t);
         }
-    if(A->opt != &A->user) // the clean copy of unsorted arrays / arrays that miss a diagonal entry
+    if(A->opt != &A->user && !keep_clean) // the clean copy of unsorted arrays / arrays that miss a diagonal entry
     {
         A->opt_copy.reset();
         A->opt       = nullptr;
         A->optimized = false;
+        A->clean_src.release(); // (its value map indexes the copy that is gone)
     }
     A->trans.reset(); // host transpose
     A->derived.clear(); // symmetric / triangular expansions (host + device + their plans)
@@ -1416,9 +1425,16 @@ void drop_derived_state(aoclsparse_matrix A)
     // ?update_values on a block-dense handle used the OLD values -- found by tests/test_gpu_r6.py)
     A->plan_user.bell.valid = A->plan_user.bell.tried = false;
     A->plan_trans.bell.valid = A->plan_trans.bell.tried = false;
-    A->dev_diag.release(); // diagonal of the clean CSR (non-unit solves, SymGS scaling)
-    for(auto &p : A->trsv_plan) // level-ordered triangles: row, block and chunk plans
+    if(!keep_clean)
+        A->dev_diag.release(), A->diag_src.release(); // diagonal of the clean CSR (non-unit solves, SymGS scaling), and its map
+    for(int i = 0; i < 6; i++) // level-ordered triangles: row, block and chunk plans
+    {
+        TrsvPlan &p = A->trsv_plan[i];
+        if(keep_clean && (keep_plans >> i & 1u))
+            continue;
         p.valid = p.rows_valid = false, p.nlevels = -1, p.blk.valid = p.blk.tried = false, p.blk.chunk.valid = p.blk.chunk.tried = false;
+        p.drop_value_maps(); // (they hold no values, but they index a layout that is gone)
+    }
 }
 } // namespace mi355
 

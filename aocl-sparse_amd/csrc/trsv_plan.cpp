@@ -72,12 +72,15 @@ struct Triangle
     std::vector<aoclsparse_int> ptr;
     RawArray<aoclsparse_int>    ind;
     RawArray<T>                 val;
+    // value map (only for a handle that keeps them, else empty): src[q] = the 0-based position of val[q] in the clean value array
+    RawArray<aoclsparse_int>    src;
     bool                        descending = false; // solve order m-1..0 (dependencies point to larger rows)
     aoclsparse_int len(aoclsparse_int i) const { return ptr[i + 1] - ptr[i]; }
     aoclsparse_int row_at(aoclsparse_int k, aoclsparse_int m) const { return descending ? m - 1 - k : k; } // k-th row in solve order
 };
 
-template <typename T>
+// MAPS: also t.src (decided at compile time: the loops without it are the ones they were)
+template <typename T, bool MAPS>
 static void build_triangle(const HostCsr &c, bool upper, bool transposed, bool conj, Triangle<T> &t)
 {
     const aoclsparse_int  m = c.m, b = c.base;
@@ -92,12 +95,16 @@ static void build_triangle(const HostCsr &c, bool upper, bool transposed, bool c
             t.ptr[i + 1] = t.ptr[i] + (e[i] - s[i]);
         t.ind.resize((size_t)std::max(t.ptr[m], 1));
         t.val.resize((size_t)std::max(t.ptr[m], 1));
+        if constexpr(MAPS)
+            t.src.resize((size_t)std::max(t.ptr[m], 1));
         parallel_for(m, 1 << 16, [&](long long i0, long long i1) {
             for(aoclsparse_int i = (aoclsparse_int)i0; i < (aoclsparse_int)i1; i++)
                 for(aoclsparse_int p = s[i] - b, q = t.ptr[i]; p < e[i] - b; p++, q++)
                 {
                     t.ind[q] = c.ind[p] - b;
                     t.val[q] = v[p];
+                    if constexpr(MAPS)
+                        t.src[q] = p;
                 }
         });
         t.descending = upper;
@@ -113,6 +120,8 @@ static void build_triangle(const HostCsr &c, bool upper, bool transposed, bool c
         t.ptr[j + 1] += t.ptr[j];
     t.ind.resize((size_t)std::max(t.ptr[m], 1));
     t.val.resize((size_t)std::max(t.ptr[m], 1));
+    if constexpr(MAPS)
+        t.src.resize((size_t)std::max(t.ptr[m], 1));
     std::vector<aoclsparse_int> next(t.ptr.begin(), t.ptr.end() - 1);
     const bool                  desc_fill = !upper; // L^T: fill from the largest source row down
     for(aoclsparse_int ii = 0; ii < m; ii++)
@@ -123,6 +132,8 @@ static void build_triangle(const HostCsr &c, bool upper, bool transposed, bool c
             const aoclsparse_int q = next[c.ind[p] - b]++;
             t.ind[q]               = i;
             t.val[q]               = v[p];
+            if constexpr(MAPS)
+                t.src[q] = p;
         }
     }
     t.descending = !upper; // L^T is upper triangular: x_c needs x_i, i > c
@@ -141,6 +152,7 @@ struct Layout
     Ints                     pptr;
     RawArray<aoclsparse_int> pind;
     RawArray<T>              pval;
+    RawArray<aoclsparse_int> psrc; // t.src in the same order (empty when the triangle has none)
 };
 template <typename T>
 static void layout_triangle(const Triangle<T> &t, const Ints &rowmap, const Ints &pos, Layout<T> &L)
@@ -151,6 +163,14 @@ static void layout_triangle(const Triangle<T> &t, const Ints &rowmap, const Ints
     L.pval.resize(t.val.size());
     for(aoclsparse_int k = 0; k < m; k++)
         L.pptr[k + 1] = L.pptr[k] + t.len(rowmap[k]);
+    if(t.src.size()) // the value map in a pass of its own: the loop below is the one it was
+    {
+        L.psrc.resize(t.src.size());
+        parallel_for(m, 1 << 16, [&](long long k0, long long k1) {
+            for(aoclsparse_int k = (aoclsparse_int)k0; k < (aoclsparse_int)k1; k++)
+                std::copy(t.src.begin() + t.ptr[rowmap[k]], t.src.begin() + t.ptr[rowmap[k] + 1], L.psrc.begin() + L.pptr[k]);
+        });
+    }
     parallel_for(m, 1 << 16, [&](long long k0, long long k1) {
         for(aoclsparse_int k = (aoclsparse_int)k0; k < (aoclsparse_int)k1; k++)
         {
@@ -255,13 +275,17 @@ static aoclsparse_status build_levels(aoclsparse_int m, const Triangle<T> &t, Tr
         l = e;
     }
     lt.lap("levels: slices + segments");
-    const aoclsparse_status rc = upload_all(Runtime::get().stream(),
+    aoclsparse_status rc = upload_all(Runtime::get().stream(),
                                             {ints(plan.rowmap, rowmap, (size_t)m), ints(plan.levels, plan.level_ptr, (size_t)nlev + 1),
                                              ints(plan.pptr, L.pptr, (size_t)m + 1), {plan.pind, L.pind.data(), sizeof(aoclsparse_int) * L.pind.size()},
                                              {plan.pval, L.pval.data(), sizeof(T) * L.pval.size()}, ints(plan.slices, slices)});
+    plan.psrc.release(); // (never a leftover of an earlier layout)
+    if(rc == aoclsparse_status_success && L.psrc.size())
+        rc = plan.psrc.upload(L.psrc.data(), sizeof(aoclsparse_int) * L.psrc.size(), Runtime::get().stream());
     lt.lap("levels: upload");
     plan.rows_valid = rc == aoclsparse_status_success;
-    free_later(std::move(L.pind), std::move(L.pval), std::move(rowmap), std::move(pos), std::move(L.pptr), std::move(level));
+    free_later(std::move(L.pind), std::move(L.pval), std::move(L.psrc), std::move(rowmap), std::move(pos), std::move(L.pptr),
+               std::move(level));
     return rc;
 }
 
@@ -779,6 +803,9 @@ static aoclsparse_status build_blocked(aoclsparse_int m, const Triangle<T> &t, T
     aoclsparse_status rc = upload_all(st, {ints(bp.rowmap, O.rowmap, (size_t)m), ints(bp.pptr, L.pptr, (size_t)m + 1),
                                            {bp.pind, L.pind.data(), sizeof(aoclsparse_int) * L.pind.size()},
                                            {bp.pval, L.pval.data(), sizeof(T) * L.pval.size()}, ints(bp.bfirst, O.bfirst), ints(bp.slices, slices)});
+    bp.psrc.release(); // (never a leftover of an earlier layout)
+    if(rc == aoclsparse_status_success && L.psrc.size())
+        rc = bp.psrc.upload(L.psrc.data(), sizeof(aoclsparse_int) * L.psrc.size(), st);
     if(rc != aoclsparse_status_success)
         return rc;
     lt.lap("blocks: upload");
@@ -790,18 +817,24 @@ static aoclsparse_status build_blocked(aoclsparse_int m, const Triangle<T> &t, T
     bp.chunk.tried = true;
     if(G.max_rows <= TRSV_CHUNK_LANES && G.max_ext <= TRSV_BLK_EXT && nb >= 64)
         (void)build_chunk_plan(m, t, G, O, bp, st, lt); // (a chunk plan that could not be uploaded leaves the block plan to serve)
-    free_later(std::move(L.pind), std::move(L.pval), std::move(O.rowmap), std::move(O.pos), std::move(L.pptr), std::move(G.brows));
+    free_later(std::move(L.pind), std::move(L.pval), std::move(L.psrc), std::move(O.rowmap), std::move(O.pos), std::move(L.pptr),
+               std::move(G.brows));
     return aoclsparse_status_success;
 }
 
 template <typename T>
-static aoclsparse_status build_plan_t(const HostCsr &c, bool upper, bool transposed, bool conj, TrsvPlan &plan, bool need_rows)
+static aoclsparse_status build_plan_t(const HostCsr &c, bool upper, bool transposed, bool conj, TrsvPlan &plan, bool need_rows,
+                                      bool maps)
 {
     Triangle<T> t;
     {
         PhaseTimer pt("trsv plan: triangle");
-        build_triangle<T>(c, upper, transposed, conj, t);
+        if(maps)
+            build_triangle<T, true>(c, upper, transposed, conj, t);
+        else
+            build_triangle<T, false>(c, upper, transposed, conj, t);
     }
+    plan.conj = conj; // (what aoclsparse_mi355_?revalue_device applies to the values it gathers through the maps)
     aoclsparse_status st = aoclsparse_status_success;
     constexpr bool    real = std::is_floating_point<T>::value;
     if(!plan.valid)
@@ -825,7 +858,7 @@ static aoclsparse_status build_plan_t(const HostCsr &c, bool upper, bool transpo
         PhaseTimer pt("trsv plan: levels + layout + upload");
         st = build_levels<T>(c.m, t, plan, true);
     }
-    free_later(std::move(t.ptr), std::move(t.ind), std::move(t.val));
+    free_later(std::move(t.ptr), std::move(t.ind), std::move(t.val), std::move(t.src));
     return st;
 }
 
@@ -866,12 +899,24 @@ aoclsparse_status ensure_trsv(aoclsparse_matrix A, bool upper, bool transposed, 
             if(st != aoclsparse_status_success)
                 return st;
         }
+        if(A->keep_maps && !A->diag_src.ptr)
+        {
+            // the diagonal's value map: the clean position gathered above, -1 where the row has no diagonal entry
+            std::vector<int> ds((size_t)std::max(m, 1), -1);
+            for(aoclsparse_int i = 0; i < std::min(c.m, c.n); i++)
+                if(c.iurow[i] == c.idiag[i] + 1)
+                    ds[(size_t)i] = c.idiag[i] - c.base;
+            st = A->diag_src.upload(ds.data(), sizeof(int) * (size_t)std::max(m, 1), rt.stream());
+            if(st != aoclsparse_status_success)
+                return st;
+        }
         st = dispatch_value_type(A->val_type, [&](auto tag) {
-            return build_plan_t<decltype(tag)>(c, upper, transposed, conj, plan, need_rows);
+            return build_plan_t<decltype(tag)>(c, upper, transposed, conj, plan, need_rows, A->keep_maps);
         });
         if(st != aoclsparse_status_success)
             return st;
         plan.valid = true;
+        A->plan_builds++; // a plan was built or extended (an observer: aoclsparse_mi355_get_value_map_info)
     }
     catch(const std::bad_alloc &)
     {

@@ -350,6 +350,45 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           4 bytes per row + (4 + sizeof(value)) per entry of the copy, released after the copy back (nothing consumes a resident
  *           clean copy yet); in case (3) also (4 + sizeof(value)) per entry for the sorted copy, and what order_mat_device needs.
  *
+ *   keep_value_maps    (round 25) Sets (on != 0) or clears a flag on a CSR-format handle, at any time.  While it is set, what is
+ *           built records where its values come from: every TRSV layout (the level-ordered rows and the blocked layout of each of
+ *           the six (fill, op) plans) one int per entry, its position in the clean CSR's value array; the diagonal the solves
+ *           read one int per row; and the clean COPY that clean_csr_device makes one int per entry, its position in the handle's
+ *           own value array (-1 for an inserted zero; for unsorted rows the position goes through the row sort, which is run a
+ *           second time over the positions as its 4-byte items).  What was built before the flag was set has no map; the clean
+ *           copy csr_optimize builds on the host never has one.  on == 0 releases every map and clears the flag.  The maps hold
+ *           no values, but they index a layout: whatever invalidates a plan or the clean copy (?set_value, ?update_values,
+ *           ?update_values_device, ?refresh_values_from_coo_device, aoclsparse_order_mat, order_mat_device,
+ *           aoclsparse_mi355_invalidate) releases its maps.  Without the flag nothing is recorded and every path allocates and
+ *           computes what it did before.  invalid_pointer for a null A, not_implemented for TCSR and BSR handles.
+ *
+ *   ?revalue_device    (round 25) ?update_values_device -- same arguments, same statuses in the same order, all decided before the
+ *           device is touched; it writes what that call writes (the resident mirror's values while the mirror is valid, the host
+ *           view by one copy back) and drops what that call drops (SELL-64 / blocked-ELL copies, host and device transposes,
+ *           derived operators, replicas) -- except for what can follow the new values through a map: (1) the clean CSR stays
+ *           when it is the handle's own arrays (sorted rows, full diagonal: nothing to do) or a copy that holds its map: the copy's
+ *           values are gathered in HBM (revalue_kernels.hip; the all-zero item for an inserted diagonal entry) and copied back
+ *           into the host copy; its row pointer, columns, idiag / iurow and the `optimized` state are untouched.  A clean copy
+ *           without a map is dropped.  (2) The diagonal in HBM stays and is gathered again when it has its map (and the clean CSR
+ *           stayed).  (3) Every valid TRSV plan whose layouts all hold maps stays valid -- levels, segments, block and chunk plans
+ *           and every index buffer untouched -- and its value arrays are gathered again from the clean values, conjugated for a
+ *           plan built with op = H; the chunk plan holds no values of its own.  A plan survives only if the clean CSR and the
+ *           diagonal it was built from survive; a plan without maps is invalidated as ?update_values_device invalidates it.
+ *           The gathers move items of 4, 8 or 16 bytes and never compute with them (the conjugate flips one sign bit): a solve
+ *           afterwards gives the bits a freshly created handle with the new values gives.  All device work goes on the library's
+ *           stream, behind earlier solves, with no host synchronisation between the gathers; the stream is synchronised once
+ *           before return.  Locking as ?update_values_device.  Failure: an allocation that fails before the first write leaves
+ *           the handle as it was; after any failure behind the first device write the handle is left with everything dropped and
+ *           all maps released (never plans with some old and some new values) and an invalid mirror (the next product uploads the
+ *           host view), and the status is reported.  Peak extra device memory: sizeof(value) per entry of a clean copy, during
+ *           the call.  Not kept (rebuilt lazily as ever): SELL-64 / blocked-ELL copies, derived operators, transposes, replicas,
+ *           ILU factors.  ?update_values, ?set_value, ?update_values_device and ?refresh_values_from_coo_device do not take this
+ *           route; a caller with a triplet map refreshes, exports the device values, and passes them here.
+ *
+ *   get_value_map_info What a handle holds of the above (struct_size as for get_coo_map_info).  plan_builds and clean_builds count
+ *           the times a TRSV plan / the clean CSR was actually built or extended since the handle was created, flag or no flag:
+ *           they show whether a solve after a value change analysed anything.
+ *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
  * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
  * arrays); a refresh that changes the set of coordinates; carrying the triplet map through aoclsparse_copy, exported state or
@@ -357,8 +396,9 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still);
  * aoclsparse_order_mat itself taking the device route; adding repeated columns while ordering; ordering CSC-created, TCSR or BSR
  * handles on the device; csr_optimize / aoclsparse_optimize choosing the device route for the clean copy by themselves; keeping the
- * clean copy resident and building TRSV plans, derived operators or ILU factors from it on the device; a values-only refresh of an
- * existing clean copy after a value update; clean copies of the transpose; a host view that is filled on first use instead of by
+ * clean copy resident and building TRSV plans, derived operators or ILU factors from it on the device; value maps for clean copies
+ * built on the host, and keeping SELL-64 / blocked-ELL copies, derived operators, transposes, replicas or ILU factors through a
+ * ?revalue_device; carrying value maps through aoclsparse_copy, exported state or replicas; clean copies of the transpose; a host view that is filled on first use instead of by
  * order_mat_device's copy back. */
 #define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
 #define AOCLSPARSE_MI355_ORDER_SHORT_MAX 32 /* order_mat_device: rows of up to this many entries are sorted by one lane */
@@ -424,6 +464,26 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrefresh_values_from_coo_device(ao
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_coo_map_info(aoclsparse_matrix A, aoclsparse_mi355_coo_map_info *info);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_clean_csr_device(aoclsparse_matrix A);
+typedef struct
+{
+    size_t         struct_size; /* in: sizeof(aoclsparse_mi355_value_map_info) as the caller knows it */
+    aoclsparse_int enabled; /* the keep_value_maps flag */
+    aoclsparse_int clean_map; /* 1: the clean CSR can follow a ?revalue_device (the handle's own arrays, or a copy with its map) */
+    aoclsparse_int plans_mapped; /* the valid TRSV plans, of the six, whose layouts all hold maps */
+    aoclsparse_int last_kept_plans; /* plans the last successful ?revalue_device carried over */
+    long long      plan_builds; /* times a TRSV plan was built or extended since the handle was created (flag or no flag) */
+    long long      clean_builds; /* the same for the clean CSR (csr_optimize / clean_csr_device doing work) */
+    long long      revalues; /* successful ?revalue_device calls */
+    long long      map_bytes; /* device memory the maps occupy */
+} aoclsparse_mi355_value_map_info;
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_keep_value_maps(aoclsparse_matrix A, aoclsparse_int on);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_srevalue_device(aoclsparse_matrix A, aoclsparse_int len, const float *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_drevalue_device(aoclsparse_matrix A, aoclsparse_int len, const double *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_crevalue_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                              const aoclsparse_float_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrevalue_device(aoclsparse_matrix A, aoclsparse_int len,
+                                                              const aoclsparse_double_complex *val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_value_map_info(aoclsparse_matrix A, aoclsparse_mi355_value_map_info *info);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
                                                                 aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
                                                                 const aoclsparse_int **col_idx, const void **val);
