@@ -174,6 +174,16 @@ def dcsrmm(order, alpha, base, val, col, row, m, B, n, ldb, beta, C, ldc):
     return st, C
 
 
+def scsrmm(order, alpha, base, val, col, row, m, B, n, ldb, beta, C, ldc):
+    """float twin of dcsrmm: order 'row' or 'col', float32 in and out."""
+    val, col, row, B = _f32(val), _i32(col), _i32(row), _f32(B)
+    C = _f32(C).copy()
+    fn = lib().orc_scsrmm_row if order == "row" else lib().orc_scsrmm_col
+    st = fn(c_flt(alpha), c_int(base), _p(val), _p(col), _p(row), c_i32(m), _p(B), c_i32(n),
+            c_i32(ldb), c_flt(beta), _p(C), c_i32(ldc))
+    return st, C
+
+
 def set_contract(fused):
     """True (default): the reference's scalar accumulation loops are fused multiply-adds (clang / AOCC build);
     False: a multiplication and an addition (GCC build with the reference's own -march=znver2: oracle.c header)."""

@@ -601,44 +601,48 @@ DEF_KT_TRSV(float, s, fmaf, CH_S, 16)
 /* ------------------------------------------------------------------------------------ */
 
 /* csrmm.hpp:69-85: sum = aval*B + sum (fma chain); C = (beta*C) + (alpha*sum), which the
- * compiler contracts to fma(beta, C, alpha*sum). */
-int orc_dcsrmm_col(double alpha, int base, const double *val, const oint *col,
-                   const oint *row, oint m, const double *B, oint n, oint ldb, double beta,
-                   double *C, oint ldc)
-{
-    for(oint j = 0; j < n; j++)
-        for(oint i = 0; i < m; i++)
-        {
-            double sum = 0.0;
-            for(oint k = row[i]; k < row[i + 1]; k++)
-                sum = CH_D(val[k - base], B[(size_t)(col[k - base] - base) + (size_t)j * ldb], sum);
-            size_t ic = (size_t)i + (size_t)j * ldc;
-            C[ic]     = fma(beta, C[ic], alpha * sum);
-        }
-    return ORC_SUCCESS;
-}
+ * compiler contracts to fma(beta, C, alpha*sum).  One text for both precisions. */
+#define DEF_CSRMM_COL(NAME, T, FMA, CH)                                                                             \
+    int NAME(T alpha, int base, const T *val, const oint *col, const oint *row, oint m, const T *B, oint n, oint ldb, \
+             T beta, T *C, oint ldc)                                                                                \
+    {                                                                                                               \
+        for(oint j = 0; j < n; j++)                                                                                 \
+            for(oint i = 0; i < m; i++)                                                                             \
+            {                                                                                                       \
+                T sum = 0;                                                                                          \
+                for(oint k = row[i]; k < row[i + 1]; k++)                                                           \
+                    sum = CH(val[k - base], B[(size_t)(col[k - base] - base) + (size_t)j * ldb], sum);              \
+                size_t ic = (size_t)i + (size_t)j * ldc;                                                            \
+                C[ic]     = FMA(beta, C[ic], alpha * sum);                                                          \
+            }                                                                                                       \
+        return ORC_SUCCESS;                                                                                         \
+    }
+DEF_CSRMM_COL(orc_dcsrmm_col, double, fma, CH_D)
+DEF_CSRMM_COL(orc_scsrmm_col, float, fmaf, CH_S)
 
 /* csrmm.hpp:123-139: C_row *= beta; then per nnz in CSR order C += (aval*B)*alpha,
  * contracted to fma(aval*B, alpha, C). */
-int orc_dcsrmm_row(double alpha, int base, const double *val, const oint *col,
-                   const oint *row, oint m, const double *B, oint n, oint ldb, double beta,
-                   double *C, oint ldc)
-{
-    for(oint i = 0; i < m; i++)
-    {
-        double *c = C + (size_t)i * ldc;
-        for(oint k = 0; k < n; k++)
-            c[k] = c[k] * beta;
-        for(oint j = row[i]; j < row[i + 1]; j++)
-        {
-            const double *brow = B + (size_t)(col[j - base] - base) * ldb;
-            double        av   = val[j - base];
-            for(oint k = 0; k < n; k++)
-                c[k] = fma(av * brow[k], alpha, c[k]);
-        }
+#define DEF_CSRMM_ROW(NAME, T, FMA)                                                                                 \
+    int NAME(T alpha, int base, const T *val, const oint *col, const oint *row, oint m, const T *B, oint n, oint ldb, \
+             T beta, T *C, oint ldc)                                                                                \
+    {                                                                                                               \
+        for(oint i = 0; i < m; i++)                                                                                 \
+        {                                                                                                           \
+            T *c = C + (size_t)i * ldc;                                                                             \
+            for(oint k = 0; k < n; k++)                                                                             \
+                c[k] = c[k] * beta;                                                                                 \
+            for(oint j = row[i]; j < row[i + 1]; j++)                                                               \
+            {                                                                                                       \
+                const T *brow = B + (size_t)(col[j - base] - base) * ldb;                                           \
+                T        av   = val[j - base];                                                                      \
+                for(oint k = 0; k < n; k++)                                                                         \
+                    c[k] = FMA(av * brow[k], alpha, c[k]);                                                          \
+            }                                                                                                       \
+        }                                                                                                           \
+        return ORC_SUCCESS;                                                                                         \
     }
-    return ORC_SUCCESS;
-}
+DEF_CSRMM_ROW(orc_dcsrmm_row, double, fma)
+DEF_CSRMM_ROW(orc_scsrmm_row, float, fmaf)
 
 /* csrmm_col_kt, level3/aoclsparse_csrmm_kt.cpp:31-197 (kid 1/2: psz = 4 lanes, kid 3 / auto on an AVX-512 host: 8).
  * Per element (i, j), four columns at a time share the loads but not the arithmetic:

@@ -159,6 +159,11 @@ int orc_dcsrmm_col(double alpha, int base, const double *val, const oint *col,
 int orc_dcsrmm_row(double alpha, int base, const double *val, const oint *col,
                    const oint *row, oint m, const double *B, oint n, oint ldb, double beta,
                    double *C, oint ldc);
+/* float twins of the two reference kernels (one macro each in oracle.c) */
+int orc_scsrmm_col(float alpha, int base, const float *val, const oint *col, const oint *row, oint m, const float *B,
+                   oint n, oint ldb, float beta, float *C, oint ldc);
+int orc_scsrmm_row(float alpha, int base, const float *val, const oint *col, const oint *row, oint m, const float *B,
+                   oint n, oint ldb, float beta, float *C, oint ldc);
 /* KT kernels (what kid 1/2/3 and the auto dispatch of an AVX host run): level3/aoclsparse_csrmm_kt.cpp:31-363;
  * psz = lanes per vector (4: kid 1/2, 8: kid 3). */
 int orc_dcsrmm_col_kt(int psz, double alpha, int base, const double *val, const oint *col,

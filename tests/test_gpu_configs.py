@@ -469,6 +469,9 @@ def test_csrmm_row_runs_stencil_bit_exact(base):
         for p in range(rp[i] - base, rp[i + 1] - base):
             acc = (np.float64(vf[p]) * Bm[ci[p] - base].astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
         assert np.array_equal(Cf.cpu().numpy().reshape(m, n)[i], acc), i
+    # ... and every entry against the float oracle (the fmaf chain itself, not its emulation)
+    so, Crf = oracle.scsrmm("col", 1.0, base, vf, ci, rp, m, np.ascontiguousarray(Bm.T).ravel(), n, m, 0.0, np.zeros(m * n, np.float32), m)
+    assert so == 0 and Cf.cpu().numpy().reshape(m, n).tobytes() == np.ascontiguousarray(Crf.reshape(n, m).T).tobytes()
 
 
 @pytest.mark.parametrize("base", [0, 1])

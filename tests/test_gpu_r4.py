@@ -217,6 +217,9 @@ def test_csrmm_column_major_window_kernel_float_and_nan_in_c():
         for p in range(rp[i], rp[i + 1]):  # fmaf chain: exact product + sum in double, one rounding to float
             acc = (np.float64(vf[p]) * Bm[:, ci[p]].astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
         assert np.array_equal(got[:, i], acc), i
+    # ... and every entry against the float oracle (the fmaf chain itself, not its emulation)
+    so, Crf = oracle.scsrmm("col", 1.0, 0, vf, ci, rp, m, Bf, n, m, 0.0, np.zeros(m * n, np.float32), m)
+    assert so == 0 and got.tobytes() == Crf.tobytes()
     Ad = P.Matrix(0, m, m, rp, ci, v)
     B = rng.uniform(-1, 1, m * n)
     Cd = torch.full((m * n,), float("nan"), dtype=torch.float64, device="cuda")
@@ -756,6 +759,11 @@ def test_float_plans_use_2048_entry_row_blocks():
             C0 = rng.uniform(-1, 1, (m, n)).astype(np.float32)
             Cw = dev(C0.ravel())
             assert P.scsrmm(P.OP_NONE, 1.5, A, d, P.ORDER_ROW, dev(B.ravel()), n, n, -0.5, Cw, n) == 0
+            torch.cuda.synchronize()
+            # every entry of the 160-column product against the float oracle: the slabs below then equal it as well
+            so, Cref = oracle.scsrmm("col", 1.5, 0, vf, ci, rp, m, np.ascontiguousarray(B.T).ravel(), n, m, -0.5,
+                                     np.ascontiguousarray(C0.T).ravel(), m)
+            assert so == 0 and Cw.cpu().numpy().reshape(m, n).tobytes() == np.ascontiguousarray(Cref.reshape(n, m).T).tobytes(), name
             for j0 in (0, 64):
                 Bs, Cs0 = np.ascontiguousarray(B[:, j0:j0 + 32]), np.ascontiguousarray(C0[:, j0:j0 + 32])
                 Cs = dev(Cs0.ravel())
@@ -1120,6 +1128,10 @@ def test_float_csrmm_four_columns_per_lane_same_bits_as_two():
         torch.cuda.synchronize()
         W = Cw.cpu().numpy().reshape(m, ldc)
         assert np.array_equal(W[:, n:], C0[:, n:])  # the padding columns of C are untouched
+        # every entry against the float oracle: the two-column kernel below then equals it as well
+        so, Cref = oracle.scsrmm("col", alpha, 0, vf, ci, rp, m, np.ascontiguousarray(B[:, :n].T).ravel(), n, k, beta,
+                                 np.ascontiguousarray(C0[:, :n].T).ravel(), m)
+        assert so == 0 and np.ascontiguousarray(W[:, :n]).tobytes() == np.ascontiguousarray(Cref.reshape(n, m).T).tobytes(), n
         for j0 in range(0, n - 127, 128):
             Bs, Cs0 = np.ascontiguousarray(B[:, j0:j0 + 128]), np.ascontiguousarray(C0[:, j0:j0 + 128])
             Cs = dev(Cs0.ravel())

@@ -1,5 +1,6 @@
-"""CPU tier of the single-precision restatements (orc_strsv_lt / _ut, orc_ssymgs, orc_selltmv, orc_ssorv, orc_scg, orc_sgmres).
-They are the same template as their double twins (oracle/oracle_tmpl.h), which the reference's golden vectors pin; here:
+"""CPU tier of the single-precision restatements (orc_strsv_lt / _ut, orc_ssymgs, orc_selltmv, orc_ssorv, orc_scg, orc_sgmres,
+orc_scsrmm_col / _row).  They are the same template as their double twins (oracle/oracle_tmpl.h; csrmm: the macros DEF_CSRMM_COL /
+DEF_CSRMM_ROW of oracle.c), which the reference's golden vectors pin; here:
 
   * dyadic data -- small integer off-diagonals, power-of-two diagonals, integer right-hand sides -- on which every
     intermediate of the double run is exactly representable in fp32, so the float function must return exactly the double
@@ -217,3 +218,127 @@ def test_sgmres_meets_its_stopping_test(precond):
         true = np.linalg.norm(b.astype(np.float64) - D @ xs.astype(np.float64))
         assert true <= rtol * np.linalg.norm(b), (dots, true)
         assert 1 <= rs[30] <= rd[30] + spread + 2, (dots, rs[30], rd[30], spread)
+
+
+# ---- orc_scsrmm_col / orc_scsrmm_row: the float instantiation of the csrmm macros (DEF_CSRMM_COL / DEF_CSRMM_ROW, oracle.c) -----
+
+def _short_rows(seed, m, k, maxlen, base, values):
+    """sorted CSR, rows of 0..maxlen entries (some empty), values drawn by values(rng, count)"""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(0, maxlen + 1, m)
+    lens[::17] = 0
+    rp = (np.concatenate([[0], np.cumsum(lens)]) + base).astype(np.int32)
+    ci = (np.concatenate([np.sort(rng.choice(k, q, replace=False)) for q in lens]) + base).astype(np.int32)
+    return rp, ci, values(rng, len(ci))
+
+
+def _dense_operand(rng, order, rows, n, ld, draw, pad):
+    """rows x n operand in `order` with leading dimension ld, flat; the padding holds `pad`.  -> (flat, mask of the padding)"""
+    buf = np.full((n, ld) if order == "col" else (rows, ld), pad, np.float64)
+    used = np.zeros(buf.shape, bool)
+    if order == "col":
+        used[:, :rows] = True
+    else:
+        used[:, :n] = True
+    buf[used] = draw(rng, int(used.sum()))
+    return buf.ravel(), ~used.ravel()
+
+
+@pytest.mark.parametrize("base", [0, 1])
+@pytest.mark.parametrize("order", ["col", "row"])
+def test_scsrmm_equals_dcsrmm_on_dyadic_data(order, base):
+    """small integers in A, B and C, power-of-two alpha and beta: every intermediate of the double run is exact in fp32"""
+    m, k, n = 23, 19, 5
+    ints = lambda rng, count: rng.integers(-4, 5, count).astype(np.float64)
+    rp, ci, v = _short_rows(13, m, k, 6, base, ints)
+    rng = np.random.default_rng(14)
+    ldb, ldc = (k + 3, m + 2) if order == "col" else (n + 3, n + 2)
+    B, _ = _dense_operand(rng, order, k, n, ldb, ints, 99.0)
+    C0, padding = _dense_operand(rng, order, m, n, ldc, ints, 77.0)
+    for alpha, beta in ((1.0, 0.0), (0.5, -2.0), (-4.0, 0.25)):
+        sd, Cd = oracle.dcsrmm(order, alpha, base, v, ci, rp, m, B, n, ldb, beta, C0, ldc)
+        ss, Cs = oracle.scsrmm(order, alpha, base, v.astype(np.float32), ci, rp, m, B.astype(np.float32), n, ldb, beta,
+                               C0.astype(np.float32), ldc)
+        assert sd == ss == 0
+        exactly_the_double_result(Cs[~padding], Cd[~padding], (order, base, alpha, beta))
+        assert np.all(Cs[padding] == 77.0) and np.all(Cd[padding] == 77.0)
+        assert np.abs(Cd[~padding]).max() > 16  # the chain did something
+
+
+@pytest.mark.parametrize("alpha,beta", [(1.0, 0.0), (1.7, -0.3)])
+def test_scsrmm_col_equals_the_kt_kernel_below_its_lane_count(alpha, beta):
+    """full mantissas, every row shorter than 8 entries: below the lane count csrmm_col_kt is the scalar chain from zero followed
+    by fma(beta, C, alpha * cij) (oracle.c DEF_CSRMM_COL_KT, pinned to the reference's templates by tests/test_oracle_kt.py), the
+    arithmetic of csrmm_col_major_ref -- so the two restatements, written apart, agree bit for bit"""
+    m, k, n = 300, 260, 9
+    uni = lambda rng, count: rng.uniform(-1, 1, count).astype(np.float32)
+    rp, ci, v = _short_rows(15, m, k, 7, 1, uni)
+    assert np.diff(rp).max() == 7 and np.any(np.diff(rp) == 0)
+    rng = np.random.default_rng(16)
+    ldb, ldc = k + 3, m + 1
+    B, C0 = uni(rng, ldb * n), uni(rng, ldc * n)
+    ss, Cs = oracle.scsrmm("col", alpha, 1, v, ci, rp, m, B, n, ldb, beta, C0, ldc)
+    assert ss == 0 and Cs.dtype == np.float32
+    for psz in (8, 16):
+        sk, Ck = oracle.scsrmm_kt("col", psz, alpha, 1, v, ci, rp, m, B, n, ldb, beta, C0, ldc)
+        assert sk == 0 and np.array_equal(bits32(Ck), bits32(Cs)), psz
+    assert not np.array_equal(Cs, C0)
+
+
+def _stencil_case():
+    """the 5-point stencil of tests/test_gpu_scsrmm_kernels.py (its matrix "lap61": laplace5(61), values perturbed with the same
+    seed) times eight columns of uniform(-1, 1), the distribution of every operand there"""
+    m, rp, ci, v = laplace5(61)
+    rng = np.random.default_rng(8)
+    v = (v * rng.uniform(0.5, 1.5, len(v))).astype(np.float32)
+    n = 8
+    B, C0 = rng.uniform(-1, 1, m * n).astype(np.float32), rng.uniform(-1, 1, m * n).astype(np.float32)
+    return m, rp, ci, v, n, B, C0
+
+
+def test_scsrmm_tells_the_fmaf_chain_from_its_neighbours():
+    """On the data the GPU tests use a kernel that multiplies and then adds, or one that accumulates in double and rounds once,
+    is a different function: measured with NumPy on 200,000 uniform(-1, 1) samples, the first differs from the fmaf chain in
+    36 % / 44 % / 56 % of the elements at row lengths 3 / 5 / 12 and the second in 34 % / 44 % / 59 %.  The floor of 20 % sits
+    under the smallest of them; it is no tolerance."""
+    m, rp, ci, v, n, B, C0 = _stencil_case()
+    ss, C = oracle.scsrmm("col", 1.0, 0, v, ci, rp, m, B, n, m, 0.0, C0, m)
+    with oracle.contract(False):
+        su, Cu = oracle.scsrmm("col", 1.0, 0, v, ci, rp, m, B, n, m, 0.0, C0, m)
+    sd, Cd = oracle.dcsrmm("col", 1.0, 0, v, ci, rp, m, B, n, m, 0.0, C0, m)
+    assert ss == su == sd == 0
+    unfused = np.mean(bits32(Cu) != bits32(C))
+    once = np.mean(bits32(Cd.astype(np.float32)) != bits32(C))
+    print("differs from the fmaf chain: unfused %.3f, double rounded once %.3f" % (unfused, once))
+    assert unfused >= 0.20 and once >= 0.20
+    ss, again = oracle.scsrmm("col", 1.0, 0, v, ci, rp, m, B, n, m, 0.0, C0, m)
+    assert np.array_equal(bits32(again), bits32(C))  # the switch was restored
+
+
+@pytest.mark.parametrize("alpha,beta", [(1.0, 0.0), (1.7, -0.3)])
+def test_scsrmm_row_against_col(alpha, beta):
+    """two different chains (row: C *= beta, then fma(a b, alpha, C) per entry; col: the dot, then fma(beta, C, alpha dot)): within
+    the bound of test_csrmm_random_vs_oracle with the float unit roundoff, (len + 3) u |alpha| sum |a b| + 2 u |beta c|"""
+    m, k, n = 200, 170, 7
+    uni = lambda rng, count: rng.uniform(-1, 1, count).astype(np.float32)
+    rp, ci, v = _short_rows(17, m, k, 13, 1, uni)
+    rng = np.random.default_rng(18)
+    Bm, Cm = uni(rng, k * n).reshape(k, n), uni(rng, m * n).reshape(m, n)
+    ldb, ldc = n + 2, n + 3
+    Br, Cr = np.zeros((k, ldb), np.float32), np.full((m, ldc), 5.0, np.float32)
+    Br[:, :n], Cr[:, :n] = Bm, Cm
+    sr, Crow = oracle.scsrmm("row", alpha, 1, v, ci, rp, m, Br.ravel(), n, ldb, beta, Cr.ravel(), ldc)
+    sc, Ccol = oracle.scsrmm("col", alpha, 1, v, ci, rp, m, np.ascontiguousarray(Bm.T).ravel(), n, k, beta,
+                             np.ascontiguousarray(Cm.T).ravel(), m)
+    assert sr == sc == 0
+    Crow = Crow.reshape(m, ldc)
+    assert np.all(Crow[:, n:] == 5.0)
+    u = float(np.finfo(np.float32).eps)  # (test_csrmm_random_vs_oracle uses finfo(float64).eps)
+    scale = np.zeros((m, n))
+    for i in range(m):
+        s, e = rp[i] - 1, rp[i + 1] - 1
+        scale[i] = np.abs(v[s:e]).astype(np.float64) @ np.abs(Bm[ci[s:e] - 1]).astype(np.float64)
+    lens = np.diff(rp)[:, None]
+    diff = np.abs(Crow[:, :n].astype(np.float64) - Ccol.reshape(n, m).T.astype(np.float64))
+    assert np.all(diff <= (lens + 3) * u * scale * abs(alpha) + 2 * u * np.abs(beta * Cm.astype(np.float64)) + 1e-300)
+    assert diff.max() > 0  # they are different chains
