@@ -28,6 +28,8 @@ MEM_MINIMAL, MEM_UNRESTRICTED = 0, 1
 PTR_AUTO, PTR_HOST, PTR_DEVICE = 0, 1, 2
 OPTION_SPMV_KERNEL, OPTION_SELL, OPTION_SPMV_STRICT, OPTION_ALTERNATE_SWEEPS, OPTION_TRSV_CHUNKS = 0, 1, 2, 3, 4  # aoclsparse_mi355_set_option
 OPTION_SELL_VALUES = 5
+OPTION_ILU_SEARCH = 16  # aoclsparse_mi355_option_ilu_search: -1 automatic, 0 scan, 1 search whenever the rows are fully sorted
+ILU_SEARCH_MIN = 21  # AOCLSPARSE_MI355_ILU_SEARCH_MIN: the automatic rule takes the search from this longest row on
 COO_KEEP, COO_SUM = 0, 1  # aoclsparse_mi355_coo_duplicates
 COO_KEEP_MAP = 16  # aoclsparse_mi355_coo_keep_map: flag ORed to either, the handle keeps the sort's map for refresh_from_coo_device
 COO_SORT_TILE = 4096  # AOCLSPARSE_MI355_COO_SORT_TILE: entries a workgroup of the triplet sort takes per pass
@@ -70,6 +72,14 @@ class CooMapInfo(ctypes.Structure):
     """aoclsparse_mi355_coo_map_info: the caller sets struct_size, the library writes no more than that"""
     _fields_ = [("struct_size", ctypes.c_size_t), ("kept", c_int32), ("mode", c_int32), ("triplets", c_int32),
                 ("entries", c_int32), ("map_bytes", ctypes.c_longlong)]
+
+
+class IluInfo(ctypes.Structure):
+    """aoclsparse_mi355_ilu_info: the caller sets struct_size, the library writes no more than that"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("factorized", c_int32), ("levels", c_int32), ("max_row", c_int32),
+                ("syncfree", c_int32), ("search", c_int32), ("plans_kept_last", c_int32), ("analyses", ctypes.c_longlong),
+                ("factorizations", ctypes.c_longlong), ("schedule_bytes", ctypes.c_longlong),
+                ("factor_plan_builds", ctypes.c_longlong)]
 
 
 class ValueMapInfo(ctypes.Structure):
@@ -433,6 +443,11 @@ SIGNATURES = {
     "aoclsparse_mi355_crevalue_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_zrevalue_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_get_value_map_info": (c_int, [_P, _P]),
+    "aoclsparse_mi355_silu0_refactor_device": (c_int, [_P, POINTER(_P)]),
+    "aoclsparse_mi355_dilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
+    "aoclsparse_mi355_cilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
+    "aoclsparse_mi355_zilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
+    "aoclsparse_mi355_get_ilu_info": (c_int, [_P, _P]),
     "aoclsparse_mi355_order_mat_device": (c_int, [_P]),
     "aoclsparse_mi355_clean_csr_device": (c_int, [_P]),
     "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
@@ -678,6 +693,21 @@ class Matrix:
         value maps, bringing them the new values in HBM -> status"""
         n = int(val.numel()) if hasattr(val, "numel") else self.nnz
         return getattr(lib(), "aoclsparse_mi355_%srevalue_device" % self._letter())(self.h, n, _ptr(val))
+
+    def ilu0_refactor_device(self, want_factor=True):
+        """aoclsparse_mi355_?ilu0_refactor_device: the ILU(0) factor again, from the values the handle holds now -> (status, address
+        of the factor's nnz values in library-owned host memory, or None)"""
+        f = _P()
+        st = getattr(lib(), "aoclsparse_mi355_%silu0_refactor_device" % self._letter())(self.h, byref(f) if want_factor else None)
+        return st, f.value
+
+    def ilu_info(self):
+        """aoclsparse_mi355_get_ilu_info -> IluInfo (factorized, levels, max_row, syncfree, search, plans_kept_last, analyses,
+        factorizations, schedule_bytes, factor_plan_builds)"""
+        info = IluInfo(struct_size=ctypes.sizeof(IluInfo))
+        st = lib().aoclsparse_mi355_get_ilu_info(self.h, byref(info))
+        assert st == 0, STATUS.get(st, st)
+        return info
 
     def value_map_info(self):
         """aoclsparse_mi355_get_value_map_info -> ValueMapInfo (enabled, clean_map, plans_mapped, last_kept_plans, plan_builds,

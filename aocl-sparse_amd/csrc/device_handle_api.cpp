@@ -423,6 +423,26 @@ namespace
     }
 } // namespace
 
+namespace mi355
+{
+aoclsparse_status revalue_device_any(aoclsparse_matrix A, aoclsparse_int len, const void *val)
+{
+    if(!A)
+        return aoclsparse_status_invalid_pointer;
+    switch(A->val_type)
+    {
+    case aoclsparse_smat:
+        return revalue_device(A, len, static_cast<const float *>(val), aoclsparse_smat);
+    case aoclsparse_dmat:
+        return revalue_device(A, len, static_cast<const double *>(val), aoclsparse_dmat);
+    case aoclsparse_cmat:
+        return revalue_device(A, len, static_cast<const aoclsparse_float_complex *>(val), aoclsparse_cmat);
+    default:
+        return revalue_device(A, len, static_cast<const aoclsparse_double_complex *>(val), aoclsparse_zmat);
+    }
+}
+} // namespace mi355
+
 extern "C" {
 
 aoclsparse_status aoclsparse_mi355_create_scsr_device(aoclsparse_matrix *mat, aoclsparse_index_base base, aoclsparse_int M,
@@ -670,6 +690,7 @@ aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A)
     if(rc == aoclsparse_status_success && !h.first_err) // (as the host call: a row mat_check refuses leaves the two as they were)
         A->sort = h.cls ? h.cls : 1, A->fulldiag = !h.notfull;
     A->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
+    A->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
     drop_derived_state(A); // every copy made of the unsorted arrays (clean CSR, SELL-64 / blocked-ELL, kept transpose, plans, replicas)
     d.valid = true; // the mirror IS the handle's CSR now: resident before any product
     if(rc != aoclsparse_status_success)

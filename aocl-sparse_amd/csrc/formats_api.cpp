@@ -776,6 +776,7 @@ aoclsparse_status aoclsparse_order_mat(aoclsparse_matrix mat)
        == aoclsparse_status_success)
         mat->sort = sort, mat->fulldiag = fd;
     mat->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
+    mat->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
     drop_derived_state(mat); // every copy made of the unsorted arrays (clean CSR, device mirrors, plans)
     return aoclsparse_status_success;
 }

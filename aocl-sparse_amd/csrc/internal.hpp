@@ -863,6 +863,28 @@ struct _aoclsparse_matrix
     bool                ilu_ready = false, ilu_factorized = false;
     void               *ilu_val = nullptr; // nnz values, library-owned (malloc)
     aoclsparse_matrix   ilu_factor = nullptr; // aliases user.ptr / user.ind / ilu_val
+    // What the factorisation computes from the PATTERN, kept from the first factorisation on (the smoother's or
+    // aoclsparse_mi355_?ilu0_refactor_device's) for every later one: the rows in level order (in HBM), where each level starts,
+    // the longest row, and the two choices made from them -- one launch per level or the sync-free launch, and the row routine
+    // that finds the updated position by a scan or by a binary search (ilu_kernels.hip).  Value changes leave it alone; whatever
+    // changes the pattern or its order releases it (aoclsparse_order_mat, order_mat_device, aoclsparse_mi355_invalidate).
+    struct IluSchedule
+    {
+        bool                        valid = false;
+        mi355::DeviceBuffer         rows; // n row numbers, level by level
+        std::vector<aoclsparse_int> level_ptr; // nlevels + 1
+        aoclsparse_int              nlevels = 0, max_row = 0;
+        bool                        syncfree = false, search = false;
+        void                        release()
+        {
+            valid = false, rows.release(), level_ptr.clear(), level_ptr.shrink_to_fit();
+            nlevels = max_row = 0, syncfree = search = false;
+        }
+    } ilu_sched;
+    // observers (aoclsparse_mi355_get_ilu_info): times the levels were computed, successful factorisations, and the TRSV plans of
+    // the factor handle the last refactorisation carried over
+    long long ilu_analyses = 0, ilu_factorizations = 0;
+    int       ilu_plans_kept_last = 0;
 
     // multi-device calls (aoclsparse_mi355_?csrmm_multi): replica[i] = a handle over the SAME host arrays whose device copy
     // and plans live on the device of runtime slot i (slot 0 is this handle itself); built on first use, dropped by
@@ -1159,6 +1181,9 @@ inline bool holds_no_csr(const _aoclsparse_matrix *A)
 }
 // allocates the ILU(0) value array as a copy of A's values (solvers_api.cpp; analysis.cpp:390-425)
 aoclsparse_status ilu_prepare(aoclsparse_matrix A);
+// aoclsparse_mi355_?revalue_device on a handle of whatever value type it has (device_handle_api.cpp): `val` = nnz values in HBM.
+// The route a new ILU(0) factor takes into its factor handle (solvers_api.cpp)
+aoclsparse_status revalue_device_any(aoclsparse_matrix A, aoclsparse_int len, const void *val);
 // builds A->trans (host transpose of the user CSR, 0-based) if absent
 aoclsparse_status build_transpose(aoclsparse_matrix A);
 // B = A^T of a device CSR in the reference's counting-sort order (transpose_kernels.hip), into buffers it allocates once the matrix
@@ -1353,15 +1378,17 @@ aoclsparse_status launch_gather_rows(hipStream_t s, aoclsparse_int n, const aocl
                                      T *dst);
 
 // one dependency level of the in-place ILU(0) factorisation (ilu_kernels.hip): rows[0..nrows) of the level,
-// diag[] = position of each finished row's diagonal, *error set on a bad pivot / missing diagonal
+// diag[] = position of each finished row's diagonal, *error set on a bad pivot / missing diagonal.  search: the position of row
+// i that an entry of row k updates is found by a binary search of the row's columns instead of a scan -- for rows in ascending
+// column order (sort class 1) ONLY; the factor's bits are the same either way
 template <typename T>
 aoclsparse_status launch_ilu0_level(hipStream_t s, int base, aoclsparse_int nrows, const aoclsparse_int *rows,
                                     const aoclsparse_int *row_ptr, const aoclsparse_int *col, T *val,
-                                    aoclsparse_int *diag, int maxlen, int *error);
+                                    aoclsparse_int *diag, int maxlen, int *error, bool search);
 template <typename T>
 aoclsparse_status launch_ilu0_syncfree(hipStream_t s, int base, aoclsparse_int n, const aoclsparse_int *rows,
                                        const aoclsparse_int *row_ptr, const aoclsparse_int *col, T *val, aoclsparse_int *diag,
-                                       int maxlen, int *error, unsigned int *ticket);
+                                       int maxlen, int *error, unsigned int *ticket, bool search);
 
 // dense-vector steps of the iterative solvers (itsol_kernels.hip); `partial` holds
 // vec_reduce_scratch_elems(k) elements, reduction results land in device memory

@@ -1349,6 +1349,7 @@ aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A)
     // every copy of the values (the one list: drop_derived_state) ...
     drop_derived_state(A);
     // ... and the structural plans of the device CSR, which a value change alone leaves valid
+    A->ilu_sched.release(); // (the ILU(0) level schedule among them)
     for(aoclsparse_matrix t : A->tcsr_tri)
         if(t)
             (void)aoclsparse_mi355_invalidate(t);

@@ -328,6 +328,7 @@ std::atomic<bool> &csrmm_beta0_overwrite_flag()
 namespace
 {
     std::atomic<int> g_plan_options[aoclsparse_mi355_option_count] = {{0}, {-1}, {0}, {1}, {-1}, {-1}};
+    std::atomic<int> g_ilu_search{-1}; // aoclsparse_mi355_option_ilu_search: numbered outside the block above
 }
 unsigned long long stream_uid(hipStream_t s)
 {
@@ -354,6 +355,8 @@ unsigned long long stream_uid(hipStream_t s)
 
 int plan_option(aoclsparse_mi355_option option)
 {
+    if(option == aoclsparse_mi355_option_ilu_search)
+        return g_ilu_search.load(std::memory_order_relaxed);
     return option >= 0 && option < aoclsparse_mi355_option_count ? g_plan_options[option].load(std::memory_order_relaxed) : 0;
 }
 
@@ -454,6 +457,13 @@ aoclsparse_status aoclsparse_mi355_release_staging(size_t *bytes_freed)
 
 aoclsparse_status aoclsparse_mi355_set_option(aoclsparse_mi355_option option, aoclsparse_int value)
 {
+    if(option == aoclsparse_mi355_option_ilu_search)
+    {
+        if(value < -1 || value > 1)
+            return aoclsparse_status_invalid_value;
+        g_ilu_search.store((int)value, std::memory_order_relaxed);
+        return aoclsparse_status_success;
+    }
     if(option < 0 || option >= aoclsparse_mi355_option_count)
         return aoclsparse_status_invalid_value;
     if(option == aoclsparse_mi355_option_spmv_kernel && (value < 0 || value > 2))

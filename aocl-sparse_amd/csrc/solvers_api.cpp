@@ -320,11 +320,16 @@ bool near_zero(T v)
 
 // ILU(0) on the user's pattern (ilu0.hpp:34-111), on the GPU: dependency levels of the strictly lower
 // pattern are computed on the host (integer work), then one launch per level eliminates the level's rows in
-// place in a device copy of the values (ilu_kernels.hip); the factors come back to `host_val` for
-// *precond_csr_val and for the factor handle.  Bit-identical to the serial IKJ loop.
+// place in a device copy of the values (ilu_kernels.hip).  Bit-identical to the serial IKJ loop.
+//
+// What depends on the pattern alone -- the schedule -- is computed by the first factorisation of a handle and kept on it
+// (A->ilu_sched) for every later one: aoclsparse_mi355_?ilu0_refactor_device factorises again after a value change.
 template <typename T>
-aoclsparse_status ilu0_factorize(aoclsparse_matrix A, T *host_val)
+aoclsparse_status ilu_schedule(aoclsparse_matrix A)
 {
+    auto &sc = A->ilu_sched;
+    if(sc.valid)
+        return aoclsparse_status_success;
     const aoclsparse_int  n = A->n, base = A->base, nnz = A->nnz;
     const aoclsparse_int *ptr = A->user.ptr, *ind = A->user.ind;
     std::vector<aoclsparse_int> level, order, lptr;
@@ -362,49 +367,187 @@ aoclsparse_status ilu0_factorize(aoclsparse_matrix A, T *host_val)
     }
     if((sizeof(T) + sizeof(aoclsparse_int)) * (size_t)maxlen > 60000) // one row must fit a workgroup's LDS
         return aoclsparse_status_not_implemented;
-
-    Runtime &rt = Runtime::get();
-    DeviceCsr *dcsr = nullptr;
-    SpmvPlan  *plan = nullptr;
-    MI355_TRY(ensure_spmv(A, false, dcsr, plan)); // the pattern (and current values) in HBM
-    DeviceBuffer dval, ddiag, drows, derr;
-    MI355_TRY(dval.alloc(sizeof(T) * (size_t)std::max<aoclsparse_int>(nnz, 1)));
-    MI355_TRY(ddiag.alloc(sizeof(aoclsparse_int) * (size_t)n));
-    MI355_TRY(derr.alloc(sizeof(int)));
+    Runtime     &rt = Runtime::get();
+    DeviceBuffer drows;
     MI355_TRY(drows.upload(order.data(), sizeof(aoclsparse_int) * (size_t)n, rt.stream()));
-    // the factor starts from the values captured by ilu_prepare (the matrix at hint/optimize time)
-    MI355_HIP_TRY(hipMemcpyAsync(dval.ptr, host_val, sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice, rt.stream()));
-    MI355_HIP_TRY(hipMemsetAsync(derr.ptr, 0, sizeof(int), rt.stream()));
+    MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // (`order` goes out of scope)
+    sc.rows.adopt(drows);
+    sc.level_ptr.swap(lptr);
+    sc.nlevels = nlev, sc.max_row = maxlen;
     // real types, deep DAGs: one sync-free launch (rows wait for the rows they need; ilu_kernels.hip) instead of one launch per
     // level -- 5,505 launches cost 390 ms on the shell-like stand-in, the sync-free launch 139 ms; with two lower entries per row
     // (2-D Laplacian) the launches win, 20 vs 44 ms.
-    bool syncfree = false;
+    sc.syncfree = false;
     if constexpr(std::is_floating_point<T>::value)
-        syncfree = nlev > 8 && (long long)nnz >= 16LL * n; // (short rows: a level's launch is cheaper than its hops)
-    if(syncfree)
+        sc.syncfree = nlev > 8 && (long long)nnz >= 16LL * n; // (short rows: a level's launch is cheaper than its hops)
+    // the position search instead of the scan: for rows in ascending column order only (a class-2 row is merely grouped
+    // lower | diagonal | upper), and by itself only where it was measured to win
+    const int opt = plan_option(aoclsparse_mi355_option_ilu_search);
+    sc.search     = A->sort == 1 && opt != 0 && (opt == 1 || maxlen >= AOCLSPARSE_MI355_ILU_SEARCH_MIN);
+    sc.valid      = true;
+    A->ilu_analyses++;
+    return aoclsparse_status_success;
+}
+
+// the factor of the values in dval (nnz of them, in HBM), in place, on A's schedule and resident pattern; waits for it.
+// numerical_error: a (near-)zero pivot or a missing diagonal -- dval is then of no use
+template <typename T>
+aoclsparse_status ilu0_run(aoclsparse_matrix A, const DeviceCsr *dcsr, T *dval)
+{
+    Runtime             &rt = Runtime::get();
+    const auto          &sc = A->ilu_sched;
+    const aoclsparse_int n = A->n, base = A->base;
+    const aoclsparse_int *rows = sc.rows.as<aoclsparse_int>();
+    DeviceBuffer          ddiag, derr, dticket;
+    MI355_TRY(ddiag.alloc(sizeof(aoclsparse_int) * (size_t)n));
+    MI355_TRY(derr.alloc(sizeof(int)));
+    MI355_HIP_TRY(hipMemsetAsync(derr.ptr, 0, sizeof(int), rt.stream()));
+    aoclsparse_status st = aoclsparse_status_success;
+    if(sc.syncfree)
     {
         if constexpr(std::is_floating_point<T>::value)
         {
-            DeviceBuffer dticket;
             MI355_TRY(dticket.alloc(sizeof(unsigned int)));
             MI355_HIP_TRY(hipMemsetAsync(dticket.ptr, 0, sizeof(unsigned int), rt.stream()));
             MI355_HIP_TRY(hipMemsetAsync(ddiag.ptr, 0xFF, sizeof(aoclsparse_int) * (size_t)n, rt.stream())); // -1: not finished
-            MI355_TRY(launch_ilu0_syncfree<T>(rt.stream(), base, n, drows.as<aoclsparse_int>(), dcsr->ptr.as<aoclsparse_int>(),
-                                              dcsr->ind.as<aoclsparse_int>(), dval.as<T>(), ddiag.as<aoclsparse_int>(),
-                                              (int)maxlen, derr.as<int>(), dticket.as<unsigned int>()));
-            MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // dticket goes out of scope
+            st = launch_ilu0_syncfree<T>(rt.stream(), base, n, rows, dcsr->ptr.as<aoclsparse_int>(), dcsr->ind.as<aoclsparse_int>(),
+                                         dval, ddiag.as<aoclsparse_int>(), (int)sc.max_row, derr.as<int>(),
+                                         dticket.as<unsigned int>(), sc.search);
         }
     }
     else
-        for(aoclsparse_int l = 0; l < nlev; l++)
-            MI355_TRY(launch_ilu0_level<T>(rt.stream(), base, lptr[l + 1] - lptr[l], drows.as<aoclsparse_int>() + lptr[l],
-                                           dcsr->ptr.as<aoclsparse_int>(), dcsr->ind.as<aoclsparse_int>(), dval.as<T>(),
-                                           ddiag.as<aoclsparse_int>(), (int)maxlen, derr.as<int>()));
+        for(aoclsparse_int l = 0; l < sc.nlevels && st == aoclsparse_status_success; l++)
+            st = launch_ilu0_level<T>(rt.stream(), base, sc.level_ptr[l + 1] - sc.level_ptr[l], rows + sc.level_ptr[l],
+                                      dcsr->ptr.as<aoclsparse_int>(), dcsr->ind.as<aoclsparse_int>(), dval,
+                                      ddiag.as<aoclsparse_int>(), (int)sc.max_row, derr.as<int>(), sc.search);
     int err = 0;
-    MI355_HIP_TRY(hipMemcpyAsync(&err, derr.ptr, sizeof(int), hipMemcpyDeviceToHost, rt.stream()));
+    if(st == aoclsparse_status_success && hipMemcpyAsync(&err, derr.ptr, sizeof(int), hipMemcpyDeviceToHost, rt.stream()) != hipSuccess)
+        st = aoclsparse_status_internal_error;
+    if(hipStreamSynchronize(rt.stream()) != hipSuccess && st == aoclsparse_status_success) // (the buffers above go out of scope)
+        st = aoclsparse_status_internal_error;
+    if(st != aoclsparse_status_success)
+        return st;
+    return err ? aoclsparse_status_numerical_error : aoclsparse_status_success;
+}
+
+// the smoother's first call: the factor of the values captured by ilu_prepare (the matrix at hint/optimize time) comes back to
+// `host_val` for *precond_csr_val and for the factor handle
+template <typename T>
+aoclsparse_status ilu0_factorize(aoclsparse_matrix A, T *host_val)
+{
+    const aoclsparse_int nnz = A->nnz;
+    Runtime             &rt  = Runtime::get();
+    MI355_TRY(ilu_schedule<T>(A));
+    DeviceCsr *dcsr = nullptr;
+    SpmvPlan  *plan = nullptr;
+    MI355_TRY(ensure_spmv(A, false, dcsr, plan)); // the pattern (and current values) in HBM
+    DeviceBuffer dval;
+    MI355_TRY(dval.alloc(sizeof(T) * (size_t)std::max<aoclsparse_int>(nnz, 1)));
+    MI355_HIP_TRY(hipMemcpyAsync(dval.ptr, host_val, sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice, rt.stream()));
+    const aoclsparse_status st = ilu0_run<T>(A, dcsr, dval.as<T>());
+    if(st != aoclsparse_status_success && st != aoclsparse_status_numerical_error)
+        return st;
     MI355_HIP_TRY(hipMemcpyAsync(host_val, dval.ptr, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost, rt.stream()));
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-    return err ? aoclsparse_status_numerical_error : aoclsparse_status_success;
+    return st;
+}
+
+// the factor values as a matrix of their own: its level-scheduled TRSV plans are the smoother's solves.  It records value maps
+// when A does, so that a refactorisation can carry its plans over
+template <typename T>
+aoclsparse_status ilu_factor_handle(aoclsparse_matrix A)
+{
+    MI355_TRY(create_csr(&A->ilu_factor, A->base, A->m, A->n, A->nnz, A->user.ptr, A->user.ind, static_cast<T *>(A->ilu_val)));
+    A->ilu_factor->keep_maps = A->keep_maps;
+    return aoclsparse_status_success;
+}
+
+// aoclsparse_mi355_?ilu0_refactor_device: the ILU(0) factor of the values the handle holds NOW, in place of the previous one
+template <typename T>
+aoclsparse_status ilu0_refactor_t(aoclsparse_matrix A, T **precond_csr_val, aoclsparse_matrix_data_type vt)
+{
+    // the smoother's statuses in its order (ilu.hpp:43-98), without its descriptor, x and b: all before the device is touched
+    if(!A)
+        return aoclsparse_status_invalid_pointer;
+    if(!A->user.ptr && !holds_no_csr(A)) // (a TCSR or BSR handle holds valid arrays: refused below)
+        return aoclsparse_status_invalid_pointer;
+    if(A->input_format != aoclsparse_csr_mat)
+        return aoclsparse_status_not_implemented;
+    if(A->sort != 1 && A->sort != 2) // fully or partially sorted (aoclsparse_matrix_sort)
+        return aoclsparse_status_unsorted_input;
+    if(!A->fulldiag)
+        return aoclsparse_status_numerical_error;
+    if(A->val_type != vt)
+        return aoclsparse_status_wrong_type;
+    if(A->m < 0 || A->n < 0 || A->m != A->n)
+        return aoclsparse_status_invalid_size;
+    if(A->m == 0 || A->n == 0)
+        return aoclsparse_status_success;
+    if(!A->user.ind || !A->user.val)
+        return aoclsparse_status_invalid_pointer;
+    CallScope cs(CallScope::Always); // the runtime, and the library's stream to this call alone
+    MI355_TRY(cs.st);
+    const size_t bytes = sizeof(T) * (size_t)A->nnz;
+    // -- nothing of the handle's ILU state is written before the new factor stands in a buffer of this call
+    const bool analysed = !A->ilu_sched.valid;
+    DeviceBuffer dval;
+    {
+        PhaseTimer pt("ilu: refactor: factorise");
+        MI355_TRY(ilu_schedule<T>(A));
+        DeviceCsr *dcsr = nullptr;
+        SpmvPlan  *plan = nullptr;
+        MI355_TRY(ensure_spmv(A, false, dcsr, plan)); // the mirror while it is valid, else the host view uploaded
+        MI355_TRY(dval.alloc(std::max<size_t>(bytes, 1)));
+        if(bytes)
+            MI355_HIP_TRY(hipMemcpyAsync(dval.ptr, dcsr->val.ptr, bytes, hipMemcpyDeviceToDevice, cs.s));
+        MI355_TRY(ilu0_run<T>(A, dcsr, dval.as<T>())); // (numerical_error: the previous factor stays in force)
+    }
+    PhaseTimer pt("ilu: refactor: factor handle");
+    // a factor handle from before the pattern's order changed (the schedule was released and analysed again) holds plans of the
+    // old order: it is made anew
+    if(A->ilu_factor && analysed)
+    {
+        aoclsparse_destroy(&A->ilu_factor);
+        A->ilu_factorized = false;
+    }
+    MI355_TRY(ilu_prepare(A)); // (ilu_val: allocated once, its address stays)
+    aoclsparse_status st;
+    A->ilu_plans_kept_last = 0;
+    if(A->ilu_factor)
+    {
+        // the route every handle's new values take: the host view (ilu_val) by one copy back, the mirror, the diagonal, and the
+        // TRSV plans through their value maps -- or invalidated, when they have none
+        DeviceScope scope; // (dval is the library's own device buffer whatever the pointer mode says)
+        st = revalue_device_any(A->ilu_factor, A->nnz, dval.ptr);
+        if(st == aoclsparse_status_success)
+            A->ilu_plans_kept_last = A->ilu_factor->last_kept_plans;
+    }
+    else
+    {
+        st = aoclsparse_status_success;
+        if(bytes && hipMemcpyAsync(A->ilu_val, dval.ptr, bytes, hipMemcpyDeviceToHost, cs.s) != hipSuccess)
+            st = aoclsparse_status_internal_error;
+        if(hipStreamSynchronize(cs.s) != hipSuccess && st == aoclsparse_status_success)
+            st = aoclsparse_status_internal_error;
+        if(st == aoclsparse_status_success)
+            st = ilu_factor_handle<T>(A);
+    }
+    if(st != aoclsparse_status_success)
+    {
+        // never a mix of old and new: A is left unfactorised, ilu_val what ilu_prepare makes of the current values
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(cs.s);
+        if(A->ilu_factor)
+            aoclsparse_destroy(&A->ilu_factor);
+        A->ilu_factorized = false;
+        std::memcpy(A->ilu_val, A->user.val, bytes);
+        return st;
+    }
+    A->ilu_factorized = true;
+    A->ilu_factorizations++;
+    if(precond_csr_val)
+        *precond_csr_val = static_cast<T *>(A->ilu_val);
+    return aoclsparse_status_success;
 }
 
 template <typename T>
@@ -451,10 +594,9 @@ aoclsparse_status ilu_smoother_t(aoclsparse_operation op, aoclsparse_matrix A, c
             MI355_TRY(ilu0_factorize<T>(A, static_cast<T *>(A->ilu_val)));
         }
         PhaseTimer pt("ilu: factor handle");
-        // the factors as a matrix of their own: its level-scheduled TRSV plans are the smoother's solves
-        MI355_TRY(create_csr(&A->ilu_factor, A->base, A->m, A->n, A->nnz, A->user.ptr, A->user.ind,
-                             static_cast<T *>(A->ilu_val)));
+        MI355_TRY(ilu_factor_handle<T>(A));
         A->ilu_factorized = true;
+        A->ilu_factorizations++;
     }
     *precond_csr_val = static_cast<T *>(A->ilu_val);
 
@@ -632,6 +774,49 @@ aoclsparse_status aoclsparse_silu_smoother(aoclsparse_operation op, aoclsparse_m
 {
     (void)approx_inv_diag;
     return ilu_smoother_t<float>(op, A, descr, precond_csr_val, x, b, aoclsparse_smat);
+}
+
+aoclsparse_status aoclsparse_mi355_silu0_refactor_device(aoclsparse_matrix A, float **precond_csr_val)
+{
+    return ilu0_refactor_t<float>(A, precond_csr_val, aoclsparse_smat);
+}
+aoclsparse_status aoclsparse_mi355_dilu0_refactor_device(aoclsparse_matrix A, double **precond_csr_val)
+{
+    return ilu0_refactor_t<double>(A, precond_csr_val, aoclsparse_dmat);
+}
+aoclsparse_status aoclsparse_mi355_cilu0_refactor_device(aoclsparse_matrix A, aoclsparse_float_complex **precond_csr_val)
+{
+    return ilu0_refactor_t<cfloat>(A, reinterpret_cast<cfloat **>(precond_csr_val), aoclsparse_cmat);
+}
+aoclsparse_status aoclsparse_mi355_zilu0_refactor_device(aoclsparse_matrix A, aoclsparse_double_complex **precond_csr_val)
+{
+    return ilu0_refactor_t<cdouble>(A, reinterpret_cast<cdouble **>(precond_csr_val), aoclsparse_zmat);
+}
+
+aoclsparse_status aoclsparse_mi355_get_ilu_info(aoclsparse_matrix A, aoclsparse_mi355_ilu_info *info)
+{
+    if(!A || !info)
+        return aoclsparse_status_invalid_pointer;
+    if(info->struct_size < sizeof(info->struct_size))
+        return aoclsparse_status_invalid_size;
+    aoclsparse_mi355_ilu_info r{};
+    {
+        // (the ILU state is written under the runtime's stage lock, by the smoother and the refactorisation alike)
+        std::lock_guard<std::recursive_mutex> sl(Runtime::get().stage_lock);
+        const auto                           &sc = A->ilu_sched;
+        r.factorized = A->ilu_factorized;
+        if(sc.valid)
+        {
+            r.levels = sc.nlevels, r.max_row = sc.max_row, r.syncfree = sc.syncfree, r.search = sc.search;
+            r.schedule_bytes = (long long)(sc.rows.bytes + sizeof(aoclsparse_int) * sc.level_ptr.size());
+        }
+        r.plans_kept_last = A->ilu_plans_kept_last;
+        r.analyses = A->ilu_analyses, r.factorizations = A->ilu_factorizations;
+        r.factor_plan_builds = A->ilu_factor ? A->ilu_factor->plan_builds : 0;
+    }
+    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
+    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
 }
 
 

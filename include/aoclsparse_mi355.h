@@ -54,7 +54,13 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_set_pointer_mode(aoclsparse_mi355_
  *                per cell, or -- a copy of short rows, where the indices of a row fit 32 bits -- one packed word of 1 / 2 / 4
  *                bytes per row (aoclsparse_mi355_get_sell_packing);
  *                0 never (the values in the cells); 1 whenever there are at most 256 patterns, whatever the size.  Read when the
- *                SELL-64 copy is built.  Same bits either way: the table holds the values' exact bit patterns. */
+ *                SELL-64 copy is built.  Same bits either way: the table holds the values' exact bit patterns.
+ *   ilu_search   -1 (default): the ILU(0) factorisation finds the position of row i that an entry of row k updates by a binary
+ *                search of the row's columns, instead of a scan of the row, when the handle's rows are fully sorted (sort class 1)
+ *                and its longest row has at least AOCLSPARSE_MI355_ILU_SEARCH_MIN entries; 0 always the scan; 1 the search whenever
+ *                the sort class is 1 (never for class 2: rows there are only grouped lower / diagonal / upper).  Read when a
+ *                handle's ILU(0) schedule is built (aoclsparse_mi355_get_ilu_info).  Same bits either way.  Its number lies
+ *                outside 0 .. option_count - 1: that block and its count stay as they are (callers and tests rely on both). */
 typedef enum aoclsparse_mi355_option_
 {
     aoclsparse_mi355_option_spmv_kernel = 0,
@@ -63,8 +69,12 @@ typedef enum aoclsparse_mi355_option_
     aoclsparse_mi355_option_alternate_sweeps = 3,
     aoclsparse_mi355_option_trsv_chunks = 4,
     aoclsparse_mi355_option_sell_values = 5,
-    aoclsparse_mi355_option_count       = 6
+    aoclsparse_mi355_option_count       = 6,
+    aoclsparse_mi355_option_ilu_search  = 16
 } aoclsparse_mi355_option;
+/* the automatic ilu_search rule: the smallest longest row from which the search was measured to win (profiles/r26/ilu_refactor.txt:
+ * by 40 % at 21 entries, a tie at 5; nothing in between was measured) */
+#define AOCLSPARSE_MI355_ILU_SEARCH_MIN 21
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_set_option(aoclsparse_mi355_option option, aoclsparse_int value);
 /* aoclsparse_?csrmm with beta == 0.  Default (0): C is read and multiplied by zero, exactly as every kernel of the reference
  * does (level3/aoclsparse_csrmm.hpp:83,129; aoclsparse_csrmm_kt.cpp:176-191,246), so a NaN / Inf already in C propagates.
@@ -381,13 +391,48 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           the handle as it was; after any failure behind the first device write the handle is left with everything dropped and
  *           all maps released (never plans with some old and some new values) and an invalid mirror (the next product uploads the
  *           host view), and the status is reported.  Peak extra device memory: sizeof(value) per entry of a clean copy, during
- *           the call.  Not kept (rebuilt lazily as ever): SELL-64 / blocked-ELL copies, derived operators, transposes, replicas,
- *           ILU factors.  ?update_values, ?set_value, ?update_values_device and ?refresh_values_from_coo_device do not take this
- *           route; a caller with a triplet map refreshes, exports the device values, and passes them here.
+ *           the call.  Not kept (rebuilt lazily as ever): SELL-64 / blocked-ELL copies, derived operators, transposes, replicas.
+ *           The ILU(0) factor is neither dropped nor recomputed: it stays the factor of the values it was made from until
+ *           ?ilu0_refactor_device is called.  ?update_values, ?set_value, ?update_values_device and
+ *           ?refresh_values_from_coo_device do not take this route; a caller with a triplet map refreshes, exports the device
+ *           values, and passes them here.
  *
  *   get_value_map_info What a handle holds of the above (struct_size as for get_coo_map_info).  plan_builds and clean_builds count
  *           the times a TRSV plan / the clean CSR was actually built or extended since the handle was created, flag or no flag:
  *           they show whether a solve after a value change analysed anything.
+ *
+ *   ?ilu0_refactor_device  (round 26) The ILU(0) factor of A again, from the values the handle holds NOW: the resident mirror
+ *           while it is valid, otherwise the host view, uploaded as every product uploads it.  In the reference and here the
+ *           smoother factorises once per handle, from the values it saw first, and a value update leaves that factor in force
+ *           (it still does); after this call aoclsparse_?ilu_smoother and the iterative solvers with "ILU0" use the new one.
+ *           precond_csr_val may be null; otherwise it receives what the smoother hands out, the factor's nnz values on A's
+ *           pattern in library-owned host memory.  That array keeps its address once it exists: a pointer handed out earlier
+ *           shows the new factor.  The call may also be the handle's first factorisation.
+ *           What the factorisation computes from the pattern alone -- the rows in level order (resident in HBM), the level
+ *           pointer, the longest row, the choice between one launch per level and the sync-free launch, and the choice of option
+ *           ilu_search -- is the handle's ILU schedule: built by the first factorisation on either route, reused by every later
+ *           one, untouched by value updates, released by aoclsparse_order_mat, order_mat_device, aoclsparse_mi355_invalidate
+ *           and destroy.  A refactorisation therefore runs no host loop over the rows and uploads nothing but, behind an invalid
+ *           mirror, the values: the factorisation runs in a fresh device buffer seeded by a device-to-device copy of the mirror's
+ *           values.  On success the factor handle (a CSR handle over A's pattern and the factor values, whose TRSV plans are the
+ *           smoother's solves) is brought up to date by ?revalue_device's own code: its host view -- the array above -- by one
+ *           copy back, its mirror, its diagonal, and its TRSV plans through their value maps.  A factor handle created while A's
+ *           keep_value_maps flag is set has the flag too; without maps its plans are invalidated as ?update_values_device
+ *           invalidates plans, and the next solve builds them again.  A factor handle that does not exist yet is created as the
+ *           smoother creates it; one from before the schedule was released is made anew.
+ *           Statuses, in the smoother's order, all decided before the device is touched: invalid_pointer for a null A or a
+ *           handle without CSR arrays (COO); not_implemented for TCSR and BSR handles; unsorted_input for a sort class other than
+ *           1 or 2; numerical_error without a full diagonal; wrong_type; invalid_size for a matrix that is not square; success at
+ *           once for m == 0.  After those a failure of the runtime's initialisation is returned as it is, and not_implemented
+ *           for a row that does not fit LDS.  A zero or near-zero pivot, or a row whose diagonal does not follow its lower part,
+ *           returns numerical_error and leaves the handle exactly as it was: the previous factor, its handle and its plans stay
+ *           in use.  A failure behind the first write into the factor handle (allocation, HIP) leaves A unfactorised -- the
+ *           factor handle destroyed, the value array a copy of the current values, as ilu_prepare makes it -- never a mix of
+ *           old and new; the status is reported and the next smoother call factorises from scratch.
+ *           The library's stream is synchronised before return.  Peak extra device memory: sizeof(value) per entry + 4 bytes per
+ *           row during the call; the schedule keeps 4 bytes per row.
+ *
+ *   get_ilu_info       What a handle holds of the above (struct_size as for get_coo_map_info).
  *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
  * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
@@ -397,8 +442,9 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  * aoclsparse_order_mat itself taking the device route; adding repeated columns while ordering; ordering CSC-created, TCSR or BSR
  * handles on the device; csr_optimize / aoclsparse_optimize choosing the device route for the clean copy by themselves; keeping the
  * clean copy resident and building TRSV plans, derived operators or ILU factors from it on the device; value maps for clean copies
- * built on the host, and keeping SELL-64 / blocked-ELL copies, derived operators, transposes, replicas or ILU factors through a
- * ?revalue_device; carrying value maps through aoclsparse_copy, exported state or replicas; clean copies of the transpose; a host view that is filled on first use instead of by
+ * built on the host, and keeping SELL-64 / blocked-ELL copies, derived operators, transposes or replicas through a
+ * ?revalue_device; computing the ILU(0) levels on the device; refactorising inside an update call by itself; a device-only ILU
+ * factor without its host array; carrying the ILU schedule through aoclsparse_copy, exported state or replicas; carrying value maps through aoclsparse_copy, exported state or replicas; clean copies of the transpose; a host view that is filled on first use instead of by
  * order_mat_device's copy back. */
 #define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
 #define AOCLSPARSE_MI355_ORDER_SHORT_MAX 32 /* order_mat_device: rows of up to this many entries are sorted by one lane */
@@ -484,6 +530,25 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_crevalue_device(aoclsparse_matrix 
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrevalue_device(aoclsparse_matrix A, aoclsparse_int len,
                                                               const aoclsparse_double_complex *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_value_map_info(aoclsparse_matrix A, aoclsparse_mi355_value_map_info *info);
+typedef struct
+{
+    size_t         struct_size; /* in: sizeof(aoclsparse_mi355_ilu_info) as the caller knows it */
+    aoclsparse_int factorized; /* 1: the handle holds an ILU(0) factor (the smoother's first call or a refactorisation made it) */
+    aoclsparse_int levels; /* the kept schedule: dependency levels of the strictly lower pattern; 0 (as the next four) without one */
+    aoclsparse_int max_row; /* ... entries of the longest row */
+    aoclsparse_int syncfree; /* ... 1: one sync-free launch over all rows; 0: one launch per level */
+    aoclsparse_int search; /* ... 1: the updated position is found by binary search; 0: by a scan (option ilu_search) */
+    aoclsparse_int plans_kept_last; /* TRSV plans of the factor handle the last ?ilu0_refactor_device carried over */
+    long long      analyses; /* times the levels were computed since the handle was created */
+    long long      factorizations; /* successful factorisations, the smoother's first call included */
+    long long      schedule_bytes; /* memory the schedule occupies: the level order in HBM, the level pointer on the host */
+    long long      factor_plan_builds; /* plan_builds (get_value_map_info) of the factor handle: did a solve analyse anything? */
+} aoclsparse_mi355_ilu_info;
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_silu0_refactor_device(aoclsparse_matrix A, float **precond_csr_val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_dilu0_refactor_device(aoclsparse_matrix A, double **precond_csr_val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_cilu0_refactor_device(aoclsparse_matrix A, aoclsparse_float_complex **precond_csr_val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zilu0_refactor_device(aoclsparse_matrix A, aoclsparse_double_complex **precond_csr_val);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_ilu_info(aoclsparse_matrix A, aoclsparse_mi355_ilu_info *info);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
                                                                 aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
                                                                 const aoclsparse_int **col_idx, const void **val);
