@@ -775,9 +775,7 @@ aoclsparse_status aoclsparse_order_mat(aoclsparse_matrix mat)
     if(mat_check(mat->m, mat->n, mat->nnz, mat->user.ptr, mat->user.ind, mat->user.val, 0, mat->base, sort, fd)
        == aoclsparse_status_success)
         mat->sort = sort, mat->fulldiag = fd;
-    mat->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
-    mat->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
-    drop_derived_state(mat); // every copy made of the unsorted arrays (clean CSR, device mirrors, plans)
+    drop_order_dependent_state(mat);
     return aoclsparse_status_success;
 }
 

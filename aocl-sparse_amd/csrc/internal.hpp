@@ -49,6 +49,15 @@ namespace mi355
             return ::mi355::map_hip_error(e__);               \
     } while(0)
 
+// (the same for a status; several files spell this one out themselves, token for token)
+#define MI355_TRY(expr)                       \
+    do                                        \
+    {                                         \
+        aoclsparse_status st__ = (expr);      \
+        if(st__ != aoclsparse_status_success) \
+            return st__;                      \
+    } while(0)
+
 aoclsparse_status map_hip_error(hipError_t e);
 
 // ---- complex values (aoclsparse_float_complex / aoclsparse_double_complex layout: {real, imag}) ---------
@@ -1159,6 +1168,12 @@ void drop_derived_state(aoclsparse_matrix A);
 // the same, except that the clean CSR with dev_diag (keep_clean) and the TRSV plans whose bit is set in keep_plans (bit i =
 // trsv_plan[i]) stay: aoclsparse_mi355_?revalue_device has brought the new values to them
 void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans);
+// drop_derived_state, and with it what indexes the entries in their order within the rows (the triplet map, the ILU(0) schedule):
+// for whoever has sorted the rows
+void drop_order_dependent_state(aoclsparse_matrix A);
+// the statuses of aoclsparse_?update_values, in its order, all decided before the handle is locked (matrix.cpp);
+// aoclsparse_mi355_?update_values_device / ?revalue_device append theirs (device_handle_api.cpp)
+aoclsparse_status update_values_status(const _aoclsparse_matrix *A, aoclsparse_int len, const void *val, aoclsparse_matrix_data_type vt);
 // value mutation on handles created from CSC / COO arrays (formats_api.cpp): the caller's arrays are the first
 // representation there; csc_refresh_csr rebuilds the handle's CSR values from the CSC arrays
 aoclsparse_status coo_set_value(aoclsparse_matrix A, aoclsparse_int row_idx, aoclsparse_int col_idx, const void *val);

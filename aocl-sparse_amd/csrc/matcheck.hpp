@@ -1,4 +1,4 @@
-// matcheck.hpp -- what matcheck_kernels.hip and its one caller (device_handle_api.cpp) share.
+// matcheck.hpp -- what matcheck_kernels.hip and the one step that launches it (device_mat_check, device_handle.hpp) share.
 #ifndef MI355_MATCHECK_HPP_
 #define MI355_MATCHECK_HPP_
 

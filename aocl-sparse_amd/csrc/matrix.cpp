@@ -1395,6 +1395,15 @@ void drop_derived_state(aoclsparse_matrix A)
     drop_derived_state_keeping(A, false, 0u);
 }
 
+// THE list of what hangs on the ORDER of the entries within A's rows (aoclsparse_order_mat and aoclsparse_mi355_order_mat_device
+// come here once the rows are sorted): every copy of the values, and the maps and schedules that index the arrays as they were
+void drop_order_dependent_state(aoclsparse_matrix A)
+{
+    A->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
+    A->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
+    drop_derived_state(A); // every copy made of the unsorted arrays (clean CSR, device mirrors, SELL-64 / blocked-ELL, plans, replicas)
+}
+
 // (keep_clean / keep_plans: aoclsparse_mi355_?revalue_device alone passes anything but false / 0 -- it has rewritten the values of
 // what it asks to keep)
 void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans)
@@ -1469,8 +1478,9 @@ static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, 
     return aoclsparse_status_invalid_index_value;
 }
 
-template <typename T>
-static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, T *val, aoclsparse_matrix_data_type vt)
+namespace mi355
+{
+aoclsparse_status update_values_status(const _aoclsparse_matrix *A, aoclsparse_int len, const void *val, aoclsparse_matrix_data_type vt)
 {
     const bool coo = A && A->input_format == aoclsparse_coo_mat, tcsr = A && holds_no_csr(A); // (or BSR: the same answers)
     if(!A || !val || (coo ? !A->coo_val : (!tcsr && !A->user.ptr)))
@@ -1483,6 +1493,17 @@ static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, 
         return aoclsparse_status_not_implemented;
     if(!coo && !A->user.val)
         return aoclsparse_status_invalid_pointer;
+    return aoclsparse_status_success;
+}
+} // namespace mi355
+
+template <typename T>
+static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, T *val, aoclsparse_matrix_data_type vt)
+{
+    const aoclsparse_status st = update_values_status(A, len, val, vt);
+    if(st != aoclsparse_status_success)
+        return st;
+    const bool                          coo = A->input_format == aoclsparse_coo_mat;
     std::unique_lock<std::shared_mutex> w(A->guard);
     if(coo) // the values follow the order of the caller's arrays (the first representation)
     {
