@@ -89,6 +89,13 @@ class ValueMapInfo(ctypes.Structure):
                 ("revalues", ctypes.c_longlong), ("map_bytes", ctypes.c_longlong)]
 
 
+class SellKeepInfo(ctypes.Structure):
+    """aoclsparse_mi355_sell_keep_info: the caller sets struct_size, the library writes no more than that"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("kept", c_int32), ("valid", c_int32), ("last_route", c_int32),
+                ("reserved", c_int32), ("structure_builds", ctypes.c_longlong), ("value_fills", ctypes.c_longlong),
+                ("searches_skipped", ctypes.c_longlong), ("kept_bytes", ctypes.c_longlong)]
+
+
 MM_STATE_BUFFERS = 14
 
 
@@ -473,6 +480,7 @@ SIGNATURES = {
     "aoclsparse_mi355_get_sell_period": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_I)]),
     "aoclsparse_mi355_sell_find_period": (c_int, [_I, _P, _P, _I, POINTER(_I), POINTER(ctypes.c_longlong)]),
     "aoclsparse_mi355_get_sell_march": (c_int, [_P, c_int, POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_I)]),
+    "aoclsparse_mi355_get_sell_keep_info": (c_int, [_P, c_int, _P]),
     "aoclsparse_mi355_sell_find_march": (c_int, [_I, _P, _P, POINTER(_I), _I, POINTER(_I)]),
     "aoclsparse_mi355_sell_march_rule": (c_int, [_I, _I, POINTER(_I), _I, _I, _I, _I, POINTER(_I)]),
     "aoclsparse_mi355_get_trsv_levels": (c_int, [_P, c_int, c_int, POINTER(_I)]),
@@ -828,6 +836,14 @@ class Matrix:
         a, b, g, c = _I(-1), _I(-1), _I(-1), _I(-1)
         assert lib().aoclsparse_mi355_get_sell_march(self.h, op, byref(a), byref(b), byref(g), byref(c)) == 0
         return a.value, b.value, g.value, c.value
+
+    def sell_keep_info(self, op=OP_NONE):
+        """aoclsparse_mi355_get_sell_keep_info -> SellKeepInfo (kept, valid, last_route, structure_builds, value_fills,
+        searches_skipped, kept_bytes): what the copy keeps through revalue_device and what its builds have done"""
+        info = SellKeepInfo(struct_size=ctypes.sizeof(SellKeepInfo))
+        st = lib().aoclsparse_mi355_get_sell_keep_info(self.h, op, byref(info))
+        assert st == 0, STATUS.get(st, st)
+        return info
 
     def trsv_info(self, fill, op=OP_NONE):
         info = TrsvInfo()

@@ -260,7 +260,9 @@ namespace
             if(v)
                 (void)hipEventDestroy(v);
         const bool ok = e.ok(); // (not ok: nothing is kept)
-        drop_derived_state_keeping(A, ok && clean_ok, ok ? keep_plans : 0u); // SELL-64 / blocked-ELL copies, derived operators, replicas
+        // SELL-64 / blocked-ELL copies, derived operators, replicas -- except the structure of the handle's own SELL-64 copy, which
+        // a handle with the flag keeps while the mirror it was built from has followed (its cells are refilled at the next product)
+        drop_derived_state_keeping(A, ok && clean_ok, ok ? keep_plans : 0u, ok && follow_maps && A->keep_maps && keep);
         if(!ok)
             A->drop_value_maps();
         if(!ok || !diag_ok) // (a diagonal without its map: ensure_trsv gathers it again; no plan was kept)

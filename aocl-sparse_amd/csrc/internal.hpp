@@ -474,6 +474,38 @@ struct SellPlan
     unsigned       malias = 0;
     bool           valid = false, tried = false;
     bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
+    // THE STRUCTURE STAGE'S RECORD (matrix.cpp: build_sell = structure, then values).  structure: pack, the widths, slice_ptr, the
+    // shared decision with cptr / lead / ccells, col, rowlen and the pristine records describe the CSR of sm rows and snnz entries
+    // under aoclsparse_mi355_option_sell == smode.  stale: aoclsparse_mi355_?revalue_device kept that structure and the cells hold
+    // the OLD values -- valid is false, no launcher runs the copy, and the next build_sell runs the values stage alone.  Every other
+    // value change clears both (drop_derived_state_keeping).
+    bool           structure = false, stale = false;
+    int            smode = -1;
+    aoclsparse_int sm = 0, snnz = 0;
+    aoclsparse_int wmax     = 0; // widest slice, in cells
+    bool           records  = false; // the copy can have slice records
+    aoclsparse_int nuniform = 0; // slices of mode 1 / 2 (what `uniform` is on a plan with ucol)
+    // the records as sell_pack_descriptors made them (nslices + SELL_DESC_PAD; host), before sell_records_kernel's flags ...
+    std::vector<SellSliceDesc> desc0;
+    // ... and what only a values stage on a kept structure allocates: their device copy, one spare set of records and uniform
+    // lists (the stage writes the new set there, compares it with the current one, and the two change places), and three words
+    // (sell_records_kernel's two counters, the compare kernel's verdict)
+    DeviceBuffer   desc0_dev, desc_spare, ucol_spare, kwords;
+    // since creation: times the structure stage / the values stage ran, times a values stage carried the periodic range over, and
+    // what the last build_sell did (0 nothing yet, 1 structure + values, 2 values with the search, 3 values, range carried over)
+    long long      structure_builds = 0, value_fills = 0, searches_skipped = 0;
+    int            last_route = 0;
+    // nothing of the structure is trusted from here on (the buffers of the copy itself stay for the next build to reuse)
+    void drop_structure()
+    {
+        structure = stale = false;
+        desc0.clear(), desc0.shrink_to_fit();
+        desc0_dev.release(), desc_spare.release(), ucol_spare.release(), kwords.release();
+    }
+    size_t kept_bytes() const
+    {
+        return sizeof(SellSliceDesc) * desc0.capacity() + desc0_dev.bytes + desc_spare.bytes + ucol_spare.bytes + kwords.bytes;
+    }
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
     // Infinity Cache (the END of its sweep) is where the next one starts (sell_kernels.hip); the bits do not depend on it
     mutable std::atomic<unsigned> products{0};
@@ -1166,8 +1198,9 @@ aoclsparse_status csr_optimize(aoclsparse_matrix A);
 // forget every copy derived from the user's arrays (clean CSR, transposes, device mirrors, SELL, TRSV plans)
 void drop_derived_state(aoclsparse_matrix A);
 // the same, except that the clean CSR with dev_diag (keep_clean) and the TRSV plans whose bit is set in keep_plans (bit i =
-// trsv_plan[i]) stay: aoclsparse_mi355_?revalue_device has brought the new values to them
-void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans);
+// trsv_plan[i]) stay: aoclsparse_mi355_?revalue_device has brought the new values to them; keep_sell: the STRUCTURE of plan_user's
+// SELL-64 copy stays (SellPlan::stale: its cells hold the old values until the next build_sell refills them)
+void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell = false);
 // drop_derived_state, and with it what indexes the entries in their order within the rows (the triplet map, the ILU(0) schedule):
 // for whoever has sorted the rows
 void drop_order_dependent_state(aoclsparse_matrix A);
@@ -1302,6 +1335,14 @@ aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsi
 // counts (device, two words, zeroed here) receives how many slices got each flag.  d = the CSR the copy mirrors.
 aoclsparse_status launch_sell_records(hipStream_t s, const DeviceCsr &d, const SellView &v, SellSliceDesc *desc, aoclsparse_int *ucol,
                                       unsigned *counts);
+// the values stage on a KEPT structure: the cells of the copy v describes from d's values alone, in v's encoding (values, one-byte
+// indices, packed row words; zero words behind m, 0 in the padding cells); ucol (nullable; preset to -1) gets the list of every
+// mode 1 / 2 slice.  Neither col nor rowlen is written.
+aoclsparse_status launch_sell_refill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *ucol);
+// behind launch_sell_records: *verdict (device, zeroed here) becomes 1 when the nslices records or the nslices x SELL_SHORT_WMAX list
+// entries of set a differ from those of set b anywhere, and stays 0 when they are equal
+aoclsparse_status launch_sell_compare(hipStream_t s, aoclsparse_int nslices, const SellSliceDesc *desc_a, const SellSliceDesc *desc_b,
+                                      const aoclsparse_int *ucol_a, const aoclsparse_int *ucol_b, unsigned *verdict);
 // distinct bit patterns of n values of vsize (4 / 8) bytes on the device: *ntab of them; table = SELL_VTAB_MAX entries of vsize
 // bytes ready to upload, ascending by bit pattern, the unused ones 0; *ntab = 0 when there are more than SELL_VTAB_MAX
 constexpr int     SELL_VTAB_MAX = 256;

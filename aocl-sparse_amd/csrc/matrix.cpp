@@ -678,20 +678,283 @@ void sell_pack_descriptors(aoclsparse_int nslices, const long long *slice_ptr, c
         out[nslices + k] = pack(slice_ptr[nslices], ccells, 0, 1, SELL_DESC_MODE_ONE);
 }
 
+// ---- build_sell = the STRUCTURE stage, then the VALUES stage ------------------------------------------------------------------
+// Structure: what row_ptr, col_idx, the sizes and aoclsparse_mi355_option_sell decide (SellPlan::structure lists it).  Values: the
+// table and the cell encoding chosen from it, the cells, ucol and the uniform lists, the device flags of the records, the periodic
+// range and the stacking facts.  A first build interleaves the two where today's order of allocations asks for it (the table pass
+// sits between the shared lists and the column arrays: where the later arrays lie in HBM moves the products by 2 - 3 %); a handle
+// whose structure aoclsparse_mi355_?revalue_device kept (SellPlan::stale) runs sell_values_kept alone.
+namespace
+{
+
+// the encoding the values stage chooses from the table pass
+struct SellEncoding
+{
+    int           ntab = 0, pbits = 0, pbytes = 0;
+    unsigned char tab[sizeof(double) * SELL_VTAB_MAX];
+};
+
+// Value table: at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil holds two) -> one byte per cell instead
+// of 4 / 8 (sell_build_kernels.hip).  Real types only; the same size gate as the shared lists (a matrix that lives in the caches gains
+// nothing); aoclsparse_mi355_set_option(sell_values, 0 / 1): never / whatever the size.  One pass over the device values.
+// With slice records the indices of a row are packed into ONE word where they fit: fields of 1 / 2 / 4 / 8 bits (the smallest that
+// holds ntab - 1), cell q at bit q * bits, in the smallest word of 1 / 2 / 4 bytes that holds the widest slice.
+aoclsparse_status sell_choose_encoding(const DeviceCsr &d, size_t vsize, bool complex_values, const SellPlan &sp, SellEncoding &enc)
+{
+    const int vmode = plan_option(aoclsparse_mi355_option_sell_values); // -1 automatic (default), 0 never, 1 whatever the size
+    if(complex_values || (vsize != sizeof(double) && vsize != sizeof(float)) || vmode == 0 || !(vmode == 1 || d.nnz >= (1 << 17)))
+        return aoclsparse_status_success;
+    int ntab = 0;
+    MI355_TRY(sell_value_table(Runtime::get().stream(), vsize, d.nnz, d.val.ptr, enc.tab, &ntab));
+    if(ntab > 0)
+    {
+        int bits = 1;
+        while((1 << bits) < ntab)
+            bits *= 2;
+        const int wbits = (int)sp.wmax * bits;
+        enc.ntab        = ntab;
+        if(sp.records && wbits <= 32)
+            enc.pbits = bits, enc.pbytes = wbits <= 8 ? 1 : (wbits <= 16 ? 2 : 4);
+    }
+    if(PhaseTimer::on())
+        std::fprintf(stderr, "[mi355 timing] sell: %d distinct value patterns%s\n", ntab, ntab ? "" : " (more than 256, or none)");
+    return aoclsparse_status_success;
+}
+
+// the table and the cell array of enc: vtab + pidx ((nslices + SELL_DESC_PAD) x 64 words, addressed by row number alone) or vidx
+// (one byte per cell), or val; what another encoding held is released.  With the SELL_CELL_PAD cells after the last: value 0 /
+// index 0 -- what the short-row kernel reads for a slice of width 0 -- and the words of the padding slices (the rows behind m in
+// the last slice are the fill kernel's).
+aoclsparse_status sell_alloc_cells(SellPlan &sp, const SellEncoding &enc, size_t vsize)
+{
+    Runtime     &rt = Runtime::get();
+    const size_t nslices = (size_t)sp.nslices, cells = (size_t)sp.cells;
+    sp.ntab = sp.pbits = sp.pbytes = 0;
+    if(enc.ntab > 0)
+    {
+        MI355_TRY(sp.vtab.upload(enc.tab, vsize * (size_t)SELL_VTAB_MAX, rt.stream()));
+        if(enc.pbits)
+        {
+            MI355_TRY(sp.pidx.alloc((nslices + SELL_DESC_PAD) * 64 * (size_t)enc.pbytes));
+            sp.vidx.release();
+        }
+        else
+        {
+            MI355_TRY(sp.vidx.alloc(cells + SELL_CELL_PAD));
+            sp.pidx.release();
+        }
+        sp.ntab = enc.ntab, sp.pbits = enc.pbits, sp.pbytes = enc.pbytes;
+        sp.val.release();
+        if(sp.pbits)
+            MI355_HIP_TRY(hipMemsetAsync(sp.pidx.as<unsigned char>() + nslices * 64 * (size_t)sp.pbytes, 0,
+                                         (size_t)SELL_DESC_PAD * 64 * (size_t)sp.pbytes, rt.stream()));
+        else
+            MI355_HIP_TRY(hipMemsetAsync(sp.vidx.as<unsigned char>() + cells, 0, SELL_CELL_PAD, rt.stream()));
+        return aoclsparse_status_success;
+    }
+    sp.vtab.release(), sp.vidx.release(), sp.pidx.release();
+    MI355_TRY(sp.val.alloc(vsize * (cells + SELL_CELL_PAD)));
+    MI355_HIP_TRY(hipMemsetAsync(sp.val.as<unsigned char>() + vsize * cells, 0, vsize * SELL_CELL_PAD, rt.stream()));
+    return aoclsparse_status_success;
+}
+
+// bytes of the uniform lists (SELL_SHORT_WMAX columns per slice, the padding slices included)
+size_t sell_ucol_bytes(aoclsparse_int nslices)
+{
+    return sizeof(aoclsparse_int) * SELL_SHORT_WMAX * ((size_t)nslices + SELL_DESC_PAD);
+}
+
+// The periodic range of the records and lists as the device now holds them (flags, words and canonical lists included: they
+// depend on the values).  A stencil's records repeat from grid line to grid line, and the short-row kernel then reads one
+// period's for the whole range (sell_period.cpp).  A copy that cannot be made keeps no range.  desc: nslices records of scratch.
+aoclsparse_status sell_search_range(SellPlan &sp, size_t vsize, std::vector<SellSliceDesc> &desc)
+{
+    Runtime                    &rt      = Runtime::get();
+    const aoclsparse_int        nslices = sp.nslices;
+    PhaseTimer                  pt("sell: periodic range of the records");
+    std::vector<aoclsparse_int> uh;
+    try
+    {
+        uh.resize((size_t)nslices * SELL_SHORT_WMAX);
+        desc.resize(std::max(desc.size(), (size_t)nslices));
+    }
+    catch(const std::bad_alloc &)
+    {
+        return aoclsparse_status_success;
+    }
+    if(uh.empty())
+        return aoclsparse_status_success;
+    MI355_HIP_TRY(hipMemcpyAsync(desc.data(), sp.desc.ptr, sizeof(SellSliceDesc) * (size_t)nslices, hipMemcpyDeviceToHost, rt.stream()));
+    MI355_HIP_TRY(hipMemcpyAsync(uh.data(), sp.ucol.ptr, sizeof(aoclsparse_int) * uh.size(), hipMemcpyDeviceToHost, rt.stream()));
+    MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
+    aoclsparse_int pr[4];
+    sell_find_period(desc.data(), uh.data(), nslices, SELL_PERIOD_CAP, pr);
+    if(sell_period_usable(nslices, pr[0], pr[1], pr[2], pr[3], vsize))
+    {
+        sp.pslo = (int)pr[0], sp.pshi = (int)pr[1], sp.pper = (int)pr[2], sp.pstride = (int)pr[3];
+        // whether the range can be stacked, and its alias map: one pass over the first period (<= SELL_PERIOD_CAP slices)
+        PhaseTimer     mt("sell: stacking and alias map of the period");
+        aoclsparse_int mr[2];
+        sell_find_march(desc.data(), uh.data(), nslices, pr, sp.pbytes, mr);
+        sp.mstack = (int)mr[0], sp.malias = (unsigned)mr[1];
+    }
+    return aoclsparse_status_success;
+}
+
+void swap_buffers(DeviceBuffer &a, DeviceBuffer &b)
+{
+    DeviceBuffer t;
+    t.adopt(a), a.adopt(b), b.adopt(t);
+}
+
+// The values stage on a kept structure: table pass, cells of the chosen encoding (buffers of another encoding class are released
+// and allocated as a first build would), the value-only fill, and -- on a copy with uniform lists and one-byte words -- the
+// records kernel on the SPARE set of records and lists (records copied from the pristine ones, lists preset to -1), a compare
+// kernel against the current set, and the host search only when the two differ or the class changed.  The spare set becomes the
+// current one either way.  Values scaled by a positive factor keep the order of their bit patterns, hence every index, word, flag
+// and list: the range is then carried over and nothing but three words comes back to the host.
+aoclsparse_status sell_values_kept(const DeviceCsr &d, size_t vsize, SpmvPlan &plan, bool complex_values)
+{
+    SellPlan            &sp      = plan.sell;
+    Runtime             &rt      = Runtime::get();
+    hipStream_t          s       = rt.stream();
+    const aoclsparse_int nslices = sp.nslices;
+    PhaseTimer           pt("sell: values (structure kept)");
+    SellEncoding         enc;
+    LapTimer             lt; // (host clock; the laps end where the stage waits for the stream anyway)
+    MI355_TRY(sell_choose_encoding(d, vsize, complex_values, sp, enc));
+    lt.lap("sell kept: table pass");
+    const bool had_ucol = sp.ucol.ptr != nullptr, want_ucol = sp.records && sp.shared && enc.pbits > 0;
+    const bool flagged  = had_ucol && sp.ntab > 0 && sp.pbytes == 1; // the current records may carry device flags
+    const bool same     = (sp.ntab > 0) == (enc.ntab > 0) && (sp.ntab > 0 ? sp.pbits : 0) == enc.pbits
+                      && (sp.ntab > 0 ? sp.pbytes : 0) == enc.pbytes && had_ucol == want_ucol;
+    const bool compare  = same && flagged; // (same class, so the new set has flags too)
+    if(!same)
+        sp.vtab.release(), sp.vidx.release(), sp.pidx.release(), sp.val.release(), sp.ucol.release(), sp.ucol_spare.release();
+    MI355_TRY(sell_alloc_cells(sp, enc, vsize));
+    lt.lap("sell kept: table + cell buffers");
+    SellSliceDesc  *desc_t = sp.desc.as<SellSliceDesc>();
+    aoclsparse_int *ucol_t = nullptr;
+    const size_t    dbytes = sizeof(SellSliceDesc) * ((size_t)nslices + SELL_DESC_PAD), ubytes = sell_ucol_bytes(nslices);
+    if(flagged) // the records kernel starts from the pristine records
+    {
+        if(sp.desc0.size() != (size_t)nslices + SELL_DESC_PAD)
+            return aoclsparse_status_internal_error;
+        if(!sp.desc0_dev.ptr)
+            MI355_TRY(sp.desc0_dev.upload(sp.desc0.data(), dbytes, s));
+        if(compare)
+        {
+            MI355_TRY(sp.desc_spare.alloc(dbytes));
+            MI355_TRY(sp.ucol_spare.alloc(ubytes + 2 * sizeof(unsigned)));
+            desc_t = sp.desc_spare.as<SellSliceDesc>(), ucol_t = sp.ucol_spare.as<aoclsparse_int>();
+        }
+        MI355_HIP_TRY(hipMemcpyAsync(desc_t, sp.desc0_dev.ptr, dbytes, hipMemcpyDeviceToDevice, s));
+    }
+    if(want_ucol && !compare)
+    {
+        MI355_TRY(sp.ucol.alloc(ubytes + 2 * sizeof(unsigned)));
+        ucol_t = sp.ucol.as<aoclsparse_int>();
+    }
+    if(ucol_t)
+        MI355_HIP_TRY(hipMemsetAsync(ucol_t, 0xff, ubytes, s));
+    sp.uniform           = want_ucol ? sp.nuniform : 0;
+    sp.uniform_words     = sp.exceptions = 0;
+    const SellView view  = sp.view(d.m, plan.max_row_nnz);
+    const bool     timed = PhaseTimer::on();
+    hipEvent_t     ev[2] = {nullptr, nullptr};
+    if(timed)
+        for(hipEvent_t &e : ev)
+            if(hipEventCreate(&e) != hipSuccess)
+                e = nullptr;
+    struct EventGuard
+    {
+        hipEvent_t *ev;
+        ~EventGuard()
+        {
+            for(int i = 0; i < 2; i++)
+                if(ev[i])
+                    (void)hipEventDestroy(ev[i]);
+        }
+    } eg{ev};
+    if(ev[0])
+        MI355_HIP_TRY(hipEventRecord(ev[0], s));
+    MI355_TRY(launch_sell_refill(s, d, vsize, view, const_cast<void *>(view.cells), ucol_t));
+    if(ev[1])
+        MI355_HIP_TRY(hipEventRecord(ev[1], s));
+    unsigned   rc[3]   = {0, 0, 1}; // flags set, exceptions, verdict (1: the sets differ)
+    const bool flags   = ucol_t && sp.pbytes == 1;
+    if(flags)
+    {
+        MI355_TRY(sp.kwords.alloc(4 * sizeof(unsigned)));
+        unsigned *kw = sp.kwords.as<unsigned>();
+        MI355_TRY(launch_sell_records(s, d, view, desc_t, ucol_t, kw));
+        if(compare)
+            MI355_TRY(launch_sell_compare(s, nslices, desc_t, sp.desc.as<SellSliceDesc>(), ucol_t, sp.ucol.as<aoclsparse_int>(), kw + 2));
+        MI355_HIP_TRY(hipMemcpyAsync(rc, kw, (compare ? 3 : 2) * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    }
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    lt.lap("sell kept: refill, flags, compare");
+    if(ev[0] && ev[1])
+    {
+        float ms = 0.0f;
+        if(hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+            std::fprintf(stderr, "[mi355 timing]     %-30s %8.3f ms\n", "sell: refill kernel events", ms);
+    }
+    if(compare) // the new set is the current one from here on
+        swap_buffers(sp.desc, sp.desc_spare), swap_buffers(sp.ucol, sp.ucol_spare);
+    sp.uniform_words = (aoclsparse_int)rc[0], sp.exceptions = (aoclsparse_int)rc[1];
+    const bool carried = compare && rc[2] == 0;
+    if(!carried)
+    {
+        sp.pslo = sp.pshi = sp.pper = sp.pstride = 0;
+        sp.mstack = 0, sp.malias = 0;
+        if(flags)
+        {
+            std::vector<SellSliceDesc> scratch;
+            MI355_TRY(sell_search_range(sp, vsize, scratch));
+        }
+    }
+    if(timed)
+        std::fprintf(stderr, "[mi355 timing] sell: values stage, periodic range %s\n",
+                     carried ? "carried over (search skipped)" : (flags ? "searched" : "not applicable"));
+    sp.searches_skipped += carried;
+    sp.last_route = carried ? 3 : 2;
+    return aoclsparse_status_success;
+}
+
+} // namespace
+
 aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr &d, size_t vsize, SpmvPlan &plan, bool complex_values)
 {
     SellPlan &sp = plan.sell;
     if(sp.valid || sp.tried)
         return aoclsparse_status_success;
     sp.tried = true;
+    const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
+    // a structure kept through ?revalue_device: the values stage alone, if it was built under this option value from this CSR
+    if(sp.stale && sp.structure && mode == sp.smode && mode != 0 && d.valid && d.m == sp.sm && d.nnz == sp.snnz && d.m > 0 && d.nnz > 0)
+    {
+        sp.stale                   = false;
+        const aoclsparse_status st = sell_values_kept(d, vsize, plan, complex_values);
+        if(st != aoclsparse_status_success) // as a failed first build: tried, not valid; nothing of the structure is trusted again
+        {
+            sp.drop_structure();
+            return st;
+        }
+        sp.value_fills++;
+        sp.valid = sp.wanted = true;
+        return aoclsparse_status_success;
+    }
+    sp.drop_structure();
     sp.ntab  = 0; // (a copy built before a value change may have had a table: it goes with the values)
     sp.pbits = sp.pbytes = 0, sp.uniform = 0, sp.uniform_words = sp.exceptions = 0;
     sp.pslo = sp.pshi = sp.pper = sp.pstride = 0;
     sp.mstack = 0, sp.malias = 0;
     sp.vtab.release(), sp.vidx.release(), sp.pidx.release(), sp.desc.release(), sp.ucol.release();
-    const int mode = plan_option(aoclsparse_mi355_option_sell); // -1 automatic (default), 0 never, 1 whatever the padding
     if(mode == 0 || d.m <= 0 || d.nnz <= 0 || !d.valid)
         return aoclsparse_status_success;
+    // -- structure: slice widths, padding verdict, shared lists
+    LapTimer               lt;
     const aoclsparse_int   m = d.m, nslices = (m + 63) / 64;
     std::vector<long long> sptr;
     try
@@ -726,6 +989,8 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     // 1.64 cells per non-zero; 1.35 keeps a margin for matrices with shorter rows.
     if(mode != 1 && (double)cells > 1.35 * (double)d.nnz + 64.0)
         return aoclsparse_status_success;
+    sp.nslices = nslices, sp.cells = cells, sp.pack = pack;
+    sp.wmax = wmax, sp.records = records, sp.nuniform = 0;
     Runtime          &rt = Runtime::get();
     aoclsparse_status st = sp.slice_ptr.upload(sptr.data(), sizeof(long long) * sptr.size(), rt.stream());
     // Shared column lists: rows that repeat the list of the row before them -- as it is (the dofs of a mesh node) or
@@ -767,64 +1032,18 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         else
             sp.lead.release();
     }
-    // Value table: at most SELL_VTAB_MAX distinct bit patterns (a constant-coefficient stencil holds two) -> one byte per cell instead
-    // of 4 / 8 (sell_build_kernels.hip).  Real types only; the same size gate as the shared lists (a matrix that lives in the caches gains
-    // nothing); aoclsparse_mi355_set_option(sell_values, 0 / 1): never / whatever the size.  One pass over the device values.
-    const int vmode = plan_option(aoclsparse_mi355_option_sell_values); // -1 automatic (default), 0 never, 1 whatever the size
-    if(st == aoclsparse_status_success && !complex_values && (vsize == sizeof(double) || vsize == sizeof(float)) && vmode != 0
-       && (vmode == 1 || d.nnz >= (1 << 17)))
-    {
-        unsigned char tab[sizeof(double) * SELL_VTAB_MAX];
-        int           ntab = 0;
-        st = sell_value_table(rt.stream(), vsize, d.nnz, d.val.ptr, tab, &ntab);
-        if(st == aoclsparse_status_success && ntab > 0)
-        {
-            st = sp.vtab.upload(tab, vsize * (size_t)SELL_VTAB_MAX, rt.stream());
-            // With slice records the indices of a row are packed into ONE word where they fit: fields of 1 / 2 / 4 / 8 bits (the
-            // smallest that holds ntab - 1), cell q at bit q * bits, in the smallest word of 1 / 2 / 4 bytes that holds the widest
-            // slice; (nslices + SELL_DESC_PAD) x 64 words, addressed by row number alone.  Otherwise one byte per cell.
-            int bits = 1;
-            while((1 << bits) < ntab)
-                bits *= 2;
-            const int wbits = (int)wmax * bits;
-            if(st == aoclsparse_status_success && records && wbits <= 32)
-            {
-                sp.pbits  = bits;
-                sp.pbytes = wbits <= 8 ? 1 : (wbits <= 16 ? 2 : 4);
-                st        = sp.pidx.alloc(((size_t)nslices + SELL_DESC_PAD) * 64 * (size_t)sp.pbytes);
-            }
-            else if(st == aoclsparse_status_success)
-                st = sp.vidx.alloc((size_t)cells + SELL_CELL_PAD);
-            if(st == aoclsparse_status_success)
-            {
-                sp.ntab = ntab;
-                sp.val.release();
-            }
-            else
-                sp.pbits = sp.pbytes = 0;
-        }
-        if(PhaseTimer::on())
-            std::fprintf(stderr, "[mi355 timing] sell: %d distinct value patterns%s\n", ntab, ntab ? "" : " (more than 256, or none)");
-    }
-    // (SELL_CELL_PAD cells / column entries after the last: value 0, index 0, column -1 -- what the short-row kernel reads for a
-    // slice of width 0)
-    if(st == aoclsparse_status_success && sp.ntab == 0)
-        st = sp.val.alloc(vsize * ((size_t)cells + SELL_CELL_PAD));
-    if(st == aoclsparse_status_success)
-        st = sp.col.alloc(sizeof(aoclsparse_int) * ((size_t)sp.ccells + SELL_CELL_PAD));
-    if(st == aoclsparse_status_success)
-        st = sp.rowlen.alloc(sizeof(aoclsparse_int) * (size_t)m);
     if(st != aoclsparse_status_success)
         return st;
-    if(sp.ntab && sp.pbits) // (the words of the padding slices; the rows behind m in the last slice are the fill kernel's)
-        MI355_HIP_TRY(hipMemsetAsync(sp.pidx.as<unsigned char>() + (size_t)nslices * 64 * (size_t)sp.pbytes, 0,
-                                     (size_t)SELL_DESC_PAD * 64 * (size_t)sp.pbytes, rt.stream()));
-    else if(sp.ntab)
-        MI355_HIP_TRY(hipMemsetAsync(sp.vidx.as<unsigned char>() + cells, 0, SELL_CELL_PAD, rt.stream()));
-    else
-        MI355_HIP_TRY(hipMemsetAsync(sp.val.as<unsigned char>() + vsize * (size_t)cells, 0, vsize * SELL_CELL_PAD, rt.stream()));
+    // -- values: the table pass and the cells of the encoding it chooses (here, between the shared lists and the column arrays:
+    // the order of a build's allocations is part of the plan)
+    SellEncoding enc;
+    MI355_TRY(sell_choose_encoding(d, vsize, complex_values, sp, enc));
+    MI355_TRY(sell_alloc_cells(sp, enc, vsize));
+    // -- structure: the column arrays (SELL_CELL_PAD column entries after the last: -1) and the pristine records
+    MI355_TRY(sp.col.alloc(sizeof(aoclsparse_int) * ((size_t)sp.ccells + SELL_CELL_PAD)));
+    MI355_TRY(sp.rowlen.alloc(sizeof(aoclsparse_int) * (size_t)m));
     MI355_HIP_TRY(hipMemsetAsync(sp.col.as<aoclsparse_int>() + sp.ccells, 0xff, sizeof(aoclsparse_int) * SELL_CELL_PAD, rt.stream()));
-    std::vector<SellSliceDesc> desc;
+    std::vector<SellSliceDesc> &desc = sp.desc0;
     if(records)
     {
         try
@@ -839,24 +1058,32 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
         st = sp.desc.upload(desc.data(), sizeof(SellSliceDesc) * desc.size(), rt.stream());
         if(st != aoclsparse_status_success)
             return st;
+        if(sp.shared)
+            for(aoclsparse_int s = 0; s < nslices; s++)
+                sp.nuniform += (nlh[s] >> 8) == SELL_DESC_MODE_LANE_SHIFT || (nlh[s] >> 8) == SELL_DESC_MODE_ONE;
+    }
+    sp.structure = true, sp.smode = mode, sp.sm = d.m, sp.snnz = d.nnz;
+    sp.structure_builds++;
+    lt.lap("sell: structure (with the table pass)");
+    // -- values: uniform lists, cells, device flags, periodic range
+    if(records)
+    {
         // uniform column lists: a slice of mode 1 / 2 (full, one leader: sell_leaders_kernel) has ONE list, which the short-row
         // kernel reads with a scalar load at 8 s -- no record needed; every other entry stays -1 (the fill kernel writes the lists).
         // Only next to packed words: with values or one-byte indices in the cells the lists gained nothing for double and lost
         // 4 - 6 % for float (profiles/r10/spw_sweep.txt, "ucol with values"), so those plans keep the kernels they had.
         if(sp.shared && sp.pbits)
         {
-            const size_t ubytes = sizeof(aoclsparse_int) * SELL_SHORT_WMAX * ((size_t)nslices + SELL_DESC_PAD);
+            const size_t ubytes = sell_ucol_bytes(nslices);
             // (+ two words behind the lists: the counters of sell_records_kernel, so that the plan makes no allocation of its own
             // for them -- where later arrays lie in HBM moves the other SELL products by 2 - 3 %)
             st                  = sp.ucol.alloc(ubytes + 2 * sizeof(unsigned));
             if(st != aoclsparse_status_success)
                 return st;
             MI355_HIP_TRY(hipMemsetAsync(sp.ucol.ptr, 0xff, ubytes, rt.stream()));
-            for(aoclsparse_int s = 0; s < nslices; s++)
-                sp.uniform += (nlh[s] >> 8) == SELL_DESC_MODE_LANE_SHIFT || (nlh[s] >> 8) == SELL_DESC_MODE_ONE;
+            sp.uniform = sp.nuniform;
         }
     }
-    sp.nslices = nslices, sp.cells = cells, sp.pack = pack;
     const SellView view = sp.view(m, plan.max_row_nnz);
     st = launch_sell_fill(rt.stream(), d, vsize, view, const_cast<void *>(view.cells), sp.col.as<aoclsparse_int>(),
                           sp.rowlen.as<aoclsparse_int>(), sp.ucol.as<aoclsparse_int>());
@@ -875,39 +1102,14 @@ aoclsparse_status build_sell(const aoclsparse_int *row_ptr_host, const DeviceCsr
     }
     MI355_HIP_TRY(hipStreamSynchronize(rt.stream())); // sptr / cptr / desc (host) are read by the uploads until here
     sp.uniform_words = (aoclsparse_int)rc[0], sp.exceptions = (aoclsparse_int)rc[1];
-    // the periodic range of the records and lists as the device now holds them (flags, words and canonical lists included: they
-    // depend on the values, so every rebuild passes here too).  A stencil's records repeat from grid line to grid line, and the
-    // short-row kernel then reads one period's for the whole range (sell_period.cpp).  A copy that cannot be made keeps no range.
+    // the periodic range of the records and lists as the device now holds them (on a host copy: the pristine records stay)
     if(sp.ucol.ptr && sp.pbytes == 1)
     {
-        PhaseTimer                  pt("sell: periodic range of the records");
-        std::vector<aoclsparse_int> uh;
-        try
-        {
-            uh.resize((size_t)nslices * SELL_SHORT_WMAX);
-        }
-        catch(const std::bad_alloc &)
-        {
-            uh.clear();
-        }
-        if(!uh.empty())
-        {
-            MI355_HIP_TRY(hipMemcpyAsync(desc.data(), sp.desc.ptr, sizeof(SellSliceDesc) * (size_t)nslices, hipMemcpyDeviceToHost, rt.stream()));
-            MI355_HIP_TRY(hipMemcpyAsync(uh.data(), sp.ucol.ptr, sizeof(aoclsparse_int) * uh.size(), hipMemcpyDeviceToHost, rt.stream()));
-            MI355_HIP_TRY(hipStreamSynchronize(rt.stream()));
-            aoclsparse_int pr[4];
-            sell_find_period(desc.data(), uh.data(), nslices, SELL_PERIOD_CAP, pr);
-            if(sell_period_usable(nslices, pr[0], pr[1], pr[2], pr[3], vsize))
-            {
-                sp.pslo = (int)pr[0], sp.pshi = (int)pr[1], sp.pper = (int)pr[2], sp.pstride = (int)pr[3];
-                // whether the range can be stacked, and its alias map: one pass over the first period (<= SELL_PERIOD_CAP slices)
-                PhaseTimer     mt("sell: stacking and alias map of the period");
-                aoclsparse_int mr[2];
-                sell_find_march(desc.data(), uh.data(), nslices, pr, sp.pbytes, mr);
-                sp.mstack = (int)mr[0], sp.malias = (unsigned)mr[1];
-            }
-        }
+        std::vector<SellSliceDesc> scratch;
+        MI355_TRY(sell_search_range(sp, vsize, scratch));
     }
+    lt.lap("sell: values (fill, flags, range)");
+    sp.value_fills++, sp.last_route = 1;
     sp.valid = sp.wanted = true;
     return aoclsparse_status_success;
 }
@@ -1406,7 +1608,7 @@ void drop_order_dependent_state(aoclsparse_matrix A)
 
 // (keep_clean / keep_plans: aoclsparse_mi355_?revalue_device alone passes anything but false / 0 -- it has rewritten the values of
 // what it asks to keep)
-void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans)
+void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell)
 {
     for(aoclsparse_matrix t : A->tcsr_tri) // TCSR: everything that holds values hangs on the two triangle handles
         if(t)
@@ -1429,8 +1631,17 @@ void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned k
     A->replicas_cloned = 0;
     A->dev_user.valid = A->dev_trans.valid = false; // device CSRs; row-block plans stay valid: structure is unchanged
     A->dev_bsr.valid = false; // the mirror of a BSR handle's arrays
+    const bool sell_live = A->plan_user.sell.valid || A->plan_user.sell.stale; // (a copy that serves products, or a kept structure)
     A->plan_user.sell.valid = A->plan_user.sell.tried = false; // the SELL copies hold values: rebuilt on optimize
     A->plan_trans.sell.valid = A->plan_trans.sell.tried = false;
+    // (the structure of the handle's own copy outlives a ?revalue_device: stale until build_sell has refilled the cells; two
+    // revalues in a row leave the same state)
+    SellPlan &us = A->plan_user.sell;
+    if(keep_sell && us.structure && sell_live && us.sm == A->m && us.snnz == A->nnz)
+        us.stale = true;
+    else
+        us.drop_structure();
+    A->plan_trans.sell.drop_structure();
     // ... and so does the blocked-ELL copy of csrmm (round 6: it was left standing, and a product after aoclsparse_?set_value /
     // ?update_values on a block-dense handle used the OLD values -- found by tests/test_gpu_r6.py)
     A->plan_user.bell.valid = A->plan_user.bell.tried = false;

@@ -397,6 +397,101 @@ void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *ce
         v.pack == 4 ? go(P4{}, std::false_type{}) : go(P1{}, std::false_type{});
 }
 
+// ---- the values stage on a kept structure (matrix.cpp: sell_values_kept) ---------------------------------------------------------
+// sell_fill_kernel's geometry -- one wavefront per slice, a lane per row -- and its cells, from row_ptr and val alone: cell p of
+// row i is entry row_ptr[i] + p of the CSR, so no value map is needed.  col and rowlen are the structure's and are not written;
+// col_idx is read only by lane 0 of a mode 1 / 2 slice, for the uniform list (ucol preset to -1 by the host; cptr carries the
+// modes and is there whenever ucol is).  Whether the column lists are shared or own makes no difference to a value cell.
+template <typename T, int PACK>
+__global__ __launch_bounds__(256) void sell_refill_kernel(aoclsparse_int m, int base, const aoclsparse_int *__restrict__ row_ptr,
+                                                          const aoclsparse_int *__restrict__ col, const T *__restrict__ val,
+                                                          aoclsparse_int nslices, const long long *__restrict__ slice_ptr,
+                                                          const long long *__restrict__ cptr, T *__restrict__ sval,
+                                                          unsigned char *__restrict__ sidx, const T *__restrict__ vtab, int ntab,
+                                                          unsigned char *__restrict__ pidx, int pbits, int pbytes,
+                                                          aoclsparse_int *__restrict__ ucol)
+{
+    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if(s >= nslices)
+        return;
+    const int       i  = s * 64 + lane;
+    const long long o0 = slice_ptr[s];
+    const int       w  = (int)((slice_ptr[s + 1] - o0) >> 6);
+    bool            uni = false; // this lane writes the slice's uniform list (a mode 1 / 2 slice is full: its lane 0 is a row)
+    if(ucol && cptr)
+    {
+        const int mode = (int)(cptr[s] >> SELL_CPTR_MODE_SHIFT);
+        uni = lane == 0 && i < m && w <= SELL_SHORT_WMAX && (mode == SELL_DESC_MODE_LANE_SHIFT || mode == SELL_DESC_MODE_ONE);
+    }
+    int b = 0, len = 0;
+    if(i < m)
+    {
+        b   = row_ptr[i] - base;
+        len = row_ptr[i + 1] - base - b;
+    }
+    unsigned word = 0;
+    for(int p = 0; p < w; p++)
+    {
+        const long long o  = o0 + cell_of<PACK>(p, lane);
+        const bool      in = p < len;
+        bool            packed = false;
+        if constexpr(std::is_floating_point_v<T>)
+            packed = pidx != nullptr;
+        if(packed)
+        {
+            if constexpr(std::is_floating_point_v<T>)
+                word |= in ? (unsigned)vtab_index(val[b + p], vtab, ntab) << (p * pbits) : 0u;
+        }
+        else
+            fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
+        if(uni)
+            ucol[(long long)s * SELL_SHORT_WMAX + p] = in ? col[b + p] - base : -1;
+    }
+    if(pidx) // (every lane of the slice: the rows behind m hold 0)
+    {
+        const long long row = (long long)s * 64 + lane;
+        if(pbytes == 1)
+            pidx[row] = (unsigned char)word;
+        else if(pbytes == 2)
+            reinterpret_cast<unsigned short *>(pidx)[row] = (unsigned short)word;
+        else
+            reinterpret_cast<unsigned *>(pidx)[row] = word;
+    }
+}
+
+template <typename T>
+void sell_refill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *cells, aoclsparse_int *ucol)
+{
+    T             *sval = v.ntab ? nullptr : static_cast<T *>(cells);
+    unsigned char *sidx = v.ntab && !v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
+    unsigned char *pidx = v.ntab && v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
+    auto           go   = [&](auto pack) {
+        hipLaunchKernelGGL((sell_refill_kernel<T, decltype(pack)::value>), dim3((v.nslices + 3) / 4), dim3(256), 0, s, v.m, d.base,
+                           d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.as<T>(), v.nslices, v.slice_ptr, v.cptr, sval,
+                           sidx, static_cast<const T *>(v.vtab), v.ntab, pidx, v.pbits, v.pbytes, ucol);
+    };
+    if(v.pack == 4)
+        go(std::integral_constant<int, 4>{});
+    else
+        go(std::integral_constant<int, 1>{});
+}
+
+// the new set of records and uniform lists against the current one, as 32-bit words: any difference raises the verdict word.
+// Every thread that sees one stores the same 1 (a plain vector store; the host zeroed the word before the launch).
+__global__ __launch_bounds__(256) void sell_compare_kernel(long long nrec, const uint32_t *__restrict__ rec_a,
+                                                           const uint32_t *__restrict__ rec_b, long long nlist,
+                                                           const aoclsparse_int *__restrict__ list_a,
+                                                           const aoclsparse_int *__restrict__ list_b, unsigned *__restrict__ verdict)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    bool            diff   = false;
+    for(long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nrec + nlist; k += stride)
+        diff = diff || (k < nrec ? rec_a[k] != rec_b[k] : list_a[k - nrec] != list_b[k - nrec]);
+    if(diff)
+        *verdict = 1u;
+}
+
 // ---- what a slice record says beyond offsets, width and mode (SELL_DESC_UWORD / SELL_DESC_EXCEPT, internal.hpp) ---------------
 // Behind the fill pass, on a copy with uniform lists and one-byte packed words; one wavefront per FULL slice.
 // Mode 1 / 2 (one list): the 64 words of the fill pass are compared; if they are one word the record carries it.
@@ -506,6 +601,39 @@ aoclsparse_status launch_sell_records(hipStream_t s, const DeviceCsr &d, const S
         return aoclsparse_status_success;
     hipLaunchKernelGGL(sell_records_kernel, dim3((v.nslices + 3) / 4), dim3(256), 0, s, v.m, d.n, d.base, d.ptr.as<aoclsparse_int>(),
                        d.ind.as<aoclsparse_int>(), v.nslices, desc, static_cast<const unsigned char *>(v.cells), v.pbits, ucol, counts);
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status launch_sell_refill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *ucol)
+{
+    if(v.nslices <= 0)
+        return aoclsparse_status_success;
+    if(!cells || !v.slice_ptr || !d.ptr.ptr || !d.val.ptr || (ucol && !d.ind.ptr))
+        return aoclsparse_status_internal_error;
+    // (as launch_sell_fill: the kernel only moves values, cfloat cells travel as 8-byte doubles)
+    if(vsize == sizeof(cdouble))
+        sell_refill_as<cdouble>(s, d, v, cells, ucol);
+    else if(vsize == sizeof(float))
+        sell_refill_as<float>(s, d, v, cells, ucol);
+    else
+        sell_refill_as<double>(s, d, v, cells, ucol);
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status launch_sell_compare(hipStream_t s, aoclsparse_int nslices, const SellSliceDesc *desc_a, const SellSliceDesc *desc_b,
+                                      const aoclsparse_int *ucol_a, const aoclsparse_int *ucol_b, unsigned *verdict)
+{
+    MI355_HIP_TRY(hipMemsetAsync(verdict, 0, sizeof(unsigned), s));
+    if(nslices <= 0)
+        return aoclsparse_status_success;
+    if(!desc_a || !desc_b || !ucol_a || !ucol_b)
+        return aoclsparse_status_internal_error;
+    const long long nrec = (long long)nslices * (long long)(sizeof(SellSliceDesc) / sizeof(uint32_t)), nlist = (long long)nslices * SELL_SHORT_WMAX;
+    const long long blocks = std::min<long long>(2048, (nrec + nlist + 255) / 256);
+    hipLaunchKernelGGL(sell_compare_kernel, dim3((unsigned)blocks), dim3(256), 0, s, nrec, reinterpret_cast<const uint32_t *>(desc_a),
+                       reinterpret_cast<const uint32_t *>(desc_b), nlist, ucol_a, ucol_b, verdict);
     MI355_HIP_TRY(hipGetLastError());
     return aoclsparse_status_success;
 }

@@ -765,6 +765,27 @@ aoclsparse_status aoclsparse_mi355_get_sell_march(const aoclsparse_matrix A, aoc
     return aoclsparse_status_success;
 }
 
+aoclsparse_status aoclsparse_mi355_get_sell_keep_info(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                      aoclsparse_mi355_sell_keep_info *info)
+{
+    if(!A || !info)
+        return aoclsparse_status_invalid_pointer;
+    if(info->struct_size < sizeof(info->struct_size))
+        return aoclsparse_status_invalid_size;
+    aoclsparse_mi355_sell_keep_info r{};
+    if(op == aoclsparse_operation_none) // (only the handle's own operator keeps anything)
+    {
+        std::shared_lock<std::shared_mutex> g(A->guard);
+        const SellPlan                     &sp = A->plan_user.sell;
+        r.kept = sp.structure, r.valid = sp.valid, r.last_route = sp.last_route;
+        r.structure_builds = sp.structure_builds, r.value_fills = sp.value_fills, r.searches_skipped = sp.searches_skipped;
+        r.kept_bytes = sp.structure ? (long long)sp.kept_bytes() : 0;
+    }
+    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
+    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
+}
+
 aoclsparse_status aoclsparse_mi355_sell_find_march(aoclsparse_int nslices, const void *records, const aoclsparse_int *lists,
                                                    const aoclsparse_int range[4], aoclsparse_int word_bytes, aoclsparse_int out[2])
 {

@@ -391,7 +391,18 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           the handle as it was; after any failure behind the first device write the handle is left with everything dropped and
  *           all maps released (never plans with some old and some new values) and an invalid mirror (the next product uploads the
  *           host view), and the status is reported.  Peak extra device memory: sizeof(value) per entry of a clean copy, during
- *           the call.  Not kept (rebuilt lazily as ever): SELL-64 / blocked-ELL copies, derived operators, transposes, replicas.
+ *           the call.  Not kept (rebuilt lazily as ever): blocked-ELL copies, the SELL-64 copies of op(A) and of derived
+ *           operators, derived operators, transposes, replicas.  (4, round 28) With the keep_value_maps flag set, the STRUCTURE
+ *           of the handle's own SELL-64 copy stays -- slice widths, shared column lists, columns, row lengths, the records
+ *           before their device flags -- when the copy was valid (or already kept) and the mirror it was built from followed the
+ *           commit.  The call itself launches and waits for nothing more: the copy is marked stale, no product runs it, and the
+ *           next product, aoclsparse_optimize or hinted complex product runs the VALUES stage alone (a value-only fill kernel that
+ *           reads row_ptr and the new values -- no map is needed: cell p of row i is entry row_ptr[i] + p --, the table pass, the
+ *           records kernel on a spare set of records and lists, and a compare kernel; when the new records and lists equal the
+ *           current ones and the cell encoding is the same, the periodic range and the stacking facts are carried over and no
+ *           host search runs).  The copy is then what a fresh handle over the new values holds, bit for bit.  A different
+ *           aoclsparse_mi355_option_sell at that time means a full build; a failure in the values stage releases the structure
+ *           and leaves the product on CSR-Adaptive.  Every other value change drops the structure with the copy.
  *           The ILU(0) factor is neither dropped nor recomputed: it stays the factor of the values it was made from until
  *           ?ilu0_refactor_device is called.  ?update_values, ?set_value, ?update_values_device and
  *           ?refresh_values_from_coo_device do not take this route; a caller with a triplet map refreshes, exports the device
@@ -442,8 +453,9 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  * aoclsparse_order_mat itself taking the device route; adding repeated columns while ordering; ordering CSC-created, TCSR or BSR
  * handles on the device; csr_optimize / aoclsparse_optimize choosing the device route for the clean copy by themselves; keeping the
  * clean copy resident and building TRSV plans, derived operators or ILU factors from it on the device; value maps for clean copies
- * built on the host, and keeping SELL-64 / blocked-ELL copies, derived operators, transposes or replicas through a
- * ?revalue_device; computing the ILU(0) levels on the device; refactorising inside an update call by itself; a device-only ILU
+ * built on the host, and keeping blocked-ELL copies, the SELL-64 copies of op(A) or of derived operators, derived operators,
+ * transposes or replicas through a ?revalue_device; keeping the SELL-64 structure through any other value change, carrying it
+ * through aoclsparse_copy, exported state or replicas, and searching the periodic range on the device; computing the ILU(0) levels on the device; refactorising inside an update call by itself; a device-only ILU
  * factor without its host array; carrying the ILU schedule through aoclsparse_copy, exported state or replicas; carrying value maps through aoclsparse_copy, exported state or replicas; clean copies of the transpose; a host view that is filled on first use instead of by
  * order_mat_device's copy back. */
 #define AOCLSPARSE_MI355_COO_SORT_TILE 4096 /* entries a workgroup of the triplet sort takes per pass */
@@ -674,7 +686,26 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sell_find_period(aoclsparse_int ns
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_march(const aoclsparse_matrix A, aoclsparse_operation op,
                                                              aoclsparse_int *first_slice, aoclsparse_int *end_slice,
                                                              aoclsparse_int *periods, aoclsparse_int *alias_map);
-/* The two plan rules behind it on the caller's host arrays (no device involved; records and lists as for
+/* What the handle's SELL-64 copy keeps through a value change (aoclsparse_mi355_?revalue_device with the keep_value_maps flag) and
+ * what its builds have done.  struct_size as for aoclsparse_mi355_get_coo_map_info: the caller sets it to sizeof(*info) and the
+ * library writes no more than that.  For op other than none and for handles without a copy (TCSR, BSR, no GPU) every field is 0 and
+ * the status is success; derived operators are not reported.  invalid_pointer for a null A or info, invalid_size for a struct_size
+ * that does not hold itself. */
+typedef struct
+{
+    size_t         struct_size; /* in: sizeof(aoclsparse_mi355_sell_keep_info) as the caller knows it */
+    aoclsparse_int kept; /* 1: a structure is held now (behind a valid copy, or stale after a ?revalue_device) */
+    aoclsparse_int valid; /* 1: the copy can serve a product now */
+    aoclsparse_int last_route; /* 0 nothing yet, 1 structure + values, 2 values with the search (or nothing to search), 3 values with the range carried over */
+    aoclsparse_int reserved;
+    long long      structure_builds; /* times the structure stage ran since creation, flag or no flag */
+    long long      value_fills; /* times the values stage ran */
+    long long      searches_skipped; /* times the values stage ran and the periodic range was carried over */
+    long long      kept_bytes; /* device and host memory the kept state adds over the copy itself */
+} aoclsparse_mi355_sell_keep_info;
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sell_keep_info(const aoclsparse_matrix A, aoclsparse_operation op,
+                                                                 aoclsparse_mi355_sell_keep_info *info);
+/* The two plan rules behind aoclsparse_mi355_get_sell_march on the caller's host arrays (no device involved; records and lists as for
  * aoclsparse_mi355_sell_find_period, range = what that search reported, word_bytes = bytes per packed row word):
  * out = {1 if the range can be stacked else 0, the alias map of its first period}. */
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sell_find_march(aoclsparse_int nslices, const void *records,
