@@ -82,6 +82,13 @@ class IluInfo(ctypes.Structure):
                 ("factor_plan_builds", ctypes.c_longlong)]
 
 
+class Sp2mPlanInfo(ctypes.Structure):
+    """aoclsparse_mi355_sp2m_plan_info: the caller sets struct_size, the library writes no more than that"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("kept", c_int32), ("heavy_rows", c_int32), ("rows_in_bin", c_int32 * 5),
+                ("plan_builds", ctypes.c_longlong), ("numeric_runs", ctypes.c_longlong), ("refused", ctypes.c_longlong),
+                ("plan_bytes", ctypes.c_longlong)]
+
+
 class ValueMapInfo(ctypes.Structure):
     """aoclsparse_mi355_value_map_info: the caller sets struct_size, the library writes no more than that"""
     _fields_ = [("struct_size", ctypes.c_size_t), ("enabled", c_int32), ("clean_map", c_int32), ("plans_mapped", c_int32),
@@ -455,6 +462,8 @@ SIGNATURES = {
     "aoclsparse_mi355_cilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
     "aoclsparse_mi355_zilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
     "aoclsparse_mi355_get_ilu_info": (c_int, [_P, _P]),
+    "aoclsparse_mi355_sp2m_numeric_device": (c_int, [c_int, _P, _P, c_int, _P, _P, _P]),
+    "aoclsparse_mi355_get_sp2m_plan_info": (c_int, [_P, _P]),
     "aoclsparse_mi355_order_mat_device": (c_int, [_P]),
     "aoclsparse_mi355_clean_csr_device": (c_int, [_P]),
     "aoclsparse_mi355_export_csr_device": (c_int, [_P, POINTER(c_int), POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
@@ -714,6 +723,14 @@ class Matrix:
         factorizations, schedule_bytes, factor_plan_builds)"""
         info = IluInfo(struct_size=ctypes.sizeof(IluInfo))
         st = lib().aoclsparse_mi355_get_ilu_info(self.h, byref(info))
+        assert st == 0, STATUS.get(st, st)
+        return info
+
+    def sp2m_plan_info(self):
+        """aoclsparse_mi355_get_sp2m_plan_info -> Sp2mPlanInfo (kept, heavy_rows, rows_in_bin[5], plan_builds, numeric_runs, refused,
+        plan_bytes): what the handle holds as the C of aoclsparse_mi355_sp2m_numeric_device"""
+        info = Sp2mPlanInfo(struct_size=ctypes.sizeof(Sp2mPlanInfo))
+        st = lib().aoclsparse_mi355_get_sp2m_plan_info(self.h, byref(info))
         assert st == 0, STATUS.get(st, st)
         return info
 

@@ -926,6 +926,36 @@ struct _aoclsparse_matrix
     // the factor handle the last refactorisation carried over
     long long ilu_analyses = 0, ilu_factorizations = 0;
     int       ilu_plans_kept_last = 0;
+    // What aoclsparse_mi355_sp2m_numeric_device computes from this handle's ROW POINTER when the handle is the C of a product
+    // (spg_product.cpp: sp2m_plan_build): the rows binned by their exact length, as the fill pass of spgemm_hash_kernel bins them.
+    // In HBM, in buffers of its own: the row order (absent when one LDS bin holds every row) and the records of the rows of the
+    // global slab; on the host what the launches need, the bin bounds, the batch list and the slab's sizes.  Structure only: value
+    // changes leave it alone, and it is released exactly where ilu_sched is.  Written under the runtime's stage lock.
+    struct Sp2mPlan
+    {
+        bool                        valid = false;
+        aoclsparse_int              bounds[5 + 1] = {}; // SPGEMM_BINS + 1
+        mi355::DeviceBuffer         order, heavy; // m row numbers bin by bin; SpgHeavy records in batches
+        std::vector<aoclsparse_int> batch; // batch b = records [batch[b], batch[b + 1])
+        long long                   slots = 0, entries = 0; // table slots / list entries of the largest batch
+        void                        release()
+        {
+            valid = false, order.release(), heavy.release(), batch.clear(), batch.shrink_to_fit();
+            std::fill(bounds, bounds + 6, 0), slots = entries = 0;
+        }
+        void adopt(Sp2mPlan &o)
+        {
+            valid = o.valid, std::copy(o.bounds, o.bounds + 6, bounds), order.adopt(o.order), heavy.adopt(o.heavy);
+            batch = std::move(o.batch), slots = o.slots, entries = o.entries;
+            o.release();
+        }
+        long long bytes() const
+        {
+            return valid ? (long long)(order.bytes + heavy.bytes + sizeof(aoclsparse_int) * batch.size() + sizeof(bounds)) : 0;
+        }
+    } sp2m_plan;
+    // observers (aoclsparse_mi355_get_sp2m_plan_info): times the plan was built, successful numeric calls, calls the verdict stopped
+    long long sp2m_plan_builds = 0, sp2m_numeric_runs = 0, sp2m_refused = 0;
 
     // multi-device calls (aoclsparse_mi355_?csrmm_multi): replica[i] = a handle over the SAME host arrays whose device copy
     // and plans live on the device of runtime slot i (slot 0 is this handle itself); built on first use, dropped by
@@ -1693,6 +1723,17 @@ private:
     aoclsparse_status bin_rows(Binned &bn, bool for_fill, const int *key, const int *limit);
     aoclsparse_status run_pass(bool pass_fill, Binned &bn, const aoclsparse_int *ptr_c, aoclsparse_int *out_i, T *out_v);
 };
+// ---- the values of D = X * Y again on a structure that is kept (aoclsparse_mi355_sp2m_numeric_device; spg_product.cpp, kernels:
+// spgemm_numeric_kernels.hip).  sp2m_plan_build: the bins of C's rows by their exact length, from C's row pointer in HBM (any base)
+// alone, in buffers of the plan's own (two host waits at most: the histogram, and the rows of the global slab).  spg_numeric: one
+// launch per populated bin and per batch of the slab; C = (ptr, ind) in HBM in base c.base, `out` = the new values in C's order,
+// *d_bad (zeroed by the caller) raised when C's structure is not the product's.  The slab's tables are staging slots
+// (SPG_SLOT_G_*): the caller holds the stage lock.
+static_assert(SPGEMM_BINS == 5, "Sp2mPlan::bounds");
+aoclsparse_status sp2m_plan_build(Runtime &rt, aoclsparse_int m, const aoclsparse_int *d_ptr_c, _aoclsparse_matrix::Sp2mPlan &plan);
+template <typename T>
+aoclsparse_status spg_numeric(Runtime &rt, const _aoclsparse_matrix::Sp2mPlan &plan, const SpgDevOp &x, const SpgDevOp &y, bool conj_x,
+                              bool conj_y, const SpgDevOp &c, T *out, unsigned int *d_bad);
 // the dense-row path of aoclsparse_syrk (spgemm_kernels.hip: aat_dense_row_kernel): the upper triangle of A * A^H for a short, wide
 // A (syrk.hpp:46-113).  (ptr_s, ind_s, val_s): A with every row sorted by column and one entry per column (repeats
 // summed), 0-based -- the searchable form of the reference's dense row.  Count pass: cnt[i]; fill pass: ind_c (in base_c) / val_c

@@ -1552,6 +1552,7 @@ aoclsparse_status aoclsparse_mi355_invalidate(aoclsparse_matrix A)
     drop_derived_state(A);
     // ... and the structural plans of the device CSR, which a value change alone leaves valid
     A->ilu_sched.release(); // (the ILU(0) level schedule among them)
+    A->sp2m_plan.release(); // (and the bins of a product's numeric phase: sp2m(stage_finalize) into this handle comes here)
     for(aoclsparse_matrix t : A->tcsr_tri)
         if(t)
             (void)aoclsparse_mi355_invalidate(t);
@@ -1603,6 +1604,7 @@ void drop_order_dependent_state(aoclsparse_matrix A)
 {
     A->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
     A->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
+    A->sp2m_plan.release(); // ... and the plan of aoclsparse_mi355_sp2m_numeric_device goes with it, as documented
     drop_derived_state(A); // every copy made of the unsorted arrays (clean CSR, device mirrors, SELL-64 / blocked-ELL, plans, replicas)
 }
 

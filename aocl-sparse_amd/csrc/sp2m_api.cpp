@@ -8,6 +8,7 @@
 // on the GPU (spgemm_kernels.hip); C's arrays are host arrays owned by the new handle, like any handle
 // created by aoclsparse_create_?csr, so export / destroy work unchanged.
 #include "spg_host.hpp"
+#include "device_handle.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -304,9 +305,185 @@ aoclsparse_status sp2m_any(aoclsparse_operation opA, const aoclsparse_mat_descr 
     return aoclsparse_status_not_implemented;
 }
 
+// ---- aoclsparse_mi355_sp2m_numeric_device: C's values again, on the structure C has ----
+template <typename T>
+aoclsparse_status sp2m_numeric_t(aoclsparse_operation opA, const aoclsparse_mat_descr descrA, const aoclsparse_matrix A,
+                                 aoclsparse_operation opB, const aoclsparse_mat_descr descrB, const aoclsparse_matrix B,
+                                 aoclsparse_matrix C, aoclsparse_matrix_data_type vt)
+{
+    // -- decided before the device is touched, in this order: the checks of a finalize call ...
+    bool              trA = false, trB = false, done = true;
+    aoclsparse_matrix c  = C;
+    aoclsparse_status st = sp2m_checks(opA, descrA, A, opB, descrB, B, aoclsparse_stage_finalize, &c, vt, trA, trB, done);
+    if(done)
+    {
+        if(!C && c) // (the empty product of a finalize call without a C: a new empty handle, which nobody asked for here)
+            aoclsparse_destroy(&c);
+        return st;
+    }
+    // ... then what this call adds
+    if(!C)
+        return aoclsparse_status_invalid_pointer;
+    if(trA && trB)
+        return aoclsparse_status_not_implemented; // C = D^T: the values would need a map
+    if(C->input_format != aoclsparse_csr_mat || C->csc_ptr || !C->user.ptr || !C->user.ind || !C->user.val)
+        return aoclsparse_status_not_implemented;
+    if(C->val_type != vt)
+        return aoclsparse_status_wrong_type;
+    if(C->m != (trA ? A->n : A->m) || C->n != (trB ? B->m : B->n))
+        return aoclsparse_status_invalid_size;
+    if(C == A || C == B)
+        return aoclsparse_status_invalid_value;
+    CallScope cs(CallScope::Always); // the SPG_SLOT_* slots are shared
+    if(!cs.ok())
+        return cs.st;
+    Runtime   &rt = cs.rt;
+    StreamLaps lt{cs.s};
+    try
+    {
+        Sp2mOperands<T> o;
+        st = sp2m_operands<T>(opA, A, opB, B, trA, trB, o);
+        if(st != aoclsparse_status_success)
+            return st;
+        SpgDevOp dx, dy, dc;
+        st = sp2m_to_device(rt, o, true, dx, dy);
+        if(st != aoclsparse_status_success)
+            return st;
+        const aoclsparse_int m = o.X->m, nnz_c = C->nnz;
+        DeviceBuffer         d_val; // the new values: nothing of C is written before the verdict is in
+        void                *p_small = nullptr;
+        unsigned int         bad     = 0;
+        bool                 built   = false;
+        _aoclsparse_matrix::Sp2mPlan fresh; // a plan built by this call goes to the handle only when the call succeeds
+        struct Events // the diagnostic times the numeric kernels by device events
+        {
+            hipEvent_t at[2] = {nullptr, nullptr};
+            ~Events()
+            {
+                for(hipEvent_t v : at)
+                    if(v)
+                        (void)hipEventDestroy(v);
+            }
+        } events;
+        hipEvent_t(&ev)[2] = events.at;
+        {
+            StreamDrain drain{cs.s}; // (a way out with work in flight: the stream finishes before d_val and `fresh` go)
+            std::unique_lock<std::shared_mutex> w(C->guard);
+            MI355_TRY(resident_mirror(C)); // uploaded when absent, as every product does
+            const DeviceCsr &d = C->dev_user;
+            if(d.nnz != nnz_c || d.val.bytes < sizeof(T) * (size_t)nnz_c)
+                return aoclsparse_status_internal_error;
+            dc = SpgDevOp{d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), nullptr, (int)d.base};
+            lt.lap("sp2m_numeric: operands + mirror");
+            if(!C->sp2m_plan.valid)
+            {
+                MI355_TRY(sp2m_plan_build(rt, m, dc.ptr, fresh));
+                built = true;
+                lt.lap("sp2m_numeric: plan build");
+            }
+            const _aoclsparse_matrix::Sp2mPlan &plan = built ? fresh : C->sp2m_plan;
+            MI355_TRY(d_val.alloc(sizeof(T) * (size_t)std::max<aoclsparse_int>(nnz_c, 1)));
+            MI355_TRY(rt.staging(SPG_SLOT_SMALL, 256, &p_small));
+            unsigned int *d_bad = static_cast<unsigned int *>(p_small);
+            MI355_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), cs.s));
+            if(lt.on)
+                for(hipEvent_t &v : ev)
+                    if(hipEventCreate(&v) != hipSuccess)
+                        v = nullptr; // (without both events no figure; `events` destroys the one that was made)
+            if(!ev[0])
+                std::swap(ev[0], ev[1]); // (ev[1] set means both are)
+            if(ev[1])
+                MI355_HIP_TRY(hipEventRecord(ev[0], cs.s));
+            MI355_TRY(spg_numeric<T>(rt, plan, dx, dy, o.conj_x, o.conj_y, dc, d_val.as<T>(), d_bad));
+            if(ev[1])
+                MI355_HIP_TRY(hipEventRecord(ev[1], cs.s));
+            // the first of the call's two waits: the verdict
+            MI355_HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, cs.s));
+            MI355_HIP_TRY(hipStreamSynchronize(cs.s));
+            drain.dismiss();
+            float ms = 0.0f;
+            if(ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+                std::fprintf(stderr, "[mi355 timing]     %-30s %8.3f ms\n", "sp2m_numeric: kernel events", ms);
+            lt.lap("sp2m_numeric: kernels + verdict");
+            if(bad)
+            {
+                C->sp2m_refused++; // C's structure is not this product's: C, what hangs on it and a kept plan stay as they were
+                return aoclsparse_status_invalid_value;
+            }
+        }
+        // the second wait is the commit's: the host view by one copy back, the mirror device to device, and what a handle with
+        // keep_value_maps keeps (?revalue_device's own code, which takes C's guard itself)
+        {
+            DeviceScope scope; // (d_val is the library's own device buffer whatever the pointer mode says)
+            st = revalue_device_any(C, nnz_c, d_val.ptr);
+        }
+        lt.lap("sp2m_numeric: commit");
+        if(st != aoclsparse_status_success)
+            return st;
+        std::unique_lock<std::shared_mutex> w(C->guard);
+        if(built)
+        {
+            C->sp2m_plan.adopt(fresh);
+            C->sp2m_plan_builds++;
+        }
+        C->sp2m_numeric_runs++;
+        return aoclsparse_status_success;
+    }
+    catch(const std::bad_alloc &)
+    {
+        return aoclsparse_status_memory_error;
+    }
+}
+
 } // namespace
 
 extern "C" {
+
+aoclsparse_status aoclsparse_mi355_sp2m_numeric_device(aoclsparse_operation opA, const aoclsparse_mat_descr descrA,
+                                                       const aoclsparse_matrix A, aoclsparse_operation opB,
+                                                       const aoclsparse_mat_descr descrB, const aoclsparse_matrix B,
+                                                       aoclsparse_matrix C)
+{
+    // dispatch on A's value type, as aoclsparse_sp2m
+    if(!A || !B || !descrA || !descrB)
+        return aoclsparse_status_invalid_pointer;
+    if(A->val_type == aoclsparse_dmat)
+        return sp2m_numeric_t<double>(opA, descrA, A, opB, descrB, B, C, aoclsparse_dmat);
+    if(A->val_type == aoclsparse_smat)
+        return sp2m_numeric_t<float>(opA, descrA, A, opB, descrB, B, C, aoclsparse_smat);
+    if(A->val_type == aoclsparse_zmat)
+        return sp2m_numeric_t<cdouble>(opA, descrA, A, opB, descrB, B, C, aoclsparse_zmat);
+    if(A->val_type == aoclsparse_cmat)
+        return sp2m_numeric_t<cfloat>(opA, descrA, A, opB, descrB, B, C, aoclsparse_cmat);
+    return aoclsparse_status_not_implemented;
+}
+
+aoclsparse_status aoclsparse_mi355_get_sp2m_plan_info(aoclsparse_matrix C, aoclsparse_mi355_sp2m_plan_info *info)
+{
+    if(!C || !info)
+        return aoclsparse_status_invalid_pointer;
+    if(info->struct_size < sizeof(info->struct_size))
+        return aoclsparse_status_invalid_size;
+    aoclsparse_mi355_sp2m_plan_info r{};
+    {
+        // (the plan is written under the runtime's stage lock and the handle's guard)
+        std::lock_guard<std::recursive_mutex> sl(Runtime::get().stage_lock);
+        std::shared_lock<std::shared_mutex>   rd(C->guard);
+        const auto                           &pl = C->sp2m_plan;
+        r.kept = pl.valid;
+        if(pl.valid)
+        {
+            for(int b = 0; b < SPGEMM_BINS; b++)
+                r.rows_in_bin[b] = pl.bounds[b + 1] - pl.bounds[b];
+            r.heavy_rows = r.rows_in_bin[SPGEMM_BINS - 1];
+        }
+        r.plan_builds = C->sp2m_plan_builds, r.numeric_runs = C->sp2m_numeric_runs, r.refused = C->sp2m_refused;
+        r.plan_bytes = pl.bytes();
+    }
+    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
+    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
+}
 
 aoclsparse_status aoclsparse_sp2m(aoclsparse_operation opA, const aoclsparse_mat_descr descrA,
                                   const aoclsparse_matrix A, aoclsparse_operation opB,

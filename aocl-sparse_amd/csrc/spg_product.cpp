@@ -2,6 +2,7 @@
 // new_csr_result, the first-touch product D = X * Y on the device (SpgProduct<T>: analyse, bin, count, scan, fill; kernels in
 // spgemm_kernels.hip) and the host pieces around it (spg_host.hpp).
 #include "spg_host.hpp"
+#include "device_handle.hpp"
 
 #include <cstring>
 #include <thread>
@@ -22,6 +23,19 @@ aoclsparse_status launch_spgemm_bin(hipStream_t s, bool fill, int bin, aoclspars
                                     const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b, const T *val_b,
                                     const aoclsparse_int *ptr_c, aoclsparse_int *cnt_or_ind_c, T *val_c, bool conj_a, bool conj_b,
                                     bool upper, unsigned int *bad);
+// spgemm_numeric_kernels.hip
+template <typename T>
+aoclsparse_status launch_spg_numeric_bin(hipStream_t s, int bin, aoclsparse_int nrows, const aoclsparse_int *rows, int base_a,
+                                         const aoclsparse_int *ptr_a, const aoclsparse_int *ind_a, const T *val_a, int base_b,
+                                         const aoclsparse_int *ptr_b, const aoclsparse_int *ind_b, const T *val_b, int base_c,
+                                         const aoclsparse_int *ptr_c, const aoclsparse_int *ind_c, T *out, bool conj_a, bool conj_b,
+                                         unsigned int *bad);
+template <typename T>
+aoclsparse_status launch_spg_numeric_heavy(hipStream_t s, aoclsparse_int nrows, const SpgHeavy *heavy, int *g_key, int *g_pos,
+                                           unsigned char *g_touched, int base_a, const aoclsparse_int *ptr_a,
+                                           const aoclsparse_int *ind_a, const T *val_a, int base_b, const aoclsparse_int *ptr_b,
+                                           const aoclsparse_int *ind_b, const T *val_b, int base_c, const aoclsparse_int *ptr_c,
+                                           const aoclsparse_int *ind_c, T *out, bool conj_a, bool conj_b, unsigned int *bad);
 
 aoclsparse_status new_csr_result(aoclsparse_matrix *C, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz,
                                  aoclsparse_matrix_data_type vt, const aoclsparse_int *row_ptr, aoclsparse_index_base base)
@@ -65,6 +79,36 @@ struct SpgProduct<T>::Binned
     const SpgHeavy             *d_heavy = nullptr;
 };
 constexpr long long SPG_SLAB_SLOTS = 1LL << 28; // 1 GiB of keys (and of slots in the fill pass) per batch
+
+// the rows of the last bin, (row, list size) in any order -> their records by ascending row, in batches whose tables fit
+// SPG_SLAB_SLOTS; slots / entries: of the largest batch
+static aoclsparse_status spg_heavy_layout(std::vector<std::pair<aoclsparse_int, int>> &rows, std::vector<SpgHeavy> &heavy,
+                                          std::vector<aoclsparse_int> &batch, long long &slots, long long &entries)
+{
+    std::sort(rows.begin(), rows.end()); // (the device appends them in arrival order)
+    heavy.reserve(rows.size());
+    long long hs = 0, cs = 0;
+    batch.push_back(0);
+    for(const auto &r : rows)
+    {
+        const long long cap = r.second;
+        if(cap > (1LL << 29))
+            return aoclsparse_status_memory_error;
+        int logh = 6;
+        while((1LL << logh) < 2 * cap)
+            logh++;
+        if(hs + (1LL << logh) > SPG_SLAB_SLOTS && hs > 0)
+        {
+            batch.push_back((aoclsparse_int)heavy.size());
+            hs = cs = 0;
+        }
+        heavy.push_back(SpgHeavy{r.first, logh, hs, cs});
+        hs += 1LL << logh, cs += cap;
+        slots = std::max(slots, hs), entries = std::max(entries, cs);
+    }
+    batch.push_back((aoclsparse_int)heavy.size());
+    return aoclsparse_status_success;
+}
 
 // ---- analysis on the device: the upper bound of every row's list, the bins, the rows of every bin (spgemm_kernels.hip) ----
 template <typename T>
@@ -134,28 +178,9 @@ aoclsparse_status SpgProduct<T>::bin_rows(Binned &bn, bool for_fill, const int *
     std::vector<std::pair<aoclsparse_int, int>> rows((size_t)nheavy);
     for(aoclsparse_int j = 0; j < nheavy; j++)
         rows[(size_t)j] = {ids[(size_t)j], caps[(size_t)j]};
-    std::sort(rows.begin(), rows.end()); // (the device appends them in arrival order)
-    bn.heavy.reserve((size_t)nheavy);
-    long long hs = 0, cs = 0;
-    bn.batch.push_back(0);
-    for(const auto &r : rows)
-    {
-        const long long cap = r.second;
-        if(cap > (1LL << 29))
-            return aoclsparse_status_memory_error;
-        int logh = 6;
-        while((1LL << logh) < 2 * cap)
-            logh++;
-        if(hs + (1LL << logh) > SPG_SLAB_SLOTS && hs > 0)
-        {
-            bn.batch.push_back((aoclsparse_int)bn.heavy.size());
-            hs = cs = 0;
-        }
-        bn.heavy.push_back(SpgHeavy{r.first, logh, hs, cs});
-        hs += 1LL << logh, cs += cap;
-        bn.slots = std::max(bn.slots, hs), bn.entries = std::max(bn.entries, cs);
-    }
-    bn.batch.push_back((aoclsparse_int)bn.heavy.size());
+    rc = spg_heavy_layout(rows, bn.heavy, bn.batch, bn.slots, bn.entries);
+    if(rc != aoclsparse_status_success)
+        return rc;
     void *ph = nullptr;
     rc       = rt.staging(for_fill ? SPG_SLOT_HEAVY_FILL : SPG_SLOT_HEAVY_COUNT, sizeof(SpgHeavy) * bn.heavy.size(), &ph);
     if(rc == aoclsparse_status_success)
@@ -233,6 +258,84 @@ aoclsparse_status SpgProduct<T>::fill(const aoclsparse_int *d_ptr, aoclsparse_in
     if(st == aoclsparse_status_success)
         st = run_pass(true, by_count, d_ptr, d_ind, d_val);
     return st;
+}
+
+// ---- the numeric phase on a kept structure (aoclsparse_mi355_sp2m_numeric_device) ----------------------------------------------
+// The bins of C's rows by their exact length: bin_rows(for_fill) without an upper bound to check against and in buffers of the
+// plan's own -- the staging slots are overwritten by the next product, the plan outlives the call.
+aoclsparse_status sp2m_plan_build(Runtime &rt, aoclsparse_int m, const aoclsparse_int *d_ptr_c, _aoclsparse_matrix::Sp2mPlan &plan)
+{
+    hipStream_t  s = rt.stream();
+    DeviceBuffer key, small, hkeys; // per row: its length; histogram (at 0) and cursors (at 16); the lengths of the slab's rows
+    StreamDrain  drain{s}; // (declared after the buffers: the stream finishes before they are released)
+    plan.release();
+    MI355_TRY(key.alloc(sizeof(int) * (size_t)std::max<aoclsparse_int>(m, 1)));
+    MI355_TRY(small.alloc(256));
+    unsigned int *d_hist = small.as<unsigned int>(), *d_cursor = d_hist + 16;
+    MI355_TRY(launch_spg_diff(s, m, d_ptr_c, key.as<int>()));
+    MI355_TRY(launch_spg_hist(s, m, key.as<int>(), nullptr, true, d_hist));
+    unsigned int hist[SPGEMM_BINS + 1];
+    MI355_HIP_TRY(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if(hist[SPGEMM_BINS])
+        return aoclsparse_status_invalid_value; // a row pointer that descends
+    bool one_bin = false;
+    for(int b = 0; b < SPGEMM_BINS; b++)
+    {
+        plan.bounds[b + 1] = plan.bounds[b] + (aoclsparse_int)hist[b];
+        one_bin |= (aoclsparse_int)hist[b] == m;
+    }
+    const aoclsparse_int nheavy = (aoclsparse_int)hist[SPGEMM_BINS - 1];
+    if(!(one_bin && nheavy == 0)) // (otherwise no list: workgroup g serves row g)
+    {
+        MI355_TRY(plan.order.alloc(sizeof(aoclsparse_int) * (size_t)m));
+        MI355_TRY(launch_spg_order(s, m, key.as<int>(), true, plan.bounds, d_cursor, plan.order.as<aoclsparse_int>()));
+    }
+    if(nheavy > 0)
+    {
+        const aoclsparse_int *d_ids = plan.order.as<aoclsparse_int>() + plan.bounds[SPGEMM_BINS - 1];
+        MI355_TRY(hkeys.alloc(sizeof(int) * (size_t)nheavy));
+        MI355_TRY(launch_spg_gather(s, nheavy, d_ids, key.as<int>(), hkeys.as<int>()));
+        std::vector<aoclsparse_int> ids((size_t)nheavy);
+        std::vector<int>            lens((size_t)nheavy);
+        MI355_HIP_TRY(hipMemcpyAsync(ids.data(), d_ids, sizeof(aoclsparse_int) * (size_t)nheavy, hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipMemcpyAsync(lens.data(), hkeys.ptr, sizeof(int) * (size_t)nheavy, hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipStreamSynchronize(s));
+        std::vector<std::pair<aoclsparse_int, int>> rows((size_t)nheavy);
+        for(aoclsparse_int j = 0; j < nheavy; j++)
+            rows[(size_t)j] = {ids[(size_t)j], lens[(size_t)j]};
+        std::vector<SpgHeavy> heavy;
+        MI355_TRY(spg_heavy_layout(rows, heavy, plan.batch, plan.slots, plan.entries));
+        MI355_TRY(plan.heavy.upload(heavy.data(), sizeof(SpgHeavy) * heavy.size(), s));
+    }
+    MI355_HIP_TRY(hipStreamSynchronize(s)); // (the order kernel has read `key`; an upload from pageable memory has left the host)
+    drain.dismiss();
+    plan.valid = true;
+    return aoclsparse_status_success;
+}
+
+template <typename T>
+aoclsparse_status spg_numeric(Runtime &rt, const _aoclsparse_matrix::Sp2mPlan &plan, const SpgDevOp &x, const SpgDevOp &y, bool conj_x,
+                              bool conj_y, const SpgDevOp &c, T *out, unsigned int *d_bad)
+{
+    hipStream_t           s  = rt.stream();
+    const T              *xv = static_cast<const T *>(x.val), *yv = static_cast<const T *>(y.val);
+    const aoclsparse_int *order = plan.order.as<const aoclsparse_int>();
+    for(int b = 0; b < SPGEMM_BINS - 2; b++) // (rows binned by their exact length: the 8,192 bin of the count pass stays empty)
+        MI355_TRY(launch_spg_numeric_bin<T>(s, b, plan.bounds[b + 1] - plan.bounds[b], order ? order + plan.bounds[b] : nullptr, x.base,
+                                            x.ptr, x.ind, xv, y.base, y.ptr, y.ind, yv, c.base, c.ptr, c.ind, out, conj_x, conj_y, d_bad));
+    if(plan.batch.size() < 2)
+        return aoclsparse_status_success;
+    void *gk = nullptr, *gp = nullptr, *gt = nullptr;
+    MI355_TRY(rt.staging(SPG_SLOT_G_KEY, sizeof(int) * (size_t)plan.slots, &gk));
+    MI355_TRY(rt.staging(SPG_SLOT_G_POS, sizeof(int) * (size_t)plan.slots, &gp));
+    MI355_TRY(rt.staging(SPG_SLOT_G_LIST, (size_t)plan.entries, &gt));
+    for(size_t b = 0; b + 1 < plan.batch.size(); b++) // (stream order: a batch reuses the slab)
+        MI355_TRY(launch_spg_numeric_heavy<T>(s, plan.batch[b + 1] - plan.batch[b], plan.heavy.as<const SpgHeavy>() + plan.batch[b],
+                                              static_cast<int *>(gk), static_cast<int *>(gp), static_cast<unsigned char *>(gt), x.base,
+                                              x.ptr, x.ind, xv, y.base, y.ptr, y.ind, yv, c.base, c.ptr, c.ind, out, conj_x, conj_y,
+                                              d_bad));
+    return aoclsparse_status_success;
 }
 
 // ---- the host side (spg_host.hpp) ---------------------------------------------------------------------------------------------
@@ -342,7 +445,9 @@ aoclsparse_status spg_fill_to_host(SpgProduct<T> &prod, bool finalize_only, aocl
 #define MI355_SPG_INSTANTIATE(T)   \
     template struct SpgProduct<T>; \
     template aoclsparse_status spg_fill_to_host<T>(SpgProduct<T> &, bool, aoclsparse_int *, aoclsparse_int *, T *, HostCsr &, \
-                                                   const std::function<void()> &)
+                                                   const std::function<void()> &);                                            \
+    template aoclsparse_status spg_numeric<T>(Runtime &, const _aoclsparse_matrix::Sp2mPlan &, const SpgDevOp &, const SpgDevOp &, \
+                                              bool, bool, const SpgDevOp &, T *, unsigned int *)
 MI355_SPG_INSTANTIATE(double);
 MI355_SPG_INSTANTIATE(float);
 MI355_SPG_INSTANTIATE(cdouble);

@@ -25,75 +25,13 @@
 //
 // Bound: neither HBM nor MFMA -- irregular, latency/instruction bound; algorithmic traffic is
 // 12 B per entry of A and of the touched B rows + 12 B per entry of C.
-#include "internal.hpp"
+#include "spgemm_device.hpp"
 
 #include <algorithm>
-
-#include <hip/hip_runtime.h>
 
 namespace mi355
 {
 
-
-__device__ __forceinline__ double sp_fma(double a, double b, double c)
-{
-    return fma(a, b, c);
-}
-__device__ __forceinline__ float sp_fma(float a, float b, float c)
-{
-    return fmaf(a, b, c);
-}
-// complex: the reference's std::complex multiply-add (csr2m.cpp:489-498 with T = std::complex); component-wise fma
-template <typename R>
-__device__ __forceinline__ cplx<R> sp_fma(cplx<R> a, cplx<R> b, cplx<R> c)
-{
-    c.re = sp_fma(a.re, b.re, c.re);
-    c.re = sp_fma(-a.im, b.im, c.re);
-    c.im = sp_fma(a.re, b.im, c.im);
-    c.im = sp_fma(a.im, b.re, c.im);
-    return c;
-}
-__device__ __forceinline__ double sp_mul(double a, double b)
-{
-    return a * b;
-}
-__device__ __forceinline__ float sp_mul(float a, float b)
-{
-    return a * b;
-}
-template <typename R>
-__device__ __forceinline__ cplx<R> sp_mul(cplx<R> a, cplx<R> b)
-{
-    return sp_fma(a, b, cplx<R>(R(0), R(0)));
-}
-__device__ __forceinline__ double sp_conj(double a, bool)
-{
-    return a;
-}
-__device__ __forceinline__ float sp_conj(float a, bool)
-{
-    return a;
-}
-template <typename R>
-__device__ __forceinline__ cplx<R> sp_conj(cplx<R> a, bool on)
-{
-    return on ? cplx<R>(a.re, -a.im) : a;
-}
-
-// value of lane `src` of the caller's group of `width` lanes
-__device__ __forceinline__ double spg_shfl(double v, int src, int width)
-{
-    return __shfl(v, src, width);
-}
-__device__ __forceinline__ float spg_shfl(float v, int src, int width)
-{
-    return __shfl(v, src, width);
-}
-template <typename R>
-__device__ __forceinline__ cplx<R> spg_shfl(cplx<R> v, int src, int width)
-{
-    return cplx<R>(__shfl(v.re, src, width), __shfl(v.im, src, width));
-}
 
 // ---- the kernel ------------------------------------------------------------------------------------------------------------------
 // LDS mode (GLOBAL = false): per group hkey[H] (open addressing, linear probing, -1 = empty) and, in the fill pass, hpos[H] (list
@@ -105,36 +43,6 @@ __device__ __forceinline__ cplx<R> spg_shfl(cplx<R> v, int src, int width)
 // Order: A's row is walked left to right; the entries of one B row are taken G at a time, lane t = t-th entry.  Either way every
 // column sees its products in the reference's order: first product stored, the later ones added with a contracted multiply-add
 // (csr2m.cpp:489-498).
-template <int G>
-__device__ __forceinline__ unsigned long long spg_group_bits(unsigned long long wave_mask, int grp)
-{
-    if constexpr(G == 64)
-        return wave_mask;
-    else
-        return (wave_mask >> (G * grp)) & ((1ull << G) - 1ull);
-}
-
-template <bool GLOBAL>
-__device__ __forceinline__ int spg_key(const int *p)
-{
-    if constexpr(GLOBAL)
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        return *p;
-}
-
-template <bool GLOBAL>
-__device__ __forceinline__ void spg_sync()
-{
-    if constexpr(GLOBAL)
-    {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    else
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-}
-
 //
 // UPPER (syrk / sypr, sypr.hpp:71-73 BUILD_ONLY_U): row i of C keeps the columns >= i only; the entries of B's rows left of that
 // are passed over in both passes (they still take part in the strictly-increasing test, which is about B's row, not about C's).

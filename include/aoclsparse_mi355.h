@@ -445,6 +445,47 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *
  *   get_ilu_info       What a handle holds of the above (struct_size as for get_coo_map_info).
  *
+ *   sp2m_numeric_device  (round 29) The values of C = op(A) * op(B) again, from the values A and B hold NOW, on the structure C
+ *           already has; one entry point for the four value types, as aoclsparse_sp2m.  C is a CSR handle whose structure is the
+ *           product's as aoclsparse_sp2m builds it -- every row's columns in first-touch order, one slot per column: the result
+ *           handle of an earlier aoclsparse_sp2m / ?csr2m of these operands, or a handle created (in either base) over arrays
+ *           that hold such a product.  Its mirror is uploaded when absent, as every product does.  After the call C's values are
+ *           bit for bit what aoclsparse_sp2m(stage_finalize) would have written: first product stored, later ones added with the
+ *           contracted multiply-add, in the reference's walk order.  C's row_ptr and col_ind, on the host and in HBM, are not
+ *           written.  The operands reach the device as in aoclsparse_sp2m: the resident mirrors where they are valid, one
+ *           transposed operand through the handle's kept transpose, conjugation applied at load.
+ *           Statuses, all decided before the device is touched, in this order: everything aoclsparse_sp2m returns for
+ *           stage_finalize before it looks at C (the quick return of an empty product succeeds and does nothing); invalid_pointer
+ *           for a null C; not_implemented when both operations transpose (C = D^T would need a map); not_implemented for a C
+ *           that is no plain CSR handle (COO- or CSC-created, TCSR, BSR); wrong_type when C's value type is not the operands';
+ *           invalid_size when C's dimensions are not the product's; invalid_value when C is A or B.
+ *           The new values are computed into a fresh device buffer, and the kernel (spgemm_numeric_kernels.hip) proves row by
+ *           row that C's structure is the product's: it raises one verdict word when a product's column is not in C's row, a
+ *           slot of C's row receives no product, C's row holds a column twice, or the k-th distinct column the walk meets does
+ *           not sit in slot k.  The word is read back before anything of C is written: a refused call returns invalid_value and
+ *           leaves C, everything derived from it and the plan exactly as they were.  No generation counter on A or B is needed.
+ *           On a good verdict the buffer goes to C by ?revalue_device's own code: one copy of the values to the host view, the
+ *           mirror updated device to device, and for a C with keep_value_maps set the clean CSR, the diagonal, the mapped TRSV
+ *           plans and the SELL-64 structure kept; failure semantics as documented there.  Limitation: a product's rows are in
+ *           first-touch order, so C's clean CSR is a copy, and only the copy aoclsparse_mi355_clean_csr_device builds holds the
+ *           value map that carries it and the TRSV plans through the commit; with the copy a solve builds on the host they are
+ *           dropped and analysed again by the next solve, as after any ?revalue_device.
+ *           What the call computes from C's ROW POINTER alone -- the rows binned by their exact length (at most 32 / 256 / 2,048
+ *           entries: tables in LDS; longer: the global slab), the row order bin by bin and the slab's row records in HBM, the
+ *           bin bounds, the batch list and the slab's sizes -- is the handle's sp2m plan: built by the first numeric call in
+ *           buffers of its own, kept only when that call succeeded, reused by every later call with any operands whose product
+ *           has C's structure, untouched by value changes of C, released by aoclsparse_order_mat, order_mat_device,
+ *           aoclsparse_mi355_invalidate (which aoclsparse_sp2m(stage_finalize) into C calls) and destroy; not carried through
+ *           aoclsparse_copy, exported state or replicas.  No upper-bound kernel, histogram or row sort runs with a kept plan: such
+ *           a call waits for the device twice, for the verdict and inside the commit.  Locking: the runtime's stage lock, then
+ *           the handles' guards one at a time.  Peak extra device memory: sizeof(value) per entry of C, and for rows of the slab
+ *           8 bytes per table slot and 1 per entry, during the call; the plan keeps 4 bytes per row.
+ *           Out of scope: both operands transposed; aoclsparse_syrk / sypr on a kept structure; a numeric ?add; keeping an
+ *           operand's transpose through its own revalue; a C without a host view; aoclsparse_sp2m(stage_finalize) taking this
+ *           route by itself.
+ *
+ *   get_sp2m_plan_info What a handle holds of the above (struct_size as for get_coo_map_info); works without a device.
+ *
  * Out of scope: aliasing the caller's device arrays without a copy; handles without a host view; 64-bit indices; creating CSC,
  * TCSR or BSR handles from device arrays; a transposing variant of create_?csr_from_coo_device (the caller swaps the two index
  * arrays); a refresh that changes the set of coordinates; carrying the triplet map through aoclsparse_copy, exported state or
@@ -561,6 +602,22 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_dilu0_refactor_device(aoclsparse_m
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_cilu0_refactor_device(aoclsparse_matrix A, aoclsparse_float_complex **precond_csr_val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zilu0_refactor_device(aoclsparse_matrix A, aoclsparse_double_complex **precond_csr_val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_ilu_info(aoclsparse_matrix A, aoclsparse_mi355_ilu_info *info);
+typedef struct
+{
+    size_t         struct_size; /* in: sizeof(aoclsparse_mi355_sp2m_plan_info) as the caller knows it */
+    aoclsparse_int kept; /* 1: the handle holds the plan of aoclsparse_mi355_sp2m_numeric_device; 0 (as the next two) without one */
+    aoclsparse_int heavy_rows; /* ... rows longer than 2,048 entries: their tables live in the global slab (= rows_in_bin[4]) */
+    aoclsparse_int rows_in_bin[5]; /* ... rows of at most 32 / 256 / 2,048 entries, (unused: always 0), longer rows */
+    long long      plan_builds; /* times the plan was built since the handle was created */
+    long long      numeric_runs; /* successful numeric calls */
+    long long      refused; /* numeric calls stopped by the verdict: C's structure was not the product's */
+    long long      plan_bytes; /* memory the plan occupies: row order and slab records in HBM, bounds and batch list on the host */
+} aoclsparse_mi355_sp2m_plan_info;
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_sp2m_numeric_device(aoclsparse_operation opA, const aoclsparse_mat_descr descrA,
+                                                                  const aoclsparse_matrix A, aoclsparse_operation opB,
+                                                                  const aoclsparse_mat_descr descrB, const aoclsparse_matrix B,
+                                                                  aoclsparse_matrix C);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_sp2m_plan_info(aoclsparse_matrix C, aoclsparse_mi355_sp2m_plan_info *info);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_csr_device(aoclsparse_matrix A, aoclsparse_index_base *base, aoclsparse_int *M,
                                                                 aoclsparse_int *N, aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
                                                                 const aoclsparse_int **col_idx, const void **val);
