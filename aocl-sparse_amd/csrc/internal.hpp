@@ -427,38 +427,72 @@ struct SellView
     int                   pbits = 0, pbytes = 0;
     // one list of SELL_SHORT_WMAX columns per slice (mode 1 / 2 slices; -1 everywhere else); nullptr when the plan has none
     const aoclsparse_int *ucol = nullptr;
-    // the periodic range of the records and lists (SellPlan::pslo ..; all zero: none)
+    // the periodic range of the records and lists (SellValues::pslo ..; all zero: none)
     int                   pslo = 0, pshi = 0, pper = 0, pstride = 0;
-    // whether that range can be stacked, and its alias map (SellPlan::mstack, malias)
+    // whether that range can be stacked, and its alias map (SellValues::mstack, malias)
     int                   mstack = 0;
     unsigned              malias = 0;
 };
 
-// SELL-64 twin of a device CSR (matrix.cpp: build_sell; layout in sell_build_kernels.hip, products in sell_kernels.hip): built by
+// SELL-64 twin of a device CSR (sell_plan.cpp: build_sell; layout in sell_build_kernels.hip, products in sell_kernels.hip): built by
 // aoclsparse_optimize for an mv hint when the padding stays small; the handle's ?mv then runs on it instead of the CSR-Adaptive
-// kernel.
-struct SellPlan
+// kernel.  Its members are grouped by what invalidates them: SellStructure (row_ptr, col_idx, the sizes or the option change),
+// SellValues (any value changes), SellCounters (nothing: since creation).
+
+// WHAT THE STRUCTURE STAGE OWNS (build_sell = structure, then values): pack, the widths, slice_ptr, the shared decision with cptr /
+// lead / ccells, col, rowlen and the records describe the CSR of m rows and nnz entries under aoclsparse_mi355_option_sell == mode.
+struct SellStructure
 {
     aoclsparse_int nslices = 0;
     int            pack    = 1; // 1: cell (p, lane) at 64 p + lane; 4: at 256 (p/4) + 4 lane + p%4
     long long      cells   = 0; // stored cells = sum over slices of 64 * (longest row of the slice)
     DeviceBuffer   slice_ptr; // nslices+1 cell offsets (long long)
-    DeviceBuffer   val, col; // cells values / 0-based columns (-1 = padding)
+    DeviceBuffer   col; // ccells 0-based columns (-1 = padding)
     DeviceBuffer   rowlen; // m row lengths (read by the 4- and 8-lane orders only)
     // shared column lists (sell_build_kernels.hip): col holds one list per leader lane of a slice, ccells entries in all;
     // cptr = nslices+1 offsets into it, lead = m x 16 bits (leader index of a row inside its slice | column shift << 8)
     bool           shared = false;
     long long      ccells = 0;
     DeviceBuffer   cptr, lead;
+    aoclsparse_int wmax     = 0; // widest slice, in cells
+    bool           records  = false; // the copy can have slice records
+    aoclsparse_int nuniform = 0; // slices of mode 1 / 2 (what SellValues::uniform is on a plan with ucol)
+    // one 16-byte record per slice for the short-row kernel (SellSliceDesc; nslices + SELL_DESC_PAD of them), allocated only
+    // when that kernel can serve the copy (pack 1, widest slice <= SELL_SHORT_WMAX, >= SELL_SHORT_MIN_SLICES slices).  desc0 (host):
+    // the records as sell_pack_descriptors made them; desc: the device copy, in which the values stage sets sell_records_kernel's flags
+    std::vector<SellSliceDesc> desc0;
+    DeviceBuffer               desc;
+    // built: all of the above is there, for the CSR and option value below
+    bool           built = false;
+    int            mode  = -1;
+    aoclsparse_int m = 0, nnz = 0;
+    // what only a values stage on a kept structure allocates: the pristine records' device copy, one spare set of records and
+    // uniform lists (the stage writes the new set there, compares it with the current one, and the two change places), and three
+    // words (sell_records_kernel's two counters, the compare kernel's verdict)
+    DeviceBuffer   desc0_dev, desc_spare, ucol_spare, kwords;
+    // nothing of the structure is trusted from here on (the buffers of the copy itself stay for the next build to reuse)
+    void drop()
+    {
+        built = false;
+        desc0.clear(), desc0.shrink_to_fit();
+        desc0_dev.release(), desc_spare.release(), ucol_spare.release(), kwords.release();
+    }
+    size_t kept_bytes() const
+    {
+        return sizeof(SellSliceDesc) * desc0.capacity() + desc0_dev.bytes + desc_spare.bytes + ucol_spare.bytes + kwords.bytes;
+    }
+};
+
+// WHAT THE VALUES STAGE OWNS: the table and the cell encoding chosen from it, the cells, the uniform lists, what the records kernel
+// counted, the periodic range and the stacking facts.
+struct SellValues
+{
     // value table (sell_build_kernels.hip): ntab > 0 -> vidx holds one byte per cell (same cell order and offsets as val would) indexing
     // vtab, ntab values sorted by bit pattern, and val is not allocated; ntab = 0 -> the values are in val
     // ... or, on a plan with slice records whose rows fit (widest slice x pbits <= 32): pidx holds one word of pbytes bytes per row
     // with pbits bits per cell ((nslices + SELL_DESC_PAD) x 64 words, the padding 0) and vidx is not allocated either
     int            ntab = 0, pbits = 0, pbytes = 0;
-    DeviceBuffer   vtab, vidx, pidx;
-    // one 16-byte record per slice for the short-row kernel (SellSliceDesc; nslices + SELL_DESC_PAD of them), allocated only
-    // when that kernel can serve the copy (pack 1, widest slice <= SELL_SHORT_WMAX, >= SELL_SHORT_MIN_SLICES slices)
-    DeviceBuffer   desc;
+    DeviceBuffer   val, vtab, vidx, pidx;
     // with slice records and shared lists: SELL_SHORT_WMAX columns per slice (nslices + SELL_DESC_PAD entries), the single list of
     // a mode 1 / 2 slice, -1 elsewhere; uniform = how many slices have one
     DeviceBuffer   ucol;
@@ -472,39 +506,56 @@ struct SellPlan
     // the range can be stacked (1 / 0) and the alias map of its first period (sell_find_march, on the same host copies)
     int            mstack = 0;
     unsigned       malias = 0;
-    bool           valid = false, tried = false;
-    bool           wanted = false; // optimize chose SELL: rebuilt lazily after the values change
-    // THE STRUCTURE STAGE'S RECORD (matrix.cpp: build_sell = structure, then values).  structure: pack, the widths, slice_ptr, the
-    // shared decision with cptr / lead / ccells, col, rowlen and the pristine records describe the CSR of sm rows and snnz entries
-    // under aoclsparse_mi355_option_sell == smode.  stale: aoclsparse_mi355_?revalue_device kept that structure and the cells hold
-    // the OLD values -- valid is false, no launcher runs the copy, and the next build_sell runs the values stage alone.  Every other
-    // value change clears both (drop_derived_state_keeping).
-    bool           structure = false, stale = false;
-    int            smode = -1;
-    aoclsparse_int sm = 0, snnz = 0;
-    aoclsparse_int wmax     = 0; // widest slice, in cells
-    bool           records  = false; // the copy can have slice records
-    aoclsparse_int nuniform = 0; // slices of mode 1 / 2 (what `uniform` is on a plan with ucol)
-    // the records as sell_pack_descriptors made them (nslices + SELL_DESC_PAD; host), before sell_records_kernel's flags ...
-    std::vector<SellSliceDesc> desc0;
-    // ... and what only a values stage on a kept structure allocates: their device copy, one spare set of records and uniform
-    // lists (the stage writes the new set there, compares it with the current one, and the two change places), and three words
-    // (sell_records_kernel's two counters, the compare kernel's verdict)
-    DeviceBuffer   desc0_dev, desc_spare, ucol_spare, kwords;
-    // since creation: times the structure stage / the values stage ran, times a values stage carried the periodic range over, and
-    // what the last build_sell did (0 nothing yet, 1 structure + values, 2 values with the search, 3 values, range carried over)
-    long long      structure_builds = 0, value_fills = 0, searches_skipped = 0;
-    int            last_route = 0;
-    // nothing of the structure is trusted from here on (the buffers of the copy itself stay for the next build to reuse)
+    void no_range()
+    {
+        pslo = pshi = pper = pstride = 0;
+        mstack = 0, malias = 0;
+    }
+    // nothing of the old values is trusted: no table, no lists, no flags, no range.  The tables, index cells and lists go; val
+    // stays for the cells of the next fill (sell_alloc_cells reuses it, or releases it for a table)
+    void reset()
+    {
+        ntab = pbits = pbytes = 0;
+        uniform = uniform_words = exceptions = 0;
+        no_range();
+        vtab.release(), vidx.release(), pidx.release(), ucol.release();
+    }
+};
+
+// since creation: times the structure stage / the values stage ran, times a values stage carried the periodic range over, and
+// what the last build_sell did (0 nothing yet, 1 structure + values, 2 values with the search, 3 values, range carried over)
+struct SellCounters
+{
+    long long structure_builds = 0, value_fills = 0, searches_skipped = 0;
+    int       last_route = 0;
+};
+
+struct SellPlan
+{
+    SellStructure st;
+    SellValues    vals;
+    SellCounters  count;
+    bool          valid = false, tried = false;
+    bool          wanted = false; // optimize chose SELL: rebuilt lazily after the values change
+    // stale: aoclsparse_mi355_?revalue_device kept the structure and the cells hold the OLD values -- valid is false, no launcher
+    // runs the copy, and the next build_sell runs the values stage alone
+    bool          stale = false;
     void drop_structure()
     {
-        structure = stale = false;
-        desc0.clear(), desc0.shrink_to_fit();
-        desc0_dev.release(), desc_spare.release(), ucol_spare.release(), kwords.release();
+        stale = false;
+        st.drop();
     }
-    size_t kept_bytes() const
+    // The values of the CSR this copy mirrors have changed: no launcher runs it and the next build_sell builds it again.  keep: the
+    // structure stays for that build (stale) if there is one, the copy served products or was stale already (two changes in a row
+    // leave the same state), and it describes a CSR of m rows and nnz entries; every other change drops it.
+    void values_changed(bool keep, aoclsparse_int m, aoclsparse_int nnz)
     {
-        return sizeof(SellSliceDesc) * desc0.capacity() + desc0_dev.bytes + desc_spare.bytes + ucol_spare.bytes + kwords.bytes;
+        const bool live = valid || stale;
+        valid = tried = false;
+        if(keep && st.built && live && st.m == m && st.nnz == nnz)
+            stale = true;
+        else
+            drop_structure();
     }
     // products served by this copy: odd ones walk the slices in descending order, so that what one product leaves in the
     // Infinity Cache (the END of its sweep) is where the next one starts (sell_kernels.hip); the bits do not depend on it
@@ -514,18 +565,18 @@ struct SellPlan
     SellView view(aoclsparse_int m, aoclsparse_int max_width) const
     {
         SellView v;
-        v.m = m, v.nslices = nslices, v.pack = pack, v.max_width = max_width, v.ntab = ntab;
-        v.slice_ptr = slice_ptr.as<long long>();
-        v.cells     = ntab ? (pbits ? pidx.ptr : vidx.ptr) : val.ptr;
-        v.pbits = ntab ? pbits : 0, v.pbytes = ntab ? pbytes : 0;
-        v.ucol = ucol.as<aoclsparse_int>();
-        v.pslo = pslo, v.pshi = pshi, v.pper = pper, v.pstride = pstride;
-        v.mstack = mstack, v.malias = malias;
-        v.col = col.as<aoclsparse_int>(), v.rowlen = rowlen.as<aoclsparse_int>();
-        v.cptr = shared ? cptr.as<long long>() : nullptr;
-        v.lead = shared ? lead.as<unsigned short>() : nullptr;
-        v.vtab = ntab ? vtab.ptr : nullptr;
-        v.desc = desc.as<SellSliceDesc>();
+        v.m = m, v.nslices = st.nslices, v.pack = st.pack, v.max_width = max_width, v.ntab = vals.ntab;
+        v.slice_ptr = st.slice_ptr.as<long long>();
+        v.cells     = vals.ntab ? (vals.pbits ? vals.pidx.ptr : vals.vidx.ptr) : vals.val.ptr;
+        v.pbits = vals.ntab ? vals.pbits : 0, v.pbytes = vals.ntab ? vals.pbytes : 0;
+        v.ucol = vals.ucol.as<aoclsparse_int>();
+        v.pslo = vals.pslo, v.pshi = vals.pshi, v.pper = vals.pper, v.pstride = vals.pstride;
+        v.mstack = vals.mstack, v.malias = vals.malias;
+        v.col = st.col.as<aoclsparse_int>(), v.rowlen = st.rowlen.as<aoclsparse_int>();
+        v.cptr = st.shared ? st.cptr.as<long long>() : nullptr;
+        v.lead = st.shared ? st.lead.as<unsigned short>() : nullptr;
+        v.vtab = vals.ntab ? vals.vtab.ptr : nullptr;
+        v.desc = st.desc.as<SellSliceDesc>();
         return v;
     }
 };
@@ -1323,7 +1374,7 @@ aoclsparse_status launch_revalue_compose(hipStream_t s, aoclsparse_int count, ao
 aoclsparse_status launch_revalue_diag_map(hipStream_t s, aoclsparse_int m, aoclsparse_int n, int base, aoclsparse_int total,
                                           const aoclsparse_int *idiag, const aoclsparse_int *iurow, int *out);
 
-// ---- device mirrors / plans ---------------------------------------------------------------------
+// ---- device mirrors / plans (spmv_plan.cpp, sell_plan.cpp) ------------------------------------------
 size_t            val_size(aoclsparse_matrix_data_type t);
 aoclsparse_status upload_csr(const HostCsr &h, size_t vsize, DeviceCsr &d);
 aoclsparse_status ensure_spmv(aoclsparse_matrix A, bool transposed, DeviceCsr *&dcsr,
@@ -1357,7 +1408,9 @@ aoclsparse_status launch_csrmv(hipStream_t s, int order, bool strict, int tile, 
 // SELL-64 plan kernels (sell_build_kernels.hip)
 // fills the cells, columns and row lengths of the copy v describes from d (values of vsize bytes; cells / col / rowlen are v's
 // arrays, writable); with a table (v.ntab > 0) the cells get one-byte indices into it instead of the values, or (v.pbits > 0) one
-// packed word per row; ucol (v.ucol, writable; preset to -1) gets the list of every mode 1 / 2 slice
+// packed word per row (zero words behind m, 0 in the padding cells); ucol (nullable; preset to -1) gets the list of every mode
+// 1 / 2 slice.  col == nullptr: the values stage on a KEPT structure -- the cells from d's values alone, neither col nor rowlen
+// is written.
 aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *col,
                                    aoclsparse_int *rowlen, aoclsparse_int *ucol);
 // behind launch_sell_fill on the same stream, for a copy with uniform lists and one-byte packed words: sets SELL_DESC_UWORD /
@@ -1365,10 +1418,6 @@ aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsi
 // counts (device, two words, zeroed here) receives how many slices got each flag.  d = the CSR the copy mirrors.
 aoclsparse_status launch_sell_records(hipStream_t s, const DeviceCsr &d, const SellView &v, SellSliceDesc *desc, aoclsparse_int *ucol,
                                       unsigned *counts);
-// the values stage on a KEPT structure: the cells of the copy v describes from d's values alone, in v's encoding (values, one-byte
-// indices, packed row words; zero words behind m, 0 in the padding cells); ucol (nullable; preset to -1) gets the list of every
-// mode 1 / 2 slice.  Neither col nor rowlen is written.
-aoclsparse_status launch_sell_refill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *ucol);
 // behind launch_sell_records: *verdict (device, zeroed here) becomes 1 when the nslices records or the nslices x SELL_SHORT_WMAX list
 // entries of set a differ from those of set b anywhere, and stays 0 when they are equal
 aoclsparse_status launch_sell_compare(hipStream_t s, aoclsparse_int nslices, const SellSliceDesc *desc_a, const SellSliceDesc *desc_b,

@@ -4,7 +4,7 @@
 // merge path).  It is cut into tiles of MP_ITEMS consecutive items -- whatever the row lengths, every
 // workgroup gets the same number of rows + non-zeros, and a row longer than a tile is spread over several
 // workgroups.  The tile coordinates {row ends consumed, non-zeros consumed} are found on the HOST at plan
-// time (one binary search per tile, integer work: matrix.cpp build_merge_plan), so the kernel does no searching:
+// time (one binary search per tile, integer work: spmv_plan.cpp build_merge_plan), so the kernel does no searching:
 //   phase 1  the tile's values and gathered x are parked in LDS together with the tile's slice of row_ptr;
 //   phase 2  a row (or the piece of a row that lies in this tile) of fewer than SPMV_TREE_MIN entries is one lane's
 //            left-to-right FMA chain -- the reference's scalar order (csrmv_kr.hpp:448-513), so a short row inside one

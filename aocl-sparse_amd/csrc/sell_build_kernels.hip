@@ -1,4 +1,4 @@
-// sell_build_kernels.hip -- plan-time kernels of the SELL-64 copy (matrix.cpp: build_sell); the products are in sell_kernels.hip.
+// sell_build_kernels.hip -- plan-time kernels of the SELL-64 copy (sell_plan.cpp: build_sell); the products are in sell_kernels.hip.
 //
 // The layout: sliced ELL with one slice per 64-wide wavefront.  Slice s holds rows [64 s, 64 s + 64) column-major, cell (p, lane) at
 // slice_ptr[s] + 64 p + lane, padded to the slice's longest row (column -1, value 0); matrices with >= 16 non-zeros per row keep
@@ -297,11 +297,24 @@ __device__ __forceinline__ long long cell_of(int p, int k, int n = 64)
     return PACK == 1 ? (long long)p * n + k : (long long)(p >> 2) * 4 * n + k * 4 + (p & 3);
 }
 
-// SHARED: the columns go to the slice's lists (cptr, follow: see above), written by the first row of every list
+// COLS: what the pass does with the structure.  SELL_COLS_OWN / SELL_COLS_SHARED (a first build): rowlen and the columns are written
+// with the cells, in one pass over the rows -- every lane's own list, or the slice's shared lists (cptr, follow: see above), written by
+// the first row of every list.  SELL_COLS_KEPT (the values stage on a kept structure: sell_plan.cpp, sell_values_kept): the cells from
+// row_ptr and val alone -- cell p of row i is entry row_ptr[i] + p of the CSR, so no value map is needed; col and rowlen are the
+// structure's and are not touched, and col_idx is read only by lane 0 of a mode 1 / 2 slice, for the uniform list.  Whether the
+// column lists are shared or own makes no difference to a value cell.
 // pidx (pbits > 0): the table indices of a row go into ONE word of pbytes bytes at row * pbytes instead of sidx, cell p at bit
 // p * pbits; unused fields, padding cells and the rows behind m hold 0
-// ucol (SHARED): the list of a mode 1 / 2 slice is ALSO written to ucol[SELL_SHORT_WMAX s ..] (preset to -1 by the host)
-template <typename T, int PACK, bool SHARED>
+// ucol (not OWN): the list of a mode 1 / 2 slice is ALSO written to ucol[SELL_SHORT_WMAX s ..] (preset to -1 by the host; cptr
+// carries the modes and is there whenever ucol is)
+enum SellCols
+{
+    SELL_COLS_KEPT,
+    SELL_COLS_OWN,
+    SELL_COLS_SHARED
+};
+
+template <typename T, int PACK, SellCols COLS>
 __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int base,
                                                         const aoclsparse_int *__restrict__ row_ptr,
                                                         const aoclsparse_int *__restrict__ col,
@@ -314,8 +327,9 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
                                                         const T *__restrict__ vtab, int ntab, unsigned char *__restrict__ pidx,
                                                         int pbits, int pbytes, aoclsparse_int *__restrict__ ucol)
 {
-    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
+    constexpr bool SHARED = COLS == SELL_COLS_SHARED, KEPT = COLS == SELL_COLS_KEPT;
+    const int      s    = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int      lane = threadIdx.x & 63;
     if(s >= nslices)
         return;
     const int       i  = s * 64 + lane;
@@ -331,13 +345,20 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
         nl  = w > 0 ? (int)(((cptr[s + 1] & SELL_CPTR_MASK) - c0) / w) : 0;
         uni = ucol && lane == 0 && w <= SELL_SHORT_WMAX && (mode == SELL_DESC_MODE_LANE_SHIFT || mode == SELL_DESC_MODE_ONE);
     }
+    if constexpr(KEPT) // (a mode 1 / 2 slice is full: its lane 0 is a row)
+        if(ucol && cptr)
+        {
+            const int mode = (int)(cptr[s] >> SELL_CPTR_MODE_SHIFT);
+            uni = lane == 0 && i < m && w <= SELL_SHORT_WMAX && (mode == SELL_DESC_MODE_LANE_SHIFT || mode == SELL_DESC_MODE_ONE);
+        }
     int  b = 0, len = 0, k = 0;
-    bool leader = !SHARED; // (own lists: every lane writes its columns, the padding rows behind m too)
+    bool leader = COLS == SELL_COLS_OWN; // (own lists: every lane writes its columns, the padding rows behind m too)
     if(i < m)
     {
         b   = row_ptr[i] - base;
         len = row_ptr[i + 1] - base - b;
-        rowlen[i] = len;
+        if constexpr(!KEPT)
+            rowlen[i] = len;
         if constexpr(SHARED)
         {
             k      = follow[i] & 0xff;
@@ -359,8 +380,9 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
         }
         else
             fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
-        if(leader)
-            scol[SHARED ? c0 + cell_of<PACK>(p, k, nl) : o] = in ? col[b + p] - base : -1;
+        if constexpr(!KEPT)
+            if(leader)
+                scol[SHARED ? c0 + cell_of<PACK>(p, k, nl) : o] = in ? col[b + p] - base : -1;
         if(uni)
             ucol[(long long)s * SELL_SHORT_WMAX + p] = in ? col[b + p] - base : -1;
     }
@@ -376,6 +398,7 @@ __global__ __launch_bounds__(256) void sell_fill_kernel(aoclsparse_int m, int ba
     }
 }
 
+// scol == nullptr: the structure is kept (neither scol nor rowlen is written)
 template <typename T>
 void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *cells, aoclsparse_int *scol, aoclsparse_int *rowlen,
                   aoclsparse_int *ucol)
@@ -383,98 +406,24 @@ void sell_fill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *ce
     T             *sval = v.ntab ? nullptr : static_cast<T *>(cells);
     unsigned char *sidx = v.ntab && !v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
     unsigned char *pidx = v.ntab && v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
-    auto           go   = [&](auto pack, auto shared) {
-        hipLaunchKernelGGL((sell_fill_kernel<T, decltype(pack)::value, decltype(shared)::value>), dim3((v.nslices + 3) / 4), dim3(256),
-                           0, s, v.m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.as<T>(), v.nslices,
+    auto           go   = [&](auto pack, auto cols) {
+        hipLaunchKernelGGL((sell_fill_kernel<T, decltype(pack)::value, decltype(cols)::value>), dim3((v.nslices + 3) / 4), dim3(256), 0,
+                           s, v.m, d.base, d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.as<T>(), v.nslices,
                            v.slice_ptr, v.cptr, v.lead, sval, scol, rowlen, sidx, static_cast<const T *>(v.vtab), v.ntab, pidx, v.pbits,
                            v.pbytes, ucol);
     };
-    using P1 = std::integral_constant<int, 1>;
-    using P4 = std::integral_constant<int, 4>;
-    if(v.cptr)
-        v.pack == 4 ? go(P4{}, std::true_type{}) : go(P1{}, std::true_type{});
-    else
-        v.pack == 4 ? go(P4{}, std::false_type{}) : go(P1{}, std::false_type{});
-}
-
-// ---- the values stage on a kept structure (matrix.cpp: sell_values_kept) ---------------------------------------------------------
-// sell_fill_kernel's geometry -- one wavefront per slice, a lane per row -- and its cells, from row_ptr and val alone: cell p of
-// row i is entry row_ptr[i] + p of the CSR, so no value map is needed.  col and rowlen are the structure's and are not written;
-// col_idx is read only by lane 0 of a mode 1 / 2 slice, for the uniform list (ucol preset to -1 by the host; cptr carries the
-// modes and is there whenever ucol is).  Whether the column lists are shared or own makes no difference to a value cell.
-template <typename T, int PACK>
-__global__ __launch_bounds__(256) void sell_refill_kernel(aoclsparse_int m, int base, const aoclsparse_int *__restrict__ row_ptr,
-                                                          const aoclsparse_int *__restrict__ col, const T *__restrict__ val,
-                                                          aoclsparse_int nslices, const long long *__restrict__ slice_ptr,
-                                                          const long long *__restrict__ cptr, T *__restrict__ sval,
-                                                          unsigned char *__restrict__ sidx, const T *__restrict__ vtab, int ntab,
-                                                          unsigned char *__restrict__ pidx, int pbits, int pbytes,
-                                                          aoclsparse_int *__restrict__ ucol)
-{
-    const int s    = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if(s >= nslices)
-        return;
-    const int       i  = s * 64 + lane;
-    const long long o0 = slice_ptr[s];
-    const int       w  = (int)((slice_ptr[s + 1] - o0) >> 6);
-    bool            uni = false; // this lane writes the slice's uniform list (a mode 1 / 2 slice is full: its lane 0 is a row)
-    if(ucol && cptr)
-    {
-        const int mode = (int)(cptr[s] >> SELL_CPTR_MODE_SHIFT);
-        uni = lane == 0 && i < m && w <= SELL_SHORT_WMAX && (mode == SELL_DESC_MODE_LANE_SHIFT || mode == SELL_DESC_MODE_ONE);
-    }
-    int b = 0, len = 0;
-    if(i < m)
-    {
-        b   = row_ptr[i] - base;
-        len = row_ptr[i + 1] - base - b;
-    }
-    unsigned word = 0;
-    for(int p = 0; p < w; p++)
-    {
-        const long long o  = o0 + cell_of<PACK>(p, lane);
-        const bool      in = p < len;
-        bool            packed = false;
-        if constexpr(std::is_floating_point_v<T>)
-            packed = pidx != nullptr;
-        if(packed)
-        {
-            if constexpr(std::is_floating_point_v<T>)
-                word |= in ? (unsigned)vtab_index(val[b + p], vtab, ntab) << (p * pbits) : 0u;
-        }
+    auto with = [&](auto cols) {
+        if(v.pack == 4)
+            go(std::integral_constant<int, 4>{}, cols);
         else
-            fill_cell(o, in, val + b + p, sval, sidx, vtab, ntab);
-        if(uni)
-            ucol[(long long)s * SELL_SHORT_WMAX + p] = in ? col[b + p] - base : -1;
-    }
-    if(pidx) // (every lane of the slice: the rows behind m hold 0)
-    {
-        const long long row = (long long)s * 64 + lane;
-        if(pbytes == 1)
-            pidx[row] = (unsigned char)word;
-        else if(pbytes == 2)
-            reinterpret_cast<unsigned short *>(pidx)[row] = (unsigned short)word;
-        else
-            reinterpret_cast<unsigned *>(pidx)[row] = word;
-    }
-}
-
-template <typename T>
-void sell_refill_as(hipStream_t s, const DeviceCsr &d, const SellView &v, void *cells, aoclsparse_int *ucol)
-{
-    T             *sval = v.ntab ? nullptr : static_cast<T *>(cells);
-    unsigned char *sidx = v.ntab && !v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
-    unsigned char *pidx = v.ntab && v.pbits ? static_cast<unsigned char *>(cells) : nullptr;
-    auto           go   = [&](auto pack) {
-        hipLaunchKernelGGL((sell_refill_kernel<T, decltype(pack)::value>), dim3((v.nslices + 3) / 4), dim3(256), 0, s, v.m, d.base,
-                           d.ptr.as<aoclsparse_int>(), d.ind.as<aoclsparse_int>(), d.val.as<T>(), v.nslices, v.slice_ptr, v.cptr, sval,
-                           sidx, static_cast<const T *>(v.vtab), v.ntab, pidx, v.pbits, v.pbytes, ucol);
+            go(std::integral_constant<int, 1>{}, cols);
     };
-    if(v.pack == 4)
-        go(std::integral_constant<int, 4>{});
+    if(!scol)
+        with(std::integral_constant<SellCols, SELL_COLS_KEPT>{});
+    else if(v.cptr)
+        with(std::integral_constant<SellCols, SELL_COLS_SHARED>{});
     else
-        go(std::integral_constant<int, 1>{});
+        with(std::integral_constant<SellCols, SELL_COLS_OWN>{});
 }
 
 // the new set of records and uniform lists against the current one, as 32-bit words: any difference raises the verdict word.
@@ -605,23 +554,6 @@ aoclsparse_status launch_sell_records(hipStream_t s, const DeviceCsr &d, const S
     return aoclsparse_status_success;
 }
 
-aoclsparse_status launch_sell_refill(hipStream_t s, const DeviceCsr &d, size_t vsize, const SellView &v, void *cells, aoclsparse_int *ucol)
-{
-    if(v.nslices <= 0)
-        return aoclsparse_status_success;
-    if(!cells || !v.slice_ptr || !d.ptr.ptr || !d.val.ptr || (ucol && !d.ind.ptr))
-        return aoclsparse_status_internal_error;
-    // (as launch_sell_fill: the kernel only moves values, cfloat cells travel as 8-byte doubles)
-    if(vsize == sizeof(cdouble))
-        sell_refill_as<cdouble>(s, d, v, cells, ucol);
-    else if(vsize == sizeof(float))
-        sell_refill_as<float>(s, d, v, cells, ucol);
-    else
-        sell_refill_as<double>(s, d, v, cells, ucol);
-    MI355_HIP_TRY(hipGetLastError());
-    return aoclsparse_status_success;
-}
-
 aoclsparse_status launch_sell_compare(hipStream_t s, aoclsparse_int nslices, const SellSliceDesc *desc_a, const SellSliceDesc *desc_b,
                                       const aoclsparse_int *ucol_a, const aoclsparse_int *ucol_b, unsigned *verdict)
 {
@@ -643,6 +575,8 @@ aoclsparse_status launch_sell_fill(hipStream_t s, const DeviceCsr &d, size_t vsi
 {
     if(v.nslices <= 0)
         return aoclsparse_status_success;
+    if(!cells || !v.slice_ptr || !d.ptr.ptr || !d.val.ptr || ((ucol || col) && !d.ind.ptr) || (col && !rowlen))
+        return aoclsparse_status_internal_error;
     // (the kernel only moves values: cfloat cells are filled as 8-byte doubles, cdouble cells need their own instantiation)
     if(vsize == sizeof(cdouble))
         sell_fill_as<cdouble>(s, d, v, cells, col, rowlen, ucol);

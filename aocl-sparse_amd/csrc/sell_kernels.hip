@@ -9,7 +9,7 @@
 //     lane for the full groups, reduce them as the AVX2 / AVX-512 kernels do, then run the scalar tail
 //     (csrmv_kr.hpp:949-1040, csrmv_avx512.cpp:36-134, csrmv_kr.hpp:734-831 for float).
 // Bytes per launch: cells*(8+4) + 8 m (y) (+ 8 m if beta != 0) (+ 4 m row lengths for orders 1 / 2) + x
-// gathers; cells <= 1.15 nnz or the handle stays on the CSR-Adaptive kernel (matrix.cpp: build_sell).
+// gathers; cells <= 1.15 nnz or the handle stays on the CSR-Adaptive kernel (sell_plan.cpp: build_sell).
 #include "internal.hpp"
 
 #include <cstdlib>

@@ -33,7 +33,7 @@
         t0 = vtab[0], t1 = vtab[1];
     else if constexpr(TAB != 0)
         t0 = vtab[threadIdx.x];
-    // PERIODIC RANGE (PERIOD: sell_mv_short_period_kernel; SellPlan::pslo .., found at plan time by sell_find_period): the records
+    // PERIODIC RANGE (PERIOD: sell_mv_short_period_kernel; SellValues::pslo .., found at plan time by sell_find_period): the records
     // and lists of slice s in [pslo + pper, pslo + plen) are those of slice s - pper with every column moved by pstride, so a
     // wavefront whose slices lie in [pslo, pslo + plen) reads the records and lists of the FIRST period -- the same few lines for
     // every wavefront, a hit in the scalar cache or the L2 instead of a cold trip to HBM -- and gathers from x + k pstride.

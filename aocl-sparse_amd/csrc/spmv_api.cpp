@@ -658,11 +658,11 @@ aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_matrix A, aocl
     info->device_resident = d.valid;
     if(!p.valid)
         return aoclsparse_status_success;
-    info->kernel      = p.sell.valid ? (p.sell.shared ? 4 : 3) : (p.merge.valid ? 2 : 1);
-    info->row_blocks  = p.sell.valid ? (p.sell.nslices < 2048 ? p.sell.nslices : (p.sell.nslices + 1) / 2) : p.nblocks;
+    info->kernel      = p.sell.valid ? (p.sell.st.shared ? 4 : 3) : (p.merge.valid ? 2 : 1);
+    info->row_blocks  = p.sell.valid ? (p.sell.st.nslices < 2048 ? p.sell.st.nslices : (p.sell.st.nslices + 1) / 2) : p.nblocks;
     info->tile        = p.tile & ~1;
-    info->sell_slices  = p.sell.valid ? p.sell.nslices : 0;
-    info->stored_cells = p.sell.valid ? p.sell.cells : 0;
+    info->sell_slices  = p.sell.valid ? p.sell.st.nslices : 0;
+    info->stored_cells = p.sell.valid ? p.sell.st.cells : 0;
     info->mm_groups    = p.mm.valid ? p.mm.ngroups : 0;
     info->mm_window_rows = p.mm.win ? p.mm.win_rows : 0;
     info->mm_bell_width  = p.bell.valid ? p.bell.width : 0;
@@ -693,130 +693,6 @@ aoclsparse_status aoclsparse_mi355_get_spmv_info(const aoclsparse_matrix A, aocl
     if(plan_option(aoclsparse_mi355_option_spmv_strict) == 1)
         strict = true;
     info->tree_min = ((info->kernel == 1 || info->kernel == 2) && order == 0 && !strict) ? SPMV_TREE_MIN : 0;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_get_sell_values(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *table_entries)
-{
-    if(!A || !table_entries)
-        return aoclsparse_status_invalid_pointer;
-    std::shared_lock<std::shared_mutex> r(A->guard);
-    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
-    *table_entries                        = p.sell.valid ? p.sell.ntab : 0;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_get_sell_packing(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *index_bits,
-                                                    aoclsparse_int *word_bytes, aoclsparse_int *uniform_slices)
-{
-    if(!A || !index_bits || !word_bytes || !uniform_slices)
-        return aoclsparse_status_invalid_pointer;
-    std::shared_lock<std::shared_mutex> r(A->guard);
-    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
-    const bool packed = p.sell.valid && p.sell.ntab > 0 && p.sell.pbits > 0;
-    *index_bits       = packed ? p.sell.pbits : 0;
-    *word_bytes       = packed ? p.sell.pbytes : 0;
-    *uniform_slices   = p.sell.valid && p.sell.ucol.ptr ? p.sell.uniform : 0;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_get_sell_records(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *uniform_word_slices,
-                                                    aoclsparse_int *exception_slices)
-{
-    if(!A || !uniform_word_slices || !exception_slices)
-        return aoclsparse_status_invalid_pointer;
-    std::shared_lock<std::shared_mutex> r(A->guard);
-    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
-    const bool                          on = p.sell.valid && p.sell.ucol.ptr;
-    *uniform_word_slices                   = on ? p.sell.uniform_words : 0;
-    *exception_slices                      = on ? p.sell.exceptions : 0;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_get_sell_period(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *first_slice,
-                                                   aoclsparse_int *end_slice, aoclsparse_int *period_slices, aoclsparse_int *column_stride)
-{
-    if(!A || !first_slice || !end_slice || !period_slices || !column_stride)
-        return aoclsparse_status_invalid_pointer;
-    std::shared_lock<std::shared_mutex> r(A->guard);
-    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
-    const bool                          on = p.sell.valid && p.sell.ucol.ptr;
-    *first_slice                           = on ? p.sell.pslo : 0;
-    *end_slice                             = on ? p.sell.pshi : 0;
-    *period_slices                         = on ? p.sell.pper : 0;
-    *column_stride                         = on ? p.sell.pstride : 0;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_get_sell_march(const aoclsparse_matrix A, aoclsparse_operation op, aoclsparse_int *first_slice,
-                                                  aoclsparse_int *end_slice, aoclsparse_int *periods, aoclsparse_int *alias_map)
-{
-    if(!A || !first_slice || !end_slice || !periods || !alias_map)
-        return aoclsparse_status_invalid_pointer;
-    std::shared_lock<std::shared_mutex> r(A->guard);
-    const SpmvPlan                     &p = op != aoclsparse_operation_none ? A->plan_trans : A->plan_user;
-    SellMarch                           mr;
-    // (what sell_launch_short asks before it calls the rule: a real plan with slice records, uniform lists and packed words)
-    if(p.sell.valid && p.sell.pack == 1 && p.sell.desc.ptr && p.sell.ucol.ptr && p.sell.ntab > 0 && p.sell.ntab <= 2 && p.sell.pbits > 0
-       && !is_complex_type(A->val_type) && p.max_row_nnz <= SELL_SHORT_WMAX)
-        mr = sell_march_rule(p.sell.nslices, p.max_row_nnz, p.sell.pslo, p.sell.pshi, p.sell.pper, p.sell.pstride, p.sell.mstack,
-                             p.sell.malias, val_size(A->val_type), sell_short_spw(p.sell.nslices, val_size(A->val_type), true));
-    *first_slice = mr.lo, *end_slice = mr.hi, *periods = mr.g, *alias_map = (aoclsparse_int)mr.alias;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_get_sell_keep_info(const aoclsparse_matrix A, aoclsparse_operation op,
-                                                      aoclsparse_mi355_sell_keep_info *info)
-{
-    if(!A || !info)
-        return aoclsparse_status_invalid_pointer;
-    if(info->struct_size < sizeof(info->struct_size))
-        return aoclsparse_status_invalid_size;
-    aoclsparse_mi355_sell_keep_info r{};
-    if(op == aoclsparse_operation_none) // (only the handle's own operator keeps anything)
-    {
-        std::shared_lock<std::shared_mutex> g(A->guard);
-        const SellPlan                     &sp = A->plan_user.sell;
-        r.kept = sp.structure, r.valid = sp.valid, r.last_route = sp.last_route;
-        r.structure_builds = sp.structure_builds, r.value_fills = sp.value_fills, r.searches_skipped = sp.searches_skipped;
-        r.kept_bytes = sp.structure ? (long long)sp.kept_bytes() : 0;
-    }
-    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
-    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_sell_find_march(aoclsparse_int nslices, const void *records, const aoclsparse_int *lists,
-                                                   const aoclsparse_int range[4], aoclsparse_int word_bytes, aoclsparse_int out[2])
-{
-    if(!records || !lists || !range || !out)
-        return aoclsparse_status_invalid_pointer;
-    if(nslices < 0)
-        return aoclsparse_status_invalid_size;
-    sell_find_march(static_cast<const SellSliceDesc *>(records), lists, nslices, range, (int)word_bytes, out);
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_sell_march_rule(aoclsparse_int nslices, aoclsparse_int max_width, const aoclsparse_int range[4],
-                                                   aoclsparse_int stack, aoclsparse_int alias_map, aoclsparse_int value_bytes,
-                                                   aoclsparse_int slices_per_wavefront, aoclsparse_int out[4])
-{
-    if(!range || !out)
-        return aoclsparse_status_invalid_pointer;
-    const SellMarch mr = sell_march_rule(nslices, max_width, (int)range[0], (int)range[1], (int)range[2], (int)range[3], (int)stack,
-                                         (unsigned)alias_map, (size_t)value_bytes, (int)slices_per_wavefront);
-    out[0] = mr.lo, out[1] = mr.hi, out[2] = mr.g, out[3] = (aoclsparse_int)mr.alias;
-    return aoclsparse_status_success;
-}
-
-aoclsparse_status aoclsparse_mi355_sell_find_period(aoclsparse_int nslices, const void *records, const aoclsparse_int *lists,
-                                                    aoclsparse_int max_period, aoclsparse_int range[4], long long *comparisons)
-{
-    if(!records || !lists || !range)
-        return aoclsparse_status_invalid_pointer;
-    if(nslices < 0 || max_period < 0)
-        return aoclsparse_status_invalid_size;
-    sell_find_period(static_cast<const SellSliceDesc *>(records), lists, nslices, max_period, range, comparisons);
     return aoclsparse_status_success;
 }
 

@@ -719,7 +719,7 @@ def test_float_short_row_kernel_four_slices_per_wavefront():
 
 
 def test_float_plans_use_2048_entry_row_blocks():
-    """Large float matrices plan 2,048-entry row blocks (round 4: matrix.cpp choose_tile).  On a 1,000^2 stencil (5 M non-zeros)
+    """Large float matrices plan 2,048-entry row blocks (round 4: spmv_plan.cpp choose_tile).  On a 1,000^2 stencil (5 M non-zeros)
     and a random matrix with rows of up to 700 entries (blocks of one to hundreds of rows, rows that do not fit the rest of a
     block): raw aoclsparse_scsrmv on device arrays and aoclsparse_smv on a handle without a SELL copy, bit for bit against the
     reference's float order; the 32-column row-major slab (csrmm_tile_kernel over the same blocks) equals the same columns of a
