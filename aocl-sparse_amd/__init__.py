@@ -96,6 +96,14 @@ class ValueMapInfo(ctypes.Structure):
                 ("revalues", ctypes.c_longlong), ("map_bytes", ctypes.c_longlong)]
 
 
+class OperatorInfo(ctypes.Structure):
+    """aoclsparse_mi355_operator_info: the caller sets struct_size, the library writes no more than that"""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("present", c_int32), ("built_on_device", c_int32), ("mapped", c_int32),
+                ("rows", c_int32), ("cols", c_int32), ("nnz", c_int32), ("followed", c_int32), ("sell_copy", c_int32),
+                ("sell_value_fills", ctypes.c_longlong), ("map_bytes", ctypes.c_longlong), ("device_builds", ctypes.c_longlong),
+                ("host_builds", ctypes.c_longlong), ("dropped_by_value_change", ctypes.c_longlong)]
+
+
 class SellKeepInfo(ctypes.Structure):
     """aoclsparse_mi355_sell_keep_info: the caller sets struct_size, the library writes no more than that"""
     _fields_ = [("struct_size", ctypes.c_size_t), ("kept", c_int32), ("valid", c_int32), ("last_route", c_int32),
@@ -457,6 +465,10 @@ SIGNATURES = {
     "aoclsparse_mi355_crevalue_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_zrevalue_device": (c_int, [_P, _I, _P]),
     "aoclsparse_mi355_get_value_map_info": (c_int, [_P, _P]),
+    "aoclsparse_mi355_build_operator_device": (c_int, [_P, _P, c_int]),
+    "aoclsparse_mi355_get_operator_info": (c_int, [_P, _P, c_int, _P]),
+    "aoclsparse_mi355_export_operator": (c_int, [_P, _P, c_int, POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_P), POINTER(_P),
+                                                 POINTER(_P)]),
     "aoclsparse_mi355_silu0_refactor_device": (c_int, [_P, POINTER(_P)]),
     "aoclsparse_mi355_dilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
     "aoclsparse_mi355_cilu0_refactor_device": (c_int, [_P, POINTER(_P)]),
@@ -741,6 +753,40 @@ class Matrix:
         st = lib().aoclsparse_mi355_get_value_map_info(self.h, byref(info))
         assert st == 0, STATUS.get(st, st)
         return info
+
+    def build_operator_device(self, descr, op=OP_NONE):
+        """aoclsparse_mi355_build_operator_device: the operator of a symmetric, Hermitian or triangular descriptor, which a product
+        otherwise builds on the host at first use, built in HBM from the clean CSR; under keep_value_maps it follows
+        revalue_device -> status"""
+        return lib().aoclsparse_mi355_build_operator_device(self.h, descr.h, op)
+
+    def operator_info(self, descr, op=OP_NONE):
+        """aoclsparse_mi355_get_operator_info -> OperatorInfo (present, built_on_device, mapped, rows, cols, nnz, sell_value_fills,
+        map_bytes of the operator of (descr, op); followed, device_builds, host_builds, dropped_by_value_change of the handle)"""
+        info = OperatorInfo(struct_size=ctypes.sizeof(OperatorInfo))
+        st = lib().aoclsparse_mi355_get_operator_info(self.h, descr.h, op, byref(info))
+        assert st == 0, STATUS.get(st, st)
+        return info
+
+    def export_operator(self, descr, op=OP_NONE, dtype=None):
+        """aoclsparse_mi355_export_operator -> dict(status, rows, cols, nnz, row_ptr, col_ind, val): copies of the host view of the
+        operator of (descr, op), 0-based; dtype: the handle's value type (numpy), by default taken from the handle"""
+        import numpy as np
+
+        rows, cols, nnz = c_int32(), c_int32(), c_int32()
+        rp, ci, v = c_void_p(), c_void_p(), c_void_p()
+        st = lib().aoclsparse_mi355_export_operator(self.h, descr.h, op, byref(rows), byref(cols), byref(nnz), byref(rp), byref(ci),
+                                                    byref(v))
+        if st != 0:
+            return dict(status=st)
+        if dtype is None:
+            dtype = {"s": np.float32, "d": np.float64, "c": np.complex64, "z": np.complex128}[self._letter()]
+        dtype, k = np.dtype(dtype), nnz.value
+        row_ptr = np.ctypeslib.as_array(ctypes.cast(rp, POINTER(c_int32)), (rows.value + 1,)).copy()
+        col = np.ctypeslib.as_array(ctypes.cast(ci, POINTER(c_int32)), (max(k, 1),))[:k].copy()
+        raw = np.ctypeslib.as_array(ctypes.cast(v, POINTER(ctypes.c_ubyte)), (max(k, 1) * dtype.itemsize,))[:k * dtype.itemsize]
+        return dict(status=0, rows=rows.value, cols=cols.value, nnz=k, row_ptr=row_ptr, col_ind=col,
+                    val=raw.copy().view(dtype))
 
     def order_device(self):
         """aoclsparse_mi355_order_mat_device: every row into ascending column order (stable), sorted in HBM; the handle is

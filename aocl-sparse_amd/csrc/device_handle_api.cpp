@@ -7,6 +7,9 @@
 //   new values  ?update_values_device, ?revalue_device (what holds a value map follows: revalue_kernels.hip) and
 //               ?refresh_values_from_coo_device (through the kept triplet map) all end in commit_values_device
 //   order       aoclsparse_order_mat on the mirror (order_kernels.hip);  clean: csr_optimize on it (clean_csr_kernels.hip)
+//   operators   aoclsparse_mi355_build_operator_device: what ensure_derived (derived.cpp) builds on the host for a symmetric,
+//               Hermitian or triangular descriptor, built from the clean CSR in HBM (derived_kernels.hip); with its source map it
+//               follows ?revalue_device
 //   export      the mirror's pointers.                     The steps several of them take are in device_handle.hpp.
 #include "device_handle.hpp"
 
@@ -187,6 +190,18 @@ namespace
                    && (!p.blk.valid || (p.blk.psrc.bytes >= sizeof(int) * ne && p.blk.pval.bytes >= vsz * ne)))
                     keep_plans |= 1u << i, kept++;
             }
+        // ... and the derived operators that hold their source map (build_operator_device under the flag): positions in the clean CSR
+        int ops_kept = 0;
+        if(clean_ok)
+            for(auto &dv : A->derived)
+            {
+                const size_t ne = (size_t)std::max<aoclsparse_int>(dv->host.nnz, 1);
+                if(dv->mapped && dv->src.ptr && dv->dev.valid && dv->dev.nnz == dv->host.nnz && dv->host.val
+                   && dv->src.bytes >= sizeof(unsigned) * ne && dv->dev.val.bytes >= vsz * ne)
+                    ops_kept++;
+                else
+                    dv->drop_value_map(); // (drop_derived_state_keeping keeps exactly the mapped ones)
+            }
         DeviceBuffer cval; // the clean copy's new values, for the gathers below and the copy back
         if(clean_ok && clean_copy && total > 0 && (e.rc = cval.alloc(vsz * (size_t)total)) != aoclsparse_status_success)
             return e.rc; // (nothing written yet: the handle is as it was; only ?revalue_device comes here)
@@ -239,6 +254,17 @@ namespace
                     e.status(launch_revalue_gather(s, p.nnz_tri, clean_n, p.blk.psrc.as<const int>(), clean_vals, p.blk.pval.ptr, vsz,
                                                    p.conj));
             }
+            // the mapped operators: their device values in place, the host view by one copy back each
+            if(clean_ok)
+                for(auto &dv : A->derived)
+                {
+                    if(!dv->mapped || !e.ok() || dv->host.nnz <= 0)
+                        continue;
+                    e.status(launch_revalue_gather_flagged(s, dv->host.nnz, clean_n, dv->src.as<const unsigned>(), clean_vals,
+                                                           dv->dev.val.ptr, vsz));
+                    if(e.ok())
+                        e.hip(hipMemcpyAsync(dv->host.val, dv->dev.val.ptr, vsz * (size_t)dv->host.nnz, hipMemcpyDeviceToHost, s));
+                }
             mark(3);
             // the one wait: the copies back have landed; `cval`, the caller's array and a refresh's buffer are no longer read
             // (an empty update has enqueued nothing)
@@ -262,14 +288,16 @@ namespace
         const bool ok = e.ok(); // (not ok: nothing is kept)
         // SELL-64 / blocked-ELL copies, derived operators, replicas -- except the structure of the handle's own SELL-64 copy, which
         // a handle with the flag keeps while the mirror it was built from has followed (its cells are refilled at the next product)
-        drop_derived_state_keeping(A, ok && clean_ok, ok ? keep_plans : 0u, ok && follow_maps && A->keep_maps && keep);
+        const bool keep_ops = ok && clean_ok && ops_kept > 0;
+        A->op_dropped_by_value_change += (long long)A->derived.size() - (keep_ops ? ops_kept : 0);
+        drop_derived_state_keeping(A, ok && clean_ok, ok ? keep_plans : 0u, ok && follow_maps && A->keep_maps && keep, keep_ops);
         if(!ok)
             A->drop_value_maps();
         if(!ok || !diag_ok) // (a diagonal without its map: ensure_trsv gathers it again; no plan was kept)
             A->dev_diag.release(), A->diag_src.release();
         d.valid = ok && keep; // (drop_derived_state has cleared it)
         if(ok && follow_maps)
-            A->revalues++, A->last_kept_plans = (int)kept;
+            A->revalues++, A->last_kept_plans = (int)kept, A->op_followed = ops_kept;
         return e.rc;
     }
 
@@ -522,6 +550,159 @@ namespace
             A->clean_builds++;
         }
     };
+
+    // The key ensure_derived looks an operator up by: H folds to T where the products fold it, symmetric and Hermitian operators
+    // ignore the operation
+    struct OperatorKey
+    {
+        int type, fill, diag, trans;
+    };
+    OperatorKey operator_key(const aoclsparse_mat_descr descr, aoclsparse_operation op)
+    {
+        const bool tri = descr->type == aoclsparse_matrix_type_triangular;
+        return {(int)descr->type, (int)descr->fill_mode, (int)descr->diag_type, tri && op != aoclsparse_operation_none ? 1 : 0};
+    }
+    Derived *find_operator(const _aoclsparse_matrix *A, const OperatorKey &k)
+    {
+        for(auto &d : A->derived)
+            if(d->type == k.type && d->fill == k.fill && d->diag == k.diag && d->trans == k.trans)
+                return d.get();
+        return nullptr;
+    }
+    // what the three operator calls decide alike, before anything else
+    aoclsparse_status operator_args_status(const _aoclsparse_matrix *A, const aoclsparse_mat_descr descr, aoclsparse_operation op)
+    {
+        if(!A || !descr)
+            return aoclsparse_status_invalid_pointer;
+        const bool valid_type = descr->type >= aoclsparse_matrix_type_general && descr->type <= aoclsparse_matrix_type_triangular;
+        const bool valid_op   = op == aoclsparse_operation_none || op == aoclsparse_operation_transpose
+                              || op == aoclsparse_operation_conjugate_transpose;
+        if(descr->base != A->base || !valid_type || !valid_op)
+            return aoclsparse_status_invalid_value;
+        return aoclsparse_status_success;
+    }
+
+    // aoclsparse_mi355_build_operator_device behind its statuses; called with the stage lock and the handle's guard held, the clean
+    // CSR made and no operator of this key on the handle.  Everything is built in buffers of the call's and registered at the very
+    // end; until then the handle is as it was (a mirror upload aside).
+    aoclsparse_status build_operator_device(aoclsparse_matrix A, const OperatorKey &key)
+    {
+        Runtime       &rt  = Runtime::get();
+        hipStream_t    s   = rt.stream();
+        const HostCsr &o   = *A->opt;
+        const bool     own = A->opt == &A->user;
+        const size_t   vsz = val_size(A->val_type), rb = sizeof(aoclsparse_int) * (size_t)std::max<aoclsparse_int>(o.m, 1);
+        if(!o.ptr || !o.ind || !o.val || !o.idiag || !o.iurow || o.m != A->m || o.n != A->n)
+            return aoclsparse_status_internal_error;
+        StreamLaps               lt{s};
+        std::unique_ptr<Derived> d(new(std::nothrow) Derived);
+        if(!d)
+            return aoclsparse_status_memory_error;
+        d->type = key.type, d->fill = key.fill, d->diag = key.diag, d->trans = key.trans;
+        DeviceBuffer   cp, ci, cv, didiag, diurow, optr, oind, oval, osrc;
+        aoclsparse_int nnz = 0;
+        FirstError     e;
+        {
+            StreamDrain     drain{s}; // (after a failure: nothing in flight into the buffers above when they go)
+            DerivedDeviceIn in;
+            in.m = o.m, in.n = o.n, in.nnz = o.nnz, in.base = (int)o.base, in.vsize = vsz, in.cplx = is_complex_type(A->val_type);
+            in.type = (aoclsparse_matrix_type)key.type, in.upper = key.fill == (int)aoclsparse_fill_mode_upper;
+            in.diag = (aoclsparse_diag_type)key.diag, in.transposed = key.trans != 0;
+            // the clean CSR as an operand: the handle's own arrays through the resident mirror, a copy through buffers of this call
+            if(own)
+            {
+                e.status(resident_mirror(A));
+                const DeviceCsr &m = A->dev_user;
+                in.ptr = m.ptr.as<const aoclsparse_int>(), in.ind = m.ind.as<const aoclsparse_int>(), in.val = m.val.ptr;
+                in.nnz = A->nnz;
+            }
+            else
+            {
+                const size_t ne = (size_t)std::max<aoclsparse_int>(o.nnz, 1);
+                e.status(cp.upload(o.ptr, sizeof(aoclsparse_int) * ((size_t)o.m + 1), s));
+                if(e.ok())
+                    e.status(ci.alloc(sizeof(aoclsparse_int) * ne));
+                if(e.ok())
+                    e.status(cv.alloc(vsz * ne));
+                if(e.ok() && o.nnz > 0)
+                {
+                    e.hip(hipMemcpyAsync(ci.ptr, o.ind, sizeof(aoclsparse_int) * (size_t)o.nnz, hipMemcpyHostToDevice, s));
+                    e.hip(hipMemcpyAsync(cv.ptr, o.val, vsz * (size_t)o.nnz, hipMemcpyHostToDevice, s));
+                }
+                in.ptr = cp.as<const aoclsparse_int>(), in.ind = ci.as<const aoclsparse_int>(), in.val = cv.ptr;
+            }
+            if(e.ok())
+                e.status(didiag.upload(o.idiag, rb, s));
+            if(e.ok())
+                e.status(diurow.upload(o.iurow, rb, s));
+            in.idiag = didiag.as<const aoclsparse_int>(), in.iurow = diurow.as<const aoclsparse_int>();
+            e.hip(lt.synced("build_operator_device: operands"));
+            if(e.ok())
+                e.status(device_build_derived(s, in, optr, oind, oval, osrc, &nnz));
+            lt.lap("build_operator_device: kernels");
+            // the host view by one copy back
+            HostCsr &h = d->host;
+            if(e.ok())
+            {
+                const bool sym = key.type != (int)aoclsparse_matrix_type_triangular;
+                h.m = (sym || !key.trans) ? o.m : o.n, h.n = (sym || !key.trans) ? o.n : o.m;
+                h.nnz = nnz, h.base = aoclsparse_index_base_zero;
+                const size_t ib = sizeof(aoclsparse_int) * (size_t)std::max<aoclsparse_int>(nnz, 1);
+                const size_t vb = vsz * (size_t)std::max<aoclsparse_int>(nnz, 1);
+                h.owned = h.result_arrays = true;
+                h.ptr = new(std::nothrow) aoclsparse_int[(size_t)h.m + 1];
+                h.ind = static_cast<aoclsparse_int *>(host_result_alloc(ib));
+                h.val = host_result_alloc(vb);
+                if(!h.ptr || !h.ind || !h.val)
+                    e.status(aoclsparse_status_memory_error);
+                else
+                {
+                    host_result_touch(h.ind, ib);
+                    host_result_touch(h.val, vb);
+                    e.hip(hipMemcpyAsync(h.ptr, optr.ptr, sizeof(aoclsparse_int) * ((size_t)h.m + 1), hipMemcpyDeviceToHost, s));
+                    if(nnz > 0)
+                    {
+                        e.hip(hipMemcpyAsync(h.ind, oind.ptr, sizeof(aoclsparse_int) * (size_t)nnz, hipMemcpyDeviceToHost, s));
+                        e.hip(hipMemcpyAsync(h.val, oval.ptr, vsz * (size_t)nnz, hipMemcpyDeviceToHost, s));
+                    }
+                    e.hip(hipStreamSynchronize(s));
+                }
+            }
+            if(e.ok())
+                drain.dismiss();
+        }
+        lt.lap("build_operator_device: host view");
+        if(!e.ok())
+        {
+            (void)hipGetLastError();
+            return e.rc;
+        }
+        DeviceCsr &dv = d->dev;
+        dv.ptr.adopt(optr), dv.ind.adopt(oind), dv.val.adopt(oval);
+        dv.m = d->host.m, dv.n = d->host.n, dv.nnz = nnz, dv.base = aoclsparse_index_base_zero;
+        dv.valid = true;
+        // the row-block plan and the SELL-64 copy as ensure_derived builds them
+        e.status(build_spmv_plan(d->host.m, d->host.nnz, d->host.base, d->host.ptr, d->plan, vsz));
+        if(e.ok() && A->mem_policy == aoclsparse_memory_usage_unrestricted && !is_complex_type(A->val_type))
+            e.status(build_sell(d->host.ptr, d->dev, vsz, d->plan));
+        lt.lap("build_operator_device: plan + SELL-64 copy");
+        d->on_device = true;
+        if(A->keep_maps) // the source map stays: ?revalue_device gathers the values through it again
+            d->src.adopt(osrc), d->mapped = true;
+        if(e.ok())
+            try
+            {
+                A->derived.push_back(std::move(d));
+                A->op_device_builds++;
+            }
+            catch(const std::bad_alloc &)
+            {
+                e.status(aoclsparse_status_memory_error);
+            }
+        if(!e.ok()) // (the operator goes with `d`: nothing in flight into its buffers by then)
+            (void)hipStreamSynchronize(s), (void)hipGetLastError();
+        return e.rc;
+    }
 } // namespace
 
 namespace mi355
@@ -661,6 +842,80 @@ aoclsparse_status aoclsparse_mi355_get_value_map_info(aoclsparse_matrix A, aocls
     }
     r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
     std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_build_operator_device(aoclsparse_matrix A, const aoclsparse_mat_descr descr, aoclsparse_operation op)
+{
+    // decided before the device is touched, in this order
+    MI355_TRY(operator_args_status(A, descr, op));
+    if(descr->type == aoclsparse_matrix_type_general)
+        return aoclsparse_status_not_implemented;
+    if(A->input_format != aoclsparse_csr_mat || A->csc_ptr) // COO-, CSC-, TCSR- and BSR-created handles, as ?revalue_device
+        return aoclsparse_status_not_implemented;
+    const bool sym = descr->type != aoclsparse_matrix_type_triangular;
+    if(descr->type == aoclsparse_matrix_type_hermitian && !is_complex_type(A->val_type))
+        return aoclsparse_status_not_implemented;
+    if(sym && A->m != A->n)
+        return aoclsparse_status_invalid_size;
+    if(A->m == 0 || A->n == 0 || A->nnz == 0)
+        return aoclsparse_status_success;
+    if(!A->user.ptr || !A->user.ind || !A->user.val)
+        return aoclsparse_status_invalid_pointer;
+    const OperatorKey key = operator_key(descr, op);
+    Runtime          &rt  = Runtime::get();
+    MI355_TRY(rt.init());
+    std::lock_guard<std::recursive_mutex> sl(rt.stage_lock); // (before the handle's guard, as everywhere)
+    MI355_TRY(csr_optimize(A)); // the clean CSR as ensure_derived makes it, or the copy clean_csr_device has made (takes the guard itself)
+    std::unique_lock<std::shared_mutex> w(A->guard);
+    if(!A->opt)
+        return aoclsparse_status_internal_error;
+    if(find_operator(A, key)) // however it was built
+        return aoclsparse_status_success;
+    return build_operator_device(A, key);
+}
+
+aoclsparse_status aoclsparse_mi355_get_operator_info(aoclsparse_matrix A, const aoclsparse_mat_descr descr, aoclsparse_operation op,
+                                                     aoclsparse_mi355_operator_info *info)
+{
+    if(!info)
+        return aoclsparse_status_invalid_pointer;
+    MI355_TRY(operator_args_status(A, descr, op));
+    if(info->struct_size < sizeof(info->struct_size))
+        return aoclsparse_status_invalid_size;
+    aoclsparse_mi355_operator_info r{};
+    {
+        std::shared_lock<std::shared_mutex> g(A->guard);
+        if(const Derived *d = find_operator(A, operator_key(descr, op)))
+        {
+            r.present = 1, r.built_on_device = d->on_device, r.mapped = d->mapped && d->src.ptr;
+            r.rows = d->host.m, r.cols = d->host.n, r.nnz = d->host.nnz;
+            r.sell_copy        = d->plan.sell.valid || (d->plan.sell.stale && d->plan.sell.st.built);
+            r.sell_value_fills = d->plan.sell.count.value_fills;
+            r.map_bytes        = (long long)d->src.bytes;
+        }
+        r.followed = A->op_followed;
+        r.device_builds = A->op_device_builds, r.host_builds = A->op_host_builds;
+        r.dropped_by_value_change = A->op_dropped_by_value_change;
+    }
+    r.struct_size = info->struct_size; // (the caller's: it says how much of the struct the caller has)
+    std::memcpy(info, &r, std::min(info->struct_size, sizeof(r))); // no more than that is written
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status aoclsparse_mi355_export_operator(aoclsparse_matrix A, const aoclsparse_mat_descr descr, aoclsparse_operation op,
+                                                   aoclsparse_int *rows, aoclsparse_int *cols, aoclsparse_int *nnz,
+                                                   const aoclsparse_int **row_ptr, const aoclsparse_int **col_ind, const void **val)
+{
+    if(!rows || !cols || !nnz || !row_ptr || !col_ind || !val)
+        return aoclsparse_status_invalid_pointer;
+    MI355_TRY(operator_args_status(A, descr, op));
+    std::shared_lock<std::shared_mutex> g(A->guard);
+    const Derived                      *d = find_operator(A, operator_key(descr, op));
+    if(!d || !d->host.ptr)
+        return aoclsparse_status_invalid_value;
+    *rows = d->host.m, *cols = d->host.n, *nnz = d->host.nnz;
+    *row_ptr = d->host.ptr, *col_ind = d->host.ind, *val = d->host.val;
     return aoclsparse_status_success;
 }
 

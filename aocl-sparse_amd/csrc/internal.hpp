@@ -847,7 +847,15 @@ struct Derived
     HostCsr   host; // owned, 0-based, sorted rows
     DeviceCsr dev;
     SpmvPlan  plan;
+    // aoclsparse_mi355_build_operator_device (device_handle_api.cpp, derived_kernels.hip) built it in HBM: host is then a copy back
+    // of dev.  mapped: src holds, per entry of dev.val, where its value comes from -- the 0-based position in the clean CSR's value
+    // array, DERIVED_SRC_CONJ set when the value is the conjugate of that entry, DERIVED_SRC_CONST for a constant (the one of a unit
+    // diagonal) -- recorded while the handle's keep_value_maps flag is set: ?revalue_device gathers dev.val again through it.
+    bool         on_device = false, mapped = false;
+    DeviceBuffer src;
+    void         drop_value_map() { src.release(), mapped = false; }
 };
+constexpr unsigned DERIVED_SRC_CONJ = 0x80000000u, DERIVED_SRC_CONST = 0xffffffffu;
 
 } // namespace mi355
 
@@ -891,6 +899,8 @@ struct _aoclsparse_matrix
         clean_src.release(), diag_src.release();
         for(auto &p : trsv_plan)
             p.drop_value_maps();
+        for(auto &d : derived)
+            d->drop_value_map();
     }
     mi355::DeviceBuffer trsv_scratch; // ticket (one per right-hand side) + timeout words of the sync-free solve
     mi355::DeviceBuffer trsv_xp; // solution(s) in level order, m x nrhs (stream-ordered reuse)
@@ -909,6 +919,10 @@ struct _aoclsparse_matrix
     // matrices derived from the clean CSR for non-general descriptors (symmetric expansion,
     // triangular slices), built on first use: see derived.cpp
     std::vector<std::unique_ptr<mi355::Derived>> derived;
+    // observers (aoclsparse_mi355_get_operator_info), since the handle was created: operators built in HBM / on the host, the
+    // operators the last successful ?revalue_device carried over, the operators value changes have dropped
+    long long op_device_builds = 0, op_host_builds = 0, op_dropped_by_value_change = 0;
+    int       op_followed = 0;
 
     // sp2m stage-1 state (C handles own their arrays)
     bool owns_user_arrays = false;
@@ -1280,8 +1294,11 @@ aoclsparse_status csr_optimize(aoclsparse_matrix A);
 void drop_derived_state(aoclsparse_matrix A);
 // the same, except that the clean CSR with dev_diag (keep_clean) and the TRSV plans whose bit is set in keep_plans (bit i =
 // trsv_plan[i]) stay: aoclsparse_mi355_?revalue_device has brought the new values to them; keep_sell: the STRUCTURE of plan_user's
-// SELL-64 copy stays (SellPlan::stale: its cells hold the old values until the next build_sell refills them)
-void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell = false);
+// SELL-64 copy stays (SellPlan::stale: its cells hold the old values until the next build_sell refills them); keep_operators: the
+// derived operators that hold a value map stay (Derived::mapped: their values have been gathered again), each with the structure
+// of its SELL-64 copy, stale in the same way; the others go
+void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell = false,
+                                bool keep_operators = false);
 // drop_derived_state, and with it what indexes the entries in their order within the rows (the triplet map, the ILU(0) schedule):
 // for whoever has sorted the rows
 void drop_order_dependent_state(aoclsparse_matrix A);
@@ -1321,6 +1338,27 @@ aoclsparse_status build_transpose(aoclsparse_matrix A);
 aoclsparse_status device_transpose(hipStream_t s, aoclsparse_int m, aoclsparse_int n, aoclsparse_int nnz, int base,
                                    const aoclsparse_int *d_ptr, const aoclsparse_int *d_ind, const void *d_val, size_t vsize,
                                    DeviceBuffer &tptr, DeviceBuffer &tind, DeviceBuffer &tval);
+// The operator build_derived (derived.cpp) makes of a clean CSR, built in HBM (derived_kernels.hip): the clean CSR of an m x n matrix
+// with its idiag / iurow (positions in `base`, as the host arrays hold them) and nnz values of vsize bytes (cplx: a pair of reals),
+// all in HBM, and the operator's key.
+struct DerivedDeviceIn
+{
+    aoclsparse_int          m = 0, n = 0, nnz = 0;
+    int                     base = 0;
+    const aoclsparse_int   *ptr = nullptr, *ind = nullptr, *idiag = nullptr, *iurow = nullptr;
+    const void             *val   = nullptr;
+    size_t                  vsize = 0;
+    bool                    cplx  = false;
+    aoclsparse_matrix_type  type  = aoclsparse_matrix_type_symmetric;
+    bool                    upper = false, transposed = false;
+    aoclsparse_diag_type    diag  = aoclsparse_diag_type_non_unit;
+};
+// optr (rows + 1), oind, oval and osrc (the source map, Derived::src; nnz items each, one at least): the 0-based operator, bit for
+// bit build_derived's, ALLOCATED HERE once the matrix is accepted.  aoclsparse_status_not_implemented when a mirrored row segment is
+// longer than the segment sort takes (the caller leaves the operator to the host); on any failure the four buffers are empty.
+// The caller holds the stage lock; returns with the stream drained.
+aoclsparse_status device_build_derived(hipStream_t s, const DerivedDeviceIn &in, DeviceBuffer &optr, DeviceBuffer &oind,
+                                       DeviceBuffer &oval, DeviceBuffer &osrc, aoclsparse_int *nnz_out);
 // CSR arrays (in the triplets' base) from nnz unordered triplets in HBM by a stable radix sort (coo_sort_kernels.hip), into buffers
 // it allocates once every index is known to be in range (invalid_index_value otherwise; the buffers are then empty).  sum == false:
 // the reference's coo2csr, *nnz_out = nnz; sum == true: sorted by (row, column), equal coordinates added left to right in triplet
@@ -1369,6 +1407,10 @@ aoclsparse_status launch_clean_finish(hipStream_t s, aoclsparse_int m, aoclspars
 // (idiag - base where iurow == idiag + 1 and the row is < min(m, n)), else -1.
 aoclsparse_status launch_revalue_gather(hipStream_t s, long long count, long long nsrc, const int *map, const void *in, void *out,
                                         size_t vsize, bool conj);
+// gather_flagged: the same through a derived operator's map (Derived::src): out[k] = in[map[k] & ~DERIVED_SRC_CONJ], conjugated where
+// DERIVED_SRC_CONJ is set (never for items of 4 bytes); out[k] is LEFT AS IT IS where map[k] == DERIVED_SRC_CONST
+aoclsparse_status launch_revalue_gather_flagged(hipStream_t s, long long count, long long nsrc, const unsigned *map, const void *in,
+                                                void *out, size_t vsize);
 aoclsparse_status launch_revalue_iota(hipStream_t s, aoclsparse_int count, int *out);
 aoclsparse_status launch_revalue_compose(hipStream_t s, aoclsparse_int count, aoclsparse_int nperm, const int *perm, int *map);
 aoclsparse_status launch_revalue_diag_map(hipStream_t s, aoclsparse_int m, aoclsparse_int n, int base, aoclsparse_int total,

@@ -765,7 +765,7 @@ void drop_order_dependent_state(aoclsparse_matrix A)
 
 // (keep_clean / keep_plans: aoclsparse_mi355_?revalue_device alone passes anything but false / 0 -- it has rewritten the values of
 // what it asks to keep)
-void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell)
+void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell, bool keep_operators)
 {
     for(aoclsparse_matrix t : A->tcsr_tri) // TCSR: everything that holds values hangs on the two triangle handles
         if(t)
@@ -781,7 +781,21 @@ void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned k
         A->clean_src.release(); // (its value map indexes the copy that is gone)
     }
     A->trans.reset(); // host transpose
-    A->derived.clear(); // symmetric / triangular expansions (host + device + their plans)
+    // symmetric / triangular expansions (host + device + their plans); one that holds a value map has followed a ?revalue_device
+    // and stays (only with the clean CSR its map indexes): its SELL-64 copy keeps its structure as the handle's own does, its
+    // blocked-ELL copy is rebuilt lazily
+    if(keep_operators && keep_clean)
+    {
+        auto &v = A->derived;
+        v.erase(std::remove_if(v.begin(), v.end(), [](const std::unique_ptr<Derived> &d) { return !d->mapped || !d->src.ptr; }), v.end());
+        for(auto &d : v)
+        {
+            d->plan.sell.values_changed(true, d->host.m, d->host.nnz);
+            d->plan.bell.valid = d->plan.bell.tried = false;
+        }
+    }
+    else
+        A->derived.clear();
     for(auto &r : A->replicas) // multi-device replicas hold device copies of the old values
         if(r)
             aoclsparse_destroy(&r);
@@ -833,6 +847,7 @@ static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, 
             static_cast<T *>(A->user.val)[p] = val;
             if(A->csc_ptr)
                 csc_set_value(A, row_idx, col_idx, &val);
+            A->op_dropped_by_value_change += (long long)A->derived.size();
             drop_derived_state(A);
             return aoclsparse_status_success;
         }
@@ -880,6 +895,7 @@ static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, 
     }
     else
         std::memcpy(A->user.val, val, sizeof(T) * (size_t)len);
+    A->op_dropped_by_value_change += (long long)A->derived.size();
     drop_derived_state(A);
     return aoclsparse_status_success;
 }

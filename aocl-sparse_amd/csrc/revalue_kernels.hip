@@ -13,6 +13,10 @@
 //                        zero item for a negative position, the conjugate and a 64-bit k added.  A position outside the source
 //                        (no map holds one) gives the zero item too: the guard is one unsigned compare.
 //
+//   rv_gather_flagged_kernel   the same through the source map of a derived operator (Derived::src, derived_kernels.hip): the
+//                        conjugate is chosen per item by one bit of the word, and an item marked as a constant (the one of a unit
+//                        diagonal) is left as it is.  It also writes the operator's values when the operator is built.
+//
 // ... brings new values to all of them.  The maps themselves come from the host (trsv_plan.cpp) or from the three small kernels
 // below, which serve aoclsparse_mi355_clean_csr_device:
 //
@@ -81,6 +85,34 @@ namespace
         }
     }
 
+    // rv_gather_kernel for a derived operator's map (Derived::src): a word is a position, DERIVED_SRC_CONJ set where the item is the
+    // conjugate of its source, or DERIVED_SRC_CONST: the target is a constant and stays as it is.  The same batching -- every map
+    // load, then every value load, then the stores; a word that names no source (none is ever written) leaves its target alone too.
+    template <typename V>
+    __global__ __launch_bounds__(RV_BLOCK) void rv_gather_flagged_kernel(long long count, unsigned nsrc, const unsigned *__restrict__ map,
+                                                                         const V *__restrict__ in, V *__restrict__ out)
+    {
+        const long long k0 = (long long)blockIdx.x * RV_TILE + threadIdx.x;
+        unsigned        w[RV_PER_LANE];
+        V               v[RV_PER_LANE];
+#pragma unroll
+        for(int j = 0; j < RV_PER_LANE; j++)
+        {
+            const long long k = k0 + (long long)j * RV_BLOCK;
+            w[j]              = k < count ? map[k] : DERIVED_SRC_CONST;
+        }
+#pragma unroll
+        for(int j = 0; j < RV_PER_LANE; j++)
+            v[j] = (w[j] & ~DERIVED_SRC_CONJ) < nsrc ? in[w[j] & ~DERIVED_SRC_CONJ] : V{};
+#pragma unroll
+        for(int j = 0; j < RV_PER_LANE; j++)
+        {
+            const long long k = k0 + (long long)j * RV_BLOCK;
+            if(k < count && (w[j] & ~DERIVED_SRC_CONJ) < nsrc)
+                out[k] = (w[j] & DERIVED_SRC_CONJ) ? rv_conj(v[j]) : v[j];
+        }
+    }
+
     __global__ __launch_bounds__(256) void rv_iota_kernel(aoclsparse_int count, int *__restrict__ out)
     {
         const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -140,6 +172,36 @@ aoclsparse_status launch_revalue_gather(hipStream_t s, long long count, long lon
         break;
     case 16:
         rv_launch_gather<Item16>(s, count, ns, map, in, out, conj);
+        break;
+    default:
+        return aoclsparse_status_not_implemented;
+    }
+    MI355_HIP_TRY(hipGetLastError());
+    return aoclsparse_status_success;
+}
+
+aoclsparse_status launch_revalue_gather_flagged(hipStream_t s, long long count, long long nsrc, const unsigned *map, const void *in,
+                                                void *out, size_t vsize)
+{
+    if(count <= 0)
+        return aoclsparse_status_success;
+    if(!map || !in || !out || nsrc > 0x7fffffffll)
+        return aoclsparse_status_internal_error;
+    const unsigned ns   = (unsigned)std::max(nsrc, 0ll);
+    const unsigned grid = (unsigned)((count + RV_TILE - 1) / RV_TILE);
+    switch(vsize)
+    {
+    case 4:
+        hipLaunchKernelGGL((rv_gather_flagged_kernel<unsigned int>), dim3(grid), dim3(RV_BLOCK), 0, s, count, ns, map,
+                           static_cast<const unsigned int *>(in), static_cast<unsigned int *>(out));
+        break;
+    case 8:
+        hipLaunchKernelGGL((rv_gather_flagged_kernel<unsigned long long>), dim3(grid), dim3(RV_BLOCK), 0, s, count, ns, map,
+                           static_cast<const unsigned long long *>(in), static_cast<unsigned long long *>(out));
+        break;
+    case 16:
+        hipLaunchKernelGGL((rv_gather_flagged_kernel<Item16>), dim3(grid), dim3(RV_BLOCK), 0, s, count, ns, map,
+                           static_cast<const Item16 *>(in), static_cast<Item16 *>(out));
         break;
     default:
         return aoclsparse_status_not_implemented;

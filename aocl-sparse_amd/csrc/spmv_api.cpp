@@ -276,6 +276,14 @@ aoclsparse_status mv_t(aoclsparse_operation op, const T *alpha, aoclsparse_matri
             return st;
         dcsr = &dv->dev;
         plan = &dv->plan;
+        // an operator kept through ?revalue_device: its SELL-64 structure is stale, the values stage refills the cells
+        if(plan->sell.wanted && !plan->sell.valid)
+        {
+            std::unique_lock<std::shared_mutex> w(A->guard);
+            st = build_sell(dv->host.ptr, *dcsr, val_size(A->val_type), *plan);
+            if(st != aoclsparse_status_success)
+                return st;
+        }
     }
     else
     {

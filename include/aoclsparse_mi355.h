@@ -391,8 +391,8 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *           the handle as it was; after any failure behind the first device write the handle is left with everything dropped and
  *           all maps released (never plans with some old and some new values) and an invalid mirror (the next product uploads the
  *           host view), and the status is reported.  Peak extra device memory: sizeof(value) per entry of a clean copy, during
- *           the call.  Not kept (rebuilt lazily as ever): blocked-ELL copies, the SELL-64 copies of op(A) and of derived
- *           operators, derived operators, transposes, replicas.  (4, round 28) With the keep_value_maps flag set, the STRUCTURE
+ *           the call.  Not kept (rebuilt lazily as ever): blocked-ELL copies, the SELL-64 copies of op(A), derived operators
+ *           without a source map (see build_operator_device), transposes, replicas.  (4, round 28) With the keep_value_maps flag set, the STRUCTURE
  *           of the handle's own SELL-64 copy stays -- slice widths, shared column lists, columns, row lengths, the records
  *           before their device flags -- when the copy was valid (or already kept) and the mirror it was built from followed the
  *           commit.  The call itself launches and waits for nothing more: the copy is marked stale, no product runs it, and the
@@ -411,6 +411,53 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  *   get_value_map_info What a handle holds of the above (struct_size as for get_coo_map_info).  plan_builds and clean_builds count
  *           the times a TRSV plan / the clean CSR was actually built or extended since the handle was created, flag or no flag:
  *           they show whether a solve after a value change analysed anything.
+ *
+ *   build_operator_device  (round 30) A product with a symmetric, Hermitian or triangular descriptor (?mv, ?csrmm, the complex
+ *           products, the iterative solvers) runs on a derived operator: the strict triangle, D' (D, I or nothing for non_unit /
+ *           unit / zero) and, for symmetric and Hermitian, the mirrored triangle (conjugated for Hermitian) -- or, for triangular
+ *           with op = T / H, the transpose of triangle + D' -- as a general CSR with its own device copy, row-block plan and
+ *           SELL-64 copy, keyed by (type, fill, diag, transposed): H folds to T where the products fold it, symmetric and
+ *           Hermitian ignore the operation.  At first use a product builds it by a serial host loop and uploads it.  This call
+ *           builds the operator of (descr, op) in HBM instead (derived_kernels.hip) and registers it on the handle: every later
+ *           product with a matching descriptor finds it, and none knows where it was built.  An operator that exists already,
+ *           however it was built, makes the call succeed and do nothing.  The clean CSR is made first as a product makes it
+ *           (csr_optimize), or is clean_csr_device's copy when there is one; it reaches the device through the resident mirror
+ *           (uploaded when absent) when it is the handle's own arrays, through buffers of the call when it is a copy; idiag /
+ *           iurow are uploaded.  The result is bit for bit the host loop's: every row in ascending column order, mirrored entries
+ *           of a row in ascending source position, the unit diagonal stored as ones.  The host view comes by one copy back; the
+ *           row-block plan and the SELL-64 copy are built as a product builds them.  A product never takes this route by itself.
+ *           Statuses, all decided before the device is touched, in this order: invalid_pointer for a null A or descr;
+ *           invalid_value for a base that is not the handle's or an invalid type or operation; not_implemented for a general
+ *           descriptor; not_implemented for handles that are no plain CSR (COO- or CSC-created, TCSR, BSR: ?revalue_device's set);
+ *           not_implemented for a Hermitian descriptor on a real value type; invalid_size for symmetric or Hermitian with
+ *           m != n.  An empty matrix (m, n or nnz zero) succeeds and builds nothing.  Declined: not_implemented, nothing
+ *           registered, when a row of the result would get more than 2,048 mirrored entries (the device segment sort's cap; the
+ *           verdict comes from the counters, before the operator's arrays are allocated): the next product builds on the host as
+ *           ever.  Failed: the allocation or HIP status, the stream drained, the error cleared.  Either way the handle is as it
+ *           was (a mirror upload aside).  Locking: the runtime's stage lock, then the handle's guard.  Peak extra device memory,
+ *           during the call: 16 bytes per row of the result and 8 per row of the clean CSR, and for a clean copy its three
+ *           arrays; the operator keeps 8 + sizeof(value) bytes per entry, 4 of them the source map below.
+ *           With keep_value_maps set at build time the operator keeps its source map, 4 bytes per entry: the clean position the
+ *           value comes from, one bit for the conjugate, one word for a constant (the unit diagonal's ones).  ?revalue_device
+ *           then brings the new values to every mapped operator -- exactly when the clean CSR itself follows -- by one gather from
+ *           the clean values into the operator's device values in place (revalue_kernels.hip; constants are left alone), next to
+ *           the TRSV plans' gathers, and one copy back into the host view; row pointer, columns, row-block plan and map stay.
+ *           The operator's SELL-64 copy keeps its structure as the handle's own does (stale; the next product runs the values
+ *           stage alone), its blocked-ELL copy is rebuilt lazily.  Operators without a map are dropped as before; so is every
+ *           operator, with the maps, on any failure behind the first write, when the clean CSR does not follow (a clean copy
+ *           built on the host has no map), and on ?update_values_device, ?set_value and ?update_values: never a mix of old and
+ *           new values.  The map is released by keep_value_maps(A, 0) (the operator stays and no longer follows) and, with the
+ *           operator, by aoclsparse_order_mat, order_mat_device, aoclsparse_mi355_invalidate and destroy; nothing is carried
+ *           through aoclsparse_copy, exported state or replicas.  get_value_map_info does not count these maps.
+ *
+ *   get_operator_info  What the handle holds for the key of (descr, op) -- present, built_on_device, mapped, rows, cols, nnz,
+ *           sell_copy, sell_value_fills (refills of its kept SELL-64 structure), map_bytes -- and the handle's counters, which
+ *           survive a drop: device_builds, host_builds, followed (operators the last successful ?revalue_device carried),
+ *           dropped_by_value_change.  struct_size as for get_coo_map_info; works without a device.  invalid_pointer for a null
+ *           argument, invalid_value as above.
+ *
+ *   export_operator    The host view of an existing operator, on whichever route it was built: 0-based arrays, valid until the
+ *           operator is dropped; invalid_value when the handle holds none for the key.  Works without a device.
  *
  *   ?ilu0_refactor_device  (round 26) The ILU(0) factor of A again, from the values the handle holds NOW: the resident mirror
  *           while it is valid, otherwise the host view, uploaded as every product uploads it.  In the reference and here the
@@ -493,8 +540,10 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_mm_state_adopt(aoclsparse_matrix *
  * the long columns of ?csr2csc and of the handles' transposes with the triplet sort (transpose_kernels.hip declines them still);
  * aoclsparse_order_mat itself taking the device route; adding repeated columns while ordering; ordering CSC-created, TCSR or BSR
  * handles on the device; csr_optimize / aoclsparse_optimize choosing the device route for the clean copy by themselves; keeping the
- * clean copy resident and building TRSV plans, derived operators or ILU factors from it on the device; value maps for clean copies
- * built on the host, and keeping blocked-ELL copies, the SELL-64 copies of op(A) or of derived operators, derived operators,
+ * clean copy resident and building TRSV plans or ILU factors from it on the device; ensure_derived / aoclsparse_optimize choosing
+ * build_operator_device's route by themselves, mirrored row segments beyond the segment sort's cap, source maps for operators built
+ * on the host, carrying operators or their maps through aoclsparse_copy, exported state or replicas; value maps for clean copies
+ * built on the host, and keeping blocked-ELL copies, the SELL-64 copies of op(A),
  * transposes or replicas through a ?revalue_device; keeping the SELL-64 structure through any other value change, carrying it
  * through aoclsparse_copy, exported state or replicas, and searching the periodic range on the device; computing the ILU(0) levels on the device; refactorising inside an update call by itself; a device-only ILU
  * factor without its host array; carrying the ILU schedule through aoclsparse_copy, exported state or replicas; carrying value maps through aoclsparse_copy, exported state or replicas; clean copies of the transpose; a host view that is filled on first use instead of by
@@ -583,6 +632,29 @@ DLL_PUBLIC aoclsparse_status aoclsparse_mi355_crevalue_device(aoclsparse_matrix 
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_zrevalue_device(aoclsparse_matrix A, aoclsparse_int len,
                                                               const aoclsparse_double_complex *val);
 DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_value_map_info(aoclsparse_matrix A, aoclsparse_mi355_value_map_info *info);
+typedef struct
+{
+    size_t         struct_size; /* in: sizeof(aoclsparse_mi355_operator_info) as the caller knows it */
+    aoclsparse_int present; /* 1: the handle holds the operator of this (type, fill, diag, op) */
+    aoclsparse_int built_on_device; /* 1: build_operator_device built it; 0: a product built it on the host */
+    aoclsparse_int mapped; /* 1: it holds its source map and follows a ?revalue_device */
+    aoclsparse_int rows, cols, nnz; /* of the operator (0 without one) */
+    aoclsparse_int followed; /* handle: operators the last successful ?revalue_device carried over */
+    aoclsparse_int sell_copy; /* 1: it holds a SELL-64 copy, valid or kept stale for the next product to refill */
+    long long      sell_value_fills; /* times the values stage refilled this operator's kept SELL-64 structure */
+    long long      map_bytes; /* device memory this operator's source map occupies */
+    long long      device_builds; /* handle, since creation: operators built in HBM */
+    long long      host_builds; /* handle, since creation: operators built on the host */
+    long long      dropped_by_value_change; /* handle, since creation: operators a value change dropped */
+} aoclsparse_mi355_operator_info;
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_build_operator_device(aoclsparse_matrix A, const aoclsparse_mat_descr descr,
+                                                                    aoclsparse_operation op);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_get_operator_info(aoclsparse_matrix A, const aoclsparse_mat_descr descr,
+                                                                aoclsparse_operation op, aoclsparse_mi355_operator_info *info);
+DLL_PUBLIC aoclsparse_status aoclsparse_mi355_export_operator(aoclsparse_matrix A, const aoclsparse_mat_descr descr,
+                                                              aoclsparse_operation op, aoclsparse_int *rows, aoclsparse_int *cols,
+                                                              aoclsparse_int *nnz, const aoclsparse_int **row_ptr,
+                                                              const aoclsparse_int **col_ind, const void **val);
 typedef struct
 {
     size_t         struct_size; /* in: sizeof(aoclsparse_mi355_ilu_info) as the caller knows it */
