@@ -1583,9 +1583,6 @@ aoclsparse_status launch_vec_fill(hipStream_t s, aoclsparse_int n, T *dst, T val
 template <typename T>
 aoclsparse_status launch_cg_direction(hipStream_t s, aoclsparse_int n, T beta, T *p, const T *z);
 template <typename T>
-aoclsparse_status launch_cg_step(hipStream_t s, aoclsparse_int n, T alpha, const T *p, const T *q, T *x, T *r,
-                                 T *partial, T *rr);
-template <typename T>
 aoclsparse_status launch_cg_step_dev(hipStream_t s, aoclsparse_int n, T rz, T tiny, const T *p, const T *q, T *x, T *r,
                                      T *partial, T *out2);
 template <typename T>

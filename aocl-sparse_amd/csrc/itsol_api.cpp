@@ -7,7 +7,10 @@
 // steps with AOCL-BLAS level-1 routines and libFLAME's lartg (neither vendored, no version pinned,
 // cmake/Dependencies.cmake:93-136); here they are the kernels of itsol_kernels.hip and a restatement of
 // LAPACK 3.10's dlartg.  Summation orders of dot / nrm2 therefore differ from the CPU library's: parity is
-// on iteration counts, exit codes, rinfo and the solution within the solver tolerances.
+// on iteration counts, exit codes, rinfo and the solution within the solver tolerances.  One deviation for every value
+// type: when GMRES stops because the new Arnoldi vector vanished (:1121-1135) the reference returns success with x as it was
+// when the cycle started; here x takes the correction of the columns built so far (gmres_correct_x), so that success means
+// a solution.  Status, iteration count and rinfo are the reference's.
 //
 // Two interfaces, as in the reference:
 //  * direct (aoclsparse_itsol_?_solve): b and x are staged to HBM once (or used in place when they are device
@@ -496,6 +499,32 @@ struct Arith : SolverBase
     }
 
     // ---- GMRES, aoclsparse_gmres_rci_solve (:910-1367) ---------------------------------------------------
+    // back substitution with the first `cols` columns of the rotated Hessenberg matrix (:885-908; the result shares the
+    // array of the rotation sines, as in the reference), then x += sum y_i v_i (z_i with a preconditioner, :1247-1273).
+    // A vanished pivot sets `singular` and leaves x alone.
+    aoclsparse_status gmres_correct_x(Runtime &rt, aoclsparse_int cols, T *x, bool &singular)
+    {
+        const aoclsparse_int m = restart;
+        for(aoclsparse_int jj = cols - 1; jj >= 0; jj--)
+        {
+            T yj = g[jj];
+            for(aoclsparse_int i = jj + 1; i < cols; i++)
+                yj -= h[(size_t)jj * m + i] * s[i];
+            const T diag = h[(size_t)jj * m + jj];
+            if(near_zero(diag))
+            {
+                singular = true;
+                return aoclsparse_status_success;
+            }
+            s[jj] = yj / diag;
+        }
+        MI355_TRY(upload_coef(rt, s.data(), (int)cols));
+        const T *basis = precond ? zz.as<T>() : v.as<T>();
+        MI355_TRY(launch_lincomb<T>(rt.stream(), 1, n, (int)cols, coef.as<T>(), basis, (long long)n, x));
+        x_dirty = true;
+        return aoclsparse_status_success;
+    }
+
     aoclsparse_status gmres_step(Runtime &rt, aoclsparse_itsol_rci_job *ircomm, T **io1, T **io2, T *x, T *rinfo)
     {
         aoclsparse_status    exit_status = aoclsparse_status_success;
@@ -577,7 +606,19 @@ struct Arith : SolverBase
                 MI355_TRY(nrm2(rt, w, hh));
                 if(hh < atol || hh < brtol)
                 {
-                    // the new direction is (numerically) inside the Krylov space already (:1121-1136)
+                    // the new direction is (numerically) inside the Krylov space already (:1121-1136).  The reference
+                    // stops here with x as it was when the cycle started: success without the correction that the
+                    // j + 1 columns built so far determine (with an exact preconditioner that is the initial guess).
+                    // Here the column is rotated like any other -- its subdiagonal entry is the vanished hh, so its own
+                    // rotation is the identity -- and x takes that correction; rinfo and the status are the reference's.
+                    for(aoclsparse_int i = 0; i < j; i++)
+                    {
+                        const T r1 = h[(size_t)i * m + j], r2 = h[(size_t)(i + 1) * m + j];
+                        h[(size_t)i * m + j]       = c[i] * r1 - s[i] * r2;
+                        h[(size_t)(i + 1) * m + j] = s[i] * r1 + c[i] * r2;
+                    }
+                    bool singular = false;
+                    MI355_TRY(gmres_correct_x(rt, j + 1, x, singular)); // (a vanished pivot: x stays, as in the reference)
                     niter += j + 1;
                     rinfo[RINFO_ITER]     = (T)niter;
                     rinfo[RINFO_RES_NORM] = hh;
@@ -619,27 +660,14 @@ struct Arith : SolverBase
             }
             case GM_UPDATE_X:
             {
-                // back substitution with the rotated Hessenberg matrix (:885-908); the result shares the
-                // array of the rotation sines, as in the reference
-                for(aoclsparse_int jj = j - 1; jj >= 0; jj--)
+                bool singular = false;
+                MI355_TRY(gmres_correct_x(rt, j, x, singular));
+                if(singular)
                 {
-                    T yj = g[jj];
-                    for(aoclsparse_int i = jj + 1; i < j; i++)
-                        yj -= h[(size_t)jj * m + i] * s[i];
-                    const T diag = h[(size_t)jj * m + jj];
-                    if(near_zero(diag))
-                    {
-                        exit_status = aoclsparse_status_numerical_error;
-                        break;
-                    }
-                    s[jj] = yj / diag;
-                }
-                if(exit_status != aoclsparse_status_success)
+                    exit_status = aoclsparse_status_numerical_error;
                     break;
-                MI355_TRY(upload_coef(rt, s.data(), (int)m));
-                MI355_TRY(launch_lincomb<T>(st, 1, n, (int)m, coef.as<T>(), precond ? Z : V, ld, x));
-                x_dirty = true;
-                rnorm2  = std::fabs(g[j]);
+                }
+                rnorm2 = std::fabs(g[j]);
                 niter += j;
                 rinfo[RINFO_ITER]     = (T)niter;
                 rinfo[RINFO_RES_NORM] = rnorm2;
@@ -878,6 +906,29 @@ struct Arith<cplx<R>> : SolverBase
         return exit_status;
     }
 
+    // back substitution over the first `cols` columns, then x += sum y_i v_i (z_i with a preconditioner), :1213-1232
+    aoclsparse_status gmres_correct_x(Runtime &rt, aoclsparse_int cols, C *x, bool &singular)
+    {
+        const aoclsparse_int m = restart;
+        for(aoclsparse_int jj = cols - 1; jj >= 0; jj--)
+        {
+            Cs yj = g[jj];
+            for(aoclsparse_int i = jj + 1; i < cols; i++)
+                yj -= h[(size_t)jj * m + i] * s[i];
+            const Cs diag = h[(size_t)jj * m + jj];
+            if(tiny(diag))
+            {
+                singular = true;
+                return aoclsparse_status_success;
+            }
+            s[jj] = yj / diag;
+        }
+        for(aoclsparse_int i = 0; i < cols; i++)
+            MI355_TRY(axpby(rt, s[i], (precond ? zz.as<C>() : v.as<C>()) + (long long)i * n, Cs(1), x, x));
+        x_dirty = true;
+        return aoclsparse_status_success;
+    }
+
     aoclsparse_status gmres_step(Runtime &rt, aoclsparse_itsol_rci_job *ircomm, C **io1, C **io2, C *x, R *rinfo)
     {
         aoclsparse_status    exit_status = aoclsparse_status_success;
@@ -948,6 +999,15 @@ struct Arith<cplx<R>> : SolverBase
                 MI355_TRY(nrm2(rt, w, hh));
                 if(hh < atol || hh < brtol)
                 {
+                    // (as for the real types: the column built so far still corrects x, which the reference leaves out)
+                    for(aoclsparse_int i = 0; i < j; i++)
+                    {
+                        const Cs r1 = h[(size_t)i * m + j], r2 = h[(size_t)(i + 1) * m + j];
+                        h[(size_t)i * m + j]       = c[i] * r1 + s[i] * r2;
+                        h[(size_t)(i + 1) * m + j] = -std::conj(s[i]) * r1 + c[i] * r2;
+                    }
+                    bool singular = false;
+                    MI355_TRY(gmres_correct_x(rt, j + 1, x, singular));
                     niter += j + 1;
                     rinfo[RINFO_ITER] = (R)niter, rinfo[RINFO_RES_NORM] = hh;
                     *ircomm = aoclsparse_rci_stop;
@@ -984,25 +1044,14 @@ struct Arith<cplx<R>> : SolverBase
             }
             case GM_UPDATE_X:
             {
-                for(aoclsparse_int jj = j - 1; jj >= 0; jj--)
+                bool singular = false;
+                MI355_TRY(gmres_correct_x(rt, j, x, singular));
+                if(singular)
                 {
-                    Cs yj = g[jj];
-                    for(aoclsparse_int i = jj + 1; i < j; i++)
-                        yj -= h[(size_t)jj * m + i] * s[i];
-                    const Cs diag = h[(size_t)jj * m + jj];
-                    if(tiny(diag))
-                    {
-                        exit_status = aoclsparse_status_numerical_error;
-                        break;
-                    }
-                    s[jj] = yj / diag;
-                }
-                if(exit_status != aoclsparse_status_success)
+                    exit_status = aoclsparse_status_numerical_error;
                     break;
-                for(aoclsparse_int i = 0; i < m; i++) // x += sum y_i v_i (z_i with a preconditioner), :1213-1232
-                    MI355_TRY(axpby(rt, s[i], (precond ? Z : V) + (long long)i * ld, Cs(1), x, x));
-                x_dirty = true;
-                rnorm2  = std::abs(g[j]);
+                }
+                rnorm2 = std::abs(g[j]);
                 niter += j;
                 rinfo[RINFO_ITER] = (R)niter, rinfo[RINFO_RES_NORM] = rnorm2;
                 const bool below_abs = R(0) < atol && rnorm2 <= atol, below_rel = R(0) < rnorm2 && rnorm2 <= brtol;

@@ -72,26 +72,8 @@ __global__ void cg_dir_kernel(aoclsparse_int n, T beta, T *p, const T *z)
         p[i] = v_fma(beta, p[i], -z[i]);
 }
 
-// x += alpha p; r += alpha q; partial[b] = sum over the block's elements of r_new^2  (:838-845)
-template <typename T>
-__global__ __launch_bounds__(256) void cg_step_kernel(aoclsparse_int n, T alpha, const T *p, const T *q, T *x, T *r,
-                                                       T *partial)
-{
-    __shared__ T sh[4];
-    T            acc = T(0);
-    for(aoclsparse_int i = blockIdx.x * 256 + threadIdx.x; i < n; i += (aoclsparse_int)gridDim.x * 256)
-    {
-        x[i]       = v_fma(alpha, p[i], x[i]);
-        const T rn = v_fma(alpha, q[i], r[i]);
-        r[i]       = rn;
-        acc        = v_fma(rn, rn, acc);
-    }
-    const T s = block_reduce_256(acc, sh);
-    if(threadIdx.x == 0)
-        partial[blockIdx.x] = s;
-}
-
-// the same step with alpha = rz / pq formed on the device from the p.q the previous launch left in *pq_dev, so the
+// x += alpha p; r += alpha q; partial[b] = sum over the block's elements of r_new^2  (:838-845),
+// with alpha = rz / pq formed on the device from the p.q the previous launch left in *pq_dev, so the
 // host does not have to wait for that dot product; a p.q the reference refuses (<= 0.02 eps or 0, :815-822) makes
 // the step a no-op and the host reports the error after the one synchronisation of the iteration
 template <typename T>
@@ -223,15 +205,6 @@ aoclsparse_status launch_cg_direction(hipStream_t s, aoclsparse_int n, T beta, T
         hipLaunchKernelGGL((cg_dir_kernel<T>), grid1(n), dim3(256), 0, s, n, beta, p, z);
     MI355_VEC_DONE();
 }
-template <typename T>
-aoclsparse_status launch_cg_step(hipStream_t s, aoclsparse_int n, T alpha, const T *p, const T *q, T *x, T *r,
-                                 T *partial, T *rr)
-{
-    const int nb = red_blocks(n);
-    hipLaunchKernelGGL((cg_step_kernel<T>), dim3(nb), dim3(256), 0, s, n, alpha, p, q, x, r, partial);
-    hipLaunchKernelGGL((reduce_final_kernel<T>), dim3(1), dim3(256), 0, s, nb, partial, rr);
-    MI355_VEC_DONE();
-}
 // out2[0] = r_new . r_new, out2[1] = p.q (both stay on the device; partial holds 2 * RED_BLOCKS elements)
 template <typename T>
 aoclsparse_status launch_cg_step_dev(hipStream_t s, aoclsparse_int n, T rz, T tiny, const T *p, const T *q, T *x, T *r,
@@ -276,8 +249,6 @@ aoclsparse_status launch_lincomb(hipStream_t s, int sign, aoclsparse_int n, int 
     template aoclsparse_status launch_vec_mul<T>(hipStream_t, aoclsparse_int, const T *, T *);                      \
     template aoclsparse_status launch_vec_fill<T>(hipStream_t, aoclsparse_int, T *, T);                             \
     template aoclsparse_status launch_cg_direction<T>(hipStream_t, aoclsparse_int, T, T *, const T *);              \
-    template aoclsparse_status launch_cg_step<T>(hipStream_t, aoclsparse_int, T, const T *, const T *, T *, T *,    \
-                                                 T *, T *);                                                         \
     template aoclsparse_status launch_cg_step_dev<T>(hipStream_t, aoclsparse_int, T, T, const T *, const T *, T *,  \
                                                      T *, T *, T *);                                                \
     template aoclsparse_status launch_multidot<T>(hipStream_t, aoclsparse_int, int, const T *, long long,           \
