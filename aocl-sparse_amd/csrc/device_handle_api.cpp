@@ -154,57 +154,31 @@ namespace
         return d.valid && d.m == A->m && d.nnz == A->nnz && d.ptr.ptr && d.ind.ptr && d.val.ptr && d.val.bytes >= bytes;
     }
 
-    // THE way new values enter a CSR handle from HBM; called with the stage lock and the handle's guard held.  `val`: A->nnz values
-    // of vsz bytes in CSR order -- the caller's array, or the mirror's own (in place).  follow_maps: the clean CSR, the diagonal
-    // and the TRSV plans that hold a value map get the new values through it (revalue_kernels.hip); what has no map, and
-    // everything without the flag, is dropped and rebuilt lazily.  `produced`: the status of what wrote `val` INTO THE HANDLE
-    // before the call (the triplet refresh).  One host wait.  A failure behind the first write into the handle leaves, on every
-    // route: everything derived and the value maps dropped (no plan with some old and some new values), the mirror invalid (it
-    // may hold either values: the next product uploads the host view), the error cleared and the stream drained.
-    aoclsparse_status commit_values_device(aoclsparse_matrix A, const void *val, size_t vsz, bool follow_maps,
-                                           aoclsparse_status produced = aoclsparse_status_success)
+    // decide: what a value change leaves standing.  The mirror while it follows; under follow_maps also what holds a value map, each
+    // kind of copy answering through its own `follows`.  How they hang together is decided here alone: the operators' and the diagonal's
+    // maps hold positions in the clean CSR, a plan divides by the diagonal, the SELL-64 copy was built from the mirror.  Writes nothing.
+    ValuesKept values_kept(const _aoclsparse_matrix *A, size_t vsz, bool follow_maps)
     {
-        hipStream_t          s     = Runtime::get().stream();
-        const aoclsparse_int len   = A->nnz;
-        const size_t         bytes = vsz * (size_t)len;
-        DeviceCsr           &d     = A->dev_user;
-        const bool           keep  = mirror_follows(A, bytes);
-        StreamLaps           lt{s, PhaseTimer::on() && follow_maps}; // (where a revalue's time goes; the laps then wait for the stream)
-        FirstError           e{produced};
-        // what can follow: the clean CSR when it is the handle's own arrays or a copy that holds its map ...
-        HostCsr *const       o          = follow_maps ? A->opt : nullptr;
-        const bool           clean_copy = o && o != &A->user;
-        const aoclsparse_int total      = o ? o->nnz : 0; // entries of the clean CSR
-        const bool           clean_ok   = o && (!clean_copy || (o == A->opt_copy.get() && o->val && A->clean_src.ptr
-                                                      && A->clean_src.bytes >= sizeof(int) * (size_t)total));
-        // ... the diagonal when it has its map, and with it the plans whose layouts all have theirs
-        const bool diag_ok = clean_ok && A->dev_diag.ptr && A->diag_src.ptr && A->dev_diag.bytes >= vsz * (size_t)A->m
-                             && A->diag_src.bytes >= sizeof(int) * (size_t)std::max<aoclsparse_int>(A->m, 1);
-        unsigned keep_plans = 0, kept = 0;
-        if(diag_ok)
-            for(int i = 0; i < 6; i++)
-            {
-                const TrsvPlan &p  = A->trsv_plan[i];
-                const size_t    ne = (size_t)std::max<aoclsparse_int>(p.nnz_tri, 0);
-                if(p.value_mapped() && (!p.rows_valid || (p.psrc.bytes >= sizeof(int) * ne && p.pval.bytes >= vsz * ne))
-                   && (!p.blk.valid || (p.blk.psrc.bytes >= sizeof(int) * ne && p.blk.pval.bytes >= vsz * ne)))
-                    keep_plans |= 1u << i, kept++;
-            }
-        // ... and the derived operators that hold their source map (build_operator_device under the flag): positions in the clean CSR
-        int ops_kept = 0;
-        if(clean_ok)
-            for(auto &dv : A->derived)
-            {
-                const size_t ne = (size_t)std::max<aoclsparse_int>(dv->host.nnz, 1);
-                if(dv->mapped && dv->src.ptr && dv->dev.valid && dv->dev.nnz == dv->host.nnz && dv->host.val
-                   && dv->src.bytes >= sizeof(unsigned) * ne && dv->dev.val.bytes >= vsz * ne)
-                    ops_kept++;
-                else
-                    dv->drop_value_map(); // (drop_derived_state_keeping keeps exactly the mapped ones)
-            }
-        DeviceBuffer cval; // the clean copy's new values, for the gathers below and the copy back
-        if(clean_ok && clean_copy && total > 0 && (e.rc = cval.alloc(vsz * (size_t)total)) != aoclsparse_status_success)
-            return e.rc; // (nothing written yet: the handle is as it was; only ?revalue_device comes here)
+        ValuesKept k;
+        k.mirror = mirror_follows(A, vsz * (size_t)A->nnz);
+        k.sell   = follow_maps && A->keep_maps && k.mirror;
+        k.clean = k.operators = follow_maps && A->clean_follows();
+        k.diag                = k.clean && A->diag_follows(vsz);
+        for(int i = 0; i < 6 && k.diag; i++)
+            if(A->trsv_plan[i].follows(vsz))
+                k.plans |= 1u << i;
+        return k;
+    }
+
+    // enqueue: the new values to the host view and to everything in `kept` (a clean COPY's through the scratch `cval`), in stream order
+    // behind every product and solve enqueued on the library's stream (they read the old values); one host wait.  The handle is written.
+    void enqueue_values(aoclsparse_matrix A, const void *val, size_t vsz, bool follow_maps, const ValuesKept &kept,
+                        const DeviceBuffer &cval, StreamLaps &lt, FirstError &e)
+    {
+        hipStream_t    s     = Runtime::get().stream();
+        const size_t   bytes = vsz * (size_t)A->nnz;
+        HostCsr *const o     = A->opt;
+        const bool     clean_copy = kept.clean && o != &A->user;
         // the diagnostic also times the gather kernels by device events: [0, 1] around the clean gather, [2, 3] around the
         // diagonal's and the plans' (no host synchronisation in between either way)
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -214,13 +188,11 @@ namespace
         };
         {
             StreamDrain drain{s};
-            // -- from here on the handle is written.  In stream order behind every product and solve enqueued on the library's
-            // stream: they read the old values.
             if(bytes && e.ok())
             {
                 e.hip(hipMemcpyAsync(A->user.val, val, bytes, hipMemcpyDeviceToHost, s));
-                if(keep && val != d.val.ptr && e.ok())
-                    e.hip(hipMemcpyAsync(d.val.ptr, val, bytes, hipMemcpyDeviceToDevice, s));
+                if(kept.mirror && val != A->dev_user.val.ptr && e.ok())
+                    e.hip(hipMemcpyAsync(A->dev_user.val.ptr, val, bytes, hipMemcpyDeviceToDevice, s));
             }
             e.hip(lt.synced("revalue_device: values to host view + mirror"));
             if(lt.on)
@@ -228,12 +200,13 @@ namespace
                     if(hipEventCreate(&v) != hipSuccess)
                         v = nullptr;
             const void *clean_vals = val; // the clean CSR's value array in HBM: the new values themselves, or the gathered copy
-            long long   clean_n    = len;
-            if(clean_ok && clean_copy)
+            long long   clean_n    = A->nnz;
+            if(clean_copy)
             {
+                const aoclsparse_int total = o->nnz;
                 mark(0);
                 if(e.ok())
-                    e.status(launch_revalue_gather(s, total, len, A->clean_src.as<const int>(), val, cval.ptr, vsz, false));
+                    e.status(launch_revalue_gather(s, total, A->nnz, A->clean_src.as<const int>(), val, cval.ptr, vsz, false));
                 mark(1);
                 if(e.ok() && total > 0)
                     e.hip(hipMemcpyAsync(o->val, cval.ptr, vsz * (size_t)total, hipMemcpyDeviceToHost, s));
@@ -241,24 +214,23 @@ namespace
                 e.hip(lt.synced("revalue_device: clean gather + copy back"));
             }
             mark(2);
-            if(diag_ok && e.ok())
+            if(kept.diag && e.ok())
                 e.status(launch_revalue_gather(s, A->m, clean_n, A->diag_src.as<const int>(), clean_vals, A->dev_diag.ptr, vsz, false));
             for(int i = 0; i < 6 && e.ok(); i++)
             {
-                if(!(keep_plans >> i & 1u))
+                if(!(kept.plans >> i & 1u))
                     continue;
                 TrsvPlan &p = A->trsv_plan[i];
                 if(p.rows_valid)
                     e.status(launch_revalue_gather(s, p.nnz_tri, clean_n, p.psrc.as<const int>(), clean_vals, p.pval.ptr, vsz, p.conj));
                 if(p.blk.valid && e.ok())
-                    e.status(launch_revalue_gather(s, p.nnz_tri, clean_n, p.blk.psrc.as<const int>(), clean_vals, p.blk.pval.ptr, vsz,
-                                                   p.conj));
+                    e.status(launch_revalue_gather(s, p.nnz_tri, clean_n, p.blk.psrc.as<const int>(), clean_vals, p.blk.pval.ptr, vsz, p.conj));
             }
-            // the mapped operators: their device values in place, the host view by one copy back each
-            if(clean_ok)
+            // the operators that follow: their device values in place, the host view by one copy back each
+            if(kept.operators)
                 for(auto &dv : A->derived)
                 {
-                    if(!dv->mapped || !e.ok() || dv->host.nnz <= 0)
+                    if(!dv->follows(vsz) || !e.ok() || dv->host.nnz <= 0)
                         continue;
                     e.status(launch_revalue_gather_flagged(s, dv->host.nnz, clean_n, dv->src.as<const unsigned>(), clean_vals,
                                                            dv->dev.val.ptr, vsz));
@@ -277,27 +249,36 @@ namespace
         for(int i = 0; i < 4; i += 2)
         {
             float ms = 0.0f;
-            if(e.ok() && ev[i] && ev[i + 1] && (i == 2 || (clean_ok && clean_copy))
-               && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+            if(e.ok() && ev[i] && ev[i + 1] && (i == 2 || clean_copy) && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
                 std::fprintf(stderr, "[mi355 timing]     %-30s %8.3f ms\n",
                              i ? "revalue_device: plan gather events" : "revalue_device: clean gather events", ms);
         }
         for(hipEvent_t v : ev)
             if(v)
                 (void)hipEventDestroy(v);
-        const bool ok = e.ok(); // (not ok: nothing is kept)
-        // SELL-64 / blocked-ELL copies, derived operators, replicas -- except the structure of the handle's own SELL-64 copy, which
-        // a handle with the flag keeps while the mirror it was built from has followed (its cells are refilled at the next product)
-        const bool keep_ops = ok && clean_ok && ops_kept > 0;
-        A->op_dropped_by_value_change += (long long)A->derived.size() - (keep_ops ? ops_kept : 0);
-        drop_derived_state_keeping(A, ok && clean_ok, ok ? keep_plans : 0u, ok && follow_maps && A->keep_maps && keep, keep_ops);
-        if(!ok)
-            A->drop_value_maps();
-        if(!ok || !diag_ok) // (a diagonal without its map: ensure_trsv gathers it again; no plan was kept)
-            A->dev_diag.release(), A->diag_src.release();
-        d.valid = ok && keep; // (drop_derived_state has cleared it)
-        if(ok && follow_maps)
-            A->revalues++, A->last_kept_plans = (int)kept, A->op_followed = ops_kept;
+    }
+
+    // THE way new values enter a CSR handle from HBM; called with the stage lock and the handle's guard held.  `val`: A->nnz values
+    // of vsz bytes in CSR order -- the caller's array, or the mirror's own (in place).  follow_maps: the clean CSR, the diagonal,
+    // the TRSV plans and the operators that hold a value map get the new values through it (revalue_kernels.hip); what has no map,
+    // and everything without the flag, is dropped and rebuilt lazily.  `produced`: the status of what wrote `val` INTO THE HANDLE
+    // before the call (the triplet refresh).  One host wait.  A failure behind the first write into the handle leaves, on every
+    // route: everything derived dropped, each value map with its holder (no plan with some old and some new values), the mirror
+    // invalid (it may hold either values: the next product uploads the host view), the error cleared and the stream drained.
+    aoclsparse_status commit_values_device(aoclsparse_matrix A, const void *val, size_t vsz, bool follow_maps,
+                                           aoclsparse_status produced = aoclsparse_status_success)
+    {
+        StreamLaps lt{Runtime::get().stream(), PhaseTimer::on() && follow_maps}; // (where a revalue's time goes; the laps then wait for the stream)
+        const ValuesKept kept = values_kept(A, vsz, follow_maps);
+        DeviceBuffer     cval;
+        if(kept.clean && A->opt != &A->user && A->opt->nnz > 0)
+            MI355_TRY(cval.alloc(vsz * (size_t)A->opt->nnz)); // (nothing written yet: the handle is as it was; only ?revalue_device comes here)
+        FirstError e{produced};
+        enqueue_values(A, val, vsz, follow_maps, kept, cval, lt, e);
+        // commit: the list drops what has not been given the new values -- after a failure, everything
+        A->op_dropped_by_value_change += (long long)drop_derived_state(A, e.ok() ? kept : ValuesKept{});
+        if(e.ok() && follow_maps)
+            A->revalues++, A->last_kept_plans = __builtin_popcount(kept.plans), A->op_followed = (int)A->derived.size();
         return e.rc;
     }
 
@@ -1016,8 +997,9 @@ aoclsparse_status aoclsparse_mi355_order_mat_device(aoclsparse_matrix A)
     // stays the handle's resident CSR, so no product uploads that view.
     if(e.ok() && !h.first_err) // (as the host call: a row mat_check refuses leaves the two as they were, and is no failure here)
         A->sort = h.cls ? h.cls : 1, A->fulldiag = !h.notfull;
-    drop_order_dependent_state(A);
-    d.valid = true; // the mirror IS the handle's CSR now: resident before any product
+    ValuesKept sorted;
+    sorted.mirror = true; // the mirror IS the handle's CSR now: resident before any product
+    drop_order_dependent_state(A, sorted);
     if(!e.ok())
         (void)hipGetLastError();
     return e.rc;

@@ -809,10 +809,17 @@ struct TrsvPlan
     DeviceBuffer psrc;
     bool         conj = false;
     void         drop_value_maps() { psrc.release(), blk.psrc.release(); }
-    // every layout this plan holds has its map: aoclsparse_mi355_?revalue_device can carry the plan over
+    // every layout this plan holds has its map (value_mapped), large enough for the triangle's entries in values of vsz bytes
+    // (follows): aoclsparse_mi355_?revalue_device can carry the plan over
     bool value_mapped() const
     {
         return valid && (rows_valid || blk.valid) && (!rows_valid || psrc.ptr) && (!blk.valid || blk.psrc.ptr);
+    }
+    bool follows(size_t vsz) const
+    {
+        const size_t ne = (size_t)std::max<aoclsparse_int>(nnz_tri, 0);
+        return value_mapped() && (!rows_valid || (psrc.bytes >= sizeof(int) * ne && pval.bytes >= vsz * ne))
+               && (!blk.valid || (blk.psrc.bytes >= sizeof(int) * ne && blk.pval.bytes >= vsz * ne));
     }
 };
 
@@ -854,8 +861,27 @@ struct Derived
     bool         on_device = false, mapped = false;
     DeviceBuffer src;
     void         drop_value_map() { src.release(), mapped = false; }
+    // ?revalue_device can carry the operator over (together with the clean CSR its map indexes): values of vsz bytes
+    bool follows(size_t vsz) const
+    {
+        const size_t ne = (size_t)std::max<aoclsparse_int>(host.nnz, 1);
+        return mapped && src.ptr && dev.valid && dev.nnz == host.nnz && host.val && src.bytes >= sizeof(unsigned) * ne
+               && dev.val.bytes >= vsz * ne;
+    }
 };
 constexpr unsigned DERIVED_SRC_CONJ = 0x80000000u, DERIVED_SRC_CONST = 0xffffffffu;
+
+// What a value change leaves standing, as drop_derived_state reads it: the copies that have the new values already.  A default one
+// keeps nothing; anything else comes from values_kept (device_handle_api.cpp), which asks every kind of copy for its `follows` and ties
+// the members together: diagonal and operators only with the clean CSR, plans only with the diagonal, SELL-64 only with the mirror.
+struct ValuesKept
+{
+    bool     mirror    = false; // dev_user stays valid
+    bool     clean = false, diag = false; // the clean CSR (and clean_src with a copy); dev_diag and diag_src
+    bool     sell      = false; // the STRUCTURE of plan_user's SELL-64 copy (SellPlan::stale: the next build_sell refills its cells)
+    unsigned plans     = 0; // bit i: trsv_plan[i]
+    bool     operators = false; // the derived operators that follow (Derived::follows), each with the structure of its SELL-64 copy
+};
 
 } // namespace mi355
 
@@ -901,6 +927,16 @@ struct _aoclsparse_matrix
             p.drop_value_maps();
         for(auto &d : derived)
             d->drop_value_map();
+    }
+    // ?revalue_device can carry over: the clean CSR, the user's arrays or a copy with its map; the diagonal (vsz bytes a value) with its map
+    bool clean_follows() const
+    {
+        return opt && (opt == &user || (opt == opt_copy.get() && opt->val && clean_src.ptr && clean_src.bytes >= sizeof(int) * (size_t)opt->nnz));
+    }
+    bool diag_follows(size_t vsz) const
+    {
+        return dev_diag.ptr && diag_src.ptr && dev_diag.bytes >= vsz * (size_t)m
+               && diag_src.bytes >= sizeof(int) * (size_t)std::max<aoclsparse_int>(m, 1);
     }
     mi355::DeviceBuffer trsv_scratch; // ticket (one per right-hand side) + timeout words of the sync-free solve
     mi355::DeviceBuffer trsv_xp; // solution(s) in level order, m x nrhs (stream-ordered reuse)
@@ -1290,18 +1326,12 @@ aoclsparse_status csr_indices(aoclsparse_int m, aoclsparse_index_base base,
                               aoclsparse_int **idiag, aoclsparse_int **iurow);
 // builds A->opt (clean CSR + idiag/iurow) if absent; thread-safe (double-checked)
 aoclsparse_status csr_optimize(aoclsparse_matrix A);
-// forget every copy derived from the user's arrays (clean CSR, transposes, device mirrors, SELL, TRSV plans)
-void drop_derived_state(aoclsparse_matrix A);
-// the same, except that the clean CSR with dev_diag (keep_clean) and the TRSV plans whose bit is set in keep_plans (bit i =
-// trsv_plan[i]) stay: aoclsparse_mi355_?revalue_device has brought the new values to them; keep_sell: the STRUCTURE of plan_user's
-// SELL-64 copy stays (SellPlan::stale: its cells hold the old values until the next build_sell refills them); keep_operators: the
-// derived operators that hold a value map stay (Derived::mapped: their values have been gathered again), each with the structure
-// of its SELL-64 copy, stale in the same way; the others go
-void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell = false,
-                                bool keep_operators = false);
+// forget every copy derived from the user's arrays (clean CSR, transposes, device mirrors, SELL, TRSV plans) except what `kept` names,
+// each value map with its holder; dev_user.valid ends as kept.mirror.  -> the operators that went (a value change counts them)
+size_t drop_derived_state(aoclsparse_matrix A, const ValuesKept &kept = {});
 // drop_derived_state, and with it what indexes the entries in their order within the rows (the triplet map, the ILU(0) schedule):
-// for whoever has sorted the rows
-void drop_order_dependent_state(aoclsparse_matrix A);
+// for whoever has sorted the rows (kept: the mirror alone, when it was sorted in place and IS the handle's CSR now)
+void drop_order_dependent_state(aoclsparse_matrix A, const ValuesKept &kept = {});
 // the statuses of aoclsparse_?update_values, in its order, all decided before the handle is locked (matrix.cpp);
 // aoclsparse_mi355_?update_values_device / ?revalue_device append theirs (device_handle_api.cpp)
 aoclsparse_status update_values_status(const _aoclsparse_matrix *A, aoclsparse_int len, const void *val, aoclsparse_matrix_data_type vt);

@@ -746,26 +746,11 @@ aoclsparse_status alias_csr(aoclsparse_matrix *mat, aoclsparse_index_base base, 
     return aoclsparse_status_success;
 }
 
-// THE list of what holds A's values besides the caller's arrays (?set_value, ?update_values, aoclsparse_order_mat, the CSC refresh
-// and aoclsparse_mi355_invalidate all come here).  A copy added to the handle that holds values is dropped here, nowhere else.
-void drop_derived_state(aoclsparse_matrix A)
-{
-    drop_derived_state_keeping(A, false, 0u);
-}
-
-// THE list of what hangs on the ORDER of the entries within A's rows (aoclsparse_order_mat and aoclsparse_mi355_order_mat_device
-// come here once the rows are sorted): every copy of the values, and the maps and schedules that index the arrays as they were
-void drop_order_dependent_state(aoclsparse_matrix A)
-{
-    A->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
-    A->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
-    A->sp2m_plan.release(); // ... and the plan of aoclsparse_mi355_sp2m_numeric_device goes with it, as documented
-    drop_derived_state(A); // every copy made of the unsorted arrays (clean CSR, device mirrors, SELL-64 / blocked-ELL, plans, replicas)
-}
-
-// (keep_clean / keep_plans: aoclsparse_mi355_?revalue_device alone passes anything but false / 0 -- it has rewritten the values of
-// what it asks to keep)
-void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned keep_plans, bool keep_sell, bool keep_operators)
+// THE list of what holds A's values besides the caller's arrays (?set_value, ?update_values, commit_values_device, aoclsparse_order_mat,
+// the CSC refresh and aoclsparse_mi355_invalidate all come here).  The rule: a copy added to the handle that holds values is dropped
+// here and nowhere else, and a copy that can follow a value change says so through a `follows` of its own, which values_kept
+// (device_handle_api.cpp) turns into `kept`.  A value map indexes a layout and goes with its holder.
+size_t drop_derived_state(aoclsparse_matrix A, const ValuesKept &kept)
 {
     for(aoclsparse_matrix t : A->tcsr_tri) // TCSR: everything that holds values hangs on the two triangle handles
         if(t)
@@ -773,53 +758,57 @@ void drop_derived_state_keeping(aoclsparse_matrix A, bool keep_clean, unsigned k
             std::unique_lock<std::shared_mutex> w(t->guard);
             drop_derived_state(t);
         }
-    if(A->opt != &A->user && !keep_clean) // the clean copy of unsorted arrays / arrays that miss a diagonal entry
+    if(A->opt != &A->user && !kept.clean) // the clean copy of unsorted arrays / arrays that miss a diagonal entry
     {
-        A->opt_copy.reset();
-        A->opt       = nullptr;
-        A->optimized = false;
-        A->clean_src.release(); // (its value map indexes the copy that is gone)
+        A->opt_copy.reset(), A->clean_src.release();
+        A->opt = nullptr, A->optimized = false;
     }
     A->trans.reset(); // host transpose
-    // symmetric / triangular expansions (host + device + their plans); one that holds a value map has followed a ?revalue_device
-    // and stays (only with the clean CSR its map indexes): its SELL-64 copy keeps its structure as the handle's own does, its
-    // blocked-ELL copy is rebuilt lazily
-    if(keep_operators && keep_clean)
+    // symmetric / triangular expansions (host + device + their plans); one that follows has been given the new values and stays:
+    // its SELL-64 copy keeps its structure as the handle's own does, its blocked-ELL copy is rebuilt lazily
+    auto        &v   = A->derived;
+    const size_t had = v.size(), vsz = val_size(A->val_type);
+    v.erase(std::remove_if(v.begin(), v.end(), [&](const std::unique_ptr<Derived> &d) { return !kept.operators || !d->follows(vsz); }), v.end());
+    for(auto &d : v)
     {
-        auto &v = A->derived;
-        v.erase(std::remove_if(v.begin(), v.end(), [](const std::unique_ptr<Derived> &d) { return !d->mapped || !d->src.ptr; }), v.end());
-        for(auto &d : v)
-        {
-            d->plan.sell.values_changed(true, d->host.m, d->host.nnz);
-            d->plan.bell.valid = d->plan.bell.tried = false;
-        }
+        d->plan.sell.values_changed(true, d->host.m, d->host.nnz);
+        d->plan.bell.valid = d->plan.bell.tried = false;
     }
-    else
-        A->derived.clear();
     for(auto &r : A->replicas) // multi-device replicas hold device copies of the old values
         if(r)
             aoclsparse_destroy(&r);
     A->replicas_cloned = 0;
-    A->dev_user.valid = A->dev_trans.valid = false; // device CSRs; row-block plans stay valid: structure is unchanged
-    A->dev_bsr.valid = false; // the mirror of a BSR handle's arrays
+    A->dev_user.valid  = kept.mirror; // device CSRs; row-block plans stay valid: structure is unchanged
+    A->dev_trans.valid = A->dev_bsr.valid = false; // (dev_bsr: the mirror of a BSR handle's arrays)
     // the SELL copies hold values: rebuilt on optimize (the structure of the handle's own copy outlives a ?revalue_device: stale
     // until build_sell has refilled the cells)
-    A->plan_user.sell.values_changed(keep_sell, A->m, A->nnz);
+    A->plan_user.sell.values_changed(kept.sell, A->m, A->nnz);
     A->plan_trans.sell.values_changed(false, A->n, A->nnz);
     // ... and so does the blocked-ELL copy of csrmm (round 6: it was left standing, and a product after aoclsparse_?set_value /
     // ?update_values on a block-dense handle used the OLD values -- found by tests/test_gpu_r6.py)
     A->plan_user.bell.valid = A->plan_user.bell.tried = false;
     A->plan_trans.bell.valid = A->plan_trans.bell.tried = false;
-    if(!keep_clean)
-        A->dev_diag.release(), A->diag_src.release(); // diagonal of the clean CSR (non-unit solves, SymGS scaling), and its map
+    if(!kept.diag) // diagonal of the clean CSR (non-unit solves, SymGS scaling), and its map: ensure_trsv gathers it again
+        A->dev_diag.release(), A->diag_src.release();
     for(int i = 0; i < 6; i++) // level-ordered triangles: row, block and chunk plans
     {
         TrsvPlan &p = A->trsv_plan[i];
-        if(keep_clean && (keep_plans >> i & 1u))
+        if(kept.plans >> i & 1u)
             continue;
         p.valid = p.rows_valid = false, p.nlevels = -1, p.blk.valid = p.blk.tried = false, p.blk.chunk.valid = p.blk.chunk.tried = false;
-        p.drop_value_maps(); // (they hold no values, but they index a layout that is gone)
+        p.drop_value_maps();
     }
+    return had - v.size();
+}
+
+// THE list of what hangs on the ORDER of the entries within A's rows (aoclsparse_order_mat and aoclsparse_mi355_order_mat_device
+// come here once the rows are sorted): every copy of the values, and the maps and schedules that index the arrays as they were
+void drop_order_dependent_state(aoclsparse_matrix A, const ValuesKept &kept)
+{
+    A->drop_coo_map(); // a kept triplet map points into the arrays as they were ordered at creation
+    A->ilu_sched.release(); // ... and so does the ILU(0) schedule: the next factorisation analyses the new order
+    A->sp2m_plan.release(); // ... and the plan of aoclsparse_mi355_sp2m_numeric_device goes with it, as documented
+    drop_derived_state(A, kept); // every copy made of the unsorted arrays (clean CSR, device mirrors, SELL-64 / blocked-ELL, plans, replicas)
 }
 } // namespace mi355
 
@@ -847,8 +836,7 @@ static aoclsparse_status set_value(aoclsparse_matrix A, aoclsparse_int row_idx, 
             static_cast<T *>(A->user.val)[p] = val;
             if(A->csc_ptr)
                 csc_set_value(A, row_idx, col_idx, &val);
-            A->op_dropped_by_value_change += (long long)A->derived.size();
-            drop_derived_state(A);
+            A->op_dropped_by_value_change += (long long)drop_derived_state(A);
             return aoclsparse_status_success;
         }
     return aoclsparse_status_invalid_index_value;
@@ -895,8 +883,7 @@ static aoclsparse_status update_values(aoclsparse_matrix A, aoclsparse_int len, 
     }
     else
         std::memcpy(A->user.val, val, sizeof(T) * (size_t)len);
-    A->op_dropped_by_value_change += (long long)A->derived.size();
-    drop_derived_state(A);
+    A->op_dropped_by_value_change += (long long)drop_derived_state(A);
     return aoclsparse_status_success;
 }
 

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 from test_gpu_value_updates import _trsv_expect, scaled  # noqa: E402
+from test_operator_device_gpu import mv as op_mv  # noqa: E402
 from test_order_device_gpu import fetch  # noqa: E402
 from test_revalue_device_gpu import dev, oracle_clean_values  # noqa: E402
 
@@ -240,3 +241,263 @@ def test_every_value_type(case, dtype):
     o, want = oracle_clean_values(M, 0, case["rp"], case["ci"], v2)
     assert c[6] and np.array_equal(c[1], o["ptr"]) and np.array_equal(c[2], o["ind"]) and same_bits(c[3], want)
     assert same_bits(fetch(A.export_device()["val"], len(v2), dtype), v2)
+
+
+# ---- every kind of copy on one handle ---------------------------------------------------------------------------------------------------
+# The handles above hold the triplet map, a clean copy with its map, the diagonal and the mapped TRSV plans.  Here a handle holds,
+# besides those, a device-built symmetric operator with its source map, a host-built triangular operator without one, and the
+# SELL-64 copy of its own plan: handle "a" is the file's handle (its clean CSR is a mapped COPY), handle "b" is over the same grid with a
+# full diagonal and sorted rows (its clean CSR is the user's arrays).  Each value change is followed by every observer there is
+# (OBSERVED below), by the operators and copies being asked for again, and by the checks of the tests above.
+EPS = {np.dtype(t): float(np.finfo(t).eps) for t in DTYPES}
+STEPS = {"a": ["revalue", "refresh", "update", "revalue"], "b": ["revalue", "update", "revalue"]}
+
+
+class Setup:
+    """one handle of `kind` and value type, its descriptors and operands, and how a fresh handle over the same arrays is made"""
+
+    def __init__(self, case, kind, dtype):
+        self.kind, self.dtype, self.order = kind, np.dtype(dtype), case["order"]
+        if kind == "a":
+            self.rp, self.ci, self.r0 = case["rp"], case["ci"], case["val"][case["order"]]
+        else:
+            _, rp, ci, v = laplace5(GRID)
+            self.rp, self.ci = np.asarray(rp, np.int32), np.asarray(ci, np.int32)
+            self.r0 = v * np.random.default_rng(41).uniform(0.5, 1.5, len(v))
+        self.v0 = typed(self.r0, dtype)  # (r0: the real values they are made from)
+        rng = np.random.default_rng(13)
+        self.x, self.y0, self.b = (typed(rng.uniform(-1, 1, M), dtype, seed=s) for s in (7, 8, 9))
+        self.dgen, self.dsym = P.Descr(), P.Descr(mtype=P.TYPE_SYMMETRIC, fill=P.FILL_LOWER)
+        self.dtri = P.Descr(mtype=P.TYPE_TRIANGULAR, fill=P.FILL_UPPER)
+        # the symmetric operator of the lower triangle as a CSR of its own, for the oracle: entry q of the handle's arrays, or its mirror
+        rows = np.repeat(np.arange(M), np.diff(self.rp))
+        low, strict = np.flatnonzero(self.ci <= rows), np.flatnonzero(self.ci < rows)
+        r, c = np.concatenate([rows[low], self.ci[strict]]), np.concatenate([self.ci[low], rows[strict]])
+        by = np.lexsort((c, r))
+        self.sym_src, self.sym_ci = np.concatenate([low, strict])[by], c[by].astype(np.int32)
+        self.sym_rp = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=M))]).astype(np.int32)
+        if kind == "a":
+            self.A = handle(case, 0, self.triplets(self.v0))
+        else:
+            self.A = self.fresh(self.v0, hint=False)
+            assert self.A.keep_value_maps() == 0
+        self.hint(self.A)
+
+    def triplets(self, v):
+        t = np.empty_like(v)
+        t[self.order] = v
+        return t
+
+    def hint(self, A):
+        assert L.aoclsparse_set_mv_hint(A.h, P.OP_NONE, self.dgen.h, 100) == 0
+
+    def fresh(self, v, hint=True):
+        F = P.Matrix.from_device(0, M, M, len(v), dev(self.rp), dev(self.ci), dev(v))
+        assert F.status == 0, P.STATUS.get(F.status, F.status)
+        if hint:
+            self.hint(F)
+            assert L.aoclsparse_optimize(F.h) == 0
+        return F
+
+    def arm(self):
+        """whatever a value change has dropped that only a call of its own brings back with a map"""
+        A = self.A
+        if self.kind == "a":
+            assert A.clean_device() == 0
+        assert A.build_operator_device(self.dsym) == 0
+        assert L.aoclsparse_optimize(A.h) == 0
+
+    def observed(self):
+        def fields(i):
+            return tuple(int(getattr(i, k)) for k, _ in i._fields_)
+
+        A = self.A
+        return (fields(A.value_map_info()), fields(A.operator_info(self.dsym)), fields(A.operator_info(self.dtri)),
+                fields(A.sell_keep_info(P.OP_NONE)), int(A.spmv_info().device_resident))
+
+    def change(self, route, v):
+        A = self.A
+        st = {"revalue": lambda: A.revalue_device(dev(v)), "update": lambda: A.update_values_device(dev(v)),
+              "refresh": lambda: A.refresh_from_coo_device(dev(self.triplets(v)))}[route]()
+        assert st == 0, (route, P.STATUS.get(st, st))
+
+    def against_the_oracle(self, d, y, v, what):
+        """the bound of the tests above, (len + 24) eps sum |a||x| per row, with the eps of the value type; the oracle computes in
+        double (oracle.dcsrmv for a real type, oracle.zmv for a complex one)"""
+        if d is self.dsym:
+            rp, ci, vv = self.sym_rp, self.sym_ci, v[self.sym_src]
+        else:
+            rp, ci, vv = self.rp, self.ci, v
+        rows = np.repeat(np.arange(M), np.diff(rp))
+        if self.dtype.kind == "c":
+            yr, _ = oracle.zmv("n", "general", "lower", "non_unit", 0, 1.25 + 0.5j, M, M, rp, ci, vv, self.x, -0.5 + 0.25j, self.y0)
+        else:
+            so, yr = oracle.dcsrmv(-1, 0, 1.25, M, len(vv), vv.astype(np.float64), ci, rp, self.x.astype(np.float64), -0.5,
+                                   self.y0.astype(np.float64))
+            assert so == 0
+        scale = np.bincount(rows, np.abs(vv).astype(np.float64) * np.abs(self.x[ci]).astype(np.float64), minlength=M)
+        bound = (np.diff(rp) + 24) * EPS[self.dtype] * scale + 1e-300
+        print(what, "max |got - oracle| / bound =", float(np.max(np.abs(y - yr) / bound)))
+        assert np.all(np.abs(y - yr) <= bound), (what, "against the oracle")
+
+    def check(self, v, what):
+        """the checks of check_double for the handle's value type, and the products with the two operators"""
+        A, F, dt = self.A, self.fresh(v), self.dtype
+        for name, d in (("mv", self.dgen), ("symmetric mv", self.dsym), ("triangular mv", self.dtri)):
+            y = op_mv(A, d, P.OP_NONE, self.x, self.y0)
+            if d is not self.dtri:
+                self.against_the_oracle(d, y, v, (what, name))
+            assert same_bits(y, op_mv(F, d, P.OP_NONE, self.x, self.y0)), (what, name, "against a fresh handle")
+        H = type("Arrays", (), dict(m=M, base=0, row_ptr=self.rp, col_ind=self.ci))
+        for fill, op in (LOWER_N, UPPER_N):
+            got = solve(A, fill, op, self.b)
+            if dt == np.float64:
+                assert np.array_equal(got, _trsv_expect(H, fill, op, True, 0.75, self.b, 0)(v)), (what, "solve against the oracle", fill)
+            assert same_bits(got, solve(F, fill, op, self.b)), (what, "solve against a fresh handle", fill)
+        erp, eci, ev, _ = exported(A, dt)
+        assert np.array_equal(erp, self.rp) and np.array_equal(eci, self.ci) and same_bits(ev, v), (what, "exported CSR")
+        o, want = oracle_clean_values(M, 0, self.rp, self.ci, v)
+        c, cf = export_clean(A, dt), export_clean(F, dt)
+        assert c[6] == (self.kind == "a") and np.array_equal(c[1], o["ptr"]) and np.array_equal(c[2], o["ind"]), (what, "clean CSR")
+        assert same_bits(c[3], want), (what, "clean values")
+        assert all(np.array_equal(c[k], cf[k]) for k in (1, 2, 4, 5)) and same_bits(c[3], cf[3]), (what, "clean CSR against a fresh handle")
+
+
+# What the observers showed on the commit before the kept set became one value, the same for the four value types: per handle one
+# entry for the set-up and two per step of STEPS -- right behind the value change, and after everything has been asked for again
+# and checked.  Each entry: (ValueMapInfo, OperatorInfo of the symmetric operator, OperatorInfo of the triangular one,
+# SellKeepInfo, device_resident), the fields in the order of their structs.
+OBSERVED = {
+    "a": [
+        ((56, 1, 1, 2, 0, 2, 1, 0, 16968), (80, 1, 1, 1, 441, 441, 2121, 0, 1, 1, 8484, 1, 1, 0),
+         (80, 1, 0, 0, 441, 441, 1281, 0, 1, 1, 0, 1, 1, 0), (56, 1, 1, 1, 0, 1, 1, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 2, 1, 1, 16968), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 1, 1, 1),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1), (56, 1, 0, 1, 0, 1, 1, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 2, 1, 1, 16968), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 2, 8484, 1, 2, 1),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 1, 2, 1), (56, 1, 1, 2, 0, 1, 2, 0, 0), 1),
+        ((56, 1, 0, 0, 2, 2, 1, 1, 0), (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 2, 3),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 2, 3), (56, 0, 0, 2, 0, 1, 2, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 4, 2, 1, 16968), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 2, 3, 3),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 2, 3, 3), (56, 1, 1, 1, 0, 2, 3, 0, 0), 1),
+        ((56, 1, 0, 0, 2, 4, 2, 1, 0), (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 2, 3, 5),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 2, 3, 5), (56, 0, 0, 1, 0, 2, 3, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 6, 3, 1, 16968), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 3, 4, 5),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 3, 4, 5), (56, 1, 1, 1, 0, 3, 4, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 6, 3, 2, 16968), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 3, 4, 6),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 3, 4, 6), (56, 1, 0, 1, 0, 3, 4, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 6, 3, 2, 16968), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 2, 8484, 3, 5, 6),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 3, 5, 6), (56, 1, 1, 2, 0, 3, 5, 0, 0), 1),
+    ],
+    "b": [
+        ((56, 1, 1, 2, 0, 2, 1, 0, 8484), (80, 1, 1, 1, 441, 441, 2121, 0, 1, 1, 8484, 1, 1, 0),
+         (80, 1, 0, 0, 441, 441, 1281, 0, 1, 1, 0, 1, 1, 0), (56, 1, 1, 1, 0, 1, 1, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 2, 1, 1, 8484), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 1, 1, 1),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1), (56, 1, 0, 1, 0, 1, 1, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 2, 1, 1, 8484), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 2, 8484, 1, 2, 1),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 1, 2, 1), (56, 1, 1, 2, 0, 1, 2, 0, 0), 1),
+        ((56, 1, 1, 0, 2, 2, 1, 1, 0), (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 2, 3),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 2, 3), (56, 0, 0, 2, 0, 1, 2, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 4, 1, 1, 8484), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 2, 3, 3),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 2, 3, 3), (56, 1, 1, 1, 0, 2, 3, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 4, 1, 2, 8484), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 1, 8484, 2, 3, 4),
+         (80, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 2, 3, 4), (56, 1, 0, 1, 0, 2, 3, 0, 0), 1),
+        ((56, 1, 1, 2, 2, 4, 1, 2, 8484), (80, 1, 1, 1, 441, 441, 2121, 1, 1, 2, 8484, 2, 4, 4),
+         (80, 1, 0, 0, 441, 441, 1281, 1, 1, 1, 0, 2, 4, 4), (56, 1, 1, 2, 0, 2, 4, 0, 0), 1),
+    ],
+}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("kind", ["a", "b"])
+def test_every_kind_of_copy_at_once(case, kind, dtype):
+    assert L.aoclsparse_mi355_set_option(P.OPTION_SELL, 1) == 0  # (a SELL-64 copy wherever the type has one, whatever the padding)
+    try:
+        S = Setup(case, kind, dtype)
+        S.arm()
+        S.check(S.v0, "set-up")
+        seen, r = [S.observed()], S.r0
+        for k, route in enumerate(STEPS[kind]):
+            r = scaled(r, 50 + k)
+            v = typed(r, dtype, seed=60 + k)
+            S.change(route, v)
+            seen.append(S.observed())
+            S.arm()
+            S.check(v, (k, route))
+            seen.append(S.observed())
+    finally:
+        assert L.aoclsparse_mi355_set_option(P.OPTION_SELL, -1) == 0
+    print("OBSERVED[%r] = %r" % (kind, seen))
+    assert seen[1][3][1:3] == (1, 0), seen[1][3]  # (not vacuous: the revalue has kept the structure of the SELL-64 copy, stale)
+    for k, (got, want) in enumerate(zip(seen, OBSERVED[kind])):
+        assert got == want, (k, got, want)
+    assert len(seen) == len(OBSERVED[kind])
+
+
+# ---- the copies of the TRANSPOSE after a host ?set_value ------------------------------------------------------------------------------------
+# The drop list resets the SELL-64 and the blocked-ELL copy of plan_trans next to those of plan_user; the products below read
+# them (the observer says so before the value changes) and are compared with the oracle on the new values.
+def test_transposed_sell_copy_after_set_value():
+    from test_gpu_value_updates import mutate, options
+
+    m, rp, ci, v = laplace5(40)
+    v = v * np.random.default_rng(71).uniform(0.5, 1.5, len(v))
+    A, d = P.Matrix(0, m, m, rp, ci, v), P.Descr()
+    rng = np.random.default_rng(72)
+    x, y0 = rng.uniform(-1, 1, m), rng.uniform(-1, 1, m)
+
+    def run():
+        y = dev(y0)
+        assert P.dmv(P.OP_TRANSPOSE, 1.3, A, d, dev(x), -0.4, y) == 0
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
+
+    def check(vals, what):
+        so, yr = oracle.dcsrmvt(0, 1.3, m, m, vals, ci, rp, x, -0.4, y0)
+        st, cp, ri, cv = oracle.dcsr2csc(m, m, len(vals), 0, 0, rp, ci, vals)
+        bound = (np.diff(cp) + 24) * EPS64 * abs_row_sums(np.asarray(cp), np.asarray(ri), np.asarray(cv), x) + 1e-300
+        got = run()
+        assert so == 0 and st == 0 and np.all(np.abs(got - yr) <= bound), (what, float(np.max(np.abs(got - yr) / bound)))
+        return got
+
+    with options(sell=1):
+        assert L.aoclsparse_set_mv_hint(A.h, P.OP_TRANSPOSE, d.h, 100) == 0 and L.aoclsparse_optimize(A.h) == 0
+        old = check(A.val.copy(), "old values")
+        # (get_sell_keep_info answers for the handle's own operator alone; spmv_info shows the copy of the transpose)
+        assert A.spmv_info(P.OP_TRANSPOSE).sell_slices > 0, "the transposed product did not run on a SELL-64 copy"
+        new = check(mutate("set_value", A, m // 2), "new values")
+    assert not np.array_equal(old, new)
+
+
+def test_transposed_blocked_ell_copy_after_set_value():
+    import standins
+    from test_gpu_value_updates import mutate
+
+    m, rp, ci, v = standins.block_dense(12, 16, 16, seed=5)
+    A, d, n = P.Matrix(0, m, m, rp, ci, v), P.Descr(), 64
+    rng = np.random.default_rng(73)
+    B, C0 = rng.uniform(-1, 1, (m, n)), rng.uniform(-1, 1, (m, n))
+
+    def oracle_product(vals, Bm, Cm):
+        """2 A^T Bm + 0.5 Cm by oracle.dcsrmm over the CSC arrays (the CSR of A^T), and the entries per row of A^T"""
+        st, cp, ri, cv = oracle.dcsr2csc(m, m, len(vals), 0, 0, rp, ci, vals)
+        so, Cr = oracle.dcsrmm("col", 2.0, 0, cv, ri, cp, m, np.ascontiguousarray(Bm.T).ravel(), n, m, 0.5,
+                               np.ascontiguousarray(Cm.T).ravel(), m)
+        assert st == 0 and so == 0
+        return np.asarray(Cr).reshape(n, m).T, np.diff(np.asarray(cp))
+
+    def check(vals, what):
+        C = C0.copy().ravel()
+        assert P.dcsrmm(P.OP_TRANSPOSE, 2.0, A, d, P.ORDER_ROW, B.ravel(), n, n, 0.5, C, n) == 0
+        ref, length = oracle_product(vals, B, C0)
+        scale, _ = oracle_product(np.abs(vals), np.abs(B), np.abs(C0))  # alpha sum |a||b| + |beta c| per entry of C
+        # the bound of this file's products, (len + 24) eps of the sum of magnitudes, with the length of the row of A^T
+        bound = (length[:, None] + 24) * EPS64 * scale + 1e-300
+        got = C.reshape(m, n)
+        print(what, "max |got - oracle| / bound =", float(np.max(np.abs(got - ref) / bound)))
+        assert np.all(np.abs(got - ref) <= bound), what
+        return C
+
+    old = check(A.val.copy(), "old values")
+    assert A.spmv_info(P.OP_TRANSPOSE).mm_bell_width > 0, "the transposed product did not run on a blocked-ELL copy"
+    new = check(mutate("set_value", A, m // 2), "new values")
+    assert not np.array_equal(old, new)
